@@ -14,7 +14,10 @@ layers 4 — run_finetune.sh:1), inputs already resident in HBM.  Videos are ind
 batches (weak scaling) and RCCL only gathers the [B,T] score matrices (one async all_gather per step, overlapped
 with the next step's kernels).
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+Prints ONE JSON line on rank 0 with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+A plain run does only what that line needs: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs
+DIR: what the last timed step returned, as DIR/<name>.npy, float32, under 64 MB in all; an output too large for that is
+a fixed seeded sample of its rows, the same on every run) and the line.  ``--full`` adds every secondary measurement:
   roofline      the dominant kernel: algorithmic FLOPs per launch / its mean launch duration, from HIP events the
                 library records around every launch in a SEPARATE profiled pass of the same K steps (the headline
                 `value` is timed with profiling off); `traffic` = HBM bytes per launch from the committed PMC passes
@@ -28,6 +31,8 @@ Prints ONE JSON line on rank 0 with the contract fields plus
   bf16_mode     the same K steps on the bf16 matrix pipe (reduced precision, opt-in): context only.
   training_step one training step on the same batch (HIP forward with dropout + masked MSE + HIP backward; SURVEY §8(f)
                 row 2), exact fp32 and under set_train_dtype("bf16"): context only.
+  pcie_inclusive_value, pcie_inclusive_overlapped_value  host-resident batches copied in before scoring (serial / overlapped)
+  eval_ms       (--workload corpus) the sharded keyshot evaluation of the scores
 
 ``--workload`` selects the BASELINE.json configuration (same launcher, same JSON contract, one rank-0 line):
   batch  (default) configs[2]: B=64 x T=1024 x D=1024 per GPU, exact fp32, weak scaling - the headline metric
@@ -104,6 +109,31 @@ def stage_flops(B, T, Din, d, H, L):
     }
 
 
+DUMP_BYTES = 60_000_000           # --dump-outputs: all arrays together, .npy headers left room under 64 MB
+
+
+def dump_outputs(dirname, outputs):
+    """Writes each output tensor as DIR/<name>.npy in float32, smallest first.  An output larger than its share of
+    DUMP_BYTES is reduced to a fixed seeded sample of its rows (all dimensions but the last flattened), sorted by row
+    index: the same rows on every run, so two builds compare output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BYTES
+    items = sorted(outputs.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        share = left // (len(items) - i)
+        if t.numel() * 4 > share:
+            rows = t.reshape(-1, t.shape[-1])
+            n = share // (rows.shape[1] * 4)
+            pick = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:n].sort().values
+            t = rows.index_select(0, pick.to(rows.device))
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -157,7 +187,14 @@ def parse_args():
     ap.add_argument("--no-emulated", action="store_true", help="skip the secondary fp16x3 measurement")
     ap.add_argument("--no-extras", action="store_true", help="skip the PCIe-inclusive and latency legs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample length")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (stage profile + roofline, fp16x3 / bf16 legs, PCIe / latency / "
+                         "training extras, CPU baseline, corpus evaluation time); the --no-* options above apply to these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, under 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     long_ = args.workload == "long"
     args.batch = args.batch or (8 if long_ else 64)
     args.frames = args.frames or (8192 if long_ else 1024)
@@ -224,6 +261,7 @@ def main():
     model.load_state_dict(sd, strict=True)
     model = model.to(dev).eval().set_compute_dtype(args.compute)
     corpus_mod = importlib.import_module("video-summarization_amd.corpus")
+    last = {}           # what the latest step returned (--dump-outputs)
     if wl == "corpus":
         # configs[3]: 50 + 25 ragged videos (tools/eval_corpus.py: lengths U[150,650] / U[100,650]),
         # the SAME corpus on every rank; a rank's shard is resident on its GPU, scores return to every rank
@@ -237,7 +275,7 @@ def main():
         gathered = None
 
         def step():
-            corpus_mod.score_corpus(lambda xx, mm: model.score(xx, mm), videos, rank=rank, world=world, device=dev,
+            last["scores"] = corpus_mod.score_corpus(lambda xx, mm: model.score(xx, mm), videos, rank=rank, world=world, device=dev,
                                     max_frames=int(os.environ.get("VS_BENCH_CORPUS_FRAMES", "65536")), packed_fn=(lambda xx, ll: model.score_packed(xx, ll)) if can_pack else None,
                                     force_collective=dist is not None)
             return None
@@ -249,7 +287,8 @@ def main():
         gathered = torch.empty((world * B, T), dtype=torch.float32, device=dev) if dist is not None else None   # rank-major rows
 
         def step():
-            logits, _hidden = model(x)
+            logits, last["hidden"] = model(x)
+            last["logits"] = logits
             if dist is not None:
                 return dist.all_gather_into_tensor(gathered, logits.view(B, T), async_op=True)
             return None
@@ -275,16 +314,26 @@ def main():
             if w is not None:
                 w.wait()
         dt = timed(args.steps)                    # the headline: profiling OFF
+        if args.dump_outputs and rank == 0:
+            outputs = dict(last)
+            if wl == "corpus":
+                outputs["scores"] = torch.cat([outputs["scores"][i] for i in sorted(outputs["scores"])])
+            if gathered is not None:
+                outputs["gathered_logits"] = gathered
+            dump_outputs(args.dump_outputs, outputs)
 
+        # everything below is --full only
         # the same K steps again with the library's per-launch HIP events on (stage table / roofline only)
-        lib.vs_profile_enable(1)
-        timed(args.steps)
-        stages = pkg._lib.profile_collect()
-        lib.vs_profile_enable(0)
+        stages = None
+        if args.full:
+            lib.vs_profile_enable(1)
+            timed(args.steps)
+            stages = pkg._lib.profile_collect()
+            lib.vs_profile_enable(0)
 
         # secondary: the same K steps with fp32 emulated on the f16 pipe (never `value`)
         emu = None
-        if wl == "batch" and args.compute == "fp32" and not args.no_emulated and d // H in (32, 64, 128):
+        if args.full and wl == "batch" and args.compute == "fp32" and not args.no_emulated and d // H in (32, 64, 128):
             exact_logits = model(x)[0].clone()
             model.set_compute_dtype("fp16x3")
             for _ in range(max(2, args.warmup // 2)):
@@ -297,7 +346,7 @@ def main():
             emu = (dt_emu, diff)
         # secondary: the same K steps with every product on the bf16 matrix pipe (reduced precision: never `value`)
         low = None
-        if wl == "batch" and args.compute == "fp32" and not args.no_emulated and d <= 256 and d // H in (32, 64):
+        if args.full and wl == "batch" and args.compute == "fp32" and not args.no_emulated and d <= 256 and d // H in (32, 64):
             exact_logits = model(x)[0].clone()
             model.set_compute_dtype("bf16")
             for _ in range(max(2, args.warmup // 2)):
@@ -312,7 +361,7 @@ def main():
         pcie_fps = pcie_overlap_fps = lat_ms = lat_splitk_ms = None
         train_ms = None
         eval_ms = None
-        if wl == "corpus":           # the consumer of the gathered scores: sharded keyshot evaluation + all_reduce of four sums
+        if args.full and wl == "corpus":           # the consumer of the gathered scores: sharded keyshot evaluation + all_reduce of four sums
             # timed on its own (not "a whole val_step minus a scoring pass"): score once, then only the evaluation of this
             # rank's shard (one C call: vs_eval_corpus) and the all_reduce of the four sums
             harness = importlib.import_module("video-summarization_amd.harness")
@@ -330,7 +379,7 @@ def main():
                 dist.all_reduce(tt)
                 torch.cuda.synchronize()
             eval_ms = (time.perf_counter() - t1) * 1e3
-        if wl == "batch" and not args.no_extras:
+        if args.full and wl == "batch" and not args.no_extras:
             # PCIe-inclusive rates (never `value`): pinned host batches -> device -> forward.  Serial = copy then
             # kernels on one stream; overlapped = corpus.score_host_batches (copy stream + compute stream).
             fence()
@@ -411,65 +460,67 @@ def main():
 
     out = None
     if rank == 0:
-        if wl == "corpus":
-            # ragged shard: per-stage FLOPs of ONE pass over rank 0's videos, divided by the launches that pass made
-            # (one per packed batch and layer) = the average launch the event durations are averaged over
-            mine_t = [lengths[i] for i in mine]
-            Msh, Q = float(sum(mine_t)), float(sum(t * t for t in mine_t))
-            per_pass = {"embed_pe": 2.0 * Msh * Din * d, "qkv_proj": L * 2.0 * Msh * d * 3 * d, "attention": L * 4.0 * Q * d,
-                        "outproj_ln": L * 2.0 * Msh * d * d, "fc1_relu": L * 2.0 * Msh * d * 4 * d,
-                        "fc2_ln_score": L * 2.0 * Msh * 4 * d * d + 2.0 * Msh * d}
-            fl = {k: per_pass[k] / max(stages.get(k, (0, 0))[1] / args.steps, 1e-9) if stages.get(k, (0, 0))[1] else 0.0
-                  for k in per_pass}
-        else:
-            fl = stage_flops(B, T, Din, d, H, L)
-        # the bf16 mode folds stages into fewer kernels: a stage that was never launched did its
-        # work inside another - the layer tail (reported as fc2_ln_score) carries the out-projection, fc1 and all but the
-        # first QKV, the embedding kernel the first QKV; FLOPs per launch follow the work
-        if stages.get("fc1_relu", (0, 0))[1] == 0 and stages.get("fc2_ln_score", (0, 0))[1]:
-            fl["fc2_ln_score"] += fl["fc1_relu"]
-            if stages.get("outproj_ln", (0, 0))[1] == 0:
-                fl["fc2_ln_score"] += fl["outproj_ln"]
-            nq = stages.get("qkv_proj", (0, 0))[1]
-            if nq < stages["fc2_ln_score"][1]:
-                per_step = stages["fc2_ln_score"][1] // L if L else 0      # timed + profiled steps recorded
-                if nq == 0:
-                    fl["embed_pe"] += fl["qkv_proj"]
-                    fl["fc2_ln_score"] += fl["qkv_proj"] * (L - 1) / L
-                elif per_step and nq == per_step:
-                    fl["fc2_ln_score"] += fl["qkv_proj"] * (L - 1) / L
-        table = {}
-        for name, (ms, n) in stages.items():
-            if n:
-                avg = ms / n
-                table[name] = {"launches": n, "avg_ms": round(avg, 4), "tflops": round(fl[name] / (avg * 1e-3) / 1e12, 2),
-                               "share": 0.0}
-        tot = sum(v["avg_ms"] * v["launches"] for v in table.values())
-        for v in table.values():
-            v["share"] = round(v["avg_ms"] * v["launches"] / tot, 3)
-        dom = max(table, key=lambda k: table[k]["share"])
-        flops_per_frame = 2 * Din * d + L * (24 * d * d + 4 * T * d) + 2 * d
-        if wl == "corpus":            # corpus average: sum over videos of T (2 Din d + L (24 d^2 + 4 T d) + 2 d) / sum T
-            flops_per_frame = sum(t * (2 * Din * d + L * (24 * d * d + 4 * t * d) + 2 * d) for t in lengths) / float(sum(lengths))
-        # peak of the arithmetic the timed path used: fp32 MFMA, or f16 MFMA / 3 products (fp16x3), or bf16 MFMA
-        peak = {"fp32": PEAK_F32_MFMA_TFLOPS, "fp16x3": PEAK_F16_MFMA_TFLOPS / 3, "bf16": PEAK_F16_MFMA_TFLOPS}[args.compute]
-        traffic, traffic_src = (None, "not the measured configuration")
-        if (wl, B, T, args.model, args.compute) == ("batch", 64, 1024, "A", "fp32"):
-            traffic, traffic_src = measured_traffic(dom)
-        roofline = {"bound": "mfma", "kernel": dom, "achieved": table[dom]["tflops"], "peak": round(peak, 1),
-                    "unit": "TFLOP/s", "frac": round(table[dom]["tflops"] / peak, 4),
-                    "traffic": traffic, "traffic_source": traffic_src, "hbm_gbps": None,
-                    "flop_per_launch": fl[dom],
-                    "whole_forward": {"flop_per_frame": flops_per_frame,
-                                      "achieved": round(value / world * flops_per_frame / 1e12, 2),
-                                      "frac": round(value / world * flops_per_frame / 1e12 / peak, 4)},
-                    "stages": table}
-        if traffic:
-            # HBM GB/s of the dominant kernel: measured bytes per launch (PMC passes) / its live average duration
-            roofline["hbm_gbps"] = round(traffic / (table[dom]["avg_ms"] * 1e-3) / 1e9, 1)
+        roofline = None
+        if stages is not None:
+            if wl == "corpus":
+                # ragged shard: per-stage FLOPs of ONE pass over rank 0's videos, divided by the launches that pass made
+                # (one per packed batch and layer) = the average launch the event durations are averaged over
+                mine_t = [lengths[i] for i in mine]
+                Msh, Q = float(sum(mine_t)), float(sum(t * t for t in mine_t))
+                per_pass = {"embed_pe": 2.0 * Msh * Din * d, "qkv_proj": L * 2.0 * Msh * d * 3 * d, "attention": L * 4.0 * Q * d,
+                            "outproj_ln": L * 2.0 * Msh * d * d, "fc1_relu": L * 2.0 * Msh * d * 4 * d,
+                            "fc2_ln_score": L * 2.0 * Msh * 4 * d * d + 2.0 * Msh * d}
+                fl = {k: per_pass[k] / max(stages.get(k, (0, 0))[1] / args.steps, 1e-9) if stages.get(k, (0, 0))[1] else 0.0
+                      for k in per_pass}
+            else:
+                fl = stage_flops(B, T, Din, d, H, L)
+            # the bf16 mode folds stages into fewer kernels: a stage that was never launched did its
+            # work inside another - the layer tail (reported as fc2_ln_score) carries the out-projection, fc1 and all but the
+            # first QKV, the embedding kernel the first QKV; FLOPs per launch follow the work
+            if stages.get("fc1_relu", (0, 0))[1] == 0 and stages.get("fc2_ln_score", (0, 0))[1]:
+                fl["fc2_ln_score"] += fl["fc1_relu"]
+                if stages.get("outproj_ln", (0, 0))[1] == 0:
+                    fl["fc2_ln_score"] += fl["outproj_ln"]
+                nq = stages.get("qkv_proj", (0, 0))[1]
+                if nq < stages["fc2_ln_score"][1]:
+                    per_step = stages["fc2_ln_score"][1] // L if L else 0      # timed + profiled steps recorded
+                    if nq == 0:
+                        fl["embed_pe"] += fl["qkv_proj"]
+                        fl["fc2_ln_score"] += fl["qkv_proj"] * (L - 1) / L
+                    elif per_step and nq == per_step:
+                        fl["fc2_ln_score"] += fl["qkv_proj"] * (L - 1) / L
+            table = {}
+            for name, (ms, n) in stages.items():
+                if n:
+                    avg = ms / n
+                    table[name] = {"launches": n, "avg_ms": round(avg, 4), "tflops": round(fl[name] / (avg * 1e-3) / 1e12, 2),
+                                   "share": 0.0}
+            tot = sum(v["avg_ms"] * v["launches"] for v in table.values())
+            for v in table.values():
+                v["share"] = round(v["avg_ms"] * v["launches"] / tot, 3)
+            dom = max(table, key=lambda k: table[k]["share"])
+            flops_per_frame = 2 * Din * d + L * (24 * d * d + 4 * T * d) + 2 * d
+            if wl == "corpus":            # corpus average: sum over videos of T (2 Din d + L (24 d^2 + 4 T d) + 2 d) / sum T
+                flops_per_frame = sum(t * (2 * Din * d + L * (24 * d * d + 4 * t * d) + 2 * d) for t in lengths) / float(sum(lengths))
+            # peak of the arithmetic the timed path used: fp32 MFMA, or f16 MFMA / 3 products (fp16x3), or bf16 MFMA
+            peak = {"fp32": PEAK_F32_MFMA_TFLOPS, "fp16x3": PEAK_F16_MFMA_TFLOPS / 3, "bf16": PEAK_F16_MFMA_TFLOPS}[args.compute]
+            traffic, traffic_src = (None, "not the measured configuration")
+            if (wl, B, T, args.model, args.compute) == ("batch", 64, 1024, "A", "fp32"):
+                traffic, traffic_src = measured_traffic(dom)
+            roofline = {"bound": "mfma", "kernel": dom, "achieved": table[dom]["tflops"], "peak": round(peak, 1),
+                        "unit": "TFLOP/s", "frac": round(table[dom]["tflops"] / peak, 4),
+                        "traffic": traffic, "traffic_source": traffic_src, "hbm_gbps": None,
+                        "flop_per_launch": fl[dom],
+                        "whole_forward": {"flop_per_frame": flops_per_frame,
+                                          "achieved": round(value / world * flops_per_frame / 1e12, 2),
+                                          "frac": round(value / world * flops_per_frame / 1e12 / peak, 4)},
+                        "stages": table}
+            if traffic:
+                # HBM GB/s of the dominant kernel: measured bytes per launch (PMC passes) / its live average duration
+                roofline["hbm_gbps"] = round(traffic / (table[dom]["avg_ms"] * 1e-3) / 1e9, 1)
         cpu = None
         latency = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle.simnet_oracle import time_cpu_baseline, usable_cpus      # the checker, timed as the CPU "port"
             # `cores` = the host cores this job may use on the box (affinity / cgroup share); `threads` = the torch
             # thread count the sweep found fastest for the oracle (never more than `cores`)
@@ -518,10 +569,13 @@ def main():
             "data": "synthetic",
             "config": cfg,
             "collective_backend": backend, "ranks_seen": ranks_seen,
-            "pcie_inclusive_value": round(pcie_fps * world, 1) if pcie_fps else None,
-            "pcie_inclusive_overlapped_value": round(pcie_overlap_fps * world, 1) if pcie_overlap_fps else None,
-            "roofline": roofline, "cpu_baseline": cpu, "latency": latency,
         }
+        if args.full:
+            out.update({
+                "pcie_inclusive_value": round(pcie_fps * world, 1) if pcie_fps else None,
+                "pcie_inclusive_overlapped_value": round(pcie_overlap_fps * world, 1) if pcie_overlap_fps else None,
+                "roofline": roofline, "cpu_baseline": cpu, "latency": latency,
+            })
         if eval_ms is not None:
             out["eval_ms"] = round(eval_ms, 3)
         if train_ms:

@@ -40,7 +40,7 @@ def test_single_rank_does_not_relaunch():
 def test_two_rank_rehearsal_through_the_self_launcher():
     """The real N > 1 control flow (per-rank batches, async all_gather per step, max-over-ranks timing), two ranks on the
     one GPU over gloo (VS_BENCH_REHEARSE=1: RCCL refuses two ranks on one device).  Numbers are meaningless here."""
-    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--frames", "256", "--no-cpu-baseline",
+    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--frames", "256", "--full", "--no-cpu-baseline",
                 "--no-emulated", "--no-extras"], {"VS_BENCH_REHEARSE": "1"}, 600)
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 4 and out["value"] > 0
     assert out["collective_backend"] == "gloo" and out["roofline"]["stages"]["attention"]["launches"] == 3 * 4
@@ -62,7 +62,7 @@ def test_bench_line_carries_the_contract_fields_and_a_traceable_traffic_figure()
     committed PMC file (its source hash must match the loaded kernels - a stale file reads as null and fails here, so a
     kernel edit without `tools/collect_traffic.sh` is caught), and the secondary legs (fp16x3, bf16) are printed beside,
     never as, `value`."""
-    out = _run(["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-extras"], {}, 900)
+    out = _run(["--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extras"], {}, 900)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline"):
         assert key in out, key
@@ -79,7 +79,7 @@ def test_bench_extras_do_not_fail_silently():
     """The extras of the bench line (latency of one T=320 video - default kernels and latency mode -, one training step in
     fp32 / bf16 / fp16) are wrapped so that they can never cost the headline line; a genuine failure would then only show
     as an {"error": ...} field.  This run keeps the extras on and asserts on them."""
-    out = _run(["--steps", "3", "--warmup", "1", "--batch", "8", "--frames", "512", "--no-cpu-baseline", "--no-emulated"], {}, 900)
+    out = _run(["--steps", "3", "--warmup", "1", "--batch", "8", "--frames", "512", "--full", "--no-cpu-baseline", "--no-emulated"], {}, 900)
     ts = out.get("training_step")
     assert ts is not None and "error" not in ts, ts
     assert ts["fp32_ms"] > 0 and ts["bf16_ms"] > 0 and ts["fp16_ms"] > 0
@@ -93,7 +93,7 @@ def test_two_rank_rehearsal_of_the_other_workloads(workload):
     """configs[3] (`--workload corpus`: strong scaling of the 75-video corpus, scores gathered to every rank, sharded
     evaluation timed beside) and configs[4] (`--workload long`: bf16) under the same self-launcher and JSON contract;
     two ranks on the one GPU over gloo (numbers meaningless), plus the one-rank form."""
-    extra = ["--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    extra = ["--workload", workload, "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     if workload == "long":
         extra += ["--batch", "1", "--frames", "512"]
     two = _run(["--gpus", "2"] + extra, {"VS_BENCH_REHEARSE": "1"}, 900)
@@ -107,3 +107,57 @@ def test_two_rank_rehearsal_of_the_other_workloads(workload):
         else:
             assert out["scaling"] == "weak" and out["dtype"].startswith("bf16") and "configs[4]" in out["config"]["workload"]
             assert out["config"]["frames_per_step"] == 512 * n and out["roofline"]["peak"] == 2500.0
+
+
+def test_dump_outputs_stays_under_its_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: small outputs are written whole, a larger one as a seeded sample of its rows that is the same on
+    every call; every file is float32 and all of them together stay under 64 MB."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outputs = {"logits": torch.randn(64, 1024, 1, generator=g), "hidden": torch.randn(64, 1024, 256, generator=g)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outputs)
+    total = 0
+    for name, t in outputs.items():
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        total += (tmp_path / "a" / (name + ".npy")).stat().st_size
+    assert np.array_equal(np.load(tmp_path / "a" / "logits.npy"), outputs["logits"].numpy())
+    hid = np.load(tmp_path / "a" / "hidden.npy")
+    rows = outputs["hidden"].reshape(-1, 256).numpy()
+    assert hid.shape[1] == 256 and 0 < hid.shape[0] < rows.shape[0]
+    where = {r.tobytes(): i for i, r in enumerate(rows)}
+    idx = [where[r.tobytes()] for r in hid]          # every sampled row is a row of the output, in row order
+    assert all(a < b for a, b in zip(idx, idx[1:]))
+    assert total <= 64 * 10 ** 6, total
+
+
+@pytest.mark.gpu
+def test_plain_run_times_only_the_headline_and_dumps_what_it_computed(tmp_path):
+    """A plain run prints the headline fields and none of the --full measurements; its dumped outputs are those of the
+    seeded inputs (checked against the CPU oracle) and the same from run to run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import importlib
+    from oracle.simnet_oracle import oracle_forward
+    args = ["--steps", "3", "--warmup", "1", "--batch", "2", "--frames", "256"]
+    outs = [_run(args + ["--dump-outputs", str(tmp_path / d)], {}, 600) for d in ("a", "b")]
+    for out in outs:
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in out, key
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["dtype"] == "f32"
+        for key in ("roofline", "cpu_baseline", "latency", "emulated_f32", "bf16_mode", "training_step"):
+            assert key not in out, key
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("logits", "hidden")}
+    for n, a in got.items():
+        assert a.dtype == np.float32 and np.array_equal(a, np.load(tmp_path / "b" / (n + ".npy"))), n
+    synth = importlib.import_module("video-summarization_amd").synth
+    sd = synth.make_state_dict(256, 4, seed=1234)
+    x = torch.randn(2, 256, 1024, generator=torch.Generator(device="cpu").manual_seed(1234))
+    ref_logits, ref_hidden = oracle_forward(sd, x, None, 4)
+    assert np.abs(got["logits"] - ref_logits.numpy()).max() < 1e-4
+    assert np.abs(got["hidden"] - ref_hidden.numpy()).max() < 1e-4

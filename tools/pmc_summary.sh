@@ -1,13 +1,15 @@
 #!/bin/bash
 # Per-kernel MFMA-pipe utilisation (cycles), effective clock and instruction mix per MFMA for one bench run.
-# GPU box:  bash tools/pmc_summary.sh > gpurun_out/pmc_summary.txt
+# GPU box:  bash tools/pmc_summary.sh > pmc_summary.txt   (counters under $OUT_ROOT/pmc_all; OUT_ROOT relative to the
+# repository root, default out)
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
+D=$ROOT/${OUT_ROOT:-out}/pmc_all
 cd /tmp && export TMPDIR=/tmp
-rm -rf $ROOT/gpurun_out/pmc_all
-timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_ANY SQ_INSTS_MFMA --kernel-trace --output-format csv -d $ROOT/gpurun_out/pmc_all -- python3 $ROOT/bench.py --steps 6 --warmup 2 --no-cpu-baseline > $ROOT/gpurun_out/pmc_all.log 2>&1
+rm -rf $D
+timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_ANY SQ_INSTS_MFMA --kernel-trace --output-format csv -d $D -- python3 $ROOT/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $D.log 2>&1
 python3 - <<PY
 import csv, collections, glob
-f=glob.glob('$ROOT/gpurun_out/pmc_all/*/*counter_collection.csv')[0]
+f=glob.glob('$D/*/*counter_collection.csv')[0]
 per=collections.OrderedDict()
 for r in csv.DictReader(open(f)):
     per.setdefault(r['Dispatch_Id'],{'name':r['Kernel_Name'].replace('void (anonymous namespace)::','').split('(')[0],'t0':int(r['Start_Timestamp']),'t1':int(r['End_Timestamp'])})[r['Counter_Name']]=float(r['Counter_Value'])
