@@ -1,0 +1,85 @@
+"""Writes tests/golden/kts_golden.npz: the reference's kernel temporal segmentation (segmentations/kts, numpy only) on
+seeded inputs.  The inputs are NOT stored: each case's recipe (tests/kts_ref.py generators + seed) is, and the tests
+rebuild them bit for bit.
+
+    python tests/golden/make_golden_kts.py --reference <checkout of the reference>/src/data/preprocess/segmentations
+"""
+import argparse
+import contextlib
+import io
+import json
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+import kts_ref  # noqa: E402
+
+# name: recipe.  fn: kts_seg (features -> K = X X^T in float32) | kts_segmentation | cpd_nonlin.
+# x: ("planted", n, D, shots, seed) | ("unstructured", n, D, seed); kernel: "dot" (float32 X X^T) | ("rbf", gamma) (float64)
+CASES = {
+    "seg_planted_n60_d1024": dict(fn="kts_seg", x=("planted", 60, 1024, 4, 11), ncp=10, vmax=1.0),
+    "seg_planted_n200_d1024": dict(fn="kts_seg", x=("planted", 200, 1024, 8, 12), ncp=20, vmax=1.0),
+    "seg_planted_n400_d1024": dict(fn="kts_seg", x=("planted", 400, 1024, 12, 13), ncp=40, vmax=1.0),
+    "seg_planted_n200_d512": dict(fn="kts_seg", x=("planted", 200, 512, 6, 14), ncp=20, vmax=1.0),
+    "seg_planted_n400_d512": dict(fn="kts_seg", x=("planted", 400, 512, 10, 15), ncp=40, vmax=1.0),
+    "seg_unstructured_n200_d1024": dict(fn="kts_seg", x=("unstructured", 200, 1024, 16), ncp=20, vmax=1.0),
+    "seg_ncp_n_minus_1_n150": dict(fn="kts_seg", x=("planted", 150, 512, 6, 17), ncp=149, vmax=1.0),
+    "auto_lmin3_lmax60_n200": dict(fn="kts_segmentation", x=("planted", 200, 512, 6, 18), kernel="dot", ncp=20, vmax=1.0,
+                                   lmin=3, lmax=60),
+    "auto_desc_rate15_n200": dict(fn="kts_segmentation", x=("planted", 200, 1024, 7, 19), kernel="dot", ncp=20, vmax=1.0,
+                                  desc_rate=15),
+    "auto_rbf_f64_n200": dict(fn="kts_segmentation", x=("planted", 200, 512, 5, 20), kernel=("rbf", 0.5), ncp=15, vmax=0.5),
+    "cpd_backtrack_lmax50_n200": dict(fn="cpd_nonlin", x=("planted", 200, 512, 6, 21), kernel="dot", ncp=8, lmin=2,
+                                      lmax=50, backtrack=True),
+    "cpd_no_backtrack_n200": dict(fn="cpd_nonlin", x=("planted", 200, 1024, 6, 22), kernel="dot", ncp=12, backtrack=False),
+    "cpd_out_scatters_n60": dict(fn="cpd_nonlin", x=("planted", 60, 1024, 3, 23), kernel="dot", ncp=5, backtrack=True,
+                                 out_scatters=True),
+}
+
+
+def features(rec):
+    if rec[0] == "planted":
+        return kts_ref.planted(*rec[1:])
+    return kts_ref.unstructured(*rec[1:])
+
+
+def kernel(x, kind):
+    if kind == "dot":
+        return np.dot(x, x.T)
+    return kts_ref.rbf(x, kind[1])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reference", required=True, help="the reference's segmentations directory (holds kts/)")
+    args = ap.parse_args()
+    sys.path.insert(0, args.reference)
+    from kts import cpd_nonlin, kts_segmentation  # noqa: the reference package, numpy only
+
+    out = {"cases": np.array(json.dumps(CASES))}
+    for name, c in CASES.items():
+        x = features(c["x"])
+        sink = io.StringIO()
+        with contextlib.redirect_stdout(sink):
+            if c["fn"] == "kts_seg":
+                cps, vals = kts_segmentation(np.dot(x, x.T), c["ncp"], c["vmax"])
+            elif c["fn"] == "kts_segmentation":
+                kw = {k: c[k] for k in ("lmin", "lmax") if k in c}
+                cps, vals = kts_segmentation(kernel(x, c["kernel"]), c["ncp"], c["vmax"], c.get("desc_rate", 1), **kw)
+            else:
+                kw = {k: c[k] for k in ("lmin", "lmax") if k in c}
+                sc = [None] if c.get("out_scatters") else None
+                cps, vals = cpd_nonlin(kernel(x, c["kernel"]), c["ncp"], backtrack=c["backtrack"], out_scatters=sc, **kw)
+                if sc is not None:
+                    out[name + "/scatters"] = np.asarray(sc[0], dtype=np.float64)
+        out[name + "/cps"] = np.asarray(cps, dtype=np.int64)
+        out[name + "/vals"] = np.asarray(vals, dtype=np.float64)
+        print("%-30s cps %3d  vals[0] %.6g" % (name, len(cps), vals[0]))
+    np.savez_compressed(os.path.join(HERE, "kts_golden.npz"), **out)
+
+
+if __name__ == "__main__":
+    main()

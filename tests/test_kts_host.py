@@ -1,0 +1,167 @@
+"""CPU (no GPU): kernel temporal segmentation - the float64 restatement against the reference's goldens, the C ABI of
+include/vs_segment.h (exports, C99, argument checks), uniform segments and the shot-range mapping."""
+import ctypes as C
+import json
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT
+import kts_ref
+
+GOLD = os.path.join(GOLDEN, "kts_golden.npz")
+
+
+def golden():
+    z = np.load(GOLD)
+    return json.loads(str(z["cases"])), z
+
+
+def case_kernel(c):
+    """The case's input as the reference saw it: K = X X^T in float32 (dot) or the float64 RBF kernel."""
+    x = kts_ref.planted(*c["x"][1:]) if c["x"][0] == "planted" else kts_ref.unstructured(*c["x"][1:])
+    if c.get("kernel", "dot") == "dot":
+        return x, np.dot(x, x.T)
+    return x, kts_ref.rbf(x, c["kernel"][1])
+
+
+def rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    assert (np.isinf(a) == np.isinf(b)).all()
+    f = np.isfinite(b)
+    return float((np.abs(a[f] - b[f]) / np.maximum(np.abs(b[f]), 1e-300)).max()) if f.any() else 0.0
+
+
+CASES, _ = golden()
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_restatement_matches_the_reference_goldens(name):
+    c, z = CASES[name], golden()[1]
+    x, K = case_kernel(c)
+    K64 = np.asarray(K, dtype=np.float64)
+    if c["fn"] == "cpd_nonlin":
+        cps, vals, _, _ = kts_ref.cpd_nonlin(K64, c["ncp"], c.get("lmin", 1), c.get("lmax", 100000), c["backtrack"])
+        if c.get("out_scatters"):
+            J = kts_ref.scatters(K64)
+            g = z[name + "/scatters"]
+            assert np.abs(J - g).max() <= 5e-5 * np.abs(g).max()
+    else:
+        cps, vals, _, _ = kts_ref.kts_segmentation(K64, c["ncp"], c["vmax"], c.get("desc_rate", 1), c.get("lmin", 1),
+                                                   c.get("lmax", 100000))
+    np.testing.assert_array_equal(cps, z[name + "/cps"])
+    assert rel(vals, z[name + "/vals"]) <= 5e-5
+
+
+def test_segment_header_is_plain_c99_and_declares_exactly_the_segment_exports(vsa):
+    vsa._lib.build()
+    lib = vsa._lib.load()
+    path = os.path.join(ROOT, "include", "vs_segment.h")
+    hdr = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    declared = set(re.findall(r"\b(vs_[a-z0-9_]+)\s*\(", hdr))
+    assert declared == set(vsa._lib.SEGMENT_EXPORTS), declared ^ set(vsa._lib.SEGMENT_EXPORTS)
+    for name in declared:
+        assert hasattr(lib, name), name
+    assert not set(vsa._lib.SEGMENT_EXPORTS) & set(vsa._lib.EXPORTS)
+    gcc = shutil.which("gcc")
+    assert gcc
+    r = subprocess.run([gcc, "-std=c99", "-pedantic", "-Werror", "-fsyntax-only", "-x", "c", path], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def _arr(v, ct):
+    return (ct * len(v))(*v)
+
+
+def _segment(lib, cu, ncp, lmin=None, lmax=None, mode=2, inp=0, d=512, vmax=(1.0,), ws=1 << 20, x=16):
+    B = len(cu) - 1
+    cps = (C.c_int64 * 1024)()
+    n_cps = (C.c_int32 * 8)()
+    scores = (C.c_double * 1024)()
+    return lib.vs_kts_segment(C.c_void_p(x), inp, d, _arr(cu, C.c_int32), B, _arr(ncp, C.c_int32),
+                              _arr(lmin, C.c_int32) if lmin else None, _arr(lmax, C.c_int32) if lmax else None,
+                              _arr(vmax, C.c_double), None, mode, cps, n_cps, scores, C.c_void_p(16), ws, None)
+
+
+def test_invalid_arguments_are_refused_with_a_message_and_no_gpu(vsa):
+    lib = vsa._lib.load()
+    bad = [
+        dict(cu=[0, 10], ncp=[10]),                             # n < (ncp + 1) lmin
+        dict(cu=[0, 10], ncp=[2], lmin=[4]),                    # n < (ncp + 1) lmin
+        dict(cu=[0, 100], ncp=[3], lmin=[1], lmax=[20]),        # n > (ncp + 1) lmax
+        dict(cu=[0, 100], ncp=[3], lmin=[5], lmax=[4]),         # lmax < lmin
+        dict(cu=[0, 100], ncp=[3], lmin=[0]),                   # lmin < 1
+        dict(cu=[0, 100], ncp=[-1]),
+        dict(cu=[1, 100], ncp=[3]),                             # cu[0] != 0
+        dict(cu=[0, 100, 90], ncp=[3, 3], vmax=(1.0, 1.0)),     # negative length
+        dict(cu=[0, 100], ncp=[3], mode=7),
+        dict(cu=[0, 100], ncp=[3], inp=5),
+        dict(cu=[0, 100], ncp=[3], d=0),
+    ]
+    for kw in bad:
+        assert _segment(lib, **kw) == vsa._lib.VS_ERR_INVALID, kw
+        assert lib.vs_last_error(), kw
+    assert _segment(lib, cu=[0, 100], ncp=[3], ws=16) == vsa._lib.VS_ERR_WORKSPACE
+    assert b"workspace" in lib.vs_last_error()
+    cu = _arr([0, 100], C.c_int32)
+    assert lib.vs_kts_workspace_bytes(cu, 1, 512, 0, _arr([150], C.c_int32), 2) == 0
+    assert lib.vs_kts_scatters(C.c_void_p(16), 0, 512, 0, C.c_void_p(16), C.c_void_p(16), 1 << 20, None) == vsa._lib.VS_ERR_INVALID
+
+
+def test_workspace_query_counts_the_prefix_table_and_the_pointer_table(vsa):
+    lib = vsa._lib.load()
+    n, m = 10000, 100
+    cu, ncp = _arr([0, n], C.c_int32), _arr([m], C.c_int32)
+    auto = lib.vs_kts_workspace_bytes(cu, 1, 1024, 0, ncp, 2)
+    scores_only = lib.vs_kts_workspace_bytes(cu, 1, 1024, 0, ncp, 0)
+    kernel_in = lib.vs_kts_workspace_bytes(cu, 1, 0, 2, ncp, 0)
+    assert (n + 1) ** 2 * 8 <= kernel_in < (n + 1) ** 2 * 8 * 1.05           # ~800 MB: the reference's quoted size
+    assert auto - scores_only >= (m + 1) * (n + 1) * 4
+    assert scores_only - kernel_in >= n * n * 4                              # the fp32 Gram
+
+
+def test_python_surface_needs_a_gpu_for_kts_and_validates_like_the_reference(vsa, monkeypatch):
+    seg = vsa.segmentation
+    with pytest.raises(NotImplementedError):
+        seg.kts_seg(np.zeros((10, 8), np.float32), 2, 1.0, kernel="rbf")
+    monkeypatch.setattr(seg.torch.cuda, "is_available", lambda: False)
+    with pytest.raises(RuntimeError, match="HIP kernels only"):
+        seg.kts_seg(np.ones((10, 8), np.float32), 2, 1.0)
+    with pytest.raises(RuntimeError, match="HIP kernels only"):
+        seg.cpd_nonlin(np.eye(10), 2, verbose=False)
+
+
+def test_uniform_seg_and_get_segment_fn(vsa):
+    seg = vsa.segmentation
+    np.testing.assert_array_equal(seg.uniform_seg(200), np.arange(0, 200, 4))
+    np.testing.assert_array_equal(seg.uniform_seg(31, sec_per_seg=3, fps=5), [0, 15, 30])
+    assert seg.get_segment_fn() is seg.uniform_seg
+    assert seg.get_segment_fn("uniform") is seg.uniform_seg
+    assert seg.get_segment_fn("kts") is seg.kts_seg
+    assert vsa.get_segment_fn("kts") is seg.kts_seg
+    with pytest.raises(NotImplementedError):
+        seg.get_segment_fn("shot")
+
+
+def test_shots_from_change_points_builds_the_eval_corpus_format(vsa):
+    seg = vsa.segmentation
+    nf = 15 * 40
+    picks = np.arange(0, nf, 15)
+    shots = seg.shots_from_change_points(np.array([4, 10, 31]), nf, picks)
+    np.testing.assert_array_equal(shots, [[0, 59], [60, 149], [150, 464], [465, 599]])
+    assert shots.dtype == np.int32
+    # the layout tools/eval_corpus.py builds: starts [0, cuts], ends [cuts - 1, nf - 1]
+    cuts = picks[[4, 10, 31]]
+    ref = np.stack([np.concatenate([[0], cuts]), np.concatenate([cuts - 1, [nf - 1]])], axis=1)
+    np.testing.assert_array_equal(shots, ref)
+    np.testing.assert_array_equal(seg.shots_from_change_points([], nf, picks), [[0, nf - 1]])
+    np.testing.assert_array_equal(seg.shots_from_change_points([0, 4, 4], nf, picks), [[0, 59], [60, nf - 1]])
+    # consumed as is by the keyshot evaluation
+    ev = __import__("importlib").import_module("video-summarization_amd.evaluation")
+    scores = np.linspace(0, 1, len(picks)).astype(np.float32)
+    s = ev.generate_summary([shots], [scores], [nf], [picks])[0]
+    assert s.shape == (nf,) and 0 < s.sum() <= int(nf * 0.15)

@@ -8,5 +8,8 @@ from . import _lib, synth  # noqa: F401
 from .simnet import SimNet, score_frames  # noqa: F401
 from .pretrain import PretrainModel  # noqa: F401
 from .losses import mse_with_mask_loss  # noqa: F401
+from . import segmentation  # noqa: F401
+from .segmentation import get_segment_fn, kts_seg, kts_seg_batch  # noqa: F401
 
-__all__ = ["SimNet", "PretrainModel", "score_frames", "synth", "mse_with_mask_loss"]
+__all__ = ["SimNet", "PretrainModel", "score_frames", "synth", "mse_with_mask_loss", "segmentation", "get_segment_fn", "kts_seg",
+           "kts_seg_batch"]

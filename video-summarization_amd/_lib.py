@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(HERE, "libvsscore.so")
 DIAG_LIB_PATH = os.path.join(HERE, "libvsscore_diag.so")
 SOURCES = ("vs_kernels.hip", "vs_attention.hip", "vs_attention_w64.hip", "vs_mlp_fused.hip", "vs_gemm_ring.hip", "vs_scorer.cpp", "vs_eval.cpp",
            "vs_train_kernels.hip", "vs_train_attention.hip", "vs_train_attention_bf16.hip", "vs_train_gemm_rows.hip", "vs_pretrain_kernels.hip",
-           "vs_train.cpp")
+           "vs_train.cpp", "vs_segment.hip", "vs_segment.cpp")
 ABI_VERSION = 3
 
 VS_OK, VS_ERR_INVALID, VS_ERR_WORKSPACE, VS_ERR_HIP = 0, 1, 2, 3
@@ -53,6 +53,10 @@ TRAIN_EXPORTS = ("vs_train_prepare", "vs_train_saved_bytes", "vs_train_workspace
                  "vs_train_dropout_mask_attention", "vs_train_dropout_mask_rows", "vs_train_dropout_site", "vs_train_saved_field", "vs_train_last_format",
                  "vs_pretrain_head_state_bytes", "vs_pretrain_head_workspace_bytes", "vs_pretrain_head_forward",
                  "vs_pretrain_head_backward")
+# include/vs_segment.h (kernel temporal segmentation)
+SEGMENT_EXPORTS = ("vs_kts_workspace_bytes", "vs_kts_segment", "vs_kts_scatters")
+VS_KTS_FEATURES_F32, VS_KTS_KERNEL_F32, VS_KTS_KERNEL_F64 = 0, 1, 2
+VS_KTS_SCORES, VS_KTS_BACKTRACK, VS_KTS_AUTO = 0, 1, 2
 NUM_STAGES = 6
 
 
@@ -125,7 +129,7 @@ def _build(out_path: str, extra, verbose: bool) -> str:
     # -fno-slp-vectorize: packed f32 VALU (v_pk_mul/add_f32) beside MFMAs costs more than the scalar
     # forms it replaces (MI355X_MICROARCH.md, cycle constants); keep elementwise epilogue/softmax ops scalar
     tmp = out_path + ".tmp.%d" % os.getpid()
-    objs = [tmp + "." + os.path.splitext(src)[0] + ".o" for src in SOURCES]
+    objs = [tmp + "." + src.replace(".", "_") + ".o" for src in SOURCES]     # vs_segment.hip / .cpp: distinct objects
 
     def compile_one(pair):
         src, obj = pair
@@ -174,7 +178,7 @@ def load() -> C.CDLL:
                 "Run `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). "
                 "There is no PyTorch/CPU fallback for the scoring path." % path)
         lib = C.CDLL(path)
-        for name in EXPORTS + EVAL_EXPORTS + TRAIN_EXPORTS:
+        for name in EXPORTS + EVAL_EXPORTS + TRAIN_EXPORTS + SEGMENT_EXPORTS:
             if not hasattr(lib, name):
                 raise RuntimeError("libvsscore.so lacks symbol %s (stale build?)" % name)
         lib.vs_abi_version.restype = C.c_int
@@ -323,6 +327,15 @@ def load() -> C.CDLL:
                                              C.POINTER(C.c_size_t)]
         lib.vs_train_dropout_site.restype = C.c_uint32
         lib.vs_train_dropout_site.argtypes = [C.c_int32, C.c_int32]
+        # include/vs_segment.h
+        lib.vs_kts_workspace_bytes.restype = C.c_size_t
+        lib.vs_kts_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+        lib.vs_kts_segment.restype = C.c_int
+        lib.vs_kts_segment.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
+                                       + [C.c_int32] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p])
+        lib.vs_kts_scatters.restype = C.c_int
+        lib.vs_kts_scatters.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]
         lib.vs_profile_enable.restype = C.c_int
         lib.vs_profile_enable.argtypes = [C.c_int32]
         lib.vs_profile_collect.restype = C.c_int

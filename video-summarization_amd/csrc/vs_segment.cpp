@@ -1,0 +1,250 @@
+// C ABI of kernel temporal segmentation (include/vs_segment.h): argument checks, the workspace plan, the stage order,
+// and the host end of the model selection (penalty and argmin in double, the reference's expression order).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "vs_kernels.h"
+#include "vs_scorer.h"
+#include "vs_segment.h"
+#include "vs_segment_kernels.h"
+
+int vs_fail_msg(int code, const char *msg);     // vs_scorer.cpp: sets the thread-local error text
+
+namespace {
+
+int fail(int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return vs_fail_msg(code, buf);
+}
+
+#define KTS_HIP(call)                                                                              \
+    do {                                                                                           \
+        const hipError_t e_ = (call);                                                              \
+        if (e_ != hipSuccess) return fail(VS_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));     \
+    } while (0)
+
+#define KTS_LAUNCH(call)                                                                           \
+    do {                                                                                           \
+        const int e_ = (call);                                                                     \
+        if (e_ > 0) return fail(VS_ERR_HIP, "%s: %s", #call, hipGetErrorString((hipError_t)e_));   \
+        if (e_ < 0) return fail(VS_ERR_INVALID, "%s: unsupported shape", #call);                   \
+    } while (0)
+
+constexpr int32_t kMaxFrames = 1 << 16;          // (n + 1)^2 doubles of W stay addressable with 32-bit row indices
+constexpr int32_t kDefaultLmax = 100000;         // the reference's cpd_nonlin default
+
+int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
+int32_t round32(int32_t v) { return (v + 31) / 32 * 32; }
+
+struct Plan {
+    std::vector<KtsVideo> vids;
+    int64_t vids_off = 0, bias_off = 0, xpad_off = 0, total = 0;
+    int32_t n_max = 0, m_max = 0, d_pad = 0;
+};
+
+// Checks everything that needs no GPU and lays out the workspace.  Returns VS_OK or VS_ERR_INVALID (message set).
+int make_plan(const int32_t *cu, int32_t batch, int32_t d, int32_t input, const int32_t *ncp, const int32_t *lmin,
+              const int32_t *lmax, int32_t mode, Plan &P) {
+    if (!cu || !ncp) return fail(VS_ERR_INVALID, "cu / ncp is NULL");
+    if (batch <= 0) return fail(VS_ERR_INVALID, "batch=%d must be positive", batch);
+    if (input != VS_KTS_FEATURES_F32 && input != VS_KTS_KERNEL_F32 && input != VS_KTS_KERNEL_F64)
+        return fail(VS_ERR_INVALID, "input=%d is not a VS_KTS_* input kind", input);
+    if (mode != VS_KTS_SCORES && mode != VS_KTS_BACKTRACK && mode != VS_KTS_AUTO)
+        return fail(VS_ERR_INVALID, "mode=%d is not a VS_KTS_* mode", mode);
+    const bool feats = input == VS_KTS_FEATURES_F32;
+    if (feats && d <= 0) return fail(VS_ERR_INVALID, "d=%d must be positive for features", d);
+    if (cu[0] != 0) return fail(VS_ERR_INVALID, "cu[0]=%d must be 0", cu[0]);
+    P.vids.assign(batch, KtsVideo{});
+    P.d_pad = feats ? round32(d) : 0;
+    int64_t off = align256((int64_t)batch * (int64_t)sizeof(KtsVideo));
+    int64_t k_in = 0;                                    // byte offset of each video's K in the caller's buffer
+    const int64_t esz = input == VS_KTS_KERNEL_F64 ? 8 : 4;
+    for (int32_t b = 0; b < batch; ++b) {
+        const int32_t n = cu[b + 1] - cu[b];
+        const int32_t m = ncp[b];
+        const int32_t lo = lmin ? lmin[b] : 1, hi = lmax ? lmax[b] : kDefaultLmax;
+        if (n <= 0 || n > kMaxFrames) return fail(VS_ERR_INVALID, "video %d: n=%d frames outside [1, %d]", b, n, kMaxFrames);
+        if (m < 0) return fail(VS_ERR_INVALID, "video %d: ncp=%d must be >= 0", b, m);
+        if (!(hi >= lo && lo >= 1)) return fail(VS_ERR_INVALID, "video %d: needs lmax >= lmin >= 1 (lmin=%d lmax=%d)", b, lo, hi);
+        if ((int64_t)n < (int64_t)(m + 1) * lo)
+            return fail(VS_ERR_INVALID, "video %d: needs n >= (ncp + 1) * lmin (n=%d ncp=%d lmin=%d)", b, n, m, lo);
+        if ((int64_t)n > (int64_t)(m + 1) * hi)
+            return fail(VS_ERR_INVALID, "video %d: needs n <= (ncp + 1) * lmax (n=%d ncp=%d lmax=%d)", b, n, m, hi);
+        KtsVideo &V = P.vids[b];
+        V.n = n; V.m = m; V.lmin = lo; V.lmax = hi; V.mbest = m;
+        const int64_t ld = n + 1;
+        if (feats) {
+            V.ldk = round32(n);
+        } else {
+            V.ldk = n;
+            V.k_off = k_in;
+            k_in += (int64_t)n * n * esz;
+        }
+        if (n > P.n_max) P.n_max = n;
+        if (m > P.m_max) P.m_max = m;
+        V.w_off = off; off = align256(off + ld * ld * 8);
+        V.t_off = off; off = align256(off + (int64_t)((n + KTS_CHUNK - 1) / KTS_CHUNK) * ld * 8);
+        V.k1_off = off; off = align256(off + ld * 8);
+        V.i_off = off; off = align256(off + 2 * ld * 8);
+        if (mode != VS_KTS_SCORES) { V.p_off = off; off = align256(off + (int64_t)(m + 1) * ld * 4); }
+        else V.p_off = -1;
+    }
+    for (int32_t b = 0; b < batch; ++b) {            // scores and change points contiguous: one copy each to the host
+        P.vids[b].s_off = off;
+        off += (int64_t)(P.vids[b].m + 1) * 8;
+    }
+    off = align256(off);
+    for (int32_t b = 0; b < batch; ++b) {
+        P.vids[b].c_off = off;
+        off += (int64_t)P.vids[b].m * 4;
+    }
+    off = align256(off + 4);
+    if (feats) {                                     // Gram: zero bias, one padded copy of X (reused per video), K
+        P.bias_off = off; off = align256(off + (int64_t)round32(P.n_max) * 4);
+        P.xpad_off = off; off = align256(off + (int64_t)round32(P.n_max) * P.d_pad * 4);
+        for (int32_t b = 0; b < batch; ++b) {
+            P.vids[b].k_off = off;
+            off = align256(off + (int64_t)P.vids[b].n * P.vids[b].ldk * 4);
+        }
+    }
+    P.total = off;
+    return VS_OK;
+}
+
+// the Gram K_b = X_b X_b^T of every video on the exact-fp32 GEMM: X_b copied into a zero-padded [round32(n)][round32(d)]
+// buffer (zero rows / columns add nothing), C = Xpad[:n] Xpad^T with a zero bias, row stride round32(n)
+int gram(const float *x, int32_t d, const int32_t *cu, const Plan &P, char *ws, hipStream_t st) {
+    float *bias = (float *)(ws + P.bias_off), *xpad = (float *)(ws + P.xpad_off);
+    KTS_HIP(hipMemsetAsync(bias, 0, (size_t)round32(P.n_max) * 4, st));
+    for (size_t b = 0; b < P.vids.size(); ++b) {
+        const KtsVideo &V = P.vids[b];
+        const int32_t npad = V.ldk;
+        if (d != P.d_pad) KTS_HIP(hipMemsetAsync(xpad, 0, (size_t)npad * P.d_pad * 4, st));
+        else if (npad > V.n) KTS_HIP(hipMemsetAsync(xpad + (size_t)V.n * P.d_pad, 0, (size_t)(npad - V.n) * P.d_pad * 4, st));
+        KTS_HIP(hipMemcpy2DAsync(xpad, (size_t)P.d_pad * 4, x + (size_t)cu[b] * d, (size_t)d * 4, (size_t)d * 4, V.n,
+                                 hipMemcpyDeviceToDevice, st));
+        KTS_LAUNCH(vsk_linear(xpad, xpad, nullptr, bias, (float *)(ws + V.k_off), V.n, npad, P.d_pad, 0, nullptr, 1, 0, st));
+    }
+    return VS_OK;
+}
+
+int upload(const Plan &P, char *ws, hipStream_t st) {
+    KTS_HIP(hipMemcpyAsync(ws, P.vids.data(), P.vids.size() * sizeof(KtsVideo), hipMemcpyHostToDevice, st));
+    return VS_OK;
+}
+
+// K (computed or the caller's) -> scatter table
+int table(const void *x, int32_t input, int32_t d, const int32_t *cu, const Plan &P, char *ws, hipStream_t st) {
+    const int B = (int)P.vids.size();
+    if (int rc = upload(P, ws, st)) return rc;
+    const KtsVideo *dv = (const KtsVideo *)ws;
+    if (input == VS_KTS_FEATURES_F32) {
+        if (int rc = gram((const float *)x, d, cu, P, ws, st)) return rc;
+        KTS_LAUNCH(vsk_kts_scatter_table(dv, B, P.n_max, ws, ws, 0, st));
+    } else {
+        KTS_LAUNCH(vsk_kts_scatter_table(dv, B, P.n_max, ws, x, input == VS_KTS_KERNEL_F64, st));
+    }
+    return VS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t vs_kts_workspace_bytes(const int32_t *cu, int32_t batch, int32_t d, int32_t input, const int32_t *ncp, int32_t mode) {
+    Plan P;
+    if (make_plan(cu, batch, d, input, ncp, nullptr, nullptr, mode, P) != VS_OK) return 0;
+    return (size_t)P.total;
+}
+
+int vs_kts_segment(const void *x, int32_t input, int32_t d, const int32_t *cu, int32_t batch, const int32_t *ncp,
+                   const int32_t *lmin, const int32_t *lmax, const double *vmax, const double *desc_rate, int32_t mode,
+                   int64_t *cps, int32_t *n_cps, double *scores, void *workspace, size_t workspace_bytes, void *stream) {
+    Plan P;
+    if (int rc = make_plan(cu, batch, d, input, ncp, lmin, lmax, mode, P)) return rc;
+    if (!x || !cps || !n_cps || !scores) return fail(VS_ERR_INVALID, "x / cps / n_cps / scores is NULL");
+    if (mode == VS_KTS_AUTO) {
+        if (!vmax) return fail(VS_ERR_INVALID, "vmax is NULL (needed by VS_KTS_AUTO)");
+        for (int32_t b = 0; b < batch; ++b)
+            if (desc_rate && !(desc_rate[b] > 0)) return fail(VS_ERR_INVALID, "video %d: desc_rate=%g must be > 0", b, desc_rate[b]);
+    }
+    if (!workspace || workspace_bytes < (size_t)P.total)
+        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    if (int rc = table(x, input, d, cu, P, ws, st)) return rc;
+    const KtsVideo *dv = (const KtsVideo *)ws;
+    KTS_LAUNCH(vsk_kts_dp_init(dv, batch, P.n_max, ws, st));
+    for (int32_t k = 1; k <= P.m_max; ++k) KTS_LAUNCH(vsk_kts_dp_step(dv, batch, P.n_max, k, ws, st));
+
+    int64_t n_scores = 0, n_total_cps = 0;
+    for (const KtsVideo &V : P.vids) { n_scores += V.m + 1; n_total_cps += V.m; }
+    KTS_HIP(hipMemcpyAsync(scores, ws + P.vids[0].s_off, (size_t)n_scores * 8, hipMemcpyDeviceToHost, st));
+    KTS_HIP(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < n_scores; ++i)
+        if (scores[i] > 1e99) scores[i] = INFINITY;           // scores[scores > 1e99] = np.inf
+
+    if (mode == VS_KTS_AUTO) {                               // cpd_auto.py: penalty, costs, first argmin
+        double *s = scores;
+        for (int32_t b = 0; b < batch; ++b) {
+            KtsVideo &V = P.vids[b];
+            const double N = (double)V.n, N2 = N * (desc_rate ? desc_rate[b] : 1.0);
+            int32_t best = 0;
+            for (int32_t c = 0; c <= V.m; ++c) {
+                const double pen = c == 0 ? 0.0 : (vmax[b] * (double)c / (2.0 * N2)) * (std::log(N2 / (double)c) + 1.0);
+                s[c] = s[c] / N + pen;
+                if (s[c] < s[best]) best = c;
+            }
+            if ((int64_t)V.n > (int64_t)(best + 1) * V.lmax)
+                return fail(VS_ERR_INVALID, "video %d: needs n <= (m_best + 1) * lmax (n=%d m_best=%d lmax=%d)", b, V.n, best,
+                            V.lmax);
+            V.mbest = best;
+            s += V.m + 1;
+        }
+    }
+    int64_t c_at = 0;
+    if (mode == VS_KTS_SCORES) {
+        for (int32_t b = 0; b < batch; ++b) n_cps[b] = P.vids[b].m;
+        std::memset(cps, 0, (size_t)n_total_cps * sizeof(int64_t));
+        return VS_OK;
+    }
+    if (int rc = upload(P, ws, st)) return rc;               // m_best
+    KTS_LAUNCH(vsk_kts_backtrack(dv, batch, ws, st));
+    std::vector<int32_t> c32((size_t)n_total_cps + 1);
+    KTS_HIP(hipMemcpyAsync(c32.data(), ws + P.vids[0].c_off, (size_t)n_total_cps * 4, hipMemcpyDeviceToHost, st));
+    KTS_HIP(hipStreamSynchronize(st));
+    for (int32_t b = 0; b < batch; ++b) {
+        const KtsVideo &V = P.vids[b];
+        n_cps[b] = V.mbest;
+        for (int32_t i = 0; i < V.m; ++i) cps[c_at + i] = i < V.mbest ? (int64_t)c32[c_at + i] : 0;
+        c_at += V.m;
+    }
+    return VS_OK;
+}
+
+int vs_kts_scatters(const void *x, int32_t input, int32_t d, int32_t n, double *scatters, void *workspace,
+                    size_t workspace_bytes, void *stream) {
+    const int32_t cu[2] = {0, n}, zero = 0;
+    Plan P;
+    if (int rc = make_plan(cu, 1, d, input, &zero, nullptr, nullptr, VS_KTS_SCORES, P)) return rc;
+    if (!x || !scatters) return fail(VS_ERR_INVALID, "x / scatters is NULL");
+    if (!workspace || workspace_bytes < (size_t)P.total)
+        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    if (int rc = table(x, input, d, cu, P, ws, st)) return rc;
+    KTS_LAUNCH(vsk_kts_scatters_out((const KtsVideo *)ws, n, ws, scatters, st));
+    KTS_HIP(hipStreamSynchronize(st));                        // the plan's host copy of the descriptors ends here
+    return VS_OK;
+}
+
+}  // extern "C"
