@@ -1757,11 +1757,12 @@ def test_scoring_forward_is_stream_capturable(vsa):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("tool,seconds,seed", [("fuzz_attn_w64.py", 20, 5), ("fuzz_attention.py", 25, 6), ("fuzz_linear.py", 15, 7)])
+@pytest.mark.parametrize("tool,seconds,seed", [("fuzz_attn_w64.py", 20, 5), ("fuzz_attention.py", 25, 6), ("fuzz_linear.py", 15, 7),
+                                               ("fuzz_train.py", 20, 8)])
 def test_kernel_soak_slices(vsa, tool, seconds, seed):
     """Fixed-seed slices of the round-4 kernel soaks (tools/): the one-wave-per-SIMD attention with late dominant keys and key
-    masks, every attention entry point x head dims, the Linear / Linear + LayerNorm entry points over random shapes - each
-    against float64.  The soaks found two real bugs in round 4; the full runs are in profiles/."""
+    masks, every attention entry point x head dims, the Linear / Linear + LayerNorm entry points over random shapes, whole
+    training steps (both GEMM families) - each against float64.  The soaks found two real bugs in round 4; the full runs are in profiles/."""
     import importlib.util
     import os as _os
     path = _os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))), "tools", tool)

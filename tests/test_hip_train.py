@@ -58,6 +58,16 @@ def _inputs(synth, c):
     return x, mask, target, R
 
 
+@pytest.fixture
+def tiled_gemms(vsa):
+    """These batches take the skinny latency GEMMs by default; VS_SKINNY_ROWS=0 pins the LDS-tiled persistent GEMMs, so the
+    training-only epilogues they carry (fc1 + ReLU + dropout, the gated fc2 dgrad, the dgrads adding the residual gradient)
+    are held to the same float64 vectors at every model width.  The *_on_tiled_gemms tests rerun a test under the pin."""
+    vsa._lib.set_option("VS_SKINNY_ROWS", 0)
+    yield
+    vsa._lib.set_option("VS_SKINNY_ROWS", -1)
+
+
 # ---------------------------------------------------------------------------------------------
 # whole model: gradients against the imported reference (float64)
 # ---------------------------------------------------------------------------------------------
@@ -106,6 +116,11 @@ def test_gradients_match_reference_golden(vsa, case):
         assert abs(g.double().norm().item() - nrm) <= 1e-4 * nrm + 1e-7, k
         worst = max(worst, err / (gmax + 1e-12) if gmax > 1e-6 else 0.0)
     print("%s: worst gradient error relative to the tensor's max: %.2e" % (c["name"], worst))
+
+
+@pytest.mark.parametrize("case", train_cases(), ids=lambda c: c["name"])
+def test_gradients_match_reference_golden_on_tiled_gemms(vsa, case, tiled_gemms):
+    test_gradients_match_reference_golden(vsa, case)
 
 
 def test_train_mode_without_dropout_equals_the_scoring_path(vsa):
@@ -787,8 +802,10 @@ def _library_masks(vsa, B, T, d, H, L, seed, p, p_embed):
     return masks
 
 
-@pytest.mark.parametrize("H,d,L,B,T,p,p_embed,masked", [(4, 256, 2, 2, 90, 0.3, 0.0, True), (8, 256, 1, 1, 130, 0.2, 0.5, False),
-                                                        (4, 512, 1, 2, 70, 0.3, 0.0, True)])
+DROPOUT_STEPS = [(4, 256, 2, 2, 90, 0.3, 0.0, True), (8, 256, 1, 1, 130, 0.2, 0.5, False), (4, 512, 1, 2, 70, 0.3, 0.0, True)]
+
+
+@pytest.mark.parametrize("H,d,L,B,T,p,p_embed,masked", DROPOUT_STEPS)
 def test_training_step_with_dropout_matches_explicit_mask_model(vsa, H, d, L, B, T, p, p_embed, masked):
     synth = vsa.synth
     sd = synth.make_state_dict(d, L, 21)
@@ -829,6 +846,11 @@ def test_training_step_with_dropout_matches_explicit_mask_model(vsa, H, d, L, B,
     with torch.no_grad():
         e, _ = m.eval()(x.to(_dev()), md)
     assert (e - pred.detach())[valid.to(_dev())].abs().max().item() > 1e-3
+
+
+@pytest.mark.parametrize("H,d,L,B,T,p,p_embed,masked", DROPOUT_STEPS)
+def test_training_step_with_dropout_on_tiled_gemms(vsa, H, d, L, B, T, p, p_embed, masked, tiled_gemms):
+    test_training_step_with_dropout_matches_explicit_mask_model(vsa, H, d, L, B, T, p, p_embed, masked)
 
 
 def test_train_loop_like_the_reference(vsa):
@@ -884,6 +906,38 @@ def test_mse_with_mask_loss_matches_reference_formula(vsa):
         (got * 3.0).backward()
         assert abs(got.item() - want.item()) < 1e-6 * max(1.0, want.item())
         assert (od.grad.cpu().double() - 3.0 * o64.grad).abs().max().item() < 1e-6
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 65535, 65536, 65537, 3 * 65536 + 5])
+def test_mse_with_mask_loss_kernels_match_float64_at_every_grid_size(vsa, n):
+    """The masked-MSE kernels against float64 on both sides of their grid limits: one block per 256 elements up to 256
+    blocks (vst_mse_mask_blocks), above 65 536 elements every thread strides.  Random masks, a fully masked input (loss
+    and gradient exactly 0), an upstream gradient other than 1; the forward's reduction order is fixed (bitwise repeat)."""
+    g = torch.Generator().manual_seed(n)
+    out = torch.randn(1, n, 1, generator=g)
+    tgt = torch.rand(1, n, generator=g)
+    masks = {"random": torch.rand(1, n, generator=g) < 0.3, "none": torch.zeros(1, n, dtype=torch.bool),
+             "all": torch.ones(1, n, dtype=torch.bool)}
+    gout = 0.37                          # upstream gradient; |d_out| stays below ~4, where fp32 rounding is far under 1e-6
+    for kind, mask in masks.items():
+        for reduction in ("avg", "sum"):
+            o64 = out.double().clone().requires_grad_(True)
+            sc = (~mask).double()
+            want = (o64.squeeze(2) * sc - tgt.double() * sc) ** 2
+            want = want.mean() if reduction == "avg" else want.sum()
+            (want * float(torch.tensor(gout, dtype=torch.float32))).backward()
+            od = out.to(_dev()).requires_grad_(True)
+            got = vsa.mse_with_mask_loss(od, tgt.to(_dev()), mask.to(_dev()), reduction)
+            again = vsa.mse_with_mask_loss(od.detach(), tgt.to(_dev()), mask.to(_dev()), reduction)
+            (got * gout).backward()
+            torch.cuda.synchronize()
+            tag = "n=%d mask=%s %s" % (n, kind, reduction)
+            assert torch.equal(got.detach(), again), tag
+            if kind == "all":
+                assert got.item() == 0.0 and not od.grad.any().item(), tag
+                continue
+            assert abs(got.item() - want.item()) < 1e-6 * max(1.0, want.item()), "%s: %.9g vs %.9g" % (tag, got.item(), want.item())
+            assert (od.grad.cpu().double() - o64.grad).abs().max().item() < 1e-6, tag
 
 
 def test_embedded_shape_trains_like_a_native_one(vsa):

@@ -86,9 +86,20 @@ def _head_reference(hidden, logits, vid, mask, W, b, temp, pen):
     return loss, center, repel
 
 
+HEAD_SHAPES = [(3, 150, 256, "entropy", True), (2, 64, 128, "norm", True), (1, 333, 512, "entropy", False), (4, 65, 256, "norm", False)]
+
+
+@pytest.fixture
+def tiled_gemms(vsa):
+    """VS_SKINNY_ROWS=0 pins the LDS-tiled GEMMs (video_transform's forward, dgrad and wgrad) that batches above the
+    skinny threshold take; these small batches get the latency kernels by default."""
+    vsa._lib.set_option("VS_SKINNY_ROWS", 0)
+    yield
+    vsa._lib.set_option("VS_SKINNY_ROWS", -1)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,T,d,pen,masked", [(3, 150, 256, "entropy", True), (2, 64, 128, "norm", True), (1, 333, 512, "entropy", False),
-                                              (4, 65, 256, "norm", False)])
+@pytest.mark.parametrize("B,T,d,pen,masked", HEAD_SHAPES)
 def test_pretrain_head_kernels_match_float64_formulas(vsa, B, T, d, pen, masked):
     """_PretrainHead (video_transform + repel + pooling + penalties + soft CE, forward and backward kernels) against
     the reference's formulas in float64, for a weighted sum of the three losses (pretrain.py:62)."""
@@ -118,6 +129,12 @@ def test_pretrain_head_kernels_match_float64_formulas(vsa, B, T, d, pen, masked)
         err = (a.grad.double().cpu() - r.grad).abs().max().item()
         scale = r.grad.abs().max().item()
         assert err <= 2e-5 * scale + 1e-9, "%s: err %.3e, max %.3e" % (name, err, scale)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,T,d,pen,masked", HEAD_SHAPES)
+def test_pretrain_head_kernels_on_tiled_gemms(vsa, B, T, d, pen, masked, tiled_gemms):
+    test_pretrain_head_kernels_match_float64_formulas(vsa, B, T, d, pen, masked)
 
 
 @pytest.mark.gpu
