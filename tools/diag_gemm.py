@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Diagnostic: where does a k-tile iteration of the persistent projection GEMM spend its cycles?
 Runs the fc1-shaped GEMM (M=65536, N=1024, K=256) in the stamped DIAG build and prints the shares.
-Never part of a product run; see cdna guide §7 'In-kernel stamps'."""
+Never part of a product run; see cdna guide §7 'In-kernel stamps'.
+
+    diag_gemm.py [M N K]            the 4-wave / 128-column forms (VS_DIAG_MODE, VS_DIAG_NWM, VS_DIAG_PREC)
+    diag_gemm.py M N K kloop        the headline exact-fp32 form gemm_nt_128<*, 4, *, 4> (256x256 tiles, 8 waves):
+                                    cycles per k-tile, barrier wait per wave, epilogue share
+    diag_gemm.py M 256 K kloop-ln   the same stamps in gemm_ln_rows<8, 0> (out-projection / fc2 + LayerNorm)"""
 import ctypes as C
 import importlib
 import os
@@ -82,5 +87,59 @@ def run(grid, diag):
         print("   start skew across waves: %.0f cycles" % (tb.max() - tb.min()).item())
 
 
+def run_kloop(ln):
+    """Stamped build of a headline instantiation on its product grid, beside the unstamped product kernel."""
+    os.environ["VS_DIAG_MODE"] = "3"
+    if ln:
+        os.environ["VS_DIAG_KERNEL"] = "ln"
+        wpb, mf_tile = 4, 4 * 8 * 4                 # waves per block; MFMAs per wave and 16-wide k-tile: 4 steps x 8 column tiles
+        blocks = min(512, (M + 127) // 128)
+    else:
+        os.environ["VS_DIAG_NJ"] = "4"
+        wpb, mf_tile = 8, 128
+        blocks = min(256, (M + 255) // 256 * (N // 256))
+    call = lambda dp: pkg._lib.check(lib.vs_diag_gemm(A.data_ptr(), W.data_ptr(), b.data_ptr(), Cc.data_ptr(), M, N, K, 0, dp, st))
+    blocks = max(blocks, 1024)                      # head-room: the library sizes the grid from the CU count
+    dbuf = torch.zeros(blocks * wpb * 8, dtype=torch.int64, device=dev)
+    for name, dp in (("product kernel", None), ("stamped build", dbuf.data_ptr())):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(3):
+            call(dp)
+        e0.record()
+        for _ in range(10):
+            call(dp)
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / 10
+        print("%-15s %s M=%d N=%d K=%d: %.4f ms  %.1f TFLOP/s (%.3f of 157.3)" % (
+            name, "gemm_ln_rows<8,0>" if ln else "gemm_nt_128<1,4,*,4>", M, N, K, ms, 2.0 * M * N * K / ms / 1e9, 2.0 * M * N * K / ms / 1e9 / 157.3))
+    d = dbuf.view(blocks * wpb, 8).double().cpu()
+    d = d[d[:, 6] > 0]
+    kt = d[:, 6]
+    issue = 2.0 * 64 * mf_tile                      # cycles of pure MFMA issue per k-tile for the SIMD's two waves
+    per = d[:, 5] / kt
+    bar = d[:, 0] / kt
+    print("   waves %d, k-tiles per wave med %.0f; cycles per k-tile and wave: mean %.0f med %.0f min %.0f max %.0f  (pure MFMA issue of the SIMD's two waves: %.0f -> %.3f)" % (
+        d.shape[0], kt.median().item(), per.mean().item(), per.median().item(), per.min().item(), per.max().item(), issue, issue / per.mean().item()))
+    print("   barrier wait per k-tile and wave: mean %.0f med %.0f min %.0f max %.0f cycles (%.1f %% of the wave's time)" % (
+        bar.mean().item(), bar.median().item(), bar.min().item(), bar.max().item(), 100 * d[:, 0].sum().item() / d[:, 5].sum().item()))
+    w = torch.arange(d.shape[0]) % wpb
+    print("   barrier wait by wave of the block (mean cycles per k-tile): " + "  ".join(
+        "w%d %.0f" % (i, bar[w == i].mean().item()) for i in range(wpb)))
+    half = wpb // 2
+    print("   first-dispatched half %.0f | second half %.0f ; share of waves waiting < 1/4 of the mean: %.2f, > 2x the mean: %.2f" % (
+        bar[w < half].mean().item(), bar[w >= half].mean().item(), (bar < bar.mean() / 4).double().mean().item(), (bar > 2 * bar.mean()).double().mean().item()))
+    hist = torch.histc(bar, bins=10, min=0, max=bar.max().item())
+    print("   histogram of per-wave barrier wait (0..%.0f cycles per k-tile): %s" % (bar.max().item(), [int(x) for x in hist.tolist()]))
+    print("   epilogue%s: %.1f %% of the wave's time (%.0f cycles per output tile)" % (
+        " (LayerNorm + stores)" if ln else "", 100 * d[:, 1].sum().item() / d[:, 5].sum().item(), (d[:, 1] * (K // (16 if ln else 32)) / kt).mean().item()))
+    if ln:
+        print("   tile prologue (C-in and first k-tile loads, 2 barriers): %.1f %% (%.0f cycles per output tile)" % (
+            100 * d[:, 2].sum().item() / d[:, 5].sum().item(), (d[:, 2] * (K // 16) / kt).mean().item()))
+
+
+if len(sys.argv) > 4 and sys.argv[4].startswith("kloop"):
+    run_kloop(sys.argv[4] == "kloop-ln")
+    sys.exit(0)
 for grid in ((256,) if os.environ.get('VS_DIAG_NWM') == '4' else (512, 256)):
     run(grid, True)

@@ -102,9 +102,16 @@ __global__ __launch_bounds__(128 * NWM, 2) void gemm_nt_128(
     const int lrow = tid / F4R, lc4 = (tid % F4R) * 4;   // staging map: rows lrow + RS*i
     const int nk = K / BK;
 
-    // Per-output-tile state, set up ONCE per tile (integer division, 64-bit row pointers, this lane's
+    // Per-output-tile state, set up ONCE per tile (integer division, row addresses, this lane's
     // bias values).  `nx_*` belongs to the tile being prefetched, `cu_*` to the tile being accumulated.
     const float *aptr[LA], *wptr[LW];
+    // PREC 0: no per-row 64-bit pointers.  The rows of the tile being staged are reached through a buffer descriptor
+    // (scalar registers) that starts at the tile's first row; a staged row is one 32-bit byte offset from it (edge rows
+    // clamped here, once per tile) and the k offset is the instruction's scalar offset - so the k-loop carries LA + LW
+    // address registers instead of 2 (LA + LW) and advances none of them.
+    __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A), 0, 0, 0x00020000);
+    __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(W), 0, 0, 0x00020000);
+    int aoff[LA], woff[LW];
     int nx_m0 = 0, nx_n0 = 0, cu_m0 = 0, cu_n0 = 0;
     float nx_bias[NJ], cu_bias[NJ];
 #pragma unroll
@@ -113,15 +120,31 @@ __global__ __launch_bounds__(128 * NWM, 2) void gemm_nt_128(
         const int tile = start + j + it * G;
         nx_m0 = (tile / tiles_n) * BM;
         nx_n0 = (tile % tiles_n) * BN;
+        if constexpr (PREC == 0) {
+            const int arows = M - nx_m0 < BM ? M - nx_m0 : BM, wrows = N - nx_n0 < BN ? N - nx_n0 : BN;
+            ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A + (size_t)nx_m0 * K), 0, arows * K * 4, 0x00020000);
+            wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(W + (size_t)nx_n0 * K), 0, wrows * K * 4, 0x00020000);
 #pragma unroll
-        for (int i = 0; i < LA; ++i) {
-            int ar = nx_m0 + lrow + RS * i; ar = ar < M ? ar : M - 1;
-            aptr[i] = A16 ? (const float *)((const a16_t *)A + (size_t)ar * K + lc4) : A + (size_t)ar * K + lc4;
-        }
+            for (int i = 0; i < LA; ++i) {
+                int ar = lrow + RS * i; ar = ar < arows ? ar : arows - 1;
+                aoff[i] = (ar * K + lc4) * 4;
+            }
 #pragma unroll
-        for (int i = 0; i < LW; ++i) {
-            int wrow = nx_n0 + lrow + RS * i; wrow = wrow < N ? wrow : N - 1;
-            wptr[i] = W + (size_t)wrow * K + lc4;
+            for (int i = 0; i < LW; ++i) {
+                int wrow = lrow + RS * i; wrow = wrow < wrows ? wrow : wrows - 1;
+                woff[i] = (wrow * K + lc4) * 4;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < LA; ++i) {
+                int ar = nx_m0 + lrow + RS * i; ar = ar < M ? ar : M - 1;
+                aptr[i] = A16 ? (const float *)((const a16_t *)A + (size_t)ar * K + lc4) : A + (size_t)ar * K + lc4;
+            }
+#pragma unroll
+            for (int i = 0; i < LW; ++i) {
+                int wrow = nx_n0 + lrow + RS * i; wrow = wrow < N ? wrow : N - 1;
+                wptr[i] = W + (size_t)wrow * K + lc4;
+            }
         }
 #pragma unroll
         for (int jj = 0; jj < NJ; ++jj) {
@@ -133,11 +156,17 @@ __global__ __launch_bounds__(128 * NWM, 2) void gemm_nt_128(
     f32x4 pa[LA], pw[LW];
     // (A16: a piece is 4 bf16 = the first two dwords of pa[i])
     auto load_a = [&](int i, int koff) __attribute__((always_inline)) {
-        if constexpr (A16 != 0) {
+        if constexpr (PREC == 0)
+            pa[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ars, aoff[i], koff * 4, 0));
+        else if constexpr (A16 != 0) {
             const f32x2 v = *(const f32x2 *)((const a16_t *)aptr[i] + koff);      // 8 bytes, moved as they are
             pa[i][0] = v[0]; pa[i][1] = v[1];
         } else
             pa[i] = *(const f32x4 *)(aptr[i] + koff);
+    };
+    auto load_w = [&](int i, int koff) __attribute__((always_inline)) {
+        if constexpr (PREC == 0) pw[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, woff[i], koff * 4, 0));
+        else pw[i] = *(const f32x4 *)(wptr[i] + koff);
     };
     constexpr int LDB = BK == 64 ? 36 : 20;             // BF: LDS row stride in floats (32 bf16 + pad = 80 B | 64 bf16 + pad = 144 B)
     auto stage = [&](int buf) __attribute__((always_inline)) {
@@ -250,10 +279,17 @@ __global__ __launch_bounds__(128 * NWM, 2) void gemm_nt_128(
         }
         const float *ap = As + (64 * wr + r) * LD + 4 * h;
         const float *wp = Ws + (32 * NJ * wc + r) * LD + 4 * h;
+        // Fragments are double-buffered by 8-k group: the 2 + NJ reads of group g + 1 are PINNED behind the first MFMAs of
+        // group g (one read per MFMA), so every read has the rest of that group's MFMAs of its own wave between issue and
+        // first use.  Left to itself the scheduler sinks them to the end of the group, and a wave that is alone on its SIMD
+        // (its partner waiting at the barrier) then idles the matrix pipe on LDS latency in every group.
+        constexpr int NR = 2 + NJ, MF = 8 * NJ, NV = (LA + LW) / 2, ND = LA + LW;
+        static_assert(NR + NV <= MF && ND <= MF, "a group's MFMAs cover its pinned memory instructions");
         f32x4 fa[2][2], fw[2][NJ];
         fa[0][0] = *(const f32x4 *)(ap);           fa[0][1] = *(const f32x4 *)(ap + 32 * LD);
 #pragma unroll
         for (int jj = 0; jj < NJ; ++jj) fw[0][jj] = *(const f32x4 *)(wp + 32 * jj * LD);
+        __builtin_amdgcn_sched_barrier(0);          // group 0's own fragments first: nothing of group 1 ahead of them
 #pragma unroll
         for (int g = 0; g < BK / 8; ++g) {
             const int c = g & 1, n = c ^ 1;
@@ -264,9 +300,9 @@ __global__ __launch_bounds__(128 * NWM, 2) void gemm_nt_128(
             }
             if (g < 2) {
 #pragma unroll
-                for (int i = 0; i < LA / 2; ++i) pa[g * (LA / 2) + i] = *(const f32x4 *)(aptr[g * (LA / 2) + i] + koff);
+                for (int i = 0; i < LA / 2; ++i) load_a(g * (LA / 2) + i, koff);
 #pragma unroll
-                for (int i = 0; i < LW / 2; ++i) pw[g * (LW / 2) + i] = *(const f32x4 *)(wptr[g * (LW / 2) + i] + koff);
+                for (int i = 0; i < LW / 2; ++i) load_w(g * (LW / 2) + i, koff);
             }
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
@@ -277,22 +313,34 @@ __global__ __launch_bounds__(128 * NWM, 2) void gemm_nt_128(
                 }
             }
             if (g == BK / 8 - 1) stage(fpar ^ 1);
+            if (g + 1 < BK / 8) {
+#pragma unroll
+                for (int q = 0; q < NR; ++q) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                           // 1 MFMA
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                           // 1 DS read of group g + 1
+                }
+            }
             if (g < 2) {
 #pragma unroll
-                for (int q = 0; q < (LA + LW) / 2; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 8 * NJ / ((LA + LW) / 2), 0);   // MFMAs
+                for (int q = 0; q < NV; ++q) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, (MF - NR) / NV, 0);              // MFMAs
                     __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                           // 1 VMEM read
                 }
             } else if (g == BK / 8 - 1) {
 #pragma unroll
-                for (int q = 0; q < LA + LW; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 8 * NJ / (LA + LW), 0);          // MFMAs
+                for (int q = 0; q < ND; ++q) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, MF / ND, 0);                     // MFMAs
                     __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                           // 1 DS write
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        __syncthreads();
+        if constexpr (DIAG != 0) {                  // dsum[0]: cycles this wave waits at the k-tile barriers
+            const unsigned long long tb = stamp();
+            __syncthreads();
+            dsum[0] += stamp() - tb;
+        } else
+            __syncthreads();
         fpar ^= 1;
     };
 
@@ -300,7 +348,7 @@ __global__ __launch_bounds__(128 * NWM, 2) void gemm_nt_128(
 #pragma unroll
     for (int i = 0; i < LA; ++i) load_a(i, 0);
 #pragma unroll
-    for (int i = 0; i < LW; ++i) pw[i] = *(const f32x4 *)wptr[i];
+    for (int i = 0; i < LW; ++i) load_w(i, 0);
     stage(0);
     __syncthreads();
     if (DIAG != 0) ts0 = stamp();
@@ -347,6 +395,8 @@ __global__ __launch_bounds__(128 * NWM, 2) void gemm_nt_128(
         // 8 lanes per row, and every store instruction writes 8 full 128-byte lines.  No block barrier is
         // needed for the transposition itself (one wave, in-order LDS), only one afterwards, before any
         // wave restages that buffer.
+        unsigned long long te = 0;
+        if constexpr (DIAG != 0) te = stamp();      // dsum[1]: cycles from the last k-tile's barrier to the epilogue's
         const int m0 = cu_m0, n0 = cu_n0;
         float *tp = smem + (fpar ^ 1) * (BM + BN) * LD + wave * (32 * LD);     // 32 x 36 floats per wave
         const int trow = lane >> 3, tc4 = (lane & 7) * 4;                       // read-back map: rows trow + 8p
@@ -417,6 +467,7 @@ __global__ __launch_bounds__(128 * NWM, 2) void gemm_nt_128(
             }
         }
         __syncthreads();
+        if constexpr (DIAG != 0) dsum[1] += stamp() - te;
     }
     if (DIAG >= 2) { ts0 = stamp(); dsum[4] = __builtin_amdgcn_s_memrealtime(); }
     if (DIAG != 0 && diag != nullptr && lane == 0) {
@@ -626,13 +677,14 @@ __global__ __launch_bounds__(256) void gemm_res_ln(
 //   Block = 4 waves = 128 rows, BK = 16 (LDS rows padded to 20 floats), 2 blocks per CU.
 // ------------------------------------------------------------------------------------------
 // A16 (PREC 1 only): A lives in HBM as bf16 (written so by the bf16 attention / the C16 fc1 epilogue)
-template <int NT, int PREC = 0, int A16 = 0>     // PREC 1: bf16 MFMA operands (see gemm_nt_128), LDS rows of 16 bf16 padded to 48 B; 2: f16 hi|lo rows (80 B)
+// DIAG (tools/diag_gemm.py only, PREC 0): per-wave stamps - barrier wait, tile prologue, epilogue (layout: gemm_nt_128's)
+template <int NT, int PREC = 0, int A16 = 0, int DIAG = 0>     // PREC 1: bf16 MFMA operands (see gemm_nt_128), LDS rows of 16 bf16 padded to 48 B; 2: f16 hi|lo rows (80 B)
 __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
     const float *__restrict__ A, const float *__restrict__ W, const float *__restrict__ bias,
     const float *__restrict__ res, const float *__restrict__ gamma, const float *__restrict__ beta,
     float *__restrict__ out, int M, int K,
     const float *__restrict__ score_w, const float *__restrict__ score_b, int num_classes,
-    int sigmoid, float *__restrict__ scores) {
+    int sigmoid, float *__restrict__ scores, unsigned long long *__restrict__ diag = nullptr) {
     constexpr int BM = 128, N = 32 * NT, BK = 16, LD = BK + 4;
     constexpr int WL = (N * BK / 4 + 255) / 256;       // float4 of W per thread per k-tile (N=256: 4)
     __shared__ __attribute__((aligned(16))) float smem[2 * (BM + N) * LD + 4 * N];
@@ -657,6 +709,19 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
         int wrow = lrow + 64 * i; wrow = wrow < N ? wrow : N - 1;
         wptr[i] = W + (size_t)wrow * K + lc4;
     }
+    // PREC 0 stages through buffer descriptors (scalar registers) and one 32-bit byte offset per staged row, the k offset
+    // being the load's scalar offset: no 64-bit address arithmetic in the k-loop (gemm_nt_128 does the same).  Its staging
+    // map covers W exactly (N % 64 == 0: WL * 64 rows), so its LDS writes need no guard and the k-loop no branch.
+    static_assert(PREC != 0 || N % 64 == 0, "the exact-fp32 staging map covers W without a guard");
+    __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A), 0, 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(W), 0, N * K * 4, 0x00020000);
+    int aoff[2], woff[WL];
+#pragma unroll
+    for (int i = 0; i < WL; ++i) woff[i] = ((lrow + 64 * i) * K + lc4) * 4;
+    auto gload = [&](int i, int kb) __attribute__((always_inline)) {       // piece i of the k-tile at byte offset kb: A 0..1, then W
+        if (i < 2) pa[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ars, aoff[i], kb, 0));
+        else pw[i - 2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, woff[i - 2], kb, 0));
+    };
     constexpr int LDB = 12;                            // BF: LDS row stride in floats (48 B: conflict-free b128)
     auto stage = [&](int buf) __attribute__((always_inline)) {
         float *As = smem + buf * (BM + N) * LD, *Ws = As + BM * LD;
@@ -695,13 +760,15 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
 #pragma unroll
             for (int i = 0; i < 2; ++i) *(f32x4 *)&As[(lrow + 64 * i) * LD + lc4] = pa[i];
 #pragma unroll
-            for (int i = 0; i < WL; ++i)
-                if (lrow + 64 * i < N) *(f32x4 *)&Ws[(lrow + 64 * i) * LD + lc4] = pw[i];
+            for (int i = 0; i < WL; ++i) *(f32x4 *)&Ws[(lrow + 64 * i) * LD + lc4] = pw[i];
         }
     };
 
     f32x16 acc[NT];
+    unsigned long long dsum[3] = {0, 0, 0}, tbegin = 0, tq = 0, ktiles = 0;
+    if constexpr (DIAG != 0) tbegin = stamp();
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        if constexpr (DIAG != 0) tq = stamp();
         const int m0 = tile * BM;
         int row = m0 + 32 * wave + r;
         const bool row_ok = row < M;
@@ -712,13 +779,21 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
             if constexpr (A16 != 0) {
                 aptr16[i] = (const unsigned short *)A + (size_t)ar * K + lc4;
                 pa16[i] = *(const u32x2 *)aptr16[i];
+            } else if constexpr (PREC == 0) {
+                aoff[i] = ((ar - m0) * K + lc4) * 4;
             } else {
                 aptr[i] = A + (size_t)ar * K + lc4;
                 pa[i] = *(const f32x4 *)aptr[i];
             }
         }
+        if constexpr (PREC == 0) {
+            ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A + (size_t)m0 * K), 0, (M - m0 < BM ? M - m0 : BM) * K * 4, 0x00020000);
 #pragma unroll
-        for (int i = 0; i < WL; ++i) pw[i] = *(const f32x4 *)wptr[i];
+            for (int i = 0; i < 2 + WL; ++i) gload(i, 0);
+        } else {
+#pragma unroll
+            for (int i = 0; i < WL; ++i) pw[i] = *(const f32x4 *)wptr[i];
+        }
         // accumulators start at the residual (C-in of the first MFMA); bias joins in the epilogue from LDS
         {
             const float *rp = res + (size_t)row * N + 4 * h;
@@ -735,6 +810,7 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
         __syncthreads();                 // previous tile's readers are done with both LDS buffers
         stage(0);
         __syncthreads();
+        if constexpr (DIAG != 0) { dsum[2] += stamp() - tq; ktiles += nk; }     // dsum[2]: tile prologue (loads of C-in and of k-tile 0)
 
         for (int kt = 0; kt < nk; ++kt) {
             const int kn = kt + 1 < nk ? kt + 1 : kt;         // last step reloads a duplicate: branch-free stream
@@ -779,43 +855,60 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
                 __syncthreads();
                 continue;
             }
+            // 2 NT steps of 4 MFMAs: step t = (g, j) contracts the 8-k group g into column tile j (a 4-step dependent chain on
+            // acc[j] issues back-to-back: latency == issue interval for 32x32x2).  The weight fragments go through a ring of
+            // three: the read of step t + 2 is PINNED behind the first MFMA of step t, so a fragment has 7 MFMAs of its own
+            // wave between its read and its use; both A fragments are read at the top.  The k-tile's 2 + WL global loads sit in
+            // the first steps, their LDS writes in the last ones, one per step.
             const float *ap = As + (32 * wave + r) * LD + 4 * h;
             const float *wp = Ws + r * LD + 4 * h;
+            constexpr int NS = 2 * NT, NL = 2 + WL;
+            constexpr int LPS = (NL + NT - 1) / NT;             // pieces per step: loads in the first half, writes in the second (NT = 8: 1)
+            constexpr int WB = NS - (NL + LPS - 1) / LPS;       // first step that writes
+            static_assert(BK == 16 && (NL + LPS - 1) / LPS <= NT, "loads and LDS writes of a k-tile occupy distinct steps");
+            f32x4 fa[2], fw[3];
+            fa[0] = *(const f32x4 *)ap;
+            fw[0] = *(const f32x4 *)wp;
+            fw[1] = *(const f32x4 *)(wp + 32 * LD);
+            fa[1] = *(const f32x4 *)(ap + 8);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int g = 0; g < BK / 8; ++g) {
-                const f32x4 fa = *(const f32x4 *)(ap + 8 * g);
-                if (g == 0) {
+            for (int t = 0; t < NS; ++t) {
+                const int g = t / NT, j = t % NT;
+                if (t + 2 < NS) fw[(t + 2) % 3] = *(const f32x4 *)(wp + 32 * ((t + 2) % NT) * LD + 8 * ((t + 2) / NT));
+                int nld = 0, nwr = 0;
 #pragma unroll
-                    for (int i = 0; i < 2; ++i) pa[i] = *(const f32x4 *)(aptr[i] + kn * BK);
-#pragma unroll
-                    for (int i = 0; i < WL; ++i) pw[i] = *(const f32x4 *)(wptr[i] + kn * BK);
-                }
-                // one 32-column tile at a time: a 4-step dependent chain on acc[j] issues back-to-back
-                // (latency == issue interval for 32x32x2), and only one weight fragment is live
-#pragma unroll
-                for (int j = 0; j < NT; ++j) {
-                    const f32x4 fw = *(const f32x4 *)(wp + 32 * j * LD + 8 * g);
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) acc[j] = MFMA32(fw[s], fa[s], acc[j]);
-                }
-                if (g == BK / 8 - 1) stage((kt + 1) & 1);
-                if (g == 0) {
-#pragma unroll
-                    for (int q = 0; q < 2 + WL; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, (4 * NT) / (2 + WL), 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 2 + WL; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, (4 * NT) / (2 + WL), 0);
-                        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+                for (int q = 0; q < LPS; ++q) {
+                    const int il = t * LPS + q, iw = (t - WB) * LPS + q;
+                    if (il < NL) { gload(il, kn * (BK * 4)); ++nld; }
+                    if (t >= WB && iw < NL) {
+                        float *Ad = smem + ((kt + 1) & 1) * (BM + N) * LD, *Wd = Ad + BM * LD;
+                        if (iw < 2) *(f32x4 *)&Ad[(lrow + 64 * iw) * LD + lc4] = pa[iw];
+                        else *(f32x4 *)&Wd[(lrow + 64 * (iw - 2)) * LD + lc4] = pw[iw - 2];
+                        ++nwr;
                     }
                 }
+#pragma unroll
+                for (int s2 = 0; s2 < 4; ++s2) acc[j] = MFMA32(fw[t % 3][s2], fa[g][s2], acc[j]);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                if (t + 2 < NS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // the fragment of step t + 2
+#pragma unroll
+                for (int q = 0; q < LPS; ++q)
+                    if (q < nld) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);     // this step's VMEM reads
+                __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+#pragma unroll
+                for (int q = 0; q < LPS; ++q)
+                    if (q < nwr) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);     // this step's DS writes
                 __builtin_amdgcn_sched_barrier(0);
             }
-            __syncthreads();
+            if constexpr (DIAG != 0) {              // dsum[0]: cycles this wave waits at the k-tile barriers
+                const unsigned long long tb = stamp();
+                __syncthreads();
+                dsum[0] += stamp() - tb;
+            } else
+                __syncthreads();
         }
+        if constexpr (DIAG != 0) tq = stamp();
 
         // ---- epilogue: LayerNorm over the row (lane-local + one lane^32 exchange), 16-byte stores ----
         // (reduction order shared with skinny_ln: per 32-column block, blocks ascending, partner last)
@@ -889,6 +982,14 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
                     scores[(size_t)row * num_classes + c] = sc;
                 }
             }
+        }
+        if constexpr (DIAG != 0) dsum[1] += stamp() - tq;       // dsum[1]: epilogue
+    }
+    if constexpr (DIAG != 0) {
+        if (diag != nullptr && lane == 0) {
+            unsigned long long *o = diag + ((size_t)blockIdx.x * 4 + wave) * 8;
+            o[0] = dsum[0]; o[1] = dsum[1]; o[2] = dsum[2]; o[3] = 0; o[4] = 0;
+            o[5] = stamp() - tbegin; o[6] = ktiles; o[7] = tbegin;
         }
     }
 }
@@ -2134,7 +2235,28 @@ int vsk_diag_gemm(const float *A, const float *W, const float *bias, float *C, i
                           : persistent_blocks(((M + 127) / 128) * ((N + 127) / 128), 2);
     if (blocks < 0) return (int)hipErrorInvalidDevice;
     if (grid > 0) blocks = grid;
-    const char *dprec = getenv("VS_DIAG_PREC");
+    const char *dprec = getenv("VS_DIAG_PREC"), *dkern = getenv("VS_DIAG_KERNEL"), *dnj = getenv("VS_DIAG_NJ");
+    if (dkern && dkern[0] == 'l') {       // gemm_ln_rows<8, 0> (N = 256: out-projection / fc2 + LayerNorm), product grid.  Timing only:
+        if (N != 256 || K < N) return -1; // the residual is read out of A's buffer (K >= N keeps it in bounds), gamma = beta = bias
+        blocks = persistent_blocks((M + 127) / 128);
+        if (blocks > (M + 127) / 128) blocks = (M + 127) / 128;
+        if (grid > 0) blocks = grid;
+        if (diag == nullptr)
+            hipLaunchKernelGGL((gemm_ln_rows<8, 0>), dim3(blocks), dim3(256), 0, st, A, W, bias, A, bias, bias, C, M, K, nullptr, nullptr, 0, 0, nullptr);
+        else
+            hipLaunchKernelGGL((gemm_ln_rows<8, 0, 0, 1>), dim3(blocks), dim3(256), 0, st, A, W, bias, A, bias, bias, C, M, K, nullptr, nullptr, 0, 0, nullptr, diag);
+        VSK_CHECK_LAUNCH();
+        return 0;
+    }
+    if (!dprec && dnj && atoi(dnj) == 4) {     // the headline form: 256x256 tiles on 8-wave blocks (N % 256 == 0)
+        if (N % 256) return -1;
+        blocks = grid > 0 ? grid : persistent_blocks(((M + 255) / 256) * (N / 256), 1);
+#define VSK_DG4(D_) hipLaunchKernelGGL((gemm_nt_128<EPI_RELU, 4, D_, 4>), dim3(blocks), dim3(512), 0, st, A, W, bias, C, M, N, K, nullptr, 1, 0, 0, diag)
+        if (diag == nullptr) VSK_DG4(0); else if (m == 2) VSK_DG4(2); else VSK_DG4(3);
+#undef VSK_DG4
+        VSK_CHECK_LAUNCH();
+        return 0;
+    }
     if (dprec && atoi(dprec) == 1) {      // the bf16 instantiation (256x256 tiles): mode 2 = without, else with the epilogue
         blocks = grid > 0 ? grid : persistent_blocks(((M + 255) / 256) * (N / 256), 1);
         if (m == 2)
