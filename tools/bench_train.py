@@ -4,7 +4,7 @@ reference's own regime (train.py: batch 4, a few hundred frames) and at the benc
 Beside it, for context only, the same step composed from torch ops on the same GPU (tests/torch_ref.py, rocBLAS /
 ATen kernels - what the reference's nn.Module does on a GPU, minus its per-layer .cpu() copy of the attention maps).
 
-    python tools/bench_train.py [--dropout 0.3] [--torch]"""
+    python tools/bench_train.py [--dropout 0.3] [--torch] [--optim {torch,torch-fused,native}]"""
 import argparse
 import importlib
 import os
@@ -24,6 +24,11 @@ ap.add_argument("--torch", action="store_true", help="also time the composed-tor
 ap.add_argument("--shapes", default="4x320,4x640,16x1024,64x1024")
 ap.add_argument("--model", default="A")
 ap.add_argument("--iters", type=int, default=10)
+ap.add_argument("--optim", choices=("torch", "torch-fused", "native"), default="torch",
+                help="optimizer of the WHOLE train_step line: torch.optim.Adam (default), its fused=True form, or the native "
+                     "Adam (video-summarization_amd/optim.py: one HIP launch, write-through into the packed weights)")
+ap.add_argument("--only-step", action="store_true", help="time only the whole fp32 train_step, repeated (for a spread)")
+ap.add_argument("--repeats", type=int, default=5, help="repetitions of --only-step")
 ap.add_argument("--only-bf16", action="store_true", help="time only the set_train_dtype('bf16') step (for a kernel profile)")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -62,7 +67,10 @@ for shape in args.shapes.split(","):
 
     # the reference's whole train_step (train.py:111-131): autocast forward, masked MSE, GradScaler, Adam - every step
     # re-packs the parameters the optimizer wrote (vs_weights_update) and rebuilds the dgrad transposes
-    optim = torch.optim.Adam(m.parameters(), lr=1e-5, weight_decay=1e-5)
+    if args.optim == "native":
+        optim = pkg.Adam(m.parameters(), lr=1e-5, weight_decay=1e-5).attach(m)      # no re-pack: the step writes the packed copy too
+    else:
+        optim = torch.optim.Adam(m.parameters(), lr=1e-5, weight_decay=1e-5, fused=True if args.optim == "torch-fused" else None)
     scaler = torch.amp.GradScaler("cuda")
 
     def full_step():
@@ -78,6 +86,11 @@ for shape in args.shapes.split(","):
         pred, _ = m(x, mask)
         return pred
 
+    if args.only_step:
+        ts = [timed(full_step, args.iters) for _ in range(args.repeats)]
+        print("B=%3d T=%4d  optim %-11s WHOLE train_step (fp32) ms: %s | min %.3f median %.3f max %.3f"
+              % (B, T, args.optim, " ".join("%.3f" % t for t in ts), min(ts), sorted(ts)[len(ts) // 2], max(ts)), flush=True)
+        continue
     if args.only_bf16:
         m.set_train_dtype("bf16")
         print("B=%3d T=%4d  bf16 fwd+loss+bwd %.3f ms" % (B, T, timed(step, args.iters)), flush=True)
@@ -99,8 +112,8 @@ for shape in args.shapes.split(","):
     flops_f = B * T * (2 * 1024 * d + L * (24 * d * d + 4 * T * d))
     # backward: 2x the Linear flops (dgrad + wgrad) + 3.5x the attention flops (7 products for the forward's 2)
     flops_b = B * T * (2 * 2 * 1024 * d + L * (2 * 24 * d * d + 14 * T * d)) - B * T * 2 * 1024 * d   # no input gradient
-    line = "B=%3d T=%4d  scoring fwd %.3f ms | train fwd %.3f ms | fwd+loss+bwd %.3f ms (bwd %.3f ms) | %.1f TF fwd, %.1f TF bwd, %.0f frames/s | WHOLE train_step (autocast + GradScaler + Adam + re-pack) %.3f ms = %.0f frames/s trained" % (
-        B, T, ev, f, s, s - f, flops_f / f / 1e9, flops_b / (s - f) / 1e9, B * T / s * 1e3, fs, B * T / fs * 1e3)
+    line = "B=%3d T=%4d  scoring fwd %.3f ms | train fwd %.3f ms | fwd+loss+bwd %.3f ms (bwd %.3f ms) | %.1f TF fwd, %.1f TF bwd, %.0f frames/s | WHOLE train_step (autocast + GradScaler + Adam [%s] + re-pack) %.3f ms = %.0f frames/s trained" % (
+        B, T, ev, f, s, s - f, flops_f / f / 1e9, flops_b / (s - f) / 1e9, B * T / s * 1e3, args.optim, fs, B * T / fs * 1e3)
     line += " | bf16 GEMMs (set_train_dtype): fwd+loss+bwd %.3f ms, whole train_step %.3f ms = %.0f frames/s" % (s16, fs16, B * T / fs16 * 1e3)
     line += " | fp16 GEMMs: fwd+loss+bwd %.3f ms, whole train_step %.3f ms = %.0f frames/s" % (sh16, fsh16, B * T / fsh16 * 1e3)
     if args.torch:

@@ -9,7 +9,9 @@ from .simnet import SimNet, score_frames  # noqa: F401
 from .pretrain import PretrainModel  # noqa: F401
 from .losses import mse_with_mask_loss  # noqa: F401
 from . import segmentation  # noqa: F401
+from . import optim  # noqa: F401
+from .optim import Adam, AdamW  # noqa: F401
 from .segmentation import get_segment_fn, kts_seg, kts_seg_batch  # noqa: F401
 
 __all__ = ["SimNet", "PretrainModel", "score_frames", "synth", "mse_with_mask_loss", "segmentation", "get_segment_fn", "kts_seg",
-           "kts_seg_batch"]
+           "kts_seg_batch", "optim", "Adam", "AdamW"]

@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(HERE, "libvsscore.so")
 DIAG_LIB_PATH = os.path.join(HERE, "libvsscore_diag.so")
 SOURCES = ("vs_kernels.hip", "vs_attention.hip", "vs_attention_w64.hip", "vs_mlp_fused.hip", "vs_gemm_ring.hip", "vs_scorer.cpp", "vs_eval.cpp",
            "vs_train_kernels.hip", "vs_train_attention.hip", "vs_train_attention_bf16.hip", "vs_train_gemm_rows.hip", "vs_pretrain_kernels.hip",
-           "vs_train.cpp", "vs_segment.hip", "vs_segment.cpp")
+           "vs_train.cpp", "vs_segment.hip", "vs_segment.cpp", "vs_optim.hip")
 ABI_VERSION = 3
 
 VS_OK, VS_ERR_INVALID, VS_ERR_WORKSPACE, VS_ERR_HIP = 0, 1, 2, 3
@@ -55,6 +55,9 @@ TRAIN_EXPORTS = ("vs_train_prepare", "vs_train_saved_bytes", "vs_train_workspace
                  "vs_pretrain_head_backward")
 # include/vs_segment.h (kernel temporal segmentation)
 SEGMENT_EXPORTS = ("vs_kts_workspace_bytes", "vs_kts_segment", "vs_kts_scatters")
+# include/vs_optim.h (the Adam step)
+OPTIM_EXPORTS = ("vs_adam_step_tensors", "vs_adam_state_bytes", "vs_adam_state_init", "vs_adam_state_field", "vs_adam_step")
+VS_ADAM_MAX_TENSORS = 64
 VS_KTS_FEATURES_F32, VS_KTS_KERNEL_F32, VS_KTS_KERNEL_F64 = 0, 1, 2
 VS_KTS_SCORES, VS_KTS_BACKTRACK, VS_KTS_AUTO = 0, 1, 2
 NUM_STAGES = 6
@@ -94,6 +97,16 @@ LayerGrads = LayerParams        # vs_layer_grads: same field names, destinations
 class ModelGrads(C.Structure):  # vs_model_grads (no positional table: it is a buffer, not a parameter)
     _fields_ = [("embed_w", C.c_void_p), ("embed_b", C.c_void_p), ("layers", C.POINTER(LayerParams)),
                 ("final_w", C.c_void_p), ("final_b", C.c_void_p)]
+
+
+class AdamCfg(C.Structure):    # vs_adam_cfg (include/vs_optim.h)
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("decoupled", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AdamTensor(C.Structure):  # vs_adam_tensor
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("mirror", C.c_void_p),
+                ("step", C.c_void_p), ("n", C.c_size_t)]
 
 
 def hipcc_path() -> str:
@@ -178,7 +191,7 @@ def load() -> C.CDLL:
                 "Run `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). "
                 "There is no PyTorch/CPU fallback for the scoring path." % path)
         lib = C.CDLL(path)
-        for name in EXPORTS + EVAL_EXPORTS + TRAIN_EXPORTS + SEGMENT_EXPORTS:
+        for name in EXPORTS + EVAL_EXPORTS + TRAIN_EXPORTS + SEGMENT_EXPORTS + OPTIM_EXPORTS:
             if not hasattr(lib, name):
                 raise RuntimeError("libvsscore.so lacks symbol %s (stale build?)" % name)
         lib.vs_abi_version.restype = C.c_int
@@ -336,6 +349,19 @@ def load() -> C.CDLL:
         lib.vs_kts_scatters.restype = C.c_int
         lib.vs_kts_scatters.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.c_void_p]
+        # include/vs_optim.h
+        lib.vs_adam_step_tensors.restype = C.c_int
+        lib.vs_adam_step_tensors.argtypes = [C.POINTER(AdamTensor), C.c_int32, C.POINTER(AdamCfg), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]
+        lib.vs_adam_state_bytes.restype = C.c_size_t
+        lib.vs_adam_state_bytes.argtypes = [C.c_void_p]
+        lib.vs_adam_state_init.restype = C.c_int
+        lib.vs_adam_state_init.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.vs_adam_state_field.restype = C.c_int
+        lib.vs_adam_state_field.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        lib.vs_adam_step.restype = C.c_int
+        lib.vs_adam_step.argtypes = [C.c_void_p, C.POINTER(ModelParams), C.POINTER(ModelGrads), C.c_void_p, C.POINTER(AdamCfg),
+                                     C.c_void_p, C.c_void_p, C.c_void_p]
         lib.vs_profile_enable.restype = C.c_int
         lib.vs_profile_enable.argtypes = [C.c_int32]
         lib.vs_profile_collect.restype = C.c_int
