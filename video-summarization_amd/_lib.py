@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(HERE, "libvsscore.so")
 DIAG_LIB_PATH = os.path.join(HERE, "libvsscore_diag.so")
 SOURCES = ("vs_kernels.hip", "vs_attention.hip", "vs_attention_w64.hip", "vs_mlp_fused.hip", "vs_gemm_ring.hip", "vs_scorer.cpp", "vs_eval.cpp",
            "vs_train_kernels.hip", "vs_train_attention.hip", "vs_train_attention_bf16.hip", "vs_train_gemm_rows.hip", "vs_pretrain_kernels.hip",
-           "vs_train.cpp", "vs_segment.hip", "vs_segment.cpp", "vs_optim.hip")
+           "vs_train.cpp", "vs_segment.hip", "vs_segment.cpp", "vs_optim.hip", "vs_attention_maps.hip")
 ABI_VERSION = 3
 
 VS_OK, VS_ERR_INVALID, VS_ERR_WORKSPACE, VS_ERR_HIP = 0, 1, 2, 3
@@ -57,6 +57,8 @@ TRAIN_EXPORTS = ("vs_train_prepare", "vs_train_saved_bytes", "vs_train_workspace
 SEGMENT_EXPORTS = ("vs_kts_workspace_bytes", "vs_kts_segment", "vs_kts_scatters")
 # include/vs_optim.h (the Adam step)
 OPTIM_EXPORTS = ("vs_adam_step_tensors", "vs_adam_state_bytes", "vs_adam_state_init", "vs_adam_state_field", "vs_adam_step")
+# include/vs_inspect.h (attention maps on request)
+INSPECT_EXPORTS = ("vs_inspect_workspace_bytes", "vs_inspect_forward", "vs_attention_probs_workspace_bytes", "vs_attention_probs_f32")
 VS_ADAM_MAX_TENSORS = 64
 VS_KTS_FEATURES_F32, VS_KTS_KERNEL_F32, VS_KTS_KERNEL_F64 = 0, 1, 2
 VS_KTS_SCORES, VS_KTS_BACKTRACK, VS_KTS_AUTO = 0, 1, 2
@@ -191,7 +193,7 @@ def load() -> C.CDLL:
                 "Run `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). "
                 "There is no PyTorch/CPU fallback for the scoring path." % path)
         lib = C.CDLL(path)
-        for name in EXPORTS + EVAL_EXPORTS + TRAIN_EXPORTS + SEGMENT_EXPORTS + OPTIM_EXPORTS:
+        for name in EXPORTS + EVAL_EXPORTS + TRAIN_EXPORTS + SEGMENT_EXPORTS + OPTIM_EXPORTS + INSPECT_EXPORTS:
             if not hasattr(lib, name):
                 raise RuntimeError("libvsscore.so lacks symbol %s (stale build?)" % name)
         lib.vs_abi_version.restype = C.c_int
@@ -362,6 +364,16 @@ def load() -> C.CDLL:
         lib.vs_adam_step.restype = C.c_int
         lib.vs_adam_step.argtypes = [C.c_void_p, C.POINTER(ModelParams), C.POINTER(ModelGrads), C.c_void_p, C.POINTER(AdamCfg),
                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        # include/vs_inspect.h
+        lib.vs_inspect_workspace_bytes.restype = C.c_size_t
+        lib.vs_inspect_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        lib.vs_inspect_forward.restype = C.c_int
+        lib.vs_inspect_forward.argtypes = ([C.c_void_p] * 4 + [C.c_int32] * 2 + [C.POINTER(C.c_int32), C.c_int32] + [C.c_void_p] * 6
+                                           + [C.c_size_t, C.c_void_p])
+        lib.vs_attention_probs_workspace_bytes.restype = C.c_size_t
+        lib.vs_attention_probs_workspace_bytes.argtypes = [C.c_int32] * 3
+        lib.vs_attention_probs_f32.restype = C.c_int
+        lib.vs_attention_probs_f32.argtypes = ([C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.c_size_t, C.c_void_p])
         lib.vs_profile_enable.restype = C.c_int
         lib.vs_profile_enable.argtypes = [C.c_int32]
         lib.vs_profile_collect.restype = C.c_int

@@ -38,6 +38,11 @@ int vsk_attention_bf16_w64(const void *q, const void *k, const void *v, const ui
                            hipStream_t st);
 int vsk_attention_bf16_w64_packed(const void *q, const void *k, const void *v, void *out, int H, int Mtot, const int *cu,
                                   const int *work, int nwork, hipStream_t st);
+// vs_attention_maps.hip (include/vs_inspect.h): the softmax weights of q k^T themselves and / or their two reductions, exact
+// fp32, head dim 32 / 64 / 128 / 256; q, k head-major [B, H, T, dh].  workspace: vsk_attention_probs_workspace_bytes, 256-byte aligned
+size_t vsk_attention_probs_workspace_bytes(int B, int H, int T);
+int vsk_attention_probs(const float *q, const float *k, const uint8_t *mask, float *maps, float *received, float *entropy,
+                        int B, int H, int T, int dh, float scale, void *workspace, hipStream_t st);
 int vsk_linear_res_ln(const float *A, const float *W, const float *Wf, const float *bias, const float *res,
                       const float *gamma, const float *beta, float *out, int M, int N, int K,
                       const float *score_w, const float *score_b, int num_classes, int sigmoid,

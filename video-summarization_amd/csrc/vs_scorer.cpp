@@ -1,6 +1,7 @@
 // vs_scorer.cpp — the C ABI of include/vs_scorer.h: argument checks, weight packing, workspace
 // carving and the per-layer launch sequence of the scorer's eval forward.
 #include "vs_scorer.h"
+#include "vs_inspect.h"
 
 #include <hip/hip_runtime.h>
 
@@ -389,12 +390,22 @@ struct PackedInfo {
     int prec;                // attention arithmetic: 0 exact fp32, 2 fp16x3
 };
 
+// vs_inspect_forward: after the QKV stage of every selected layer the attention-map kernels READ that layer's q / k planes
+// (exact path: fp32, head-major) - nothing the forward computes depends on it
+struct InspectHook {
+    const int32_t *layers;   // host, ascending
+    int n_layers;
+    float *maps, *received, *entropy;      // [n_layers, B, H, N, N] / [n_layers, B, H, N] / [n_layers, B, H, N], any nullptr
+    void *workspace;         // vsk_attention_probs_workspace_bytes(B, H, N)
+};
+
 // cls != nullptr (use_cls=True, reference simnet.py:205-206, 214-216, 47-51): x has T frames per video, a class token
 // [d_model] is prepended AFTER the positional encoding, so the encoder sees T + 1 positions (the token is never
 // padding) and scores / hidden have T + 1 rows per video.
 int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mask, int32_t B,
                  int32_t T, uint32_t flags, float *scores, float *hidden, void *workspace,
-                 size_t workspace_bytes, void *stream, const PackedInfo *pk, const float *cls = nullptr) {
+                 size_t workspace_bytes, void *stream, const PackedInfo *pk, const float *cls = nullptr,
+                 const InspectHook *ins = nullptr) {
     if (!w || !x || !scores) return fail(VS_ERR_INVALID, "weights/x/scores is NULL");
     if (B <= 0 || T <= 0) return fail(VS_ERR_INVALID, "B=%d T=%d", B, T);
     const vs_model_desc &D = w->desc;
@@ -542,6 +553,15 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
             VS_LAUNCH(vsk_qkv(h0, w->p(P.wqkv), w->p(lbf == 2 ? P.h_wqkv : P.f_wqkv), w->p(P.bqkv), qkv, B, T, d, H,
                               qkv16 ? (1 | VSK_STORE16) : lbf, st, qkv16 ? vsk_attention_qscale(scale) : 1.0f));
         }
+        if (ins) {
+            for (int i = 0; i < ins->n_layers; ++i) {
+                if (ins->layers[i] != l) continue;
+                const size_t rows = (size_t)B * H * T;
+                VS_LAUNCH(vsk_attention_probs(qkv, qkv + (size_t)M * d, key_pad_mask, ins->maps ? ins->maps + i * rows * T : nullptr,
+                                              ins->received ? ins->received + i * rows : nullptr,
+                                              ins->entropy ? ins->entropy + i * rows : nullptr, B, H, T, d / H, scale, ins->workspace, st));
+            }
+        }
         {
             StageScope ps(VS_STAGE_ATTENTION, st);
             if (pk)
@@ -658,6 +678,58 @@ int vs_scorer_forward_cls(const vs_weights *w, const float *x, const uint8_t *ke
                           size_t workspace_bytes, void *stream) {
     if (!cls_token) return fail(VS_ERR_INVALID, "cls_token is NULL");
     return forward_core(w, x, key_pad_mask, B, T, flags, scores, hidden, workspace, workspace_bytes, stream, nullptr, cls_token);
+}
+
+// ---- attention maps (include/vs_inspect.h) ----
+size_t vs_inspect_workspace_bytes(const vs_weights *w, int32_t B, int32_t T, int32_t with_cls) {
+    if (!w || B <= 0 || T <= 0) return 0;
+    const size_t core = with_cls ? vs_scorer_workspace_bytes_cls(w, B, T) : vs_scorer_workspace_bytes(w, B, T);
+    return align_up(core, 256) + vsk_attention_probs_workspace_bytes(B, w->desc.num_heads, T + (with_cls ? 1 : 0));
+}
+
+int vs_inspect_forward(const vs_weights *w, const float *x, const uint8_t *key_pad_mask, const float *cls_token,
+                       int32_t B, int32_t T, const int32_t *layers, int32_t n_layers,
+                       float *scores, float *hidden, float *maps, float *received, float *entropy,
+                       void *workspace, size_t workspace_bytes, void *stream) {
+    if (!w) return fail(VS_ERR_INVALID, "weights is NULL");
+    if (!layers || n_layers <= 0) return fail(VS_ERR_INVALID, "layers is NULL or n_layers=%d", n_layers);
+    for (int i = 0; i < n_layers; ++i) {
+        if (layers[i] < 0 || layers[i] >= w->desc.num_layers)
+            return fail(VS_ERR_INVALID, "layers[%d]=%d out of range (num_layers=%d)", i, layers[i], w->desc.num_layers);
+        if (i && layers[i] <= layers[i - 1]) return fail(VS_ERR_INVALID, "layers must be strictly ascending (layers[%d]=%d after %d)", i, layers[i], layers[i - 1]);
+    }
+    if (!maps && !received && !entropy) return fail(VS_ERR_INVALID, "maps, received and entropy are all NULL");
+    if (((uintptr_t)maps | (uintptr_t)received | (uintptr_t)entropy) & 15)
+        return fail(VS_ERR_INVALID, "maps / received / entropy must be 16-byte aligned");
+    if (B <= 0 || T <= 0) return fail(VS_ERR_INVALID, "B=%d T=%d", B, T);
+    const size_t core = align_up(cls_token ? vs_scorer_workspace_bytes_cls(w, B, T) : vs_scorer_workspace_bytes(w, B, T), 256);
+    const size_t need = vs_inspect_workspace_bytes(w, B, T, cls_token != nullptr);
+    if (!workspace || workspace_bytes < need)
+        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
+    const InspectHook ins{layers, n_layers, maps, received, entropy, (char *)workspace + core};
+    return forward_core(w, x, key_pad_mask, B, T, 0u, scores, hidden, workspace, core, stream, nullptr, cls_token, &ins);
+}
+
+size_t vs_attention_probs_workspace_bytes(int32_t B, int32_t H, int32_t T) {
+    if (B <= 0 || H <= 0 || T <= 0) return 0;
+    return vsk_attention_probs_workspace_bytes(B, H, T);
+}
+
+int vs_attention_probs_f32(const float *q, const float *k, const uint8_t *key_pad_mask, float *maps, float *received,
+                           float *entropy, int32_t B, int32_t H, int32_t T, int32_t dh, float scale, void *workspace,
+                           size_t workspace_bytes, void *stream) {
+    if (!q || !k) return fail(VS_ERR_INVALID, "q / k is NULL");
+    if (!maps && !received && !entropy) return fail(VS_ERR_INVALID, "maps, received and entropy are all NULL");
+    if (B <= 0 || H <= 0 || T <= 0) return fail(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
+    if (dh != 32 && dh != 64 && dh != 128 && dh != 256) return fail(VS_ERR_INVALID, "head_dim=%d unsupported (32, 64, 128 or 256)", dh);
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)maps | (uintptr_t)received | (uintptr_t)entropy) & 15)
+        return fail(VS_ERR_INVALID, "q / k / maps / received / entropy must be 16-byte aligned");
+    const size_t need = vsk_attention_probs_workspace_bytes(B, H, T);
+    if (!workspace || workspace_bytes < need)
+        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 255) return fail(VS_ERR_INVALID, "workspace must be 256-byte aligned");
+    VS_LAUNCH(vsk_attention_probs(q, k, key_pad_mask, maps, received, entropy, B, H, T, dh, scale, workspace, (hipStream_t)stream));
+    return VS_OK;
 }
 
 // ---- packed ragged batches ----

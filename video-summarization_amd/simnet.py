@@ -554,6 +554,82 @@ class SimNet(nn.Module):
                                                   _lib.VS_FLAG_SIGMOID | self._attention_flag(), False)
         return scores.squeeze(-1)
 
+    # ---- attention maps on request (include/vs_inspect.h) ----------------------------------
+    def _inspect(self, x: Tensor, mask, layers, want_maps: bool):
+        """One ``vs_inspect_forward`` call: the exact fp32 eval forward plus the attention-map kernels on the q / k planes of
+        the selected layers.  Returns (logits, maps or None, received or None, entropy or None), stacked over the layers."""
+        if x.dim() != 3 or x.size(2) != self.in_features:
+            raise RuntimeError("expected x of shape [B, T, %d], got %s" % (self.in_features, tuple(x.shape)))
+        mask = mask if isinstance(mask, Tensor) else None
+        if self.use_pos and x.size(1) > self.pe_len:
+            raise RuntimeError("T=%d exceeds the positional table (%d rows)" % (x.size(1), self.pe_len))
+        if not x.is_cuda:
+            raise RuntimeError("SimNet runs on the MI355X HIP kernels only: move the module and its "
+                               "input to a HIP device (there is no CPU path for the scorer)")
+        L = self.num_layers
+        want = list(range(L)) if layers is None else [int(l) for l in layers]
+        sel = [l + L if l < 0 else l for l in want]
+        if not sel or any(l < 0 or l >= L for l in sel) or len(set(sel)) != len(sel):
+            raise IndexError("layers must be distinct indices of the %d encoder layers, got %r" % (L, want))
+        asc = sorted(sel)
+        lib = _lib.load()
+        B, T, _ = x.shape
+        dev = x.device
+        N, H = T + (1 if self.use_cls else 0), self.num_heads
+        x32 = (x if x.dtype == torch.float32 else x.float()).contiguous()
+        packed = self._packed_weights(dev)
+        cls = None
+        if self.use_cls:
+            cls = self.embedding_layer.cls_token.detach().to(torch.float32).contiguous()
+            if self._plan:
+                cls = self._pad(cls, ("res",)).contiguous()
+        m = None
+        if mask is not None:
+            m = mask.contiguous()
+            m = m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
+        scores = torch.empty((B, N, self.num_classes), dtype=torch.float32, device=dev)
+        maps = torch.empty((len(asc), B, H, N, N), dtype=torch.float32, device=dev) if want_maps else None
+        received = None if want_maps else torch.empty((len(asc), B, H, N), dtype=torch.float32, device=dev)
+        entropy = None if want_maps else torch.empty((len(asc), B, H, N), dtype=torch.float32, device=dev)
+        host_layers = (C.c_int32 * len(asc))(*asc)
+        with torch.cuda.device(dev):
+            need = lib.vs_inspect_workspace_bytes(packed.handle, B, T, 1 if self.use_cls else 0)
+            ws = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(lib.vs_inspect_forward(packed.handle, x32.data_ptr(), _ptr(m), _ptr(cls), B, T, host_layers, len(asc),
+                                              scores.data_ptr(), None, _ptr(maps), _ptr(received), _ptr(entropy),
+                                              ws.data_ptr(), ws.numel(), st))
+        if sel != asc:      # the caller's order
+            order = torch.tensor([asc.index(l) for l in sel], device=dev)
+            maps, received, entropy = (t if t is None else t.index_select(0, order) for t in (maps, received, entropy))
+        return scores, maps, received, entropy
+
+    @torch.no_grad()
+    def attention_maps(self, x: Tensor, mask=None, layers=None):
+        """The softmax weights of the self-attention layers (reference simnet.py:155-164, the ``attention_maps`` list of
+        :112-113): returns ``(logits, maps)``, ``maps`` a list with one ``[B, H, N, N]`` fp32 device tensor per selected
+        layer (``N = T``, or ``T + 1`` with ``use_cls``, token first).  ``layers=None`` selects every layer; negative
+        indices count from the last.  ``maps[l][b, h, i, j]`` is the weight query ``i`` gives key ``j``: taken before
+        dropout (the reference's tensor in eval mode), a masked key column is exactly 0, padded query rows are computed
+        like any other row.  ``B * H * N * N * 4`` bytes per layer: use ``attention_summary`` for long videos.
+
+        The maps describe the EXACT fp32 path: whatever ``set_compute_dtype`` / ``set_latency_mode`` / ``fused_sigmoid``
+        / ``model.training`` say, this call runs the default exact kernels in eval semantics (it changes none of those
+        settings), and ``logits`` are the raw logits of ``forward`` in the default mode, bit for bit.  Unlike the
+        reference the tensors stay on the device.  No autograd, no packed batches, no CPU path."""
+        scores, maps, _, _ = self._inspect(x, mask, layers, True)
+        return scores, list(maps.unbind(0))
+
+    @torch.no_grad()
+    def attention_summary(self, x: Tensor, mask=None, layers=None):
+        """Two reductions of the attention maps that never store ``[N, N]`` (any video length): returns
+        ``(logits, received, entropy)``, both ``[n_layers, B, H, N]`` fp32 device tensors.  ``received[l, b, h, j]`` is the
+        mean weight frame ``j`` receives from the video's non-padding frames (sums to 1 over ``j``; 0 for a masked frame);
+        ``entropy[l, b, h, i]`` is the entropy of frame ``i``'s weights in nats (0: it attends to one frame; ``log n``:
+        uniform over the ``n`` valid frames).  Same arithmetic, modes and limits as ``attention_maps``."""
+        scores, _, received, entropy = self._inspect(x, mask, layers, False)
+        return scores, received, entropy
+
     @property
     def attention_dtype(self) -> str:
         return self._attention_dtype
