@@ -108,6 +108,42 @@ int vs_train_backward(vs_weights *w, const float *x, const uint8_t *key_pad_mask
                       size_t saved_bytes, const vs_model_grads *grads, float *dx, void *workspace,
                       size_t workspace_bytes, void *stream);
 
+/* ---- Packed ragged batches: training without padded rows --------------------------------------------------------------
+ * The counterpart of vs_scorer_forward_packed for the training path.  x [Mtot, in_features] holds the frames of B videos
+ * concatenated (video b = rows sum(lengths[:b]) ..., Mtot = sum(lengths)); there is no sentinel row and no key mask.  Every
+ * Linear, LayerNorm, dgrad and wgrad runs over Mtot rows instead of B * max(lengths), the attention kernels stream only a
+ * video's own rows, and the activation record scales with Mtot (its attention keep words with sum T_b * ceil(T_b / 32)).
+ * `lengths` is a HOST array (it sizes the launches), `lengths_dev` the same values on the device: the row offsets and the
+ * attention work list are built there, so no host memory is read after the call returns.  Same conventions as
+ * vs_train_forward / _backward: stream-ordered, no allocation, int status + vs_last_error(); scores [Mtot, num_classes],
+ * hidden [Mtot, d_model], d_scores / d_hidden / dx likewise.  A video's outputs do not depend on the batch it is packed in.
+ * Dropout: the row dropouts hash (seed, site, packed row, column); the attention weights hash (seed, site, head * Mtot +
+ * packed row of the query, key index within the video).
+ * Low precision: VS_TRAIN_FLAG_BF16_LINEAR (and VS_TRAIN_FLAG_FP16) apply as in the padded form, counted on Mtot rows; the
+ * packed attention is exact fp32 - VS_TRAIN_FLAG_BF16_ATTENTION is accepted and ignored.
+ * VS_ERR_INVALID: lengths[b] <= 0, a length above the positional table (each video starts at position 0, so max(lengths)
+ * is what the table bounds, not Mtot), NULL lengths / lengths_dev.  (There is no class-token form of the training path.) */
+int vs_train_check_packed(const vs_model_desc *desc, const int32_t *lengths, int32_t B);      /* the checks above, from a description alone */
+/* Record bytes from a description alone (no handle, no device): lengths != NULL - the packed record of these B videos (T is
+ * ignored); lengths == NULL - the padded [B, T] record.  0 on invalid input. */
+size_t vs_train_saved_bytes_desc(const vs_model_desc *desc, const int32_t *lengths, int32_t B, int32_t T);
+size_t vs_train_saved_bytes_packed(const vs_weights *w, const int32_t *lengths, int32_t B);
+size_t vs_train_workspace_bytes_packed(const vs_weights *w, const int32_t *lengths, int32_t B);
+int vs_train_forward_packed(const vs_weights *w, const float *x, const int32_t *lengths, const int32_t *lengths_dev, int32_t B,
+                            const vs_dropout_cfg *drop, float *scores, float *hidden, void *saved, size_t saved_bytes,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int vs_train_backward_packed(vs_weights *w, const float *x, const int32_t *lengths, const int32_t *lengths_dev, int32_t B,
+                             const vs_dropout_cfg *drop, const float *d_scores, const float *d_hidden, const void *saved,
+                             size_t saved_bytes, const vs_model_grads *grads, float *dx, void *workspace,
+                             size_t workspace_bytes, void *stream);
+/* The loss of a packed batch: sum over its n = Mtot entries of (output - target)^2, divided by `denom`.  With
+ * denom = B * max(lengths) this is the value (and gradient) of mse_with_mask_loss(reduction "avg") on the padded batch of
+ * the same videos - the reference averages over ALL B * T entries, masked ones included; denom = 1 is reduction "sum". */
+int vs_mse_packed_loss_forward(const float *output, const float *target, int32_t n, double denom, float *scratch, float *loss,
+                               void *stream);
+int vs_mse_packed_loss_backward(const float *output, const float *target, const float *d_loss, int32_t n, double denom,
+                                float *d_output, void *stream);
+
 /* Replaces: utils.mse_with_mask_loss(output, targets, mask, reduction) (reference src/utils/utils.py:45-56, called
  * at train.py:122): mean (reduction "avg") or sum over ALL n = B*T entries of ((output - target) * scale)^2 with
  * scale = 0 on masked frames.  output/target [n] fp32, mask [n] bytes or NULL; scratch >= 256 floats; loss [1]. */
@@ -169,6 +205,26 @@ int vs_train_attention_backward_bf16(const float *q, const float *k, const float
                                      const float *out, const float *d_out, const float *lse2, float *dqkv, float *scratch,
                                      int32_t B, int32_t H, int32_t T, int32_t dh, float scale, float p, const void *dbits,
                                      int32_t in16, void *stream);
+
+/* The exact attention kernels on a packed batch: q, k, v head-major over the packed rows [H, Mtot, dh] (vs_qkv_proj_f32 with
+ * B = 1, T = Mtot), out / d_out [Mtot, H*dh], lse2 [H, Mtot], dqkv [Mtot, 3*H*dh]; every head dim of the padded kernels.
+ * scratch >= vs_train_attention_packed_scratch_bytes, 256-byte aligned. */
+size_t vs_train_attention_packed_scratch_bytes(const int32_t *lengths, int32_t B, int32_t H);
+int vs_train_attention_forward_packed(const float *q, const float *k, const float *v, float *out, float *lse2,
+                                      const int32_t *lengths, const int32_t *lengths_dev, int32_t B, int32_t H, int32_t dh,
+                                      float scale, uint64_t seed, uint32_t site, float p, void *scratch, size_t scratch_bytes,
+                                      void *stream);
+int vs_train_attention_backward_packed(const float *q, const float *k, const float *v, const float *out, const float *d_out,
+                                       const float *lse2, float *dqkv, const int32_t *lengths, const int32_t *lengths_dev,
+                                       int32_t B, int32_t H, int32_t dh, float scale, uint64_t seed, uint32_t site, float p,
+                                       void *scratch, size_t scratch_bytes, void *stream);
+/* keep masks of a packed batch's attention-weight dropout, exactly as those kernels (and the bit-packed copies of the full
+ * path) draw them: video after video, [H, T_b, T_b] bytes each - H * sum T_b^2 bytes in all. */
+int vs_train_dropout_mask_attention_packed(uint8_t *keep, const int32_t *lengths, int32_t B, int32_t H, uint64_t seed,
+                                           uint32_t site, float p, void *stream);
+/* vs_train_saved_field for the record of vs_train_forward_packed (counts over Mtot rows); field 4: lse2 [H, Mtot]. */
+int vs_train_saved_field_packed(const vs_weights *w, const int32_t *lengths, int32_t B, int32_t layer, int32_t field,
+                                size_t *offset_bytes, size_t *count);
 
 /* dW [N,K] = dY[M,N]^T X[M,K], db [N] = column sums of dY; scratch >= vs_train_wgrad_scratch_floats(M,N,K) floats. */
 size_t vs_train_wgrad_scratch_floats(int32_t M, int32_t N, int32_t K);

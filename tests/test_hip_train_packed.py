@@ -1,0 +1,599 @@
+"""GPU tests of TRAINING ON PACKED RAGGED BATCHES (include/vs_train.h: vs_train_forward_packed / _backward_packed;
+SimNet.forward_packed_train, losses.mse_packed_loss, harness.train_step_packed).
+
+Checkers: (1) float64 gradients of the IMPORTED reference on the padded batch of the same videos
+(tests/golden/make_golden_train_packed.py, and the padded goldens of make_golden_train.py whose loss takes nothing from padded
+rows); (2) the float64 torch restatement with explicit dropout masks (tests/torch_ref.py), run per video and fed with the
+keep masks the library exports for the packed batch; (3) bit-equality properties: a video's bits do not depend on the batch
+it is packed in, a one-video packed batch is the padded B = 1 call, two runs with one seed agree.
+
+Tolerances are those of tests/test_hip_train.py for the padded path (tests/tolerances.py): nothing is added."""
+import ctypes as C
+import importlib
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN
+import torch_ref
+import tolerances as tol
+
+pytestmark = pytest.mark.gpu
+ATOL, RTOL = tol.TRAIN_GRAD_ATOL, tol.TRAIN_GRAD_RTOL
+
+
+def _dev():
+    assert torch.cuda.is_available(), "these tests need a HIP device"
+    return torch.device("cuda:0")
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _i32(values):
+    return (C.c_int32 * len(values))(*values)
+
+
+def _close(got, want, what="", atol=ATOL, rtol=RTOL):
+    got, want = got.detach().double().cpu(), want.detach().double().cpu()
+    err = (got - want).abs().max().item()
+    scale = want.abs().max().item()
+    assert (atol is None or err <= atol) and err <= rtol * scale + 1e-6, "%s: max err %.3e (max |want| %.3e)" % (what, err, scale)
+    return err / (scale + 1e-30)
+
+
+def _cu(lengths):
+    return [0] + list(np.cumsum(lengths))
+
+
+def packed_cases():
+    with open(os.path.join(GOLDEN, "train_packed_index.json")) as f:
+        return json.load(f)["cases"]
+
+
+def padded_cases_that_can_run_packed():
+    """The padded goldens that record `lengths`: train_ma_t320_pad and train_mb_t150_pad have hidden_w = 0, so their loss takes
+    nothing from padded rows and the packed step must reproduce it.  LEFT OUT: train_d768_h12_t60_pad, train_d128_h8_t90_pad
+    and train_d256_h1_t90_pad - make_golden_train.py adds hidden_w * sum(hidden * R) over ALL B * T rows there, padded query
+    rows included (they attend to the valid keys and depend on every parameter), a term a packed batch has no rows for; the
+    packed goldens carry a head-dim-256 and an embedded case with that term on the valid rows instead."""
+    with open(os.path.join(GOLDEN, "train_index.json")) as f:
+        cases = json.load(f)["cases"]
+    return [c for c in cases if c.get("lengths") is not None and not c["hidden_w"]]
+
+
+def _model(vsa, c, dropout=0.0, sparsity=0.0):
+    m = vsa.SimNet(num_heads=c["H"], d_model=c["d"], num_layers=c["L"], sparsity=sparsity, dropout=dropout)
+    m.load_state_dict(vsa.synth.make_state_dict(c["d"], c["L"], c["wseed"]), strict=True)
+    return m.to(_dev()).train()
+
+
+def _packed_inputs(vsa, c):
+    """the packed batch of a packed golden (same recipe as make_golden_train_packed.build_inputs)"""
+    lengths = c["lengths"]
+    B, T = len(lengths), max(lengths)
+    x = vsa.synth.make_features(B, T, c["xseed"], c["kind"], lengths)
+    mask = vsa.synth.padding_mask(x)
+    rng = np.random.Generator(np.random.PCG64(c["tseed"]))
+    target = torch.from_numpy(rng.random(size=(B, T)).astype(np.float32))
+    R = torch.from_numpy(rng.standard_normal(size=(sum(lengths), c["d"])).astype(np.float32))
+    valid = ~mask
+    return x[valid], target[valid], R, lengths
+
+
+def _packed_step(vsa, m, c, xp, tp, R, lengths):
+    xd = xp.to(_dev()).requires_grad_(True)
+    pred, hidden = m.forward_packed_train(xd, lengths)
+    assert pred.requires_grad and hidden.requires_grad
+    assert pred.shape == (sum(lengths), 1) and hidden.shape == (sum(lengths), c["d"])
+    loss = vsa.mse_packed_loss(pred, tp.to(_dev()), lengths)
+    if c["hidden_w"]:
+        loss = loss + c["hidden_w"] * (hidden * R.to(_dev())).sum()
+    loss.backward()
+    torch.cuda.synchronize()
+    grads = {"x": xd.grad}
+    grads.update({k: p.grad for k, p in m.named_parameters()})
+    return loss, pred, grads
+
+
+def _check_exact(z, loss, pred, grads, name):
+    """the checks of test_hip_train.test_gradients_match_reference_golden, on packed tensors"""
+    print("%s: loss %.9f (float64 %.9f)" % (name, loss.item(), float(z["loss"])))
+    assert abs(loss.item() - float(z["loss"])) <= 2e-6 * max(1.0, abs(float(z["loss"])))
+    assert (pred.detach().cpu().view(-1) - torch.from_numpy(z["logits"]).view(-1)).abs().max().item() < 1e-4
+    keys = json.loads(str(z["keys"]))
+    assert sorted(keys) == sorted(grads.keys())
+    worst = 0.0
+    for k in keys:
+        g = grads[k]
+        assert g is not None and torch.isfinite(g).all(), k
+        g2 = g.reshape(-1, g.shape[-1]) if g.dim() > 1 else g.reshape(1, -1)
+        rows = torch.from_numpy(z["r:" + k])
+        want = torch.from_numpy(z["g:" + k])
+        tot, nrm, gmax, ref32 = z["s:" + k]
+        got = g2[rows.to(g2.device)].double().cpu()
+        err = (got - want.double()).abs().max().item()
+        assert err <= ATOL and err <= RTOL * gmax + 1e-6, "%s: err %.3e, max|g| %.3e (reference fp32 own err %.3e)" % (k, err, gmax, ref32)
+        assert abs(g.double().sum().item() - tot) <= 1e-3 * max(abs(tot), nrm) + 0.25 * RTOL * gmax * g.numel() ** 0.5 + 1e-7, k
+        assert abs(g.double().norm().item() - nrm) <= 1e-4 * nrm + 1e-7, k
+        worst = max(worst, err / (gmax + 1e-12) if gmax > 1e-6 else 0.0)
+    print("%s: worst gradient error relative to the tensor's max: %.2e" % (name, worst))
+
+
+# ---------------------------------------------------------------------------------------------
+# whole model against the imported reference (float64)
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", packed_cases(), ids=lambda c: c["name"])
+def test_packed_gradients_match_reference_golden(vsa, case):
+    """Loss, logits, dx on the valid frames and every parameter gradient of a packed step against the reference's float64
+    run on the PADDED batch of the same videos (its mask, its mse_with_mask_loss)."""
+    c = case
+    z = np.load(os.path.join(GOLDEN, c["name"] + ".npz"))
+    xp, tp, R, lengths = _packed_inputs(vsa, c)
+    m = _model(vsa, c)
+    loss, pred, grads = _packed_step(vsa, m, c, xp, tp, R, lengths)
+    assert m.last_train_dtype == "fp32"
+    _check_exact(z, loss, pred, grads, c["name"])
+
+
+@pytest.mark.parametrize("case", padded_cases_that_can_run_packed(), ids=lambda c: c["name"])
+def test_padded_goldens_run_packed(vsa, case):
+    """The existing padded goldens (make_golden_train.py) whose loss takes nothing from padded rows, run packed: same loss,
+    same parameter gradients; dx on the valid rows (the padded rows' dx is zero in the reference)."""
+    c = case
+    assert [k["name"] for k in padded_cases_that_can_run_packed()] == ["train_ma_t320_pad", "train_mb_t150_pad"]
+    z = np.load(os.path.join(GOLDEN, c["name"] + ".npz"))
+    x = vsa.synth.make_features(c["B"], c["T"], c["xseed"], c["kind"], c["lengths"])
+    mask = vsa.synth.padding_mask(x)
+    rng = np.random.Generator(np.random.PCG64(c["tseed"]))
+    target = torch.from_numpy(rng.random(size=(c["B"], c["T"])).astype(np.float32))
+    valid = ~mask
+    lengths = [int(v) for v in valid.sum(1)]
+    assert lengths == c["lengths"]
+    m = _model(vsa, c)
+    loss, pred, grads = _packed_step(vsa, m, c, x[valid], target[valid], None, lengths)
+    assert abs(loss.item() - float(z["loss"])) <= 2e-6 * max(1.0, abs(float(z["loss"])))
+    assert (pred.detach().cpu().view(-1) - torch.from_numpy(z["logits"])[valid].view(-1)).abs().max().item() < 1e-4
+    # the golden's x gradient is [B * T, 1024] in padded order: scatter the packed one back (zeros on padded rows)
+    dx = torch.zeros(c["B"], c["T"], x.shape[2])
+    dx[valid] = grads["x"].cpu()
+    grads["x"] = dx
+    for k in json.loads(str(z["keys"])):
+        g = grads[k]
+        g2 = g.reshape(-1, g.shape[-1]) if g.dim() > 1 else g.reshape(1, -1)
+        rows = torch.from_numpy(z["r:" + k])
+        tot, nrm, gmax, ref32 = z["s:" + k]
+        err = (g2[rows.to(g2.device)].double().cpu() - torch.from_numpy(z["g:" + k]).double()).abs().max().item()
+        assert err <= ATOL and err <= RTOL * gmax + 1e-6, "%s: err %.3e, max|g| %.3e" % (k, err, gmax)
+        assert abs(g.double().norm().item() - nrm) <= 1e-4 * nrm + 1e-7, k
+
+
+def test_positional_table_bounds_the_longest_video_not_the_batch(vsa):
+    """Every video starts at position 0: sum(lengths) may exceed the table, max(lengths) may not - in the module and in the C ABI."""
+    lib = vsa._lib.load()
+    c = dict(H=4, d=256, L=1, wseed=3)
+    m = _model(vsa, c)
+    lengths = [1500, 900]                                   # 2400 rows, table of 2000
+    x = torch.randn(sum(lengths), 1024, generator=torch.Generator().manual_seed(1)).to(_dev())
+    pred, _ = m.forward_packed_train(x, lengths)
+    alone, _ = m.forward_packed_train(x[1500:], [900])
+    assert torch.isfinite(pred).all() and torch.equal(pred[1500:], alone)
+    with pytest.raises(RuntimeError, match="positional table"):
+        m.forward_packed_train(torch.zeros(2001, 1024, device=_dev()), [2001])
+    handle = m._packed_weights(_dev()).handle
+    dl = torch.tensor([2001, 5], dtype=torch.int32, device=_dev())
+    p = x.data_ptr()
+    assert lib.vs_train_forward_packed(handle, p, _i32([2001, 5]), dl.data_ptr(), 2, None, p, None, p, 0, p, 0, _stream()) == vsa._lib.VS_ERR_INVALID
+    assert b"positional table" in lib.vs_last_error()
+    assert lib.vs_train_forward_packed(handle, p, _i32([5, 0]), dl.data_ptr(), 2, None, p, None, p, 0, p, 0, _stream()) == vsa._lib.VS_ERR_INVALID
+    assert b"lengths[1]=0" in lib.vs_last_error()
+    # the handle's sizes are the description's, and the ragged record is smaller than the padded one
+    desc = vsa._lib.ModelDesc(256, 4, 1, 1024, 2000, 1)
+    a = lib.vs_train_saved_bytes_packed(handle, _i32(lengths), 2)
+    assert a == lib.vs_train_saved_bytes_desc(C.byref(desc), _i32(lengths), 2, 0) and 0 < a < lib.vs_train_saved_bytes(handle, 2, 1500)
+    assert lib.vs_train_workspace_bytes_packed(handle, _i32(lengths), 2) > 0
+
+
+def test_scoring_packed_calls_keep_their_no_grad_behaviour(vsa):
+    m = _model(vsa, dict(H=4, d=256, L=2, wseed=3))
+    x = torch.randn(100, 1024, generator=torch.Generator().manual_seed(1)).to(_dev()).requires_grad_(True)
+    a, h = m.forward_packed(x, [60, 40])
+    assert not a.requires_grad and not h.requires_grad and not m.score_packed(x, [60, 40]).requires_grad
+    b, _ = m.eval().forward_packed_train(x, [60, 40])       # eval mode under autograd: the training kernels, dropout off
+    assert b.requires_grad and (a - b.detach()).abs().max().item() < 2e-5
+
+
+# ---------------------------------------------------------------------------------------------
+# bit-equality properties
+# ---------------------------------------------------------------------------------------------
+def _lse_of(vsa, module, out_tensor, lengths, layer):
+    """lse2 [H, Mtot] of one layer from the activation record of a packed forward"""
+    lib = vsa._lib.load()
+    saved = out_tensor.grad_fn.saved_tensors[2]
+    off, cnt = C.c_size_t(), C.c_size_t()
+    vsa._lib.check(lib.vs_train_saved_field_packed(module._packed.handle, _i32(lengths), len(lengths), layer, 4, C.byref(off), C.byref(cnt)))
+    return saved[off.value: off.value + 4 * cnt.value].view(torch.float32).view(module.num_heads, sum(lengths)).clone()
+
+
+@pytest.mark.parametrize("H,d,L,lengths", [(4, 256, 4, [320, 211, 129, 33]), (4, 512, 2, [150, 97, 64, 1]), (1, 256, 1, [131, 90])])
+def test_a_videos_bits_do_not_depend_on_the_batch_it_is_packed_in(vsa, H, d, L, lengths):
+    m = _model(vsa, dict(H=H, d=d, L=L, wseed=5))
+    x = torch.randn(sum(lengths), 1024, generator=torch.Generator().manual_seed(2)).to(_dev())
+    pred, hid = m.forward_packed_train(x, lengths)
+    lse = [_lse_of(vsa, m, pred, lengths, l) for l in range(L)]
+    cu = _cu(lengths)
+    for b, t in enumerate(lengths):
+        p1, h1 = m.forward_packed_train(x[cu[b]:cu[b + 1]], [t])
+        assert torch.equal(p1, pred[cu[b]:cu[b + 1]]) and torch.equal(h1, hid[cu[b]:cu[b + 1]]), b
+        for l in range(L):
+            assert torch.equal(_lse_of(vsa, m, p1, [t], l), lse[l][:, cu[b]:cu[b + 1]]), (b, l)
+
+
+@pytest.mark.parametrize("H,d,L,T", [(4, 256, 2, 211), (4, 512, 1, 150), (1, 256, 1, 90), (8, 256, 1, 33)])
+def test_a_one_video_packed_batch_is_the_padded_call_with_b_1(vsa, H, d, L, T):
+    """B = 1, dropout off: forward outputs and every gradient of the packed path are the bits of vs_train_forward /
+    _backward with B = 1, T = lengths[0] and no mask; and so are the attention kernels' out, lse2 and dqkv."""
+    lib = vsa._lib.load()
+    m = _model(vsa, dict(H=H, d=d, L=L, wseed=6))
+    x = torch.randn(T, 1024, generator=torch.Generator().manual_seed(3))
+    R = torch.randn(T, d, generator=torch.Generator().manual_seed(4)).to(_dev())
+    res = []
+    for packed in (False, True):
+        m.zero_grad(set_to_none=True)
+        xd = x.to(_dev()).requires_grad_(True)
+        pred, hid = m.forward_packed_train(xd, [T]) if packed else m(xd[None], None)
+        ((pred.reshape(-1) ** 2).mean() + 1e-3 * (hid.reshape(T, d) * R).sum()).backward()
+        res.append([("pred", pred.detach().reshape(-1).clone()), ("hidden", hid.detach().reshape(T, d).clone()), ("dx", xd.grad.clone())]
+                   + [(n, q.grad.clone()) for n, q in m.named_parameters()])
+    for (n, a), (_n, b) in zip(*res):
+        assert torch.equal(a, b), n
+    # the kernels alone
+    dh = d // H
+    g = torch.Generator().manual_seed(7)
+    q, k, v = (torch.randn(1, H, T, dh, generator=g).to(_dev()) for _ in range(3))
+    dO = torch.randn(1, T, d, generator=g).to(_dev())
+    scale, seed, site = d ** -0.5, 0x1234567887654321, 7
+    for p in (0.0, 0.3):
+        out = [torch.full((1, T, d), float("nan"), device=_dev()) for _ in range(2)]
+        lse = [torch.full((1, H, T), float("nan"), device=_dev()) for _ in range(2)]
+        dqkv = [torch.full((1, T, 3 * d), float("nan"), device=_dev()) for _ in range(2)]
+        scr = torch.empty(H * T, device=_dev())
+        vsa._lib.check(lib.vs_train_attention_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), None, out[0].data_ptr(), lse[0].data_ptr(),
+                                                      1, H, T, dh, scale, seed, site, p, _stream()))
+        vsa._lib.check(lib.vs_train_attention_backward(q.data_ptr(), k.data_ptr(), v.data_ptr(), None, out[0].data_ptr(), dO.data_ptr(),
+                                                       lse[0].data_ptr(), dqkv[0].data_ptr(), scr.data_ptr(), 1, H, T, dh, scale, seed, site, p, _stream()))
+        host, dl = _i32([T]), torch.tensor([T], dtype=torch.int32, device=_dev())
+        ws = torch.empty(lib.vs_train_attention_packed_scratch_bytes(host, 1, H), dtype=torch.uint8, device=_dev())
+        vsa._lib.check(lib.vs_train_attention_forward_packed(q.data_ptr(), k.data_ptr(), v.data_ptr(), out[1].data_ptr(), lse[1].data_ptr(),
+                                                             host, dl.data_ptr(), 1, H, dh, scale, seed, site, p, ws.data_ptr(), ws.numel(), _stream()))
+        vsa._lib.check(lib.vs_train_attention_backward_packed(q.data_ptr(), k.data_ptr(), v.data_ptr(), out[1].data_ptr(), dO.data_ptr(),
+                                                              lse[1].data_ptr(), dqkv[1].data_ptr(), host, dl.data_ptr(), 1, H, dh, scale,
+                                                              seed, site, p, ws.data_ptr(), ws.numel(), _stream()))
+        torch.cuda.synchronize()
+        assert torch.isfinite(dqkv[0]).all()
+        assert torch.equal(out[0], out[1]) and torch.equal(lse[0], lse[1]) and torch.equal(dqkv[0], dqkv[1]), p
+
+
+def test_two_packed_runs_with_one_seed_are_bitwise_equal(vsa):
+    c = dict(H=4, d=256, L=2, wseed=8, hidden_w=0.0)
+    lengths = [211, 129, 33, 70]
+    x = torch.randn(sum(lengths), 1024, generator=torch.Generator().manual_seed(5))
+    t = torch.rand(sum(lengths), generator=torch.Generator().manual_seed(6))
+
+    def run(seed):
+        m = _model(vsa, c, dropout=0.3, sparsity=0.2)
+        torch.manual_seed(seed)
+        loss, pred, grads = _packed_step(vsa, m, c, x, t, None, lengths)
+        return [loss.detach().clone(), pred.detach().clone()] + [grads[k].clone() for k in sorted(grads)]
+    a, b, other = run(11), run(11), run(12)
+    assert all(torch.equal(u, v) for u, v in zip(a, b))
+    assert not torch.equal(a[1], other[1])                  # another seed, another mask
+
+
+# ---------------------------------------------------------------------------------------------
+# dropout: the exported keep masks drive a float64 torch model, video by video
+# ---------------------------------------------------------------------------------------------
+def _packed_masks(vsa, lengths, d, H, L, seed, p, p_embed):
+    """keep masks of a packed step exactly as the library draws them: row dropouts [Mtot, cols] on the packed row, attention
+    weights per video [H, T_b, T_b] (vs_train_dropout_mask_attention_packed)"""
+    lib = vsa._lib.load()
+    M = sum(lengths)
+
+    def rows(site, cols, pp):
+        k = torch.empty(M, cols, dtype=torch.uint8, device=_dev())
+        vsa._lib.check(lib.vs_train_dropout_mask_rows(k.data_ptr(), M, cols, seed, site, pp, _stream()))
+        return k.cpu()
+
+    masks = {}
+    if p_embed > 0:
+        masks["embed"] = rows(lib.vs_train_dropout_site(-1, 0), d, p_embed)
+    for l in range(L):
+        k = torch.empty(H * sum(t * t for t in lengths), dtype=torch.uint8, device=_dev())
+        vsa._lib.check(lib.vs_train_dropout_mask_attention_packed(k.data_ptr(), _i32(lengths), len(lengths), H, seed,
+                                                                  lib.vs_train_dropout_site(l, 0), p, _stream()))
+        k, off, per = k.cpu(), 0, []
+        for t in lengths:
+            per.append(k[off: off + H * t * t].view(1, H, t, t))
+            off += H * t * t
+        masks["attn%d" % l] = per
+        masks["drop1_%d" % l] = rows(lib.vs_train_dropout_site(l, 1), d, p)
+        masks["mlp%d" % l] = rows(lib.vs_train_dropout_site(l, 2), 4 * d, p)
+        masks["drop2_%d" % l] = rows(lib.vs_train_dropout_site(l, 3), d, p)
+    return masks
+
+
+def _packed_gates(vsa, module, out_tensor, lengths, d, L):
+    lib = vsa._lib.load()
+    saved = out_tensor.grad_fn.saved_tensors[2]
+    gates = {}
+    for l in range(L):
+        off, cnt = C.c_size_t(), C.c_size_t()
+        vsa._lib.check(lib.vs_train_saved_field_packed(module._packed.handle, _i32(lengths), len(lengths), l, 0, C.byref(off), C.byref(cnt)))
+        act = saved[off.value: off.value + 4 * cnt.value].view(torch.float32).view(sum(lengths), 4 * module._lib_d)
+        gates["gate%d" % l] = (act[..., :4 * d] > 0).cpu()
+    return gates
+
+
+PACKED_DROPOUT_STEPS = [(4, 256, 2, [90, 67, 33], 0.3, 0.0), (8, 256, 1, [130], 0.2, 0.5), (4, 512, 1, [70, 47, 1], 0.3, 0.0),
+                        (1, 256, 1, [65, 40], 0.3, 0.0)]
+
+
+@pytest.mark.parametrize("H,d,L,lengths,p,p_embed", PACKED_DROPOUT_STEPS)
+def test_packed_training_step_with_dropout_matches_explicit_mask_model(vsa, H, d, L, lengths, p, p_embed):
+    """test_hip_train.test_training_step_with_dropout_matches_explicit_mask_model on a packed batch: dropout p, the float64
+    model of tests/torch_ref.py run video by video with the keep masks (and ReLU gates) of the packed step; same tolerances.
+    Also: the kept fraction of every exported mask lies in the band test_dropout_hash_statistics uses (5 sigma)."""
+    synth = vsa.synth
+    sd = synth.make_state_dict(d, L, 21)
+    m = vsa.SimNet(num_heads=H, d_model=d, num_layers=L, sparsity=p_embed, dropout=p)
+    m.load_state_dict(sd, strict=True)
+    m = m.to(_dev()).train()
+    M, B, cu = sum(lengths), len(lengths), _cu(lengths)
+    x = torch.randn(M, 1024, generator=torch.Generator().manual_seed(22))
+    target = torch.rand(M, generator=torch.Generator().manual_seed(1))
+    torch.manual_seed(77)
+    seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())        # what forward_packed_train will draw
+    torch.manual_seed(77)
+    xd = x.to(_dev()).requires_grad_(True)
+    pred, hidden = m.forward_packed_train(xd, lengths)
+    loss = vsa.mse_packed_loss(pred, target.to(_dev()), lengths) + 1e-3 * hidden.sum()
+    gates = _packed_gates(vsa, m, pred, lengths, d, L)
+    loss.backward()
+    torch.cuda.synchronize()
+    masks = _packed_masks(vsa, lengths, d, H, L, seed, p, p_embed)
+    for name, k in masks.items():
+        for part in (k if isinstance(k, list) else [k]):
+            pp = p_embed if name == "embed" else p
+            rate, n = part.double().mean().item(), part.numel()
+            assert abs(rate - (1 - pp)) < 5 * math.sqrt(pp * (1 - pp) / n), (name, rate, n)
+    params = {k: v.double().clone().requires_grad_(k != "embedding_layer.positional_encoding.pos_embedding") for k, v in sd.items()}
+    x64 = x.double().clone().requires_grad_(True)
+    rloss, rl = 0.0, []
+    for b, t in enumerate(lengths):
+        sl = slice(cu[b], cu[b + 1])
+        mb = {k: (v[b] if isinstance(v, list) else v[sl][None]) for k, v in masks.items()}
+        gb = {k: v[sl][None] for k, v in gates.items()}
+        logits, hid = torch_ref.forward_with_masks(params, x64[sl][None], None, H, p, p_embed, mb, None, gb)
+        rloss = rloss + ((logits.view(-1) - target[sl].double()) ** 2).sum() / (B * max(lengths)) + 1e-3 * hid.sum()
+        rl.append(logits.detach().view(-1))
+    rloss.backward()
+    assert (pred.detach().cpu().double().view(-1) - torch.cat(rl)).abs().max().item() < 1e-4
+    assert abs(loss.item() - rloss.item()) < 1e-5 * max(1.0, abs(rloss.item()))
+    _close(xd.grad, x64.grad, "dx")
+    for k, prm in m.named_parameters():
+        _close(prm.grad, params[k].grad, k)
+    with torch.no_grad():                                    # and dropout really happened
+        e, _ = m.eval().forward_packed_train(x.to(_dev()), lengths)      # (the scoring packed call has no head dim 256)
+    assert (e - pred.detach()).abs().max().item() > 1e-3
+
+
+# ---------------------------------------------------------------------------------------------
+# the attention kernels alone, against float64 per video
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("H,dh,lengths,p", [(4, 64, [320, 211, 129, 33], 0.0), (8, 32, [65, 1, 97], 0.5), (2, 128, [260, 150, 33], 0.2),
+                                            (4, 128, [150, 97, 64, 1], 0.0), (1, 256, [131, 40], 0.0), (1, 256, [90, 57], 0.3)])
+def test_packed_attention_forward_and_backward_kernels(vsa, H, dh, lengths, p):
+    """vs_train_attention_forward_packed / _backward_packed (values, saved log-sum-exp, dq | dk | dv) against float64 torch
+    autograd per video, the library's own keep mask applied in the checker; the bounds of
+    test_hip_train.test_attention_forward_and_backward_kernels."""
+    lib = vsa._lib.load()
+    B, M, d, cu = len(lengths), sum(lengths), H * dh, _cu(lengths)
+    scale, seed, site = d ** -0.5, 0x1234567887654321, 7
+    g = torch.Generator().manual_seed(100 + M)
+    q, k, v = (torch.randn(H, M, dh, generator=g, dtype=torch.float64) for _ in range(3))
+    dO = torch.randn(M, d, generator=torch.Generator().manual_seed(9), dtype=torch.float64)
+    keep = None
+    if p > 0:
+        kd = torch.empty(H * sum(t * t for t in lengths), dtype=torch.uint8, device=_dev())
+        vsa._lib.check(lib.vs_train_dropout_mask_attention_packed(kd.data_ptr(), _i32(lengths), B, H, seed, site, p, _stream()))
+        kd, off, keep = kd.cpu(), 0, []
+        for t in lengths:
+            keep.append(kd[off: off + H * t * t].view(1, H, t, t))
+            off += H * t * t
+        rate = kd.double().mean().item()
+        assert abs(rate - (1 - p)) < 5 * math.sqrt(p * (1 - p) / kd.numel()), rate
+    qd, kd_, vd = (t.float().to(_dev()).contiguous() for t in (q, k, v))
+    host, dl = _i32(lengths), torch.tensor(lengths, dtype=torch.int32, device=_dev())
+    ws = torch.empty(lib.vs_train_attention_packed_scratch_bytes(host, B, H), dtype=torch.uint8, device=_dev())
+    out = torch.full((M, d), float("nan"), device=_dev())
+    lse = torch.full((H, M), float("nan"), device=_dev())
+    dqkv = torch.full((M, 3 * d), float("nan"), device=_dev())
+    dOd = dO.float().to(_dev())
+    vsa._lib.check(lib.vs_train_attention_forward_packed(qd.data_ptr(), kd_.data_ptr(), vd.data_ptr(), out.data_ptr(), lse.data_ptr(), host,
+                                                         dl.data_ptr(), B, H, dh, scale, seed, site, p, ws.data_ptr(), ws.numel(), _stream()))
+    vsa._lib.check(lib.vs_train_attention_backward_packed(qd.data_ptr(), kd_.data_ptr(), vd.data_ptr(), out.data_ptr(), dOd.data_ptr(),
+                                                          lse.data_ptr(), dqkv.data_ptr(), host, dl.data_ptr(), B, H, dh, scale, seed, site, p,
+                                                          ws.data_ptr(), ws.numel(), _stream()))
+    torch.cuda.synchronize()
+    assert torch.isfinite(out).all() and torch.isfinite(lse).all() and torch.isfinite(dqkv).all()       # every row written
+    for b, t in enumerate(lengths):
+        sl = slice(cu[b], cu[b + 1])
+        qb, kb, vb = (u[:, sl][None].clone().requires_grad_(True) for u in (q, k, v))
+        want, lse2 = torch_ref.attention_with_mask(qb, kb, vb, None, scale, None if keep is None else keep[b], p)
+        want.backward(dO[sl][None])
+        _close(out[sl], want[0], "attention out, video %d" % b)
+        assert (lse[:, sl].cpu().double() - lse2.detach()[0]).abs().max().item() < 1e-4
+        tok = lambda gr: gr[0].permute(1, 0, 2).reshape(t, d)       # noqa: E731  head-major grad -> token-major
+        _close(dqkv[sl, :d], tok(qb.grad), "dq, video %d" % b)
+        _close(dqkv[sl, d:2 * d], tok(kb.grad), "dk, video %d" % b)
+        _close(dqkv[sl, 2 * d:], tok(vb.grad), "dv, video %d" % b)
+
+
+# ---------------------------------------------------------------------------------------------
+# low precision: Linears / dgrad / wgrad on the 16-bit pipe, the packed attention exact
+# ---------------------------------------------------------------------------------------------
+@pytest.fixture
+def lp_train_everywhere(vsa):
+    vsa._lib.set_option("VS_TRAIN_LP_MIN_ROWS", 0)
+    yield
+    vsa._lib.set_option("VS_TRAIN_LP_MIN_ROWS", -1)
+
+
+def test_packed_bf16_training_gradients_within_the_low_precision_tolerance(vsa, lp_train_everywhere):
+    """set_train_dtype("bf16") on the M-A packed golden: loss and gradients at tests/tolerances.py's TRAIN_LP_* (the checks of
+    test_hip_train.test_bf16_training_gradients_within_the_low_precision_tolerance); the attention ran exact."""
+    c = [k for k in packed_cases() if k["name"] == "train_packed_ma"][0]
+    z = np.load(os.path.join(GOLDEN, c["name"] + ".npz"))
+    xp, tp, R, lengths = _packed_inputs(vsa, c)
+    m = _model(vsa, c).set_train_dtype("bf16")
+    loss, pred, grads = _packed_step(vsa, m, c, xp, tp, R, lengths)
+    assert m.last_train_dtype == "bf16"
+    assert (int(vsa._lib.load().vs_train_last_format()) & 3) == 1          # bf16 Linears, exact attention
+    want = float(z["loss"])
+    assert abs(loss.item() - want) <= tol.TRAIN_LP_LOSS_RTOL * max(1.0, abs(want)), (loss.item(), want)
+    worst, worst_l2 = 0.0, 0.0
+    for k in json.loads(str(z["keys"])):
+        g = grads[k]
+        assert g is not None and torch.isfinite(g).all(), k
+        g2 = g.reshape(-1, g.shape[-1]) if g.dim() > 1 else g.reshape(1, -1)
+        rows = torch.from_numpy(z["r:" + k])
+        want_g = torch.from_numpy(z["g:" + k]).double()
+        tot, nrm, gmax, ref32 = z["s:" + k]
+        diff = g2[rows.to(g2.device)].double().cpu() - want_g
+        err = diff.abs().max().item()
+        l2 = diff.norm().item() / (want_g.norm().item() + 1e-30)
+        if gmax < 1e-6:
+            assert g.double().norm().item() <= tol.TRAIN_LP_ZERO_ATOL, "%s: |g| %.3e" % (k, g.double().norm().item())
+            continue
+        assert err <= tol.TRAIN_LP_GRAD_RTOL * gmax + 1e-6, "%s: err %.3e, max|g| %.3e" % (k, err, gmax)
+        if k.endswith("mlp.fc1.weight") and diff.dim() > 1 and diff.shape[0] >= 4 and l2 > tol.TRAIN_LP_GRAD_L2:
+            sq = diff.pow(2).sum(-1)                         # the ReLU-flip allowance of tests/tolerances.py, fc1.weight only
+            keep_rows = torch.ones_like(sq, dtype=torch.bool)
+            keep_rows[sq.argmax()] = False
+            l2 = sq[keep_rows].sum().sqrt().item() / (want_g[keep_rows].norm().item() + 1e-30)
+            assert l2 <= tol.TRAIN_LP_FC1_L2, "%s: relative L2 error %.3e with the flipped unit's row set aside" % (k, l2)
+            l2 = 0.0
+        assert l2 <= (tol.TRAIN_LP_FC1_L2 if k.endswith("mlp.fc1.bias") else tol.TRAIN_LP_GRAD_L2), "%s: relative L2 error %.3e" % (k, l2)
+        assert abs(g.double().norm().item() - nrm) <= 2e-2 * nrm + 1e-7, k
+        worst, worst_l2 = max(worst, err / gmax), max(worst_l2, l2)
+    assert worst > 1e-5, "the low-precision path did not run (gradients at exact-fp32 accuracy)"
+    print("train_packed_ma: bf16 Linears, worst error relative to the tensor's max %.2e, worst relative L2 %.2e" % (worst, worst_l2))
+    m.set_train_dtype("fp16")
+    m.zero_grad(set_to_none=True)
+    loss16, _, g16 = _packed_step(vsa, m, c, xp, tp, R, lengths)
+    assert m.last_train_dtype == "fp16" and abs(loss16.item() - want) <= tol.TRAIN_FP16_LOSS_RTOL * max(1.0, abs(want))
+    assert all(torch.isfinite(t).all() for t in g16.values())
+
+
+# ---------------------------------------------------------------------------------------------
+# the reference's loop on packed batches
+# ---------------------------------------------------------------------------------------------
+def _videos(n, seed):
+    rng = np.random.Generator(np.random.PCG64(seed))
+    vids = []
+    for _ in range(n):
+        t = int(rng.integers(40, 200))
+        f = (np.abs(rng.standard_normal((t, 1024))) * 0.5).astype(np.float32)
+        gt = 1.0 / (1.0 + np.exp(-(f[:, :8].sum(1) - f[:, 8:16].sum(1))))
+        vids.append((torch.from_numpy(f), torch.from_numpy(gt.astype(np.float32))))
+    return vids
+
+
+def test_packed_loss_curve_tracks_float64_like_the_padded_path(vsa):
+    """20 steps of harness.train_step_packed (autocast, GradScaler, Adam) against tests/torch_ref.py in float64 on the PADDED
+    batches - same initial weights, dropout 0 - and, measured in the same test, the padded HIP path on the same batches.
+    The packed loss curve may leave the float64 curve by at most twice what the padded HIP path leaves it, plus 1e-7."""
+    data = importlib.import_module("video-summarization_amd.data")
+    harness = importlib.import_module("video-summarization_amd.harness")
+    H, d, L, steps = 4, 256, 2, 20
+    sd = vsa.synth.make_state_dict(d, L, 3)
+    vids = _videos(6, 41)
+    batches = [vids[:3], vids[3:]]
+    adam = dict(lr=1e-4, weight_decay=0.01)
+
+    def hip(packed):
+        m = vsa.SimNet(num_heads=H, d_model=d, num_layers=L, sparsity=0.0, dropout=0.0)
+        m.load_state_dict(sd)
+        m = m.to(_dev())
+        opt = torch.optim.Adam(m.parameters(), **adam)
+        scaler = torch.amp.GradScaler("cuda")
+        curve = []
+        for i in range(steps):
+            if packed:
+                curve.append(harness.train_step_packed(m, opt, [data.collate_fn_train_packed(batches[i % 2])], scaler, _dev()))
+                continue
+            feature, target = (t.to(_dev()) for t in data.collate_fn_train(batches[i % 2]))        # train.py:111-131
+            m.train()
+            mask = (feature[:, :, 0] == 1000)
+            with torch.amp.autocast("cuda"):
+                pred, _ = m(feature, mask)
+                loss = vsa.mse_with_mask_loss(pred, target, mask)
+            opt.zero_grad()
+            scaler.scale(loss).backward()
+            scaler.step(opt)
+            scaler.update()
+            curve.append(loss.item())
+        return curve
+
+    def f64():
+        params = {k: v.double().clone().requires_grad_(k != "embedding_layer.positional_encoding.pos_embedding") for k, v in sd.items()}
+        opt = torch.optim.Adam([p for p in params.values() if p.requires_grad], **adam)
+        curve = []
+        for i in range(steps):
+            feature, target = data.collate_fn_train(batches[i % 2])
+            mask = (feature[:, :, 0] == 1000)
+            pred, _ = torch_ref.forward_with_masks(params, feature.double(), mask, H)
+            loss = (((pred.squeeze(2) - target.double()) * (~mask).double()) ** 2).mean()       # utils.py:45-56
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            curve.append(loss.item())
+        return curve
+
+    ref, padded, packed = f64(), hip(False), hip(True)
+    dev_padded = max(abs(a - b) for a, b in zip(padded, ref))
+    dev_packed = max(abs(a - b) for a, b in zip(packed, ref))
+    print("loss curve over %d steps: float64 %.6f -> %.6f; max |padded HIP - float64| %.3e, max |packed HIP - float64| %.3e"
+          % (steps, ref[0], ref[-1], dev_padded, dev_packed))
+    assert all(math.isfinite(v) for v in packed) and ref[-1] < ref[0]
+    assert dev_packed <= 2.0 * dev_padded + 1e-7, (dev_packed, dev_padded)
+
+
+@pytest.mark.parametrize("native", [False, True])
+def test_train_step_packed_with_both_optimizers_and_an_unmodified_gradscaler(vsa, native):
+    """dropout on, several epochs over a shuffled DataLoader: the loss falls with torch.optim.Adam and with the native Adam
+    (one HIP launch, write-through into the packed weights), under a plain torch.amp.GradScaler; same seed, same bits."""
+    from torch.utils.data import DataLoader
+    data = importlib.import_module("video-summarization_amd.data")
+    harness = importlib.import_module("video-summarization_amd.harness")
+    vids = _videos(8, 43)
+
+    def run():
+        torch.manual_seed(1234)
+        m = vsa.SimNet(num_heads=4, d_model=256, num_layers=2, sparsity=0.0, dropout=0.3).to(_dev())
+        m.load_state_dict(vsa.synth.make_state_dict(256, 2, 3))
+        opt = vsa.Adam(m.parameters(), lr=3e-4, weight_decay=0.01).attach(m) if native else torch.optim.Adam(m.parameters(), lr=3e-4, weight_decay=0.01)
+        scaler = torch.amp.GradScaler("cuda")
+        loader = DataLoader(vids, shuffle=True, num_workers=0, collate_fn=data.collate_fn_train_packed, batch_size=4,
+                            generator=torch.Generator().manual_seed(5))
+        losses = [harness.train_step_packed(m, opt, loader, scaler, _dev()) for _ in range(10)]
+        return losses, [p.detach().clone() for p in m.parameters()]
+    l1, p1 = run()
+    l2, p2 = run()
+    assert all(math.isfinite(v) for v in l1) and min(l1[-3:]) < l1[0], l1
+    assert l1 == l2 and all(torch.equal(a, b) for a, b in zip(p1, p2))

@@ -4,10 +4,20 @@ reference's own regime (train.py: batch 4, a few hundred frames) and at the benc
 Beside it, for context only, the same step composed from torch ops on the same GPU (tests/torch_ref.py, rocBLAS /
 ATen kernels - what the reference's nn.Module does on a GPU, minus its per-layer .cpu() copy of the attention maps).
 
-    python tools/bench_train.py [--dropout 0.3] [--torch] [--optim {torch,torch-fused,native}]"""
+    python tools/bench_train.py [--dropout 0.3] [--torch] [--optim {torch,torch-fused,native}]
+
+``--packed``: training on packed ragged batches against the padded step on the SAME videos (lengths drawn with a fixed seed
+from ``synth.corpus_lengths``: 100 to 650 frames), forward + loss + backward, exact fp32 and bf16, at ``--batches`` (default
+the reference's 4, and 64).  Every timed leg runs in a child process of its own under a time limit; beside the times it prints
+the batch's fill sum T_i / (B Tmax) - the expected ratio of the Linears - and sum T_i^2 / (B Tmax^2), that of the attention,
+and the bytes of the activation record in both forms.
+
+    python tools/bench_train.py --packed [--batches 4,64] [--seed 7] [--leg-timeout 240]"""
 import argparse
 import importlib
+import json
 import os
+import subprocess
 import sys
 import time
 
@@ -30,7 +40,51 @@ ap.add_argument("--optim", choices=("torch", "torch-fused", "native"), default="
 ap.add_argument("--only-step", action="store_true", help="time only the whole fp32 train_step, repeated (for a spread)")
 ap.add_argument("--repeats", type=int, default=5, help="repetitions of --only-step")
 ap.add_argument("--only-bf16", action="store_true", help="time only the set_train_dtype('bf16') step (for a kernel profile)")
+ap.add_argument("--packed", action="store_true", help="packed ragged batches against the padded step on the same videos")
+ap.add_argument("--batches", default="4,64", help="--packed: batch sizes")
+ap.add_argument("--seed", type=int, default=7, help="--packed: seed of the length draw")
+ap.add_argument("--leg-timeout", type=int, default=240, help="--packed: seconds each timed leg may take")
+ap.add_argument("--packed-leg", default=None, help="(internal) one timed leg: B,dtype,form")
 args = ap.parse_args()
+
+
+def packed_driver():
+    """one child process per timed leg (this process never opens the GPU), then the table"""
+    H_, d_, L_ = (4, 256, 4) if args.model == "A" else (4, 512, 3)
+    print("packed ragged batches vs the padded step on the same videos: model M-%s, dropout %g, fwd + loss + bwd, %d iterations per leg"
+          % (args.model, args.dropout, args.iters), flush=True)
+    for B in (int(v) for v in args.batches.split(",")):
+        ls = pkg.synth.corpus_lengths(B, args.seed)
+        tmax, rows = max(ls), sum(ls)
+        fill, att = rows / (B * tmax), sum(t * t for t in ls) / (B * tmax * tmax)
+        print("B=%d  lengths %d..%d (seed %d)  rows %d packed / %d padded  fill sum T / (B Tmax) = %.3f  attention sum T^2 / (B Tmax^2) = %.3f"
+              % (B, min(ls), tmax, args.seed, rows, B * tmax, fill, att), flush=True)
+        # "bf16-linear": VS_TRAIN_FLAG_BF16_LINEAR alone in BOTH forms (exact attention) - what the packed form runs under
+        # set_train_dtype("bf16"), whose padded form has the bf16 attention kernels on top
+        for dtype in ("fp32", "bf16", "bf16-linear"):
+            res = {}
+            for form in ("padded", "packed"):
+                cmd = [sys.executable, os.path.abspath(__file__), "--packed-leg", "%d,%s,%s" % (B, dtype, form), "--seed", str(args.seed),
+                       "--model", args.model, "--dropout", str(args.dropout), "--iters", str(args.iters)]
+                try:
+                    r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.leg_timeout)
+                except subprocess.TimeoutExpired:
+                    print("  %s %s: no result within %d s - stopping" % (dtype, form, args.leg_timeout), flush=True)
+                    sys.exit(1)
+                if r.returncode != 0:
+                    print("  %s %s: exit status %d - stopping\n%s" % (dtype, form, r.returncode, r.stderr[-2000:]), flush=True)
+                    sys.exit(1)
+                res[form] = json.loads(r.stdout.strip().split("\n")[-1])
+            a, b = res["padded"], res["packed"]
+            print("  %-11s (ran %s / %s)  padded %.3f ms  packed %.3f ms  packed / padded = %.3f  | record %.1f MiB padded, %.1f MiB packed (%.3f)"
+                  % (dtype, a["ran"], b["ran"], a["ms"], b["ms"], b["ms"] / a["ms"], a["record"] / 2 ** 20, b["record"] / 2 ** 20,
+                     b["record"] / a["record"]), flush=True)
+
+
+if args.packed and not args.packed_leg:
+    packed_driver()
+    sys.exit(0)
+
 dev = torch.device("cuda:0")
 H, d, L = (4, 256, 4) if args.model == "A" else (4, 512, 3)
 sd = pkg.synth.make_state_dict(d, L, 1234)
@@ -49,6 +103,45 @@ def timed(fn, iters):
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / iters * 1e3
 
+
+if args.packed_leg:
+    import ctypes
+    B, dtype, form = args.packed_leg.split(",")
+    B = int(B)
+    ls = pkg.synth.corpus_lengths(B, args.seed)
+    tmax = max(ls)
+    g = torch.Generator().manual_seed(args.seed)
+    xp = torch.randn(sum(ls), 1024, generator=g).to(dev)
+    tp = torch.rand(sum(ls), generator=g).to(dev)
+    x = torch.full((B, tmax, 1024), 1000.0, device=dev)
+    target = torch.full((B, tmax), 1000.0, device=dev)
+    off = 0
+    for b, n in enumerate(ls):
+        x[b, :n], target[b, :n] = xp[off:off + n], tp[off:off + n]
+        off += n
+    mask = x[:, :, 0] == 1000
+    m.set_train_dtype("bf16" if dtype == "bf16-linear" else dtype)
+    if dtype == "bf16-linear":
+        m._train_flags = lambda: pkg._lib.VS_TRAIN_FLAG_BF16_LINEAR
+
+    def padded_step():
+        pred, _ = m(x, mask)
+        loss = pkg.mse_with_mask_loss(pred, target, mask)
+        m.zero_grad(set_to_none=True)
+        loss.backward()
+
+    def packed_step():
+        pred, _ = m.forward_packed_train(xp, ls)
+        loss = pkg.mse_packed_loss(pred, tp, ls)
+        m.zero_grad(set_to_none=True)
+        loss.backward()
+
+    ms = timed(packed_step if form == "packed" else padded_step, args.iters)
+    lib, handle = pkg._lib.load(), m._packed_weights(dev).handle
+    record = (lib.vs_train_saved_bytes_packed(handle, (ctypes.c_int32 * B)(*ls), B) if form == "packed"
+              else lib.vs_train_saved_bytes(handle, B, tmax))
+    print(json.dumps({"B": B, "dtype": dtype, "form": form, "ms": ms, "record": int(record), "ran": m.last_train_dtype}))
+    sys.exit(0)
 
 for shape in args.shapes.split(","):
     B, T = (int(v) for v in shape.split("x"))

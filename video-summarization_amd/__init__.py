@@ -7,11 +7,11 @@ module ``video_summarization_amd``.
 from . import _lib, synth  # noqa: F401
 from .simnet import SimNet, score_frames  # noqa: F401
 from .pretrain import PretrainModel  # noqa: F401
-from .losses import mse_with_mask_loss  # noqa: F401
+from .losses import mse_packed_loss, mse_with_mask_loss  # noqa: F401
 from . import segmentation  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import Adam, AdamW  # noqa: F401
 from .segmentation import get_segment_fn, kts_seg, kts_seg_batch  # noqa: F401
 
-__all__ = ["SimNet", "PretrainModel", "score_frames", "synth", "mse_with_mask_loss", "segmentation", "get_segment_fn", "kts_seg",
+__all__ = ["SimNet", "PretrainModel", "score_frames", "synth", "mse_with_mask_loss", "mse_packed_loss", "segmentation", "get_segment_fn", "kts_seg",
            "kts_seg_batch", "optim", "Adam", "AdamW"]

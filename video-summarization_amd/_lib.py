@@ -52,7 +52,12 @@ TRAIN_EXPORTS = ("vs_train_prepare", "vs_train_saved_bytes", "vs_train_workspace
                  "vs_train_attention_forward_bf16", "vs_train_attention_backward_bf16", "vs_train_wgrad_scratch_floats", "vs_train_wgrad", "vs_train_wgrad_bf16",
                  "vs_train_dropout_mask_attention", "vs_train_dropout_mask_rows", "vs_train_dropout_site", "vs_train_saved_field", "vs_train_last_format",
                  "vs_pretrain_head_state_bytes", "vs_pretrain_head_workspace_bytes", "vs_pretrain_head_forward",
-                 "vs_pretrain_head_backward")
+                 "vs_pretrain_head_backward",
+                 # packed ragged batches
+                 "vs_train_check_packed", "vs_train_saved_bytes_desc", "vs_train_saved_bytes_packed", "vs_train_workspace_bytes_packed",
+                 "vs_train_forward_packed", "vs_train_backward_packed", "vs_mse_packed_loss_forward", "vs_mse_packed_loss_backward",
+                 "vs_train_attention_packed_scratch_bytes", "vs_train_attention_forward_packed", "vs_train_attention_backward_packed",
+                 "vs_train_dropout_mask_attention_packed", "vs_train_saved_field_packed")
 # include/vs_segment.h (kernel temporal segmentation)
 SEGMENT_EXPORTS = ("vs_kts_workspace_bytes", "vs_kts_segment", "vs_kts_scatters")
 # include/vs_optim.h (the Adam step)
@@ -342,6 +347,40 @@ def load() -> C.CDLL:
                                              C.POINTER(C.c_size_t)]
         lib.vs_train_dropout_site.restype = C.c_uint32
         lib.vs_train_dropout_site.argtypes = [C.c_int32, C.c_int32]
+        # ... packed ragged batches (lengths: host int32 array, then the same values on the device)
+        lib.vs_train_check_packed.restype = C.c_int
+        lib.vs_train_check_packed.argtypes = [C.POINTER(ModelDesc), C.c_void_p, C.c_int32]
+        lib.vs_train_saved_bytes_desc.restype = C.c_size_t
+        lib.vs_train_saved_bytes_desc.argtypes = [C.POINTER(ModelDesc), C.c_void_p, C.c_int32, C.c_int32]
+        lib.vs_train_saved_bytes_packed.restype = C.c_size_t
+        lib.vs_train_saved_bytes_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        lib.vs_train_workspace_bytes_packed.restype = C.c_size_t
+        lib.vs_train_workspace_bytes_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        lib.vs_train_forward_packed.restype = C.c_int
+        lib.vs_train_forward_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(DropoutCfg),
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.vs_train_backward_packed.restype = C.c_int
+        lib.vs_train_backward_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(DropoutCfg),
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ModelGrads), C.c_void_p,
+                                                 C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.vs_mse_packed_loss_forward.restype = C.c_int
+        lib.vs_mse_packed_loss_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.vs_mse_packed_loss_backward.restype = C.c_int
+        lib.vs_mse_packed_loss_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
+        lib.vs_train_attention_packed_scratch_bytes.restype = C.c_size_t
+        lib.vs_train_attention_packed_scratch_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        lib.vs_train_attention_forward_packed.restype = C.c_int
+        lib.vs_train_attention_forward_packed.argtypes = ([C.c_void_p] * 7 + [C.c_int32] * 3 + [C.c_float, C.c_uint64, C.c_uint32, C.c_float,
+                                                                                            C.c_void_p, C.c_size_t, C.c_void_p])
+        lib.vs_train_attention_backward_packed.restype = C.c_int
+        lib.vs_train_attention_backward_packed.argtypes = ([C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_float, C.c_uint64, C.c_uint32, C.c_float,
+                                                                                             C.c_void_p, C.c_size_t, C.c_void_p])
+        lib.vs_train_dropout_mask_attention_packed.restype = C.c_int
+        lib.vs_train_dropout_mask_attention_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32,
+                                                               C.c_float, C.c_void_p]
+        lib.vs_train_saved_field_packed.restype = C.c_int
+        lib.vs_train_saved_field_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t),
+                                                    C.POINTER(C.c_size_t)]
         # include/vs_segment.h
         lib.vs_kts_workspace_bytes.restype = C.c_size_t
         lib.vs_kts_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]

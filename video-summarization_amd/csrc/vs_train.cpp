@@ -52,14 +52,42 @@ struct RecordForm {
     }
 };
 thread_local uint32_t g_last_format = 0;
-RecordForm derive_form(const vs_weights *w, const vs_dropout_cfg *drop, int B, int T) {
+
+// A packed ragged batch (vs_train_forward_packed) as the host sees it: every row-wise kernel runs it as ONE "video" of Mtot
+// rows (B = 1, T = Mtot below); the positional rows, the attention, its keep words and the loss know the boundaries.
+struct PackedCtx {
+    int B = 0, Mtot = 0, tmax = 0, nwork = 0;      // nwork: (video, 128-row owner tile) pairs
+    size_t words = 0;                              // keep words per head and orientation: sum T_b * ceil(T_b / 32)
+    const int *lengths_dev = nullptr;
+};
+
+int packed_ctx(const vs_model_desc &D, const int32_t *lengths, int32_t B, PackedCtx &pc) {
+    if (!lengths || B <= 0) return failf(VS_ERR_INVALID, "lengths is NULL or B=%d", B);
+    pc = PackedCtx{};
+    pc.B = B;
+    long long rows = 0, words = 0, nwork = 0;
+    for (int b = 0; b < B; ++b) {
+        const int t = lengths[b];
+        if (t <= 0) return failf(VS_ERR_INVALID, "lengths[%d]=%d", b, t);
+        if (D.max_len > 0 && t > D.max_len)
+            return failf(VS_ERR_INVALID, "lengths[%d]=%d exceeds the positional table (max_len=%d)", b, t, D.max_len);
+        rows += t; words += (long long)t * ((t + 31) / 32); nwork += (t + 127) / 128;
+        pc.tmax = t > pc.tmax ? t : pc.tmax;
+    }
+    if (rows > (1ll << 28) || words >= (1ll << 31)) return failf(VS_ERR_INVALID, "too many frames (%lld rows, %lld keep words per head)", rows, words);
+    pc.Mtot = (int)rows; pc.words = (size_t)words; pc.nwork = (int)nwork;
+    return VS_OK;
+}
+
+RecordForm derive_form(const vs_weights *w, const vs_dropout_cfg *drop, int B, int T, bool packed = false) {
     RecordForm f{};
     // low-precision training (VS_TRAIN_FLAG_BF16_LINEAR): every Linear / dgrad / wgrad GEMM on the bf16 matrix pipe, from the
     // batch size up where that pays (VS_TRAIN_LP_MIN_ROWS, default 1024 frames: tools/sweep_lp_min_rows.py,
     // profiles/r04_lp_min_rows_sweep.txt - break-even at ~1280 frames, never slower; rounds 2-3 used the scoring path's 8192)
     f.lp = (drop && (drop->flags & VS_TRAIN_FLAG_BF16_LINEAR) && (long long)B * T > vsk_options().train_lp_min_rows) ? 1 : 0;
     // ... and (VS_TRAIN_FLAG_BF16_ATTENTION) the attention products of the forward and the backward (head dim 32 / 64 / 128)
-    f.lpa = drop && (drop->flags & VS_TRAIN_FLAG_BF16_ATTENTION) && (long long)B * T > vsk_options().train_lp_min_rows &&
+    // (packed ragged batches: the attention stays exact fp32 whatever the flag says - there is no packed bf16 form yet)
+    f.lpa = !packed && drop && (drop->flags & VS_TRAIN_FLAG_BF16_ATTENTION) && (long long)B * T > vsk_options().train_lp_min_rows &&
             vst_attention_bf16_supported(w->desc.d_model / w->desc.num_heads);
     // bf16 STORAGE of the tensors that are only ever bf16 matrix operands (VS_LP_STORE32 = 1 keeps them fp32: an A/B switch -
     // the kernels round the fp32-stored values to the same bf16, so every result is bit-identical either way)
@@ -80,7 +108,7 @@ struct SavedLayout {
     size_t h0 = 0, total = 0;
     std::vector<LayerSaved> layers;
 };
-SavedLayout saved_layout(const vs_model_desc &D, int B, int T) {
+SavedLayout saved_layout(const vs_model_desc &D, int B, int T, const PackedCtx *pc = nullptr) {
     SavedLayout S;
     const size_t M = (size_t)B * T, d = D.d_model;
     size_t off = 0;
@@ -92,15 +120,16 @@ SavedLayout saved_layout(const vs_model_desc &D, int B, int T) {
         L.z1 = take(M * d); L.st1 = take(2 * M); L.y1 = take(M * d);
         L.ffn = take(4 * M * d);
         L.z2 = take(M * d); L.st2 = take(2 * M); L.y2 = take(M * d);
-        L.dbits = take(vst_attention_dropout_bits_words(B, D.num_heads, T));     // the layer's attention keep masks, bit-packed
+        // the layer's attention keep masks, bit-packed (packed batches: per video, T_b * ceil(T_b / 32) words, not Mtot^2 / 32)
+        L.dbits = take(pc ? 2 * (size_t)D.num_heads * pc->words : vst_attention_dropout_bits_words(B, D.num_heads, T));
     }
     S.total = off;
     return S;
 }
 
 // ---- scratch (floats): the forward uses `a` only ----
-struct WorkLayout { size_t a, g0, g1, dz, dbr, gf, dy1, datt, dqkv, delta, part, wg, total; };
-WorkLayout work_layout(const vs_model_desc &D, int B, int T) {
+struct WorkLayout { size_t a, g0, g1, dz, dbr, gf, dy1, datt, dqkv, delta, part, wg, pe, plan, total; };
+WorkLayout work_layout(const vs_model_desc &D, int B, int T, const PackedCtx *pc = nullptr) {
     WorkLayout W{};
     const size_t M = (size_t)B * T, d = D.d_model, din = D.in_features;
     size_t off = 0;
@@ -121,15 +150,18 @@ WorkLayout work_layout(const vs_model_desc &D, int B, int T) {
         wg = f > wg ? f : wg;
     }
     W.wg = take(wg);
+    // packed batches: the positional rows gathered per frame (forward) and the device plan (cu | bo | work list)
+    W.pe = take(pc && D.max_len > 0 ? M * d : 0);
+    W.plan = take(pc ? vst_packed_plan_ints(pc->B, pc->nwork) : 0);
     W.total = off;
     return W;
 }
 
-int check_common(const vs_weights *w, const float *x, int B, int T, const vs_dropout_cfg *drop) {
+int check_common(const vs_weights *w, const float *x, int B, int T, const vs_dropout_cfg *drop, bool packed = false) {
     if (!w || !x) return failf(VS_ERR_INVALID, "weights/x is NULL");
     if (B <= 0 || T <= 0) return failf(VS_ERR_INVALID, "B=%d T=%d", B, T);
     if ((long long)B * T > (1ll << 28)) return failf(VS_ERR_INVALID, "B*T too large");
-    if (w->has_pe && T > w->desc.max_len)
+    if (!packed && w->has_pe && T > w->desc.max_len)
         return failf(VS_ERR_INVALID, "T=%d exceeds the positional table (max_len=%d)", T, w->desc.max_len);
     if (drop && (drop->p < 0.f || drop->p >= 1.f || drop->p_embed < 0.f || drop->p_embed >= 1.f))
         return failf(VS_ERR_INVALID, "dropout probabilities must be in [0, 1): p=%g p_embed=%g", drop->p, drop->p_embed);
@@ -261,14 +293,15 @@ uint32_t vs_train_last_format(void) { return g_last_format; }
 
 uint32_t vs_train_dropout_site(int32_t layer, int32_t which) { return layer < 0 ? VS_SITE_EMBED : VS_SITE_LAYER(layer, which); }
 
-int vs_train_forward(const vs_weights *w, const float *x, const uint8_t *key_pad_mask, int32_t B, int32_t T,
-                     const vs_dropout_cfg *drop, float *scores, float *hidden, void *saved, size_t saved_bytes,
-                     void *workspace, size_t workspace_bytes, void *stream) {
-    if (int rc = check_common(w, x, B, T, drop)) return rc;
+// pc != nullptr: a packed ragged batch, B = 1 and T = Mtot (no key mask)
+static int forward_impl(const vs_weights *w, const float *x, const uint8_t *key_pad_mask, int32_t B, int32_t T,
+                        const vs_dropout_cfg *drop, float *scores, float *hidden, void *saved, size_t saved_bytes,
+                        void *workspace, size_t workspace_bytes, void *stream, const PackedCtx *pc) {
+    if (int rc = check_common(w, x, B, T, drop, pc != nullptr)) return rc;
     if (!scores || !saved || !workspace) return failf(VS_ERR_INVALID, "scores/saved/workspace is NULL");
     const vs_model_desc &D = w->desc;
-    const SavedLayout S = saved_layout(D, B, T);
-    const WorkLayout W = work_layout(D, B, T);
+    const SavedLayout S = saved_layout(D, B, T, pc);
+    const WorkLayout W = work_layout(D, B, T, pc);
     if (saved_bytes < S.total * sizeof(float))
         return failf(VS_ERR_WORKSPACE, "saved %zu bytes < %zu needed", saved_bytes, S.total * sizeof(float));
     if (workspace_bytes < W.total * sizeof(float))
@@ -280,7 +313,7 @@ int vs_train_forward(const vs_weights *w, const float *x, const uint8_t *key_pad
     const float p = drop ? drop->p : 0.f;
     // the embedding dropout lives INSIDE PositionalEncoding (simnet.py:224,237): a use_pos=False model has none
     const float p_embed = (drop && w->has_pe) ? drop->p_embed : 0.f;
-    const RecordForm form = derive_form(w, drop, B, T);
+    const RecordForm form = derive_form(w, drop, B, T, pc != nullptr);
     g_last_format = form.bits();
     const int F = form.f16 ? VSK_F16 : 0;            // fp16 mode: rides on every 16-bit precision word below
     const int lp = form.lp ? (1 | F) : 0;
@@ -295,10 +328,21 @@ int vs_train_forward(const vs_weights *w, const float *x, const uint8_t *key_pad
     vsw_order(w, stream);
     if (M <= vsk_skinny_max_rows()) if (int rc = vsw_ensure(w, VSW_FRAGMENTS, stream)) return rc;
     if (rows16) if (int rc = vsw_ensure(w, VSW_ROWS16, stream)) return rc;          // bf16 copy of W1 for the A-stationary fc1
+    // packed: the device builds cu / bo / the work list from the device lengths (no host memory is read after return), and
+    // the positional rows are gathered per video - the embedding then adds row m of them to frame m
+    VstPackedPlan pk{};
+    const float *pe = w->has_pe ? w->p(w->pe) : nullptr;
+    if (pc) {
+        VST_LAUNCH(vst_plan_packed(pc->lengths_dev, pc->B, M, pc->words, (int *)(ws + W.plan), pc->nwork, st, &pk));
+        if (w->has_pe) {
+            VST_LAUNCH(vsk_gather_rows(w->p(w->pe), pk.cu, pc->B, pc->tmax, d, ws + W.pe, st));
+            pe = ws + W.pe;
+        }
+    }
     // Embedding + positional table + dropout(sparsity)   simnet.py:211, 237-238
     float *h0 = sv + S.h0;
     VST_LAUNCH(vsk_linear(x, w->p(w->embed_w), w->p(w->f_embed_w), w->p(w->embed_b), h0, M, d, D.in_features, 0,
-                          w->has_pe ? w->p(w->pe) : nullptr, T, lp, st));
+                          pe, T, lp, st));
     if (p_embed > 0.f) VST_LAUNCH(vst_dropout_rows(h0, M, d, seed, VS_SITE_EMBED, p_embed, st));
     const float *h_in = h0;
     for (int l = 0; l < L; ++l) {
@@ -316,8 +360,12 @@ int vs_train_forward(const vs_weights *w, const float *x, const uint8_t *key_pad
         VST_LAUNCH(vsk_qkv(h_in, w->p(P.wqkv), w->p(P.f_wqkv), w->p(P.bqkv), qkv, B, T, d, H, qkv16 ? (1 | VSK_STORE16 | F) : lp, st,
                            qkv16 ? vsk_attention_qscale(scale) : 1.0f));         // :148-153
         unsigned *dbits = p > 0.f ? (unsigned *)(sv + A.dbits) : nullptr;
-        if (dbits) VST_LAUNCH(vst_attention_dropout_bits(dbits, B, H, T, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st));
-        if (lpa)
+        if (dbits && pc) VST_LAUNCH(vst_attention_dropout_bits_packed(dbits, pc->B, H, pc->tmax, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st, pk));
+        else if (dbits) VST_LAUNCH(vst_attention_dropout_bits(dbits, B, H, T, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st));
+        if (pc)
+            VST_LAUNCH(vst_attention_fwd_packed(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, sv + A.att, sv + A.lse, H, d / H,
+                                                scale, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st, dbits, pk));
+        else if (lpa)
             VST_LAUNCH(vst_attention_fwd_bf16(qkv, qkv + kvs, qkv + 2 * kvs, key_pad_mask, sv + A.att,
                                               sv + A.lse, B, H, T, d / H, scale, p, dbits, st, (qkv16 ? 1 : 0) | F));
         else
@@ -347,17 +395,17 @@ int vs_train_forward(const vs_weights *w, const float *x, const uint8_t *key_pad
     return VS_OK;
 }
 
-int vs_train_backward(vs_weights *w, const float *x, const uint8_t *key_pad_mask, int32_t B, int32_t T,
-                      const vs_dropout_cfg *drop, const float *d_scores, const float *d_hidden, const void *saved,
-                      size_t saved_bytes, const vs_model_grads *grads, float *dx, void *workspace,
-                      size_t workspace_bytes, void *stream) {
-    if (int rc = check_common(w, x, B, T, drop)) return rc;
+static int backward_impl(vs_weights *w, const float *x, const uint8_t *key_pad_mask, int32_t B, int32_t T,
+                         const vs_dropout_cfg *drop, const float *d_scores, const float *d_hidden, const void *saved,
+                         size_t saved_bytes, const vs_model_grads *grads, float *dx, void *workspace,
+                         size_t workspace_bytes, void *stream, const PackedCtx *pc) {
+    if (int rc = check_common(w, x, B, T, drop, pc != nullptr)) return rc;
     if (!saved || !workspace || !grads || !grads->layers || !grads->embed_w || !grads->embed_b || !grads->final_w ||
         !grads->final_b)
         return failf(VS_ERR_INVALID, "saved/workspace/grads is NULL");
     const vs_model_desc &D = w->desc;
-    const SavedLayout S = saved_layout(D, B, T);
-    const WorkLayout W = work_layout(D, B, T);
+    const SavedLayout S = saved_layout(D, B, T, pc);
+    const WorkLayout W = work_layout(D, B, T, pc);
     if (saved_bytes < S.total * sizeof(float))
         return failf(VS_ERR_WORKSPACE, "saved %zu bytes < %zu needed", saved_bytes, S.total * sizeof(float));
     if (workspace_bytes < W.total * sizeof(float))
@@ -371,13 +419,13 @@ int vs_train_backward(vs_weights *w, const float *x, const uint8_t *key_pad_mask
     const float p_embed = (drop && w->has_pe) ? drop->p_embed : 0.f;
     // the form the record was written in: handed back by the caller (vs_dropout_cfg.reserved = vs_train_last_format() of the
     // forward), else derived again from the same inputs
-    RecordForm form = derive_form(w, drop, B, T);
+    RecordForm form = derive_form(w, drop, B, T, pc != nullptr);
     if (drop && (drop->reserved & 0x80000000u)) {
         const uint32_t fb = drop->reserved;
         form.lp = (fb & 1u) ? 1 : 0; form.lpa = (fb & 2u) != 0; form.qkv16 = (fb & 4u) != 0; form.h16 = (fb & 8u) != 0; form.rows16 = (fb & 16u) != 0;
         form.f16 = (fb & 32u) != 0;
         if ((form.qkv16 && !(form.lp && form.lpa)) || (form.h16 && !form.lp) || (form.rows16 && !form.h16) ||
-            (form.f16 && (form.rows16 || !(form.lp || form.lpa))) || (fb & 0x7fffffc0u) ||
+            (form.f16 && (form.rows16 || !(form.lp || form.lpa))) || (fb & 0x7fffffc0u) || (pc && form.lpa) ||
             (form.lpa && !vst_attention_bf16_supported(w->desc.d_model / w->desc.num_heads)) ||
             (form.rows16 && !vst_gemm_rows16_supported(B * T, 4 * w->desc.d_model, w->desc.d_model, true)))
             return failf(VS_ERR_INVALID, "vs_dropout_cfg.reserved = 0x%08x is not a record form this model / batch can have", fb);
@@ -397,6 +445,8 @@ int vs_train_backward(vs_weights *w, const float *x, const uint8_t *key_pad_mask
     float *dqkv = ws + W.dqkv, *delta = ws + W.delta, *part = ws + W.part, *wg = ws + W.wg;
     const float *zeros = w->tp(w->zeros);
     const int nblk = vst_ln_bwd_blocks(M);
+    VstPackedPlan pk{};       // packed: the plan is rebuilt from the device lengths (one small launch), not kept in the record
+    if (pc) VST_LAUNCH(vst_plan_packed(pc->lengths_dev, pc->B, M, pc->words, (int *)(ws + W.plan), pc->nwork, st, &pk));
 
     // final_layer (simnet.py:42): d_W = d_scores^T hidden, d_b = column sums of d_scores
     {
@@ -455,7 +505,11 @@ int vs_train_backward(vs_weights *w, const float *x, const uint8_t *key_pad_mask
         // attention
         const float *qkv = sv + A.qkv;
         VST_LAUNCH(vst_head_rowdot(datt, sv + A.att, delta, M, T, H, d / H, st, qkv16 ? (1 | F) : lpa ? (2 | F) : 0));
-        if (lpa)
+        if (pc)
+            VST_LAUNCH(vst_attention_bwd_packed(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, datt, sv + A.lse, delta, dqkv, H, d / H,
+                                                scale, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st,
+                                                p > 0.f ? (const unsigned *)(sv + A.dbits) : nullptr, pk));
+        else if (lpa)
             VST_LAUNCH(vst_attention_bwd_bf16(qkv, qkv + kvs, qkv + 2 * kvs, key_pad_mask, datt, sv + A.lse,
                                               delta, dqkv, B, H, T, d / H, scale, p,
                                               p > 0.f ? (const unsigned *)(sv + A.dbits) : nullptr, st, (qkv16 ? 1 : 0) | F, qkv16));
@@ -477,6 +531,167 @@ int vs_train_backward(vs_weights *w, const float *x, const uint8_t *key_pad_mask
     VST_LAUNCH(vst_wgrad(gh0, d, x, D.in_features, M, d, D.in_features, grads->embed_w, nullptr, nullptr, grads->embed_b,
                          nullptr, nullptr, d, wg, st, lp));
     if (dx) VST_LAUNCH(vsk_linear(gh0, w->tp(w->t_embed_w), w->tp(w->tf_embed_w), zeros, dx, M, D.in_features, d, 0, nullptr, 1, lp, st));
+    return VS_OK;
+}
+
+int vs_train_forward(const vs_weights *w, const float *x, const uint8_t *key_pad_mask, int32_t B, int32_t T,
+                     const vs_dropout_cfg *drop, float *scores, float *hidden, void *saved, size_t saved_bytes,
+                     void *workspace, size_t workspace_bytes, void *stream) {
+    return forward_impl(w, x, key_pad_mask, B, T, drop, scores, hidden, saved, saved_bytes, workspace, workspace_bytes, stream, nullptr);
+}
+
+int vs_train_backward(vs_weights *w, const float *x, const uint8_t *key_pad_mask, int32_t B, int32_t T,
+                      const vs_dropout_cfg *drop, const float *d_scores, const float *d_hidden, const void *saved,
+                      size_t saved_bytes, const vs_model_grads *grads, float *dx, void *workspace,
+                      size_t workspace_bytes, void *stream) {
+    return backward_impl(w, x, key_pad_mask, B, T, drop, d_scores, d_hidden, saved, saved_bytes, grads, dx, workspace,
+                         workspace_bytes, stream, nullptr);
+}
+
+// ---- packed ragged batches ----
+int vs_train_check_packed(const vs_model_desc *desc, const int32_t *lengths, int32_t B) {
+    if (!desc) return failf(VS_ERR_INVALID, "desc is NULL");
+    PackedCtx pc;
+    return packed_ctx(*desc, lengths, B, pc);
+}
+
+size_t vs_train_saved_bytes_desc(const vs_model_desc *desc, const int32_t *lengths, int32_t B, int32_t T) {
+    if (!desc || desc->d_model <= 0 || desc->num_heads <= 0 || desc->num_layers <= 0 || B <= 0) return 0;
+    if (!lengths) return T > 0 ? saved_layout(*desc, B, T).total * sizeof(float) : 0;
+    PackedCtx pc;
+    if (packed_ctx(*desc, lengths, B, pc) != VS_OK) return 0;
+    return saved_layout(*desc, 1, pc.Mtot, &pc).total * sizeof(float);
+}
+
+size_t vs_train_saved_bytes_packed(const vs_weights *w, const int32_t *lengths, int32_t B) {
+    return (w && lengths) ? vs_train_saved_bytes_desc(&w->desc, lengths, B, 0) : 0;
+}
+
+size_t vs_train_workspace_bytes_packed(const vs_weights *w, const int32_t *lengths, int32_t B) {
+    PackedCtx pc;
+    if (!w || !lengths || packed_ctx(w->desc, lengths, B, pc) != VS_OK) return 0;
+    return work_layout(w->desc, 1, pc.Mtot, &pc).total * sizeof(float);
+}
+
+int vs_train_saved_field_packed(const vs_weights *w, const int32_t *lengths, int32_t B, int32_t layer, int32_t field,
+                                size_t *offset_bytes, size_t *count) {
+    PackedCtx pc;
+    if (!w || !offset_bytes || !count || layer < 0 || layer >= w->desc.num_layers)
+        return failf(VS_ERR_INVALID, "saved_field: bad arguments");
+    if (int rc = packed_ctx(w->desc, lengths, B, pc)) return rc;
+    const SavedLayout S = saved_layout(w->desc, 1, pc.Mtot, &pc);
+    const LayerSaved &A = S.layers[layer];
+    const size_t Md = (size_t)pc.Mtot * w->desc.d_model;
+    switch (field) {
+        case 0: *offset_bytes = A.ffn * sizeof(float); *count = 4 * Md; break;
+        case 1: *offset_bytes = A.att * sizeof(float); *count = Md; break;
+        case 2: *offset_bytes = A.y1 * sizeof(float); *count = Md; break;
+        case 3: *offset_bytes = A.y2 * sizeof(float); *count = Md; break;
+        case 4: *offset_bytes = A.lse * sizeof(float); *count = (size_t)pc.Mtot * w->desc.num_heads; break;
+        default: return failf(VS_ERR_INVALID, "saved_field: unknown field %d", field);
+    }
+    return VS_OK;
+}
+
+int vs_train_forward_packed(const vs_weights *w, const float *x, const int32_t *lengths, const int32_t *lengths_dev, int32_t B,
+                            const vs_dropout_cfg *drop, float *scores, float *hidden, void *saved, size_t saved_bytes,
+                            void *workspace, size_t workspace_bytes, void *stream) {
+    if (!w) return failf(VS_ERR_INVALID, "weights is NULL");
+    if (!lengths_dev) return failf(VS_ERR_INVALID, "lengths_dev is NULL");
+    PackedCtx pc;
+    if (int rc = packed_ctx(w->desc, lengths, B, pc)) return rc;
+    pc.lengths_dev = lengths_dev;
+    return forward_impl(w, x, nullptr, 1, pc.Mtot, drop, scores, hidden, saved, saved_bytes, workspace, workspace_bytes, stream, &pc);
+}
+
+int vs_train_backward_packed(vs_weights *w, const float *x, const int32_t *lengths, const int32_t *lengths_dev, int32_t B,
+                             const vs_dropout_cfg *drop, const float *d_scores, const float *d_hidden, const void *saved,
+                             size_t saved_bytes, const vs_model_grads *grads, float *dx, void *workspace,
+                             size_t workspace_bytes, void *stream) {
+    if (!w) return failf(VS_ERR_INVALID, "weights is NULL");
+    if (!lengths_dev) return failf(VS_ERR_INVALID, "lengths_dev is NULL");
+    PackedCtx pc;
+    if (int rc = packed_ctx(w->desc, lengths, B, pc)) return rc;
+    pc.lengths_dev = lengths_dev;
+    return backward_impl(w, x, nullptr, 1, pc.Mtot, drop, d_scores, d_hidden, saved, saved_bytes, grads, dx, workspace,
+                         workspace_bytes, stream, &pc);
+}
+
+int vs_mse_packed_loss_forward(const float *output, const float *target, int32_t n, double denom, float *scratch, float *loss,
+                               void *stream) {
+    if (!output || !target || !scratch || !loss || n <= 0 || !(denom > 0.0)) return failf(VS_ERR_INVALID, "mse_packed_loss: bad arguments");
+    VST_LAUNCH(vst_mse_scaled_fwd(output, target, n, (float)(1.0 / denom), scratch, loss, (hipStream_t)stream));
+    return VS_OK;
+}
+
+int vs_mse_packed_loss_backward(const float *output, const float *target, const float *d_loss, int32_t n, double denom,
+                                float *d_output, void *stream) {
+    if (!output || !target || !d_loss || !d_output || n <= 0 || !(denom > 0.0)) return failf(VS_ERR_INVALID, "mse_packed_loss: bad arguments");
+    VST_LAUNCH(vst_mse_scaled_bwd(output, target, d_loss, n, (float)(1.0 / denom), d_output, (hipStream_t)stream));
+    return VS_OK;
+}
+
+// scratch of the two per-kernel entry points below: the device plan, then delta [H][Mtot]
+static size_t attention_packed_plan_floats(const PackedCtx &pc) { return align_floats(vst_packed_plan_ints(pc.B, pc.nwork)); }
+
+size_t vs_train_attention_packed_scratch_bytes(const int32_t *lengths, int32_t B, int32_t H) {
+    PackedCtx pc;
+    vs_model_desc none{};
+    if (H <= 0 || packed_ctx(none, lengths, B, pc) != VS_OK) return 0;
+    return (attention_packed_plan_floats(pc) + align_floats((size_t)H * pc.Mtot)) * sizeof(float);
+}
+
+int vs_train_attention_forward_packed(const float *q, const float *k, const float *v, float *out, float *lse2,
+                                      const int32_t *lengths, const int32_t *lengths_dev, int32_t B, int32_t H, int32_t dh,
+                                      float scale, uint64_t seed, uint32_t site, float p, void *scratch, size_t scratch_bytes,
+                                      void *stream) {
+    if (!q || !k || !v || !out || !lse2 || !lengths_dev || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
+    PackedCtx pc;
+    vs_model_desc none{};
+    if (H <= 0) return failf(VS_ERR_INVALID, "H=%d", H);
+    if (int rc = packed_ctx(none, lengths, B, pc)) return rc;
+    if (scratch_bytes < vs_train_attention_packed_scratch_bytes(lengths, B, H) || ((uintptr_t)scratch & 255))
+        return failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, vs_train_attention_packed_scratch_bytes(lengths, B, H));
+    hipStream_t st = (hipStream_t)stream;
+    VstPackedPlan pk{};
+    VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.words, (int *)scratch, pc.nwork, st, &pk));
+    VST_LAUNCH(vst_attention_fwd_packed(q, k, v, out, lse2, H, dh, scale, seed, site, p, st, nullptr, pk));
+    return VS_OK;
+}
+
+int vs_train_attention_backward_packed(const float *q, const float *k, const float *v, const float *out, const float *d_out,
+                                       const float *lse2, float *dqkv, const int32_t *lengths, const int32_t *lengths_dev,
+                                       int32_t B, int32_t H, int32_t dh, float scale, uint64_t seed, uint32_t site, float p,
+                                       void *scratch, size_t scratch_bytes, void *stream) {
+    if (!q || !k || !v || !out || !d_out || !lse2 || !dqkv || !lengths_dev || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
+    PackedCtx pc;
+    vs_model_desc none{};
+    if (H <= 0) return failf(VS_ERR_INVALID, "H=%d", H);
+    if (int rc = packed_ctx(none, lengths, B, pc)) return rc;
+    if (scratch_bytes < vs_train_attention_packed_scratch_bytes(lengths, B, H) || ((uintptr_t)scratch & 255))
+        return failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, vs_train_attention_packed_scratch_bytes(lengths, B, H));
+    hipStream_t st = (hipStream_t)stream;
+    float *delta = (float *)scratch + attention_packed_plan_floats(pc);
+    VstPackedPlan pk{};
+    VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.words, (int *)scratch, pc.nwork, st, &pk));
+    VST_LAUNCH(vst_head_rowdot(d_out, out, delta, pc.Mtot, pc.Mtot, H, dh, st));
+    VST_LAUNCH(vst_attention_bwd_packed(q, k, v, d_out, lse2, delta, dqkv, H, dh, scale, seed, site, p, st, nullptr, pk));
+    return VS_OK;
+}
+
+int vs_train_dropout_mask_attention_packed(uint8_t *keep, const int32_t *lengths, int32_t B, int32_t H, uint64_t seed,
+                                           uint32_t site, float p, void *stream) {
+    PackedCtx pc;
+    vs_model_desc none{};
+    if (!keep || H <= 0) return failf(VS_ERR_INVALID, "bad arguments");
+    if (int rc = packed_ctx(none, lengths, B, pc)) return rc;
+    size_t off = 0;
+    int row0 = 0;
+    for (int b = 0; b < B; ++b) {
+        VST_LAUNCH(vst_attention_dropout_mask_video(keep + off, H, lengths[b], pc.Mtot, row0, seed, site, p, (hipStream_t)stream));
+        off += (size_t)H * lengths[b] * lengths[b];
+        row0 += lengths[b];
+    }
     return VS_OK;
 }
 

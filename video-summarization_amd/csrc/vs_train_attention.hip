@@ -25,6 +25,13 @@
 // kernel whose lanes own keys - which the forward leaves in the activation record for the backward: a kernel reads one
 // word per tile and lane and extracts a bit per element (3 instructions).  Same hash, same masks (GPU test: the two
 // forms give bit-identical outputs).
+//
+// PACKED (packed ragged batches, vs_train_forward_packed): the videos' frames are concatenated, q / k / v are head-major over
+// the packed rows ([H][Mtot][DH], what vsk_qkv writes for B = 1, T = Mtot), lse2 / delta are [H][Mtot] and out / dO / dqkv
+// token-major over the packed rows.  A block takes (head, video, 128-row owner tile) from a work list built on the device
+// (plan_packed_train) and streams only that video's rows cu[b] .. cu[b+1]: the difference to the padded form is confined to
+// owner_tile() - where the block's rows, its keep words and its dropout row keys live - so a video's tile loops, LDS layout
+// and summation order are those of the same video run alone.  No key mask: a packed batch has no padded rows.
 #include <atomic>
 
 #include "vs_train_device.h"
@@ -78,6 +85,38 @@ __device__ __forceinline__ f32x16 zero16() {
     return z;
 }
 
+// Where a block works.  Padded batches: (video * H + head, owner tile) from blockIdx, T the common length.  Packed ragged
+// batches: (head, video, owner tile) from the work list, T = that video's length.  plane: first row of the (video, head) in
+// the head-major planes (and in lse2 / delta; + query = the dropout row key); tok: first row of the video in the
+// token-major tensors; wbase: first word of the (video, head) in one bit-packed copy of the keep decisions, wall: words of
+// one copy (the key-major copy follows the query-major one).
+struct Owner { int T, b, hd, tile; size_t plane, tok, wbase, wall; };
+template <bool PACKED>
+__device__ __forceinline__ Owner owner_tile(int H, int T, const VstPackedPlan &pk) {
+    Owner o;
+    if constexpr (PACKED) {
+        const int wi = blockIdx.x / H, hd = blockIdx.x - wi * H;      // the heads of a tile side by side: the list's order is the grid's
+        const int b = pk.work[2 * wi];
+        o.hd = hd; o.b = b; o.tile = pk.work[2 * wi + 1];
+        if (b < 0) { o.T = 0; o.plane = o.tok = o.wbase = o.wall = 0; return o; }      // (device lengths gave fewer tiles than the host's)
+        const int r0 = pk.cu[b];
+        o.T = pk.cu[b + 1] - r0;
+        o.plane = (size_t)hd * pk.Mtot + r0;
+        o.tok = (size_t)r0;
+        o.wbase = (size_t)hd * pk.words + pk.bo[b];
+        o.wall = (size_t)H * pk.words;
+    } else {
+        const int nt = (T + 127) / 128, W = (T + 31) / 32;
+        const int bh = blockIdx.x / nt;
+        o.T = T; o.tile = blockIdx.x - bh * nt; o.b = bh / H; o.hd = bh - o.b * H;
+        o.plane = (size_t)bh * T;
+        o.tok = (size_t)o.b * T;
+        o.wbase = (size_t)bh * T * W;
+        o.wall = (size_t)gridDim.x / nt * T * W;
+    }
+    return o;
+}
+
 // S^T tile (lane = query): sum_c K[key][c] * Qs[query][c] + key bias; keys in rows
 template <int DH>
 __device__ __forceinline__ f32x16 st_tile(const TileLds<DH> &t, const f32x4 (&qf)[DH / 8], int r, int h) {
@@ -100,21 +139,22 @@ __device__ __forceinline__ f32x16 st_tile(const TileLds<DH> &t, const f32x4 (&qf
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
-template <int DH, int DROP>        // DROP 0: none, 1: hash per element, 2: bit-packed keep masks (dbits)
+template <int DH, int DROP, bool PACKED>        // DROP 0: none, 1: hash per element, 2: bit-packed keep masks (dbits)
 __global__ __launch_bounds__(256) void attn_fwd_train(
     const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
-    const uint8_t *__restrict__ mask, float *__restrict__ out, float *__restrict__ lse2, int H, int T, float scale,
-    unsigned long long seed, unsigned site, float p, const unsigned *__restrict__ dbits) {
+    const uint8_t *__restrict__ mask, float *__restrict__ out, float *__restrict__ lse2, int H, int T_all, float scale,
+    unsigned long long seed, unsigned site, float p, const unsigned *__restrict__ dbits, const VstPackedPlan pk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];      // 2 x TileLds<DH>: 68 KB at head dim 128
     TileLds<DH> *lds = reinterpret_cast<TileLds<DH> *>(lds_raw);
-    const int nq = (T + 127) / 128;
-    const int bh = blockIdx.x / nq, qt = blockIdx.x - bh * nq, b = bh / H, hd = bh - b * H;
+    const Owner own = owner_tile<PACKED>(H, T_all, pk);
+    if (PACKED && own.T <= 0) return;
+    const int T = own.T, qt = own.tile, hd = own.hd;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int qi = qt * 128 + wave * 32 + r, qc = qi < T ? qi : T - 1;
     const float sl2 = scale * 1.4426950408889634f;
-    const float *qb = q + (size_t)bh * T * DH, *kb = k + (size_t)bh * T * DH, *vb = v + (size_t)bh * T * DH;
+    const float *qb = q + own.plane * DH, *kb = k + own.plane * DH, *vb = v + own.plane * DH;
     const DropSite ds = drop_site(seed, site, p);
-    const unsigned rkq = drop_rowkey(ds, (unsigned)(bh * T + qc));
+    const unsigned rkq = drop_rowkey(ds, (unsigned)(own.plane + qc));
 
     f32x4 qf[DH / 8];
 #pragma unroll
@@ -128,11 +168,11 @@ __global__ __launch_bounds__(256) void attn_fwd_train(
     auto side = [&](TileLds<DH> &t, int key0) __attribute__((always_inline)) {
         if (tid < 32) {
             const int key = key0 + tid;
-            t.s0[tid] = (key >= T || (mask != nullptr && mask[(size_t)b * T + key])) ? NEG_INF : 0.f;
+            t.s0[tid] = (key >= T || (!PACKED && mask != nullptr && mask[own.tok + key])) ? NEG_INF : 0.f;
         }
     };
     const int nkt = (T + 31) / 32;
-    const unsigned *bq = DROP == 2 ? dbits + ((size_t)bh * T + qc) * nkt : nullptr;      // this query's keep words
+    const unsigned *bq = DROP == 2 ? dbits + own.wbase + (size_t)qc * nkt : nullptr;      // this query's keep words
     unsigned kw = DROP == 2 ? bq[0] : 0u;
     sg.load(kb, DH, vb, DH, 0, T, 1.0f);
     sg.store(lds[0]);
@@ -184,7 +224,7 @@ __global__ __launch_bounds__(256) void attn_fwd_train(
     const float l_tot = pair_sum(l_run);
     const float inv = 1.0f / l_tot;         // l_tot == 0 (every key masked): NaN rows, like softmax of all -inf
     if (qi < T) {
-        float *op = out + ((size_t)b * T + qi) * (H * DH) + hd * DH;
+        float *op = out + (own.tok + qi) * (H * DH) + hd * DH;
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb)
 #pragma unroll
@@ -194,37 +234,38 @@ __global__ __launch_bounds__(256) void attn_fwd_train(
                 for (int e = 0; e < 4; ++e) w[e] = o[cb][4 * tg + e] * inv;
                 *(f32x4 *)(op + 32 * cb + 8 * tg + 4 * h) = w;
             }
-        if (h == 0) lse2[(size_t)bh * T + qi] = m_run + log2f(l_tot);
+        if (h == 0) lse2[own.plane + qi] = m_run + log2f(l_tot);
     }
 }
 
 // ------------------------------------------------------------------------------------------
 // backward, queries own: dQ
 // ------------------------------------------------------------------------------------------
-template <int DH, int DROP>
+template <int DH, int DROP, bool PACKED>
 __global__ __launch_bounds__(256) void attn_bwd_dq(
     const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
     const uint8_t *__restrict__ mask, const float *__restrict__ dO, const float *__restrict__ lse2,
-    const float *__restrict__ delta, float *__restrict__ dqkv, int H, int T, float scale, unsigned long long seed,
-    unsigned site, float p, const unsigned *__restrict__ dbits) {
+    const float *__restrict__ delta, float *__restrict__ dqkv, int H, int T_all, float scale, unsigned long long seed,
+    unsigned site, float p, const unsigned *__restrict__ dbits, const VstPackedPlan pk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];      // 2 x TileLds<DH>: 68 KB at head dim 128
     TileLds<DH> *lds = reinterpret_cast<TileLds<DH> *>(lds_raw);
-    const int nq = (T + 127) / 128, d = H * DH;
-    const int bh = blockIdx.x / nq, qt = blockIdx.x - bh * nq, b = bh / H, hd = bh - b * H;
+    const Owner own = owner_tile<PACKED>(H, T_all, pk);
+    if (PACKED && own.T <= 0) return;
+    const int T = own.T, qt = own.tile, hd = own.hd, d = H * DH;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int qi = qt * 128 + wave * 32 + r, qc = qi < T ? qi : T - 1;
     const float sl2 = scale * 1.4426950408889634f;
-    const float *qb = q + (size_t)bh * T * DH, *kb = k + (size_t)bh * T * DH, *vb = v + (size_t)bh * T * DH;
+    const float *qb = q + own.plane * DH, *kb = k + own.plane * DH, *vb = v + own.plane * DH;
     const DropSite ds = drop_site(seed, site, p);
-    const unsigned rkq = drop_rowkey(ds, (unsigned)(bh * T + qc));
+    const unsigned rkq = drop_rowkey(ds, (unsigned)(own.plane + qc));
 
     f32x4 qf[DH / 8], dof[DH / 8];
 #pragma unroll
     for (int g = 0; g < DH / 8; ++g) {
         qf[g] = *(const f32x4 *)(qb + (size_t)qc * DH + 8 * g + 4 * h) * sl2;
-        dof[g] = *(const f32x4 *)(dO + ((size_t)b * T + qc) * d + hd * DH + 8 * g + 4 * h);
+        dof[g] = *(const f32x4 *)(dO + (own.tok + qc) * d + hd * DH + 8 * g + 4 * h);
     }
-    const float lq = lse2[(size_t)bh * T + qc], dq_delta = delta[(size_t)bh * T + qc];
+    const float lq = lse2[own.plane + qc], dq_delta = delta[own.plane + qc];
     f32x16 acc[DH / 32];
 #pragma unroll
     for (int cb = 0; cb < DH / 32; ++cb) acc[cb] = zero16();
@@ -233,11 +274,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(
     auto side = [&](TileLds<DH> &t, int key0) __attribute__((always_inline)) {
         if (tid < 32) {
             const int key = key0 + tid;
-            t.s0[tid] = (key >= T || (mask != nullptr && mask[(size_t)b * T + key])) ? NEG_INF : 0.f;
+            t.s0[tid] = (key >= T || (!PACKED && mask != nullptr && mask[own.tok + key])) ? NEG_INF : 0.f;
         }
     };
     const int nkt = (T + 31) / 32;
-    const unsigned *bq = DROP == 2 ? dbits + ((size_t)bh * T + qc) * nkt : nullptr;
+    const unsigned *bq = DROP == 2 ? dbits + own.wbase + (size_t)qc * nkt : nullptr;
     unsigned kw = DROP == 2 ? bq[0] : 0u;
     sg.load(kb, DH, vb, DH, 0, T, 1.0f);
     sg.store(lds[0]);
@@ -276,7 +317,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(
         __syncthreads();
     }
     if (qi < T) {
-        float *op = dqkv + ((size_t)b * T + qi) * (3 * d) + hd * DH;
+        float *op = dqkv + (own.tok + qi) * (3 * d) + hd * DH;
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb)
 #pragma unroll
@@ -292,21 +333,22 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(
 // ------------------------------------------------------------------------------------------
 // backward, keys own: dK and dV
 // ------------------------------------------------------------------------------------------
-template <int DH, int DROP>
+template <int DH, int DROP, bool PACKED>
 __global__ __launch_bounds__(256) void attn_bwd_dkdv(
     const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v,
     const uint8_t *__restrict__ mask, const float *__restrict__ dO, const float *__restrict__ lse2,
-    const float *__restrict__ delta, float *__restrict__ dqkv, int H, int T, float scale, unsigned long long seed,
-    unsigned site, float p, const unsigned *__restrict__ dbits) {
+    const float *__restrict__ delta, float *__restrict__ dqkv, int H, int T_all, float scale, unsigned long long seed,
+    unsigned site, float p, const unsigned *__restrict__ dbits, const VstPackedPlan pk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];      // 2 x TileLds<DH>: 68 KB at head dim 128
     TileLds<DH> *lds = reinterpret_cast<TileLds<DH> *>(lds_raw);
-    const int nk = (T + 127) / 128, d = H * DH;
-    const int bh = blockIdx.x / nk, ktile = blockIdx.x - bh * nk, b = bh / H, hd = bh - b * H;
+    const Owner own = owner_tile<PACKED>(H, T_all, pk);
+    if (PACKED && own.T <= 0) return;
+    const int T = own.T, ktile = own.tile, hd = own.hd, d = H * DH;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int ki = ktile * 128 + wave * 32 + r, kc = ki < T ? ki : T - 1;
     const float sl2 = scale * 1.4426950408889634f;
-    const float *qb = q + (size_t)bh * T * DH, *kb = k + (size_t)bh * T * DH, *vb = v + (size_t)bh * T * DH;
-    const float *dob = dO + (size_t)b * T * d + hd * DH;          // row stride d
+    const float *qb = q + own.plane * DH, *kb = k + own.plane * DH, *vb = v + own.plane * DH;
+    const float *dob = dO + own.tok * d + hd * DH;          // row stride d
     const DropSite ds = drop_site(seed, site, p);
 
     f32x4 kf[DH / 8], vf[DH / 8];
@@ -315,7 +357,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv(
         kf[g] = *(const f32x4 *)(kb + (size_t)kc * DH + 8 * g + 4 * h);
         vf[g] = *(const f32x4 *)(vb + (size_t)kc * DH + 8 * g + 4 * h);
     }
-    const float kbias = (ki >= T || (mask != nullptr && mask[(size_t)b * T + kc])) ? NEG_INF : 0.f;
+    const float kbias = (ki >= T || (!PACKED && mask != nullptr && mask[own.tok + kc])) ? NEG_INF : 0.f;
     f32x16 dk[DH / 32], dv[DH / 32];
 #pragma unroll
     for (int cb = 0; cb < DH / 32; ++cb) { dk[cb] = zero16(); dv[cb] = zero16(); }
@@ -325,14 +367,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv(
         if (tid < 32) {
             const int qi = q0 + tid;
             const bool ok = qi < T;
-            t.s0[tid] = ok ? lse2[(size_t)bh * T + qi] : __builtin_inff();      // p = exp2(s - inf) = 0 on rows >= T
-            t.s1[tid] = ok ? delta[(size_t)bh * T + qi] : 0.f;
-            if (DROP == 1) t.rk[tid] = drop_rowkey(ds, (unsigned)(bh * T + (ok ? qi : 0)));
+            t.s0[tid] = ok ? lse2[own.plane + qi] : __builtin_inff();      // p = exp2(s - inf) = 0 on rows >= T
+            t.s1[tid] = ok ? delta[own.plane + qi] : 0.f;
+            if (DROP == 1) t.rk[tid] = drop_rowkey(ds, (unsigned)(own.plane + (ok ? qi : 0)));
         }
     };
     const int nqt = (T + 31) / 32;
     // DROP 2: the key-major copy (second half of dbits): one word per (key, 32 queries)
-    const unsigned *bk = DROP == 2 ? dbits + (size_t)gridDim.x / nk * T * nqt + ((size_t)bh * T + kc) * nqt : nullptr;
+    const unsigned *bk = DROP == 2 ? dbits + own.wall + own.wbase + (size_t)kc * nqt : nullptr;
     unsigned kw = DROP == 2 ? bk[0] : 0u;
     sg.load(qb, DH, dob, d, 0, T, sl2);
     sg.store(lds[0]);
@@ -395,7 +437,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv(
         __syncthreads();
     }
     if (ki < T) {
-        float *op = dqkv + ((size_t)b * T + ki) * (3 * d) + hd * DH;
+        float *op = dqkv + (own.tok + ki) * (3 * d) + hd * DH;
         const float ln2 = 0.6931471805599453f;       // dK = scale * dS^T Q = (dS^T Qs) / log2(e)
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb)
@@ -414,25 +456,31 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv(
 // keep(query, key 32 w + j), then words [BH][T keys][W] with bit j of word w = keep(query 32 w + j, key); W = ceil(T / 32).
 // A wave owns 32 queries x 64 keys: lane l hashes query (l & 31) against the 32 keys of word (l >> 5); the transposed
 // words come from 32 ballots (bit j of every lane's word = the column of key j).  Bits beyond T are 0.
-__global__ __launch_bounds__(256) void attn_dropout_bits(unsigned *__restrict__ bits, int BH, int T, unsigned long long seed,
-                                                         unsigned site, float p) {
+// PACKED: blockIdx.y = video; BH = heads, rows / words of video b at (head * Mtot + cu[b]) / (head * words + bo[b]).
+template <bool PACKED>
+__global__ __launch_bounds__(256) void attn_dropout_bits(unsigned *__restrict__ bits, int BH, int T_all, unsigned long long seed,
+                                                         unsigned site, float p, const VstPackedPlan pk) {
+    const int r0 = PACKED ? pk.cu[blockIdx.y] : 0;
+    const int T = PACKED ? pk.cu[blockIdx.y + 1] - r0 : T_all;
     const int W = (T + 31) / 32, W2 = (W + 1) / 2;
     const DropSite ds = drop_site(seed, site, p);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, g = lane >> 5;
     const size_t ntile = (size_t)BH * W * W2;
-    unsigned *bitsK = bits + (size_t)BH * T * W;
+    unsigned *bitsK = bits + (PACKED ? (size_t)BH * pk.words : (size_t)BH * T * W);
     for (size_t tile = (size_t)blockIdx.x * 4 + wave; tile < ntile; tile += (size_t)gridDim.x * 4) {
         const int t2 = (int)(tile % W2), qt = (int)((tile / W2) % W), bh = (int)(tile / ((size_t)W2 * W));
+        const size_t plane = PACKED ? (size_t)bh * pk.Mtot + r0 : (size_t)bh * T;               // dropout row key of query 0
+        const size_t wbase = PACKED ? (size_t)bh * pk.words + pk.bo[blockIdx.y] : (size_t)bh * T * W;
         const int q = 32 * qt + r, kw = 2 * t2 + g;
         unsigned word = 0u;
         if (q < T && kw < W) {
-            const unsigned rk = drop_rowkey(ds, (unsigned)(bh * T + q));
+            const unsigned rk = drop_rowkey(ds, (unsigned)(plane + q));
 #pragma unroll 8
             for (int j = 0; j < 32; ++j) {
                 const int key = 32 * kw + j;
                 word |= (key < T && drop_keep(ds, rk, (unsigned)key)) ? (1u << j) : 0u;
             }
-            bits[((size_t)bh * T + q) * W + kw] = word;
+            bits[wbase + (size_t)q * W + kw] = word;
         }
         unsigned mine = 0u;
 #pragma unroll 8
@@ -441,7 +489,51 @@ __global__ __launch_bounds__(256) void attn_dropout_bits(unsigned *__restrict__ 
             if (r == j) mine = g == 0 ? (unsigned)bal : (unsigned)(bal >> 32);
         }
         const int key = 64 * t2 + 32 * g + r;       // lane (r, g) holds the queries-of-this-tile word of key 64 t2 + 32 g + r
-        if (key < T) bitsK[((size_t)bh * T + key) * W + qt] = mine;
+        if (key < T) bitsK[wbase + (size_t)key * W + qt] = mine;
+    }
+}
+
+// cu [B+1] row offsets, bo [B+1] keep-word offsets (T_b * ceil(T_b / 32) words per video and head) and the (video, 128-row
+// owner tile) work list of a packed batch, from DEVICE lengths (one thread: B is a few hundred at most).  The list is
+// ordered longest video first (by its number of owner tiles): a block's time grows with the rows it streams, and the grid is
+// a few waves of blocks deep, so the long blocks must not start last.  The host sized the launches from its copy of the
+// lengths: rows beyond Mtot are cut, pairs beyond work_cap dropped, and the unused tail of the list is marked (video -1:
+// the block returns).
+__global__ void plan_packed_train(const int *__restrict__ lengths, int B, int Mtot, int *__restrict__ cu, int *__restrict__ bo,
+                                  int *__restrict__ work, int work_cap) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int row = 0, words = 0, most = 0;
+    for (int b = 0; b < B; ++b) {
+        cu[b] = row;
+        bo[b] = words;
+        int t = lengths[b];
+        t = t < 0 ? 0 : (t > Mtot - row ? Mtot - row : t);
+        most = (t + 127) / 128 > most ? (t + 127) / 128 : most;
+        row += t;
+        words += t * ((t + 31) / 32);
+    }
+    cu[B] = row;
+    bo[B] = words;
+    int n = 0;
+    for (int nt = most; nt >= 1; --nt)
+        for (int b = 0; b < B; ++b) {
+            if ((cu[b + 1] - cu[b] + 127) / 128 != nt) continue;
+            for (int q = 0; q < nt; ++q) {
+                if (n < work_cap) { work[2 * n] = b; work[2 * n + 1] = q; }
+                ++n;
+            }
+        }
+    for (; n < work_cap; ++n) { work[2 * n] = -1; work[2 * n + 1] = 0; }
+}
+
+// keep[h][query][key] (bytes) of ONE video of a packed batch: T frames from packed row row0
+__global__ __launch_bounds__(256) void attn_dropout_mask_video(uint8_t *__restrict__ keep, int H, int T, int Mtot, int row0,
+                                                               unsigned long long seed, unsigned site, float p) {
+    const DropSite ds = drop_site(seed, site, p);
+    const size_t total = (size_t)H * T * T;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const unsigned j = (unsigned)(i % T), qh = (unsigned)(i / T), query = qh % (unsigned)T, hd = qh / (unsigned)T;
+        keep[i] = drop_keep(ds, drop_rowkey(ds, hd * (unsigned)Mtot + (unsigned)row0 + query), j) ? 1 : 0;
     }
 }
 
@@ -479,25 +571,25 @@ static int allow_lds(const void *kernel, size_t bytes, std::atomic<unsigned char
     return rc;
 }
 
-#define VST_ATTN_LAUNCH(KERNEL_, DH_, DROP_, ...)                                                               \
+#define VST_ATTN_LAUNCH(KERNEL_, PK_, DH_, DROP_, ...)                                                          \
     do {                                                                                                        \
         static std::atomic<unsigned char> done_[64];                                                            \
         constexpr size_t lds_bytes_ = 2 * sizeof(TileLds<DH_>);                                                 \
-        if (const int rc_ = allow_lds((const void *)KERNEL_<DH_, DROP_>, lds_bytes_, done_)) return rc_;        \
-        hipLaunchKernelGGL((KERNEL_<DH_, DROP_>), grid, dim3(256), lds_bytes_, st, __VA_ARGS__);                \
+        if (const int rc_ = allow_lds((const void *)KERNEL_<DH_, DROP_, PK_>, lds_bytes_, done_)) return rc_;   \
+        hipLaunchKernelGGL((KERNEL_<DH_, DROP_, PK_>), grid, dim3(256), lds_bytes_, st, __VA_ARGS__);           \
     } while (0)
-#define VST_ATTN_DH(KERNEL_, DH_, ...)                                                                          \
+#define VST_ATTN_DH(KERNEL_, PK_, DH_, ...)                                                                     \
     do {                                                                                                        \
-        if (!(p > 0.f)) VST_ATTN_LAUNCH(KERNEL_, DH_, 0, __VA_ARGS__);                                          \
-        else if (dbits != nullptr) VST_ATTN_LAUNCH(KERNEL_, DH_, 2, __VA_ARGS__);                               \
-        else VST_ATTN_LAUNCH(KERNEL_, DH_, 1, __VA_ARGS__);                                                     \
+        if (!(p > 0.f)) VST_ATTN_LAUNCH(KERNEL_, PK_, DH_, 0, __VA_ARGS__);                                     \
+        else if (dbits != nullptr) VST_ATTN_LAUNCH(KERNEL_, PK_, DH_, 2, __VA_ARGS__);                          \
+        else VST_ATTN_LAUNCH(KERNEL_, PK_, DH_, 1, __VA_ARGS__);                                                \
     } while (0)
-#define VST_ATTN_DISPATCH(KERNEL_, ...)                                                                         \
+#define VST_ATTN_DISPATCH(KERNEL_, PK_, ...)      /* PK_: packed ragged batch (work list) */                    \
     do {                                                                                                        \
-        if (dh == 32) VST_ATTN_DH(KERNEL_, 32, __VA_ARGS__);                                                    \
-        else if (dh == 64) VST_ATTN_DH(KERNEL_, 64, __VA_ARGS__);                                               \
-        else if (dh == 128) VST_ATTN_DH(KERNEL_, 128, __VA_ARGS__);                                             \
-        else if (dh == 256) VST_ATTN_DH(KERNEL_, 256, __VA_ARGS__);      /* round 4: correctness first (1 wave / SIMD, spills) */ \
+        if (dh == 32) VST_ATTN_DH(KERNEL_, PK_, 32, __VA_ARGS__);                                               \
+        else if (dh == 64) VST_ATTN_DH(KERNEL_, PK_, 64, __VA_ARGS__);                                          \
+        else if (dh == 128) VST_ATTN_DH(KERNEL_, PK_, 128, __VA_ARGS__);                                        \
+        else if (dh == 256) VST_ATTN_DH(KERNEL_, PK_, 256, __VA_ARGS__);      /* round 4: correctness first (1 wave / SIMD, spills) */ \
         else return -1;                                                                                         \
     } while (0)
 
@@ -509,7 +601,66 @@ int vst_attention_dropout_bits(unsigned *dbits, int B, int H, int T, unsigned lo
     const int W = (T + 31) / 32;
     const size_t ntile = (size_t)B * H * W * ((W + 1) / 2);
     const int blocks = (int)((ntile + 3) / 4 < 16384 ? (ntile + 3) / 4 : 16384);
-    hipLaunchKernelGGL(attn_dropout_bits, dim3(blocks < 1 ? 1 : blocks), dim3(256), 0, st, dbits, B * H, T, seed, site, p);
+    hipLaunchKernelGGL(attn_dropout_bits<false>, dim3(blocks < 1 ? 1 : blocks), dim3(256), 0, st, dbits, B * H, T, seed, site, p,
+                       VstPackedPlan{});
+    VSK_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- packed ragged batches ----
+size_t vst_packed_plan_ints(int B, int work_cap) { return 2 * (size_t)(B + 1) + 2 * (size_t)work_cap; }
+
+// plan (vst_packed_plan_ints(B, work_cap) ints) <- cu | bo | work from the device lengths; the VstPackedPlan of the kernels
+int vst_plan_packed(const int *lengths_dev, int B, int Mtot, size_t words, int *plan, int work_cap, hipStream_t st,
+                    VstPackedPlan *pk) {
+    int *cu = plan, *bo = plan + (B + 1), *work = plan + 2 * (B + 1);
+    hipLaunchKernelGGL(plan_packed_train, dim3(1), dim3(64), 0, st, lengths_dev, B, Mtot, cu, bo, work, work_cap);
+    VSK_CHECK_LAUNCH();
+    *pk = VstPackedPlan{cu, bo, work, work_cap, Mtot, (unsigned)words};
+    return 0;
+}
+
+// dbits (2 * H * pk.words words) <- both bit-packed copies of the keep decisions of every video; tmax: the longest video
+int vst_attention_dropout_bits_packed(unsigned *dbits, int B, int H, int tmax, unsigned long long seed, unsigned site, float p,
+                                      hipStream_t st, const VstPackedPlan &pk) {
+    const int W = (tmax + 31) / 32;
+    const size_t ntile = (size_t)H * W * ((W + 1) / 2);
+    const int blocks = (int)((ntile + 3) / 4 < 1024 ? (ntile + 3) / 4 : 1024);
+    hipLaunchKernelGGL(attn_dropout_bits<true>, dim3(blocks < 1 ? 1 : blocks, B), dim3(256), 0, st, dbits, H, 0, seed, site, p, pk);
+    VSK_CHECK_LAUNCH();
+    return 0;
+}
+
+int vst_attention_fwd_packed(const float *q, const float *k, const float *v, float *out, float *lse2, int H, int dh, float scale,
+                             unsigned long long seed, unsigned site, float p, hipStream_t st, const unsigned *dbits,
+                             const VstPackedPlan &pk) {
+    if (p < 0.f || p >= 1.f || pk.nwork <= 0) return -1;
+    const dim3 grid(H * pk.nwork);
+    const uint8_t *mask = nullptr;
+    VST_ATTN_DISPATCH(attn_fwd_train, true, q, k, v, mask, out, lse2, H, 0, scale, seed, site, p, dbits, pk);
+    VSK_CHECK_LAUNCH();
+    return 0;
+}
+
+int vst_attention_bwd_packed(const float *q, const float *k, const float *v, const float *dO, const float *lse2,
+                             const float *delta, float *dqkv, int H, int dh, float scale, unsigned long long seed, unsigned site,
+                             float p, hipStream_t st, const unsigned *dbits, const VstPackedPlan &pk) {
+    if (p < 0.f || p >= 1.f || pk.nwork <= 0) return -1;
+    const dim3 grid(H * pk.nwork);
+    const uint8_t *mask = nullptr;
+    VST_ATTN_DISPATCH(attn_bwd_dkdv, true, q, k, v, mask, dO, lse2, delta, dqkv, H, 0, scale, seed, site, p, dbits, pk);
+    VSK_CHECK_LAUNCH();
+    VST_ATTN_DISPATCH(attn_bwd_dq, true, q, k, v, mask, dO, lse2, delta, dqkv, H, 0, scale, seed, site, p, dbits, pk);
+    VSK_CHECK_LAUNCH();
+    return 0;
+}
+
+// test hook: keep (H * T * T bytes) of one video of a packed batch (T frames from packed row row0 of Mtot)
+int vst_attention_dropout_mask_video(uint8_t *keep, int H, int T, int Mtot, int row0, unsigned long long seed, unsigned site,
+                                     float p, hipStream_t st) {
+    const size_t total = (size_t)H * T * T;
+    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    hipLaunchKernelGGL(attn_dropout_mask_video, dim3(blocks < 1 ? 1 : blocks), dim3(256), 0, st, keep, H, T, Mtot, row0, seed, site, p);
     VSK_CHECK_LAUNCH();
     return 0;
 }
@@ -520,7 +671,7 @@ int vst_attention_fwd(const float *q, const float *k, const float *v, const uint
                       hipStream_t st, const unsigned *dbits) {
     if (p < 0.f || p >= 1.f) return -1;
     const dim3 grid(B * H * ((T + 127) / 128));
-    VST_ATTN_DISPATCH(attn_fwd_train, q, k, v, mask, out, lse2, H, T, scale, seed, site, p, dbits);
+    VST_ATTN_DISPATCH(attn_fwd_train, false, q, k, v, mask, out, lse2, H, T, scale, seed, site, p, dbits, VstPackedPlan{});
     VSK_CHECK_LAUNCH();
     return 0;
 }
@@ -530,9 +681,9 @@ int vst_attention_bwd(const float *q, const float *k, const float *v, const uint
                       unsigned long long seed, unsigned site, float p, hipStream_t st, const unsigned *dbits) {
     if (p < 0.f || p >= 1.f) return -1;
     const dim3 grid(B * H * ((T + 127) / 128));
-    VST_ATTN_DISPATCH(attn_bwd_dkdv, q, k, v, mask, dO, lse2, delta, dqkv, H, T, scale, seed, site, p, dbits);
+    VST_ATTN_DISPATCH(attn_bwd_dkdv, false, q, k, v, mask, dO, lse2, delta, dqkv, H, T, scale, seed, site, p, dbits, VstPackedPlan{});
     VSK_CHECK_LAUNCH();
-    VST_ATTN_DISPATCH(attn_bwd_dq, q, k, v, mask, dO, lse2, delta, dqkv, H, T, scale, seed, site, p, dbits);
+    VST_ATTN_DISPATCH(attn_bwd_dq, false, q, k, v, mask, dO, lse2, delta, dqkv, H, T, scale, seed, site, p, dbits, VstPackedPlan{});
     VSK_CHECK_LAUNCH();
     return 0;
 }

@@ -15,7 +15,8 @@ namespace {
 //     keep  <=>  element >= threshold = round(p * 2^16)       (p is honoured to 1 / 65 536)
 // `site` numbers the dropout module (embedding; per layer: attention weights, dropout1, mlp.dropout, dropout2 —
 // reference simnet.py:237, 159, 107, 181, 110); for the attention weights row = (video*H + head)*T + query and
-// col = key, elsewhere row = frame index and col = feature index.  The stream differs from torch's Philox stream
+// col = key (packed ragged batches: row = head*Mtot + packed row of the query, col = key index within the video),
+// elsewhere row = frame index (packed: packed row) and col = feature index.  The stream differs from torch's Philox stream
 // (the reference's masks cannot be reproduced by any re-implementation); what is pinned by tests is the keep rate,
 // the independence across sites/rows, and that forward and backward use the SAME mask (finite differences and an
 // explicit-mask torch model).

@@ -40,6 +40,9 @@ int vst_mse_mask_fwd(const float *out, const float *tgt, const unsigned char *ma
                      float *loss, hipStream_t st);
 int vst_mse_mask_bwd(const float *out, const float *tgt, const unsigned char *mask, const float *gout, int n, int mean,
                      float *dout, hipStream_t st);
+// the same sum of squares over n unmasked entries with a caller-given normaliser (packed batches: 1 / (B * Tmax))
+int vst_mse_scaled_fwd(const float *out, const float *tgt, int n, float inv_n, float *part, float *loss, hipStream_t st);
+int vst_mse_scaled_bwd(const float *out, const float *tgt, const float *gout, int n, float inv_n, float *dout, hipStream_t st);
 
 // ---- attention (vs_train_attention.hip); q, k, v head-major [B,H,T,dh]; out / dO token-major [B*T, H*dh] ----
 // forward with dropout on the attention weights; lse2[b,h,t] = log2 sum_j exp(s_ij) (base-2 log-sum-exp of the
@@ -63,6 +66,24 @@ int vst_attention_fwd_bf16(const float *q, const float *k, const float *v, const
 int vst_attention_bwd_bf16(const float *q, const float *k, const float *v, const uint8_t *mask, const float *dO,
                            const float *lse2, const float *delta, float *dqkv, int B, int H, int T, int dh, float scale,
                            float p, const unsigned *dbits, hipStream_t st, int in16 = 0, int out16 = 0);      // in16: q (pre-scaled), k, v stored as bf16; out16: dqkv written as bf16
+// ---- packed ragged batches (vs_train_forward_packed): q, k, v head-major over the packed rows [H][Mtot][dh], lse2 / delta
+// [H][Mtot], out / dO / dqkv token-major over the packed rows; exact fp32 only ----
+// The device plan: cu [B+1] row offsets | bo [B+1] keep-word offsets (video b: T_b * ceil(T_b / 32) words per head) |
+// work [nwork][2] (video, 128-row owner tile; video -1: nothing).  words = bo[B] as the host counted it.
+struct VstPackedPlan { const int *cu, *bo, *work; int nwork, Mtot; unsigned words; };
+size_t vst_packed_plan_ints(int B, int work_cap);
+int vst_plan_packed(const int *lengths_dev, int B, int Mtot, size_t words, int *plan, int work_cap, hipStream_t st,
+                    VstPackedPlan *pk);
+int vst_attention_dropout_bits_packed(unsigned *dbits, int B, int H, int tmax, unsigned long long seed, unsigned site, float p,
+                                      hipStream_t st, const VstPackedPlan &pk);       // dbits: 2 * H * pk.words words
+int vst_attention_fwd_packed(const float *q, const float *k, const float *v, float *out, float *lse2, int H, int dh, float scale,
+                             unsigned long long seed, unsigned site, float p, hipStream_t st, const unsigned *dbits,
+                             const VstPackedPlan &pk);
+int vst_attention_bwd_packed(const float *q, const float *k, const float *v, const float *dO, const float *lse2,
+                             const float *delta, float *dqkv, int H, int dh, float scale, unsigned long long seed, unsigned site,
+                             float p, hipStream_t st, const unsigned *dbits, const VstPackedPlan &pk);
+int vst_attention_dropout_mask_video(uint8_t *keep, int H, int T, int Mtot, int row0, unsigned long long seed, unsigned site,
+                                     float p, hipStream_t st);
 // test hook: keep[b,h,i,j] (bytes) of the attention-weight dropout, exactly as the two kernels above draw it
 int vst_attention_dropout_mask(uint8_t *keep, int B, int H, int T, unsigned long long seed, unsigned site, float p,
                                hipStream_t st);

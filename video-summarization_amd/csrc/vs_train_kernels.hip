@@ -917,3 +917,19 @@ int vst_mse_mask_bwd(const float *out, const float *tgt, const unsigned char *ma
     VSK_CHECK_LAUNCH();
     return 0;
 }
+
+int vst_mse_scaled_fwd(const float *out, const float *tgt, int n, float inv_n, float *part, float *loss, hipStream_t st) {
+    const int blocks = vst_mse_mask_blocks(n);
+    hipLaunchKernelGGL(mse_mask_partial, dim3(blocks), dim3(256), 0, st, out, tgt, (const unsigned char *)nullptr, n, part);
+    VSK_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mse_mask_final, dim3(1), dim3(64), 0, st, part, blocks, inv_n, loss);
+    VSK_CHECK_LAUNCH();
+    return 0;
+}
+
+int vst_mse_scaled_bwd(const float *out, const float *tgt, const float *gout, int n, float inv_n, float *dout, hipStream_t st) {
+    hipLaunchKernelGGL(mse_mask_bwd, dim3(vst_mse_mask_blocks(n)), dim3(256), 0, st, out, tgt, (const unsigned char *)nullptr,
+                       gout, n, inv_n, dout);
+    VSK_CHECK_LAUNCH();
+    return 0;
+}

@@ -195,6 +195,13 @@ def collate_fn_train(batch):                                 # dataset.py:157-16
             pad_sequence(targets, batch_first=True, padding_value=PAD_VALUE))
 
 
+def collate_fn_train_packed(batch):
+    """``collate_fn_train`` without the padding: (features [sum T_i, 1024], targets [sum T_i], lengths) - the videos' frames
+    concatenated in batch order, for ``SimNet.forward_packed_train`` / ``losses.mse_packed_loss``."""
+    features, targets = zip(*batch)
+    return torch.cat(features, dim=0), torch.cat(targets, dim=0), [int(f.shape[0]) for f in features]
+
+
 def collate_fn_test(batch):                                  # dataset.py:164-168
     features, targets, user_summaries = batch[0]
     return features.unsqueeze(0), targets.unsqueeze(0), user_summaries

@@ -1,4 +1,5 @@
-"""Evaluation harness: the counterpart of the reference's ``val_step`` (``src/train.py:134-152``).
+"""Training and evaluation harness: the counterparts of the reference's ``train_step`` (``src/train.py:111-131``, on packed
+ragged batches: ``train_step_packed``) and ``val_step`` (``src/train.py:134-152``).
 
 ``val_step(model, loader, device)`` keeps the reference's contract: ``loader`` yields
 ``(feature [1,T,1024], target [1,T], user)`` per video (reference ``collate_fn_test``,
@@ -19,6 +20,27 @@ import torch.nn.functional as F
 
 from .corpus import plan_shards, score_corpus
 from .evaluation import eval_metrics, eval_videos
+from .losses import mse_packed_loss
+
+
+def train_step_packed(model, optim, loader: Iterable, scaler, device):
+    """The reference's ``train_step`` (``src/train.py:111-131``) on PACKED batches: ``loader`` yields ``(feature [sum T_i, 1024],
+    target [sum T_i], lengths)`` (``data.collate_fn_train_packed``); no sentinel rows, no mask, the same loss value and
+    gradients as the padded step.  Any ``torch.optim`` optimizer or the native ``Adam``; an unmodified ``GradScaler``.
+    Returns the mean loss over the batches."""
+    model.train()
+    total, n = 0.0, 0
+    for feature, target, lengths in loader:
+        feature, target = feature.to(device), target.to(device)
+        with torch.amp.autocast("cuda"):                                    # train.py:120
+            pred, _ = model.forward_packed_train(feature, lengths)
+            loss = mse_packed_loss(pred, target, lengths)                   # train.py:122
+        optim.zero_grad()
+        scaler.scale(loss).backward()
+        scaler.step(optim)
+        scaler.update()
+        total, n = total + loss.item(), n + 1
+    return total / max(n, 1)
 
 
 @torch.no_grad()

@@ -156,33 +156,7 @@ class _TrainForward(torch.autograd.Function):
         if module._packed_key != ctx.packed_key or module._packed is not packed:
             raise RuntimeError("SimNet parameters were modified between forward and backward")
         B, T, _ = x.shape
-        params = [t for t in module._tensors() if isinstance(t, nn.Parameter)]
-        # ONE allocation for every gradient, viewed per parameter (was ~70 torch.empty_like per backward)
-        axes = [ax for t, ax in zip(module._tensors(), module._tensor_axes()) if isinstance(t, nn.Parameter)]
-        shapes = [t.shape for t in params]
-        if module._plan:      # embedded model: the library writes gradients of ITS shape; the true-shaped parts go back
-            shapes = [module._padded_shape(t.shape, ax) for t, ax in zip(params, axes)]
-        sizes = [int(torch.Size(sh).numel()) for sh in shapes]
-        if all(n_ % 4 == 0 for n_ in sizes[:-1]):
-            # dense packing keeps every view 16-byte aligned (all the kernels need); the views come from ONE C++ call
-            flat = torch.empty((sum(sizes),), dtype=torch.float32, device=x.device)
-            grads = [g.view(sh) for g, sh in zip(flat.split_with_sizes(sizes), shapes)]
-        else:
-            offs = [0]
-            for n_ in sizes:
-                offs.append(offs[-1] + (n_ + 63) // 64 * 64)          # 256-byte aligned views
-            flat = torch.empty((offs[-1],), dtype=torch.float32, device=x.device)
-            grads = [flat[o: o + n_].view(sh) for o, n_, sh in zip(offs, sizes, shapes)]
-        it = iter(grads)
-        G = _lib.ModelGrads()
-        G.embed_w, G.embed_b = next(it).data_ptr(), next(it).data_ptr()
-        layers = (_lib.LayerGrads * max(module.num_layers, 1))()
-        for l in range(module.num_layers):
-            for name in ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln1_g", "ln1_b",
-                         "w1", "b1", "w2", "b2", "ln2_g", "ln2_b"):
-                setattr(layers[l], name, next(it).data_ptr())
-        G.layers = layers
-        G.final_w, G.final_b = next(it).data_ptr(), next(it).data_ptr()
+        grads, G, finish = _grad_destinations(module, x.device)
         dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
         ds = None if d_scores is None else d_scores.contiguous().float()
         dh = None if d_hidden is None else d_hidden.contiguous().float()
@@ -195,10 +169,110 @@ class _TrainForward(torch.autograd.Function):
             _lib.check(lib.vs_train_backward(packed.handle, x.data_ptr(), _ptr(m), B, T, C.byref(cfg), _ptr(ds), _ptr(dh),
                                              saved.data_ptr(), saved.numel(), C.byref(G), _ptr(dx), ws.data_ptr(),
                                              ws.numel(), stream))
+        return (None, dx, None, None, None, None, None, *finish(grads))
+
+
+def _grad_destinations(module, device):
+    """The gradient tensors of one backward and the ``vs_model_grads`` that points at them: ONE allocation, viewed per
+    parameter (was ~70 torch.empty_like per backward).  Returns (grads, G, finish); ``finish(grads)`` gives autograd's
+    per-parameter return values (true shapes of an embedded model, None where no gradient is required)."""
+    params = [t for t in module._tensors() if isinstance(t, nn.Parameter)]
+    axes = [ax for t, ax in zip(module._tensors(), module._tensor_axes()) if isinstance(t, nn.Parameter)]
+    shapes = [t.shape for t in params]
+    if module._plan:      # embedded model: the library writes gradients of ITS shape; the true-shaped parts go back
+        shapes = [module._padded_shape(t.shape, ax) for t, ax in zip(params, axes)]
+    sizes = [int(torch.Size(sh).numel()) for sh in shapes]
+    if all(n_ % 4 == 0 for n_ in sizes[:-1]):
+        # dense packing keeps every view 16-byte aligned (all the kernels need); the views come from ONE C++ call
+        flat = torch.empty((sum(sizes),), dtype=torch.float32, device=device)
+        grads = [g.view(sh) for g, sh in zip(flat.split_with_sizes(sizes), shapes)]
+    else:
+        offs = [0]
+        for n_ in sizes:
+            offs.append(offs[-1] + (n_ + 63) // 64 * 64)          # 256-byte aligned views
+        flat = torch.empty((offs[-1],), dtype=torch.float32, device=device)
+        grads = [flat[o: o + n_].view(sh) for o, n_, sh in zip(offs, sizes, shapes)]
+    it = iter(grads)
+    G = _lib.ModelGrads()
+    G.embed_w, G.embed_b = next(it).data_ptr(), next(it).data_ptr()
+    layers = (_lib.LayerGrads * max(module.num_layers, 1))()
+    for l in range(module.num_layers):
+        for name in ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln1_g", "ln1_b",
+                     "w1", "b1", "w2", "b2", "ln2_g", "ln2_b"):
+            setattr(layers[l], name, next(it).data_ptr())
+    G.layers = layers
+    G.final_w, G.final_b = next(it).data_ptr(), next(it).data_ptr()
+
+    def finish(gs):
         if module._plan:
-            grads = [module._unpad(g, ax).contiguous() for g, ax in zip(grads, axes)]
-        out = [g if t.requires_grad else None for g, t in zip(grads, params)]
-        return (None, dx, None, None, None, None, None, *out)
+            gs = [module._unpad(g, ax).contiguous() for g, ax in zip(gs, axes)]
+        return [g if t.requires_grad else None for g, t in zip(gs, params)]
+    return grads, G, finish
+
+
+class _TrainForwardPacked(torch.autograd.Function):
+    """``SimNet.forward_packed_train`` under autograd: ``vs_train_forward_packed`` / ``vs_train_backward_packed`` on the frames
+    of several videos concatenated - no sentinel rows, no mask, nothing computed for padding.  Same structure as
+    ``_TrainForward``: parameters as inputs, the activation record one uint8 tensor saved for the backward."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, module, x, lengths, p, p_embed, seed, tflags, *params):
+        lib = _lib.load()
+        x = x.contiguous()
+        M, Bv = x.size(0), len(lengths)
+        host = (C.c_int32 * Bv)(*lengths)
+        packed = module._packed_weights(x.device)
+        scores = torch.empty((M, module.num_classes), dtype=torch.float32, device=x.device)
+        hidden = torch.empty((M, module._lib_d), dtype=torch.float32, device=x.device)
+        cfg = _lib.DropoutCfg(float(p_embed), float(p), int(seed), int(tflags), 0)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            if not getattr(packed, "train_prepared", False):
+                _lib.check(lib.vs_train_prepare(packed.handle, stream))
+                packed.train_prepared = True
+            dev_len = torch.tensor(lengths, dtype=torch.int32, device=x.device)
+            need = lib.vs_train_saved_bytes_packed(packed.handle, host, Bv)
+            if need == 0:       # invalid lengths: the forward says why
+                _lib.check(lib.vs_train_forward_packed(packed.handle, x.data_ptr(), host, dev_len.data_ptr(), Bv, C.byref(cfg),
+                                                       scores.data_ptr(), None, None, 0, None, 0, stream))
+            saved = torch.empty((need,), dtype=torch.uint8, device=x.device)
+            ws = torch.empty((lib.vs_train_workspace_bytes_packed(packed.handle, host, Bv),), dtype=torch.uint8, device=x.device)
+            _lib.check(lib.vs_train_forward_packed(packed.handle, x.data_ptr(), host, dev_len.data_ptr(), Bv, C.byref(cfg),
+                                                   scores.data_ptr(), hidden.data_ptr(), saved.data_ptr(), saved.numel(),
+                                                   ws.data_ptr(), ws.numel(), stream))
+            fmt = int(lib.vs_train_last_format())
+        ctx.save_for_backward(x, dev_len, saved)
+        ctx.module, ctx.cfg, ctx.packed, ctx.packed_key = module, (float(p_embed), float(p), int(seed), int(tflags), fmt), packed, module._packed_key
+        ctx.lengths = tuple(lengths)
+        module._note_train_arithmetic(int(tflags) & ~_lib.VS_TRAIN_FLAG_BF16_ATTENTION, fmt, M)
+        ctx.set_materialize_grads(False)
+        return scores, (hidden[..., :module.d_model] if module._plan else hidden)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, d_scores, d_hidden):
+        lib = _lib.load()
+        x, dev_len, saved = ctx.saved_tensors
+        module, packed = ctx.module, ctx.packed
+        if module._packed_key != ctx.packed_key or module._packed is not packed:
+            raise RuntimeError("SimNet parameters were modified between forward and backward")
+        Bv = len(ctx.lengths)
+        host = (C.c_int32 * Bv)(*ctx.lengths)
+        grads, G, finish = _grad_destinations(module, x.device)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        ds = None if d_scores is None else d_scores.contiguous().float()
+        dh = None if d_hidden is None else d_hidden.contiguous().float()
+        if dh is not None and module._plan:
+            dh = module._pad(dh, ("res",)).contiguous()
+        cfg = _lib.DropoutCfg(*ctx.cfg)
+        with torch.cuda.device(x.device):
+            ws = torch.empty((lib.vs_train_workspace_bytes_packed(packed.handle, host, Bv),), dtype=torch.uint8, device=x.device)
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            _lib.check(lib.vs_train_backward_packed(packed.handle, x.data_ptr(), host, dev_len.data_ptr(), Bv, C.byref(cfg),
+                                                    _ptr(ds), _ptr(dh), saved.data_ptr(), saved.numel(), C.byref(G), _ptr(dx),
+                                                    ws.data_ptr(), ws.numel(), stream))
+        return (None, dx, None, None, None, None, None, *finish(grads))
 
 
 # --------------------------------------------------------------------------------------------
@@ -473,10 +547,7 @@ class SimNet(nn.Module):
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if (p > 0.0 or p_embed > 0.0) else 0
         params = [t for t in self._tensors() if isinstance(t, nn.Parameter)]
         x32 = x if x.dtype == torch.float32 else x.float()
-        tflags = (_lib.VS_TRAIN_FLAG_BF16_LINEAR | _lib.VS_TRAIN_FLAG_BF16_ATTENTION) if self._train_dtype in ("bf16", "fp16") else 0
-        if self._train_dtype == "fp16":
-            tflags |= _lib.VS_TRAIN_FLAG_FP16
-        return _TrainForward.apply(self, x32, mask, p, p_embed, seed, tflags, *params)
+        return _TrainForward.apply(self, x32, mask, p, p_embed, seed, self._train_flags(), *params)
 
     def forward(self, x: Tensor, mask=None, vis_attention=None, model_score: bool = False):
         """Same contract as reference ``SimNet.forward`` (simnet.py:32-45): returns
@@ -695,11 +766,47 @@ class SimNet(nn.Module):
         significant bits, gradients ~8x closer to the truth (TRAIN_FP16_*), but a range of 65 504 / 6e-8: train with a loss
         scale exactly as the reference does (``torch.amp.GradScaler``, train.py:60,126-128) - ``scaler.scale(loss).backward()``
         reaches these kernels as a scaled ``d_scores``, an overflow surfaces as inf / NaN gradients and GradScaler skips
-        the step and halves the scale."""
+        the step and halves the scale.
+        Packed ragged batches (``forward_packed_train``): the Linears, dgrad and wgrad follow this setting; the packed attention
+        is exact fp32 in every mode."""
         if value not in ("fp32", "bf16", "fp16"):
             raise ValueError("train dtype must be 'fp32', 'bf16' or 'fp16', got %r" % (value,))
         self._train_dtype = value
         return self
+
+    def _train_flags(self) -> int:
+        tflags = (_lib.VS_TRAIN_FLAG_BF16_LINEAR | _lib.VS_TRAIN_FLAG_BF16_ATTENTION) if self._train_dtype in ("bf16", "fp16") else 0
+        return tflags | (_lib.VS_TRAIN_FLAG_FP16 if self._train_dtype == "fp16" else 0)
+
+    def forward_packed_train(self, x: Tensor, lengths):
+        """``forward`` under autograd on a RAGGED batch without padding: x [sum(lengths), in_features] = the videos' frames
+        concatenated (``data.collate_fn_train_packed``).  Returns (logits [Mtot, num_classes], hidden [Mtot, d_model]), both
+        differentiable; video i = rows sum(lengths[:i]) ...  Where the reference pads every batch to its longest video with
+        the 1000.0 sentinel and masks (dataset.py:157-161, train.py:118), no padded row is computed here - forward or
+        backward - and the activation record scales with sum(lengths): masked keys and masked loss rows contribute exactly
+        zero to every gradient, so with ``losses.mse_packed_loss`` the step equals the padded one.  With dropout off a
+        video's outputs are bit-identical to running it alone.  Dropout is active iff ``self.training`` (seed drawn like
+        ``forward``'s).  ``set_train_dtype("bf16" | "fp16")`` runs the Linears, dgrad and wgrad in low precision above
+        VS_TRAIN_LP_MIN_ROWS packed frames; the packed ATTENTION stays exact fp32 in every mode (``last_train_dtype`` names
+        the arithmetic of the Linears).  Every head dim of the padded training path; embedded shapes work; no class token."""
+        if self.use_cls:
+            raise NotImplementedError("packed batches are not available with use_cls=True")
+        if not x.is_cuda:
+            raise RuntimeError("SimNet runs on the MI355X HIP kernels only: move the module and its "
+                               "input to a HIP device (there is no CPU path for the scorer)")
+        lengths = [int(t) for t in lengths]
+        if x.dim() != 2 or x.size(1) != self.in_features or x.size(0) != sum(lengths):
+            raise RuntimeError("expected x of shape [sum(lengths)=%d, %d], got %s" % (sum(lengths), self.in_features, tuple(x.shape)))
+        if not lengths or min(lengths) <= 0:
+            raise RuntimeError("lengths must be positive, got %r" % (lengths,))
+        if self.use_pos and max(lengths) > self.pe_len:
+            raise RuntimeError("T=%d exceeds the positional table (%d rows)" % (max(lengths), self.pe_len))
+        p = self.drop_rate if self.training else 0.0
+        p_embed = self.sparsity if (self.training and self.use_pos) else 0.0
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if (p > 0.0 or p_embed > 0.0) else 0
+        params = [t for t in self._tensors() if isinstance(t, nn.Parameter)]
+        x32 = x if x.dtype == torch.float32 else x.float()
+        return _TrainForwardPacked.apply(self, x32, lengths, p, p_embed, seed, self._train_flags(), *params)
 
     @torch.no_grad()
     def forward_packed(self, x: Tensor, lengths, want_hidden: bool = True):

@@ -146,3 +146,10 @@ def random_mask(B: int, T: int, seed: int, p: float = 0.3) -> torch.Tensor:
     m = rng.random(size=(B, T)) < p
     m[:, 0] = False
     return torch.from_numpy(m)
+
+
+def corpus_lengths(n: int, seed: int, lo: int = 100, hi: int = 650) -> list:
+    """Frame counts of ``n`` videos drawn like the corpus this project targets (TVSum / SumMe at 2 fps: 100 to 650 frames per
+    video, uniform) - what a shuffled training batch looks like before it is padded to its longest video."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    return [int(t) for t in rng.integers(lo, hi + 1, size=n)]
