@@ -116,7 +116,11 @@ int vs_train_backward(vs_weights *w, const float *x, const uint8_t *key_pad_mask
  * `lengths` is a HOST array (it sizes the launches), `lengths_dev` the same values on the device: the row offsets and the
  * attention work list are built there, so no host memory is read after the call returns.  Same conventions as
  * vs_train_forward / _backward: stream-ordered, no allocation, int status + vs_last_error(); scores [Mtot, num_classes],
- * hidden [Mtot, d_model], d_scores / d_hidden / dx likewise.  A video's outputs do not depend on the batch it is packed in.
+ * hidden [Mtot, d_model], d_scores / d_hidden / dx likewise.  A video's outputs do not depend on the batch it is packed in
+ * (bit for bit, also between a batch above VS_SKINNY_ROWS rows and one at or below it).  lengths_dev that disagree with
+ * lengths cannot make the call write outside the buffers the host sized: a length is cut at max(lengths), rows beyond Mtot
+ * are cut, and a video whose attention keep words would not fit in the record gets length 0 (rows that no video covers
+ * are left unwritten).
  * Dropout: the row dropouts hash (seed, site, packed row, column); the attention weights hash (seed, site, head * Mtot +
  * packed row of the query, key index within the video).
  * Low precision: VS_TRAIN_FLAG_BF16_LINEAR (and VS_TRAIN_FLAG_FP16) apply as in the padded form, counted on Mtot rows; the

@@ -339,6 +339,40 @@ def _packed_gates(vsa, module, out_tensor, lengths, d, L):
     return gates
 
 
+def _per_video_float64(sd, x, target, lengths, H, p, p_embed, masks, gates, hidden_w=1e-3):
+    """The float64 checker of a packed step: tests/torch_ref.py run VIDEO BY VIDEO with the keep masks (_packed_masks) and the
+    ReLU-and-dropout gates (_packed_gates) of the packed step; loss = mse_packed_loss + hidden_w * hidden.sum().  Returns the
+    loss, the logits [Mtot] and the gradients {"x": dx, parameter name: gradient}."""
+    B, cu = len(lengths), _cu(lengths)
+    params = {k: v.double().clone().requires_grad_(k != "embedding_layer.positional_encoding.pos_embedding") for k, v in sd.items()}
+    x64 = x.double().clone().requires_grad_(True)
+    rloss, rl = 0.0, []
+    for b, t in enumerate(lengths):
+        sl = slice(cu[b], cu[b + 1])
+        mb = {k: (v[b] if isinstance(v, list) else v[sl][None]) for k, v in masks.items()}
+        gb = {k: v[sl][None] for k, v in gates.items()}
+        logits, hid = torch_ref.forward_with_masks(params, x64[sl][None], None, H, p, p_embed, mb, None, gb)
+        rloss = rloss + ((logits.view(-1) - target[sl].double()) ** 2).sum() / (B * max(lengths)) + hidden_w * hid.sum()
+        rl.append(logits.detach().view(-1))
+    rloss.backward()
+    grads = {"x": x64.grad}
+    grads.update({k: v.grad for k, v in params.items() if v.requires_grad})
+    return rloss.item(), torch.cat(rl), grads
+
+
+def _check_against_per_video_float64(sd, x, target, lengths, H, p, p_embed, masks, gates, loss, pred, grads, hidden_w=1e-3):
+    """loss, logits, dx and every parameter gradient of a packed step (grads: {"x": dx, name: gradient}) against
+    _per_video_float64, at the tolerances of the dropout test"""
+    rloss, rlogits, rgrads = _per_video_float64(sd, x, target, lengths, H, p, p_embed, masks, gates, hidden_w)
+    assert (pred.detach().cpu().double().view(-1) - rlogits).abs().max().item() < 1e-4
+    assert abs(loss.item() - rloss) < 1e-5 * max(1.0, abs(rloss))
+    assert sorted(grads) == sorted(rgrads)
+    _close(grads["x"], rgrads["x"], "dx")
+    for k, g in grads.items():
+        if k != "x":
+            _close(g, rgrads[k], k)
+
+
 PACKED_DROPOUT_STEPS = [(4, 256, 2, [90, 67, 33], 0.3, 0.0), (8, 256, 1, [130], 0.2, 0.5), (4, 512, 1, [70, 47, 1], 0.3, 0.0),
                         (1, 256, 1, [65, 40], 0.3, 0.0)]
 
@@ -353,7 +387,7 @@ def test_packed_training_step_with_dropout_matches_explicit_mask_model(vsa, H, d
     m = vsa.SimNet(num_heads=H, d_model=d, num_layers=L, sparsity=p_embed, dropout=p)
     m.load_state_dict(sd, strict=True)
     m = m.to(_dev()).train()
-    M, B, cu = sum(lengths), len(lengths), _cu(lengths)
+    M = sum(lengths)
     x = torch.randn(M, 1024, generator=torch.Generator().manual_seed(22))
     target = torch.rand(M, generator=torch.Generator().manual_seed(1))
     torch.manual_seed(77)
@@ -371,22 +405,9 @@ def test_packed_training_step_with_dropout_matches_explicit_mask_model(vsa, H, d
             pp = p_embed if name == "embed" else p
             rate, n = part.double().mean().item(), part.numel()
             assert abs(rate - (1 - pp)) < 5 * math.sqrt(pp * (1 - pp) / n), (name, rate, n)
-    params = {k: v.double().clone().requires_grad_(k != "embedding_layer.positional_encoding.pos_embedding") for k, v in sd.items()}
-    x64 = x.double().clone().requires_grad_(True)
-    rloss, rl = 0.0, []
-    for b, t in enumerate(lengths):
-        sl = slice(cu[b], cu[b + 1])
-        mb = {k: (v[b] if isinstance(v, list) else v[sl][None]) for k, v in masks.items()}
-        gb = {k: v[sl][None] for k, v in gates.items()}
-        logits, hid = torch_ref.forward_with_masks(params, x64[sl][None], None, H, p, p_embed, mb, None, gb)
-        rloss = rloss + ((logits.view(-1) - target[sl].double()) ** 2).sum() / (B * max(lengths)) + 1e-3 * hid.sum()
-        rl.append(logits.detach().view(-1))
-    rloss.backward()
-    assert (pred.detach().cpu().double().view(-1) - torch.cat(rl)).abs().max().item() < 1e-4
-    assert abs(loss.item() - rloss.item()) < 1e-5 * max(1.0, abs(rloss.item()))
-    _close(xd.grad, x64.grad, "dx")
-    for k, prm in m.named_parameters():
-        _close(prm.grad, params[k].grad, k)
+    grads = {"x": xd.grad}
+    grads.update({k: prm.grad for k, prm in m.named_parameters()})
+    _check_against_per_video_float64(sd, x, target, lengths, H, p, p_embed, masks, gates, loss, pred, grads)
     with torch.no_grad():                                    # and dropout really happened
         e, _ = m.eval().forward_packed_train(x.to(_dev()), lengths)      # (the scoring packed call has no head dim 256)
     assert (e - pred.detach()).abs().max().item() > 1e-3

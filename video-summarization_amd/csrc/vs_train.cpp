@@ -333,7 +333,7 @@ static int forward_impl(const vs_weights *w, const float *x, const uint8_t *key_
     VstPackedPlan pk{};
     const float *pe = w->has_pe ? w->p(w->pe) : nullptr;
     if (pc) {
-        VST_LAUNCH(vst_plan_packed(pc->lengths_dev, pc->B, M, pc->words, (int *)(ws + W.plan), pc->nwork, st, &pk));
+        VST_LAUNCH(vst_plan_packed(pc->lengths_dev, pc->B, M, pc->tmax, pc->words, (int *)(ws + W.plan), pc->nwork, st, &pk));
         if (w->has_pe) {
             VST_LAUNCH(vsk_gather_rows(w->p(w->pe), pk.cu, pc->B, pc->tmax, d, ws + W.pe, st));
             pe = ws + W.pe;
@@ -446,7 +446,7 @@ static int backward_impl(vs_weights *w, const float *x, const uint8_t *key_pad_m
     const float *zeros = w->tp(w->zeros);
     const int nblk = vst_ln_bwd_blocks(M);
     VstPackedPlan pk{};       // packed: the plan is rebuilt from the device lengths (one small launch), not kept in the record
-    if (pc) VST_LAUNCH(vst_plan_packed(pc->lengths_dev, pc->B, M, pc->words, (int *)(ws + W.plan), pc->nwork, st, &pk));
+    if (pc) VST_LAUNCH(vst_plan_packed(pc->lengths_dev, pc->B, M, pc->tmax, pc->words, (int *)(ws + W.plan), pc->nwork, st, &pk));
 
     // final_layer (simnet.py:42): d_W = d_scores^T hidden, d_b = column sums of d_scores
     {
@@ -654,7 +654,7 @@ int vs_train_attention_forward_packed(const float *q, const float *k, const floa
         return failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, vs_train_attention_packed_scratch_bytes(lengths, B, H));
     hipStream_t st = (hipStream_t)stream;
     VstPackedPlan pk{};
-    VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.words, (int *)scratch, pc.nwork, st, &pk));
+    VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
     VST_LAUNCH(vst_attention_fwd_packed(q, k, v, out, lse2, H, dh, scale, seed, site, p, st, nullptr, pk));
     return VS_OK;
 }
@@ -673,7 +673,7 @@ int vs_train_attention_backward_packed(const float *q, const float *k, const flo
     hipStream_t st = (hipStream_t)stream;
     float *delta = (float *)scratch + attention_packed_plan_floats(pc);
     VstPackedPlan pk{};
-    VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.words, (int *)scratch, pc.nwork, st, &pk));
+    VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
     VST_LAUNCH(vst_head_rowdot(d_out, out, delta, pc.Mtot, pc.Mtot, H, dh, st));
     VST_LAUNCH(vst_attention_bwd_packed(q, k, v, d_out, lse2, delta, dqkv, H, dh, scale, seed, site, p, st, nullptr, pk));
     return VS_OK;

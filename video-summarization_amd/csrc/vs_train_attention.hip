@@ -497,17 +497,22 @@ __global__ __launch_bounds__(256) void attn_dropout_bits(unsigned *__restrict__ 
 // owner tile) work list of a packed batch, from DEVICE lengths (one thread: B is a few hundred at most).  The list is
 // ordered longest video first (by its number of owner tiles): a block's time grows with the rows it streams, and the grid is
 // a few waves of blocks deep, so the long blocks must not start last.  The host sized the launches from its copy of the
-// lengths: rows beyond Mtot are cut, pairs beyond work_cap dropped, and the unused tail of the list is marked (video -1:
-// the block returns).
-__global__ void plan_packed_train(const int *__restrict__ lengths, int B, int Mtot, int *__restrict__ cu, int *__restrict__ bo,
-                                  int *__restrict__ work, int work_cap) {
+// lengths: a length is cut at the host's longest video tmax (the positional gather and the keep-word launch are sized by
+// it) and rows beyond Mtot are cut, a video whose keep words would not fit in the words_cap words the host sized per head
+// and copy gets length 0 (every consumer skips it: no tile in the list, cu[b + 1] == cu[b]), pairs beyond work_cap are
+// dropped, and the unused tail of the list is marked (video -1: the block returns).  So cu, bo and the list are all bounded
+// by what the host allocated, whatever the device lengths say.
+__global__ void plan_packed_train(const int *__restrict__ lengths, int B, int Mtot, int tmax, unsigned words_cap,
+                                  int *__restrict__ cu, int *__restrict__ bo, int *__restrict__ work, int work_cap) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int row = 0, words = 0, most = 0;
     for (int b = 0; b < B; ++b) {
         cu[b] = row;
         bo[b] = words;
         int t = lengths[b];
+        t = t > tmax ? tmax : t;
         t = t < 0 ? 0 : (t > Mtot - row ? Mtot - row : t);
+        if ((unsigned long long)words + (unsigned long long)t * ((t + 31) / 32) > words_cap) t = 0;
         most = (t + 127) / 128 > most ? (t + 127) / 128 : most;
         row += t;
         words += t * ((t + 31) / 32);
@@ -611,10 +616,11 @@ int vst_attention_dropout_bits(unsigned *dbits, int B, int H, int T, unsigned lo
 size_t vst_packed_plan_ints(int B, int work_cap) { return 2 * (size_t)(B + 1) + 2 * (size_t)work_cap; }
 
 // plan (vst_packed_plan_ints(B, work_cap) ints) <- cu | bo | work from the device lengths; the VstPackedPlan of the kernels
-int vst_plan_packed(const int *lengths_dev, int B, int Mtot, size_t words, int *plan, int work_cap, hipStream_t st,
+int vst_plan_packed(const int *lengths_dev, int B, int Mtot, int tmax, size_t words, int *plan, int work_cap, hipStream_t st,
                     VstPackedPlan *pk) {
     int *cu = plan, *bo = plan + (B + 1), *work = plan + 2 * (B + 1);
-    hipLaunchKernelGGL(plan_packed_train, dim3(1), dim3(64), 0, st, lengths_dev, B, Mtot, cu, bo, work, work_cap);
+    hipLaunchKernelGGL(plan_packed_train, dim3(1), dim3(64), 0, st, lengths_dev, B, Mtot, tmax, (unsigned)words, cu, bo, work,
+                       work_cap);
     VSK_CHECK_LAUNCH();
     *pk = VstPackedPlan{cu, bo, work, work_cap, Mtot, (unsigned)words};
     return 0;

@@ -72,7 +72,7 @@ int vst_attention_bwd_bf16(const float *q, const float *k, const float *v, const
 // work [nwork][2] (video, 128-row owner tile; video -1: nothing).  words = bo[B] as the host counted it.
 struct VstPackedPlan { const int *cu, *bo, *work; int nwork, Mtot; unsigned words; };
 size_t vst_packed_plan_ints(int B, int work_cap);
-int vst_plan_packed(const int *lengths_dev, int B, int Mtot, size_t words, int *plan, int work_cap, hipStream_t st,
+int vst_plan_packed(const int *lengths_dev, int B, int Mtot, int tmax, size_t words, int *plan, int work_cap, hipStream_t st,
                     VstPackedPlan *pk);
 int vst_attention_dropout_bits_packed(unsigned *dbits, int B, int H, int tmax, unsigned long long seed, unsigned site, float p,
                                       hipStream_t st, const VstPackedPlan &pk);       // dbits: 2 * H * pk.words words
