@@ -188,6 +188,8 @@ int vs_scorer_forward_packed(const vs_weights *w, const float *x, const int32_t 
 #define VS_STAGE_OUTPROJ_LN 3  /* feature_projection + residual + norm1     gemm_res_ln       */
 #define VS_STAGE_FC1 4         /* mlp.fc1 + ReLU                            gemm_nt_128<RELU> */
 #define VS_STAGE_FC2_LN 5      /* mlp.fc2 + residual + norm2 (+ score head) gemm_res_ln       */
+/* exact fp32 at d_model 256 above the latency threshold: stage 3 is never recorded - its work runs in the kernel recorded
+ * as stage 4 (layer_outproj_ln_fc1) - and stage 5 carries every QKV projection but the first layer's (layer_fc2_ln_qkv) */
 #define VS_NUM_STAGES 6
 int vs_profile_enable(int32_t on);
 int vs_profile_collect(double *ms_sum, int64_t *launches);
@@ -196,8 +198,9 @@ const char *vs_stage_name(int32_t stage);
 /* A/B and test switches (DESIGN.md "Environment switches"; none selects a fallback).  Their defaults come from
  * environment variables of the same name, read ONCE when the library is first used - no forward calls getenv.
  * value < 0 restores the environment / built-in default.  Names: VS_SKINNY_ROWS, VS_LP_MIN_ROWS, VS_LP_MIN_ROWS_FUSED, VS_TRAIN_LP_MIN_ROWS, VS_ATTN_W64, VS_ATTN_W64_CHECKED, VS_GEMM_NWM2,
- * VS_GEMM_NJ2, VS_ATTN_NW4, VS_ATTN_LP_SIMPLE, VS_LP_STORE32, VS_LP_MLP_UNFUSED, VS_LP_TAIL_UNFUSED, VS_LP_QKV_UNFUSED, VS_LP_EMBED_UNFUSED, VS_LP_TILE256 (+ VS_MLP_FUSION, VS_MLP_ABL, VS_ATTN_LEGACY, which only the
- * diagnostic build of the library acts on).  Process-wide; not meant to be flipped while forwards are in flight. */
+ * VS_GEMM_NJ2, VS_ATTN_NW4, VS_ATTN_LP_SIMPLE, VS_LP_STORE32, VS_LP_MLP_UNFUSED, VS_LP_TAIL_UNFUSED, VS_LP_QKV_UNFUSED, VS_LP_EMBED_UNFUSED, VS_LP_TILE256,
+ * VS_EXACT_UNFUSED (exact fp32, d_model 256: the four stand-alone Linear kernels of a layer instead of the two fused ones; same bits)
+ * (+ VS_MLP_FUSION, VS_MLP_ABL, VS_ATTN_LEGACY, which only the diagnostic build of the library acts on).  Process-wide; not meant to be flipped while forwards are in flight. */
 int vs_set_option(const char *name, int32_t value);
 
 /* Per-kernel entry points (same stream/pointer conventions), exported so each HIP kernel can be

@@ -24,7 +24,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
     acc = collections.defaultdict(list)
     for r in csv.DictReader(open(f)):
         if r["Counter_Name"] == c:
-            name = r["Kernel_Name"].replace("void (anonymous namespace)::", "")
+            name = r["Kernel_Name"].replace("void (anonymous namespace)::", "").replace("(anonymous namespace)::", "")
             acc[name.split("(")[0]].append(float(r["Counter_Value"]))
     for k, v in acc.items():
         out[k][c + "_KiB_avg"] = sum(v) / len(v)

@@ -12,7 +12,7 @@ import csv, collections, glob
 f=glob.glob('$D/*/*counter_collection.csv')[0]
 per=collections.OrderedDict()
 for r in csv.DictReader(open(f)):
-    per.setdefault(r['Dispatch_Id'],{'name':r['Kernel_Name'].replace('void (anonymous namespace)::','').split('(')[0],'t0':int(r['Start_Timestamp']),'t1':int(r['End_Timestamp'])})[r['Counter_Name']]=float(r['Counter_Value'])
+    per.setdefault(r['Dispatch_Id'],{'name':r['Kernel_Name'].replace('void (anonymous namespace)::','').replace('(anonymous namespace)::','').split('(')[0],'t0':int(r['Start_Timestamp']),'t1':int(r['End_Timestamp'])})[r['Counter_Name']]=float(r['Counter_Value'])
 agg=collections.defaultdict(list)
 for v in per.values():
     if v.get('SQ_VALU_MFMA_BUSY_CYCLES',0)>0:

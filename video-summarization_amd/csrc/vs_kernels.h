@@ -47,6 +47,15 @@ int vsk_linear_res_ln(const float *A, const float *W, const float *Wf, const flo
                       const float *gamma, const float *beta, float *out, int M, int N, int K,
                       const float *score_w, const float *score_b, int num_classes, int sigmoid,
                       float *scores, int bf16, hipStream_t st);
+// Exact fp32, d_model 256, M above the skinny threshold: vsk_linear_res_ln followed, in the same kernel and from registers, by
+// the next Linear - bit-identical to the two stand-alone kernels (-1: shape outside these kernels).
+//   vsk_outproj_ln_fc1: h1 = LN(att * Wo^T + bo + res), hidden [M, 4d] = relu(h1 * W1^T + b1)
+//   vsk_fc2_ln_qkv:     out = LN(hidden * W2^T + b2 + res), qkv = out * Wqkv^T + bqkv as vsk_qkv writes it (M = B * T)
+bool vsk_layer_fused_supported(int M, int d);
+int vsk_outproj_ln_fc1(const float *att, const float *Wo, const float *bo, const float *res, const float *gamma, const float *beta,
+                       float *h1, const float *W1, const float *b1, float *hidden, int M, int d, hipStream_t st);
+int vsk_fc2_ln_qkv(const float *hidden, const float *W2, const float *b2, const float *res, const float *gamma, const float *beta,
+                   float *out, const float *Wqkv, const float *bqkv, float *qkv, int B, int T, int d, int H, hipStream_t st);
 // out = LayerNorm(a + res) * gamma + beta (+ score head): the row pass behind a plain GEMM for d_model > 256
 int vsk_rows_res_ln(const float *a, const float *res, const float *gamma, const float *beta, float *out, int M, int d,
                     const float *score_w, const float *score_b, int num_classes, int sigmoid, float *scores,
@@ -145,6 +154,7 @@ struct VskOptions {
     int lp_qkv_unfused;   // VS_LP_QKV_UNFUSED  bf16 mode runs every layer's QKV projection as its own kernel (A/B)
     int lp_tile256;       // VS_LP_TILE256     the fused bf16 layer kernels always use 256-row tiles / 8-wave blocks (A/B)
     int lp_embed_unfused; // VS_LP_EMBED_UNFUSED bf16 mode runs the embedding as the generic GEMM + the first QKV kernel (A/B)
+    int exact_unfused;    // VS_EXACT_UNFUSED  exact fp32, d_model 256: out-projection + norm1, fc1, fc2 + norm2 and QKV as four kernels (A/B, bit-identity tests)
     int mlp_fusion;       // VS_MLP_FUSION    (diagnostic builds only)
     int mlp_abl;          // VS_MLP_ABL       (diagnostic builds only)
     int attn_w64_checked; // VS_ATTN_W64_CHECKED the one-wave-per-SIMD attention skips its optimistic pass (every tile checked; A/B and test pin)

@@ -678,17 +678,35 @@ __global__ __launch_bounds__(256) void gemm_res_ln(
 // ------------------------------------------------------------------------------------------
 // A16 (PREC 1 only): A lives in HBM as bf16 (written so by the bf16 attention / the C16 fc1 epilogue)
 // DIAG (tools/diag_gemm.py only, PREC 0): per-wave stamps - barrier wait, tile prologue, epilogue (layout: gemm_nt_128's)
-template <int NT, int PREC = 0, int A16 = 0, int DIAG = 0>     // PREC 1: bf16 MFMA operands (see gemm_nt_128), LDS rows of 16 bf16 padded to 48 B; 2: f16 hi|lo rows (80 B)
-__global__ __launch_bounds__(256, 2) void gemm_ln_rows(
+// TAIL (exact fp32, d_model 256 only): a second, REGISTER-FED product behind the LayerNorm epilogue.  The epilogue leaves the
+// wave's 32 normalised rows in acc[8] - lane (r,h): row r, columns 32j + 8q + 4h + e - which is the B-operand fragment layout
+// of the next product with the k pairing {8g + s, 8g + 4 + s} of the tiled kernels.  So the rows just written are multiplied by
+// the next Linear's weight without being staged again: only the weight streams through LDS (128 output columns x 32 k per
+// step, double-buffered in the staging area the k-loop has left idle), the accumulators of one 128-column chunk (64 registers)
+// sit beside the rows (128), and each chunk leaves through the wave's transposition corner as full 128-byte lines.
+//   TAIL 1: C2 = relu(rows * W2^T + b2), [M, 1024] row-major              (the MLP's fc1 behind out-projection + norm1)
+//   TAIL 2: q / k / v = rows * W2^T + b2, head-major planes [B, H, T, dh]   (the next layer's QKV behind fc2 + norm2)
+// Per output the accumulator starts at the bias x ones MFMA and takes its k in ascending order, as in gemm_nt_128: same bits.
+struct LnTail {
+    const float *W2, *b2;       // [N2, 256], [N2]
+    float *C2;
+    int T, H, dhs;              // TAIL 2: frames per video, heads, log2 of the head dim (256 / H: a power of two)
+};
+
+template <int NT, int PREC, int A16, int DIAG, int TAIL>
+__device__ __forceinline__ void ln_rows_tiles(
     const float *__restrict__ A, const float *__restrict__ W, const float *__restrict__ bias,
     const float *__restrict__ res, const float *__restrict__ gamma, const float *__restrict__ beta,
     float *__restrict__ out, int M, int K,
     const float *__restrict__ score_w, const float *__restrict__ score_b, int num_classes,
-    int sigmoid, float *__restrict__ scores, unsigned long long *__restrict__ diag = nullptr) {
+    int sigmoid, float *__restrict__ scores, unsigned long long *__restrict__ diag, const LnTail tl) {
+    static_assert(TAIL == 0 || (NT == 8 && PREC == 0 && DIAG == 0), "the register-fed tail exists for exact fp32 at d_model 256");
     constexpr int BM = 128, N = 32 * NT, BK = 16, LD = BK + 4;
     constexpr int WL = (N * BK / 4 + 255) / 256;       // float4 of W per thread per k-tile (N=256: 4)
-    __shared__ __attribute__((aligned(16))) float smem[2 * (BM + N) * LD + 4 * N];
+    constexpr int TN2 = TAIL == 2 ? 3 * N : 4 * N;      // TAIL: output columns of the second product
+    __shared__ __attribute__((aligned(16))) float smem[2 * (BM + N) * LD + 4 * N + (TAIL != 0 ? TN2 : 0)];
     float *gam_s = smem + 2 * (BM + N) * LD, *bet_s = gam_s + N, *sw_s = bet_s + N, *bias_s = sw_s + N;
+    float *bias2_s = bias_s + N;                        // TAIL: the second product's bias
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -697,6 +715,8 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
 
     constexpr float SC = PREC == 2 ? F16X3_WS : 1.0f;      // scale of the accumulators (see F16X3_WS)
     for (int i = tid; i < N; i += 256) { gam_s[i] = gamma[i]; bet_s[i] = beta[i]; bias_s[i] = bias[i] * SC; }
+    if constexpr (TAIL != 0)
+        for (int i = tid; i < TN2; i += 256) bias2_s[i] = tl.b2[i];
 
     // staging map: A 128 rows x 4 float4 (2 per thread), W N rows x 4 float4 (WL per thread)
     const int lrow = tid >> 2, lc4 = (tid & 3) * 4;
@@ -765,6 +785,62 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
     };
 
     f32x16 acc[NT];
+
+    // ---- TAIL: the weight tiles of the register-fed product.  Step (c, kt) consumes W2 rows 128c .. 128c + 127, k 32kt .. 32kt + 31
+    // from LDS buffer kt & 1: [128][36] floats (conflict-free b128 fragment reads, as gemm_nt_128), 4 float4 per thread.  The two
+    // buffers lie behind the four transposition corners of the epilogues, inside the k-loop's staging area. ----
+    constexpr int TCH = 128, TNC = TN2 / TCH, TWB = 4 * 32 * 36, TBUF = TCH * 36;
+    static_assert(TAIL == 0 || TWB + 2 * TBUF <= 2 * (BM + N) * LD, "corners and weight tiles fit the staging area");
+    const int r2 = tid >> 3, c2 = (tid & 7) * 4;           // staging map of a weight tile: rows r2 + 32i
+    const __amdgpu_buffer_rsrc_t wrs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(tl.W2), 0, TN2 * N * 4, 0x00020000);
+    const int woff2 = (r2 * N + c2) * 4;
+    f32x4 pw2[4];
+    f32x16 U[4];
+    auto tail_soff = [&](int c, int kt) __attribute__((always_inline)) { return (TCH * c * N + 32 * kt) * 4; };
+    auto tail_load = [&](int i, int soff) __attribute__((always_inline)) {
+        pw2[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs2, woff2, soff + 32 * i * N * 4, 0));
+    };
+    auto tail_stage = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *(f32x4 *)&smem[TWB + buf * TBUF + (r2 + 32 * i) * 36 + c2] = pw2[i];
+    };
+    auto bias_mfma = [&](int c) __attribute__((always_inline)) {       // accumulators start at the bias: A[n = r][k = h] x ones, C = 0
+        const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const float bv = bias2_s[TCH * c + 32 * jj + r];
+            U[jj] = MFMA32(h == 0 ? bv : 0.f, 1.0f, zero);
+        }
+    };
+    // One step = 16 groups t = (g, jj) of 4 MFMAs: the 8-k group g of acc[kt] into the chunk's column tile jj.  The schedule is
+    // the k-loop's: weight fragments through a ring of three, the read of group t + 2 pinned behind the first MFMA of group t;
+    // the next step's four global loads in the first groups, their LDS writes in the last ones; one barrier per step.
+    auto tail_step = [&](auto ktc, int nsoff) __attribute__((always_inline)) {
+        constexpr int kt = decltype(ktc)::value;
+        const float *wp = smem + TWB + (kt & 1) * TBUF + r * 36 + 4 * h;
+        float *wd = smem + TWB + ((kt + 1) & 1) * TBUF + r2 * 36 + c2;
+        f32x4 fw[3];
+        fw[0] = *(const f32x4 *)wp;
+        fw[1] = *(const f32x4 *)(wp + 32 * 36);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const int g = t / 4, jj = t % 4;
+            if (t + 2 < 16) fw[(t + 2) % 3] = *(const f32x4 *)(wp + 32 * ((t + 2) % 4) * 36 + 8 * ((t + 2) / 4));
+            if (t < 4) tail_load(t, nsoff);
+            if (t >= 12) *(f32x4 *)(wd + 32 * (t - 12) * 36) = pw2[t - 12];
+#pragma unroll
+            for (int s2 = 0; s2 < 4; ++s2) U[jj] = MFMA32(fw[t % 3][s2], acc[kt][4 * g + s2], U[jj]);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (t + 2 < 16) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // the fragment of group t + 2
+            if (t < 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);           // this group's VMEM read
+            __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+            if (t >= 12) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);         // this group's DS write
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();
+    };
+
     unsigned long long dsum[3] = {0, 0, 0}, tbegin = 0, tq = 0, ktiles = 0;
     if constexpr (DIAG != 0) tbegin = stamp();
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -909,6 +985,10 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
                 __syncthreads();
         }
         if constexpr (DIAG != 0) tq = stamp();
+        if constexpr (TAIL != 0) {          // the tail's first weight tile: in flight under the LayerNorm epilogue
+#pragma unroll
+            for (int i = 0; i < 4; ++i) tail_load(i, tail_soff(0, 0));
+        }
 
         // ---- epilogue: LayerNorm over the row (lane-local + one lane^32 exchange), 16-byte stores ----
         // (reduction order shared with skinny_ln: per 32-column block, blocks ascending, partner last)
@@ -984,6 +1064,65 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
             }
         }
         if constexpr (DIAG != 0) dsum[1] += stamp() - tq;       // dsum[1]: epilogue
+        if constexpr (TAIL != 0) {
+            // ---- the register-fed product: NC chunks of 128 output columns, 8 steps (k-tiles of 32 = one acc[kt]) each ----
+            tail_stage(0);                      // step 0's weight tile: loaded ahead of the LayerNorm epilogue
+            int rowoff[4];                      // this lane's four store rows (read-back map of the transposition corner)
+            __amdgpu_buffer_rsrc_t crs;
+            if constexpr (TAIL == 1) {          // rows past M lie beyond the descriptor's end: their stores are dropped
+                crs = __builtin_amdgcn_make_buffer_rsrc(tl.C2 + (size_t)m0 * TN2, 0, (M - m0 < BM ? M - m0 : BM) * TN2 * 4, 0x00020000);
+#pragma unroll
+                for (int p = 0; p < 4; ++p) rowoff[p] = ((32 * wave + trow + 8 * p) * TN2 + tc4) * 4;
+            } else {
+                crs = __builtin_amdgcn_make_buffer_rsrc(tl.C2, 0, 0, 0x00020000);
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const int orow = m0 + 32 * wave + trow + 8 * p;
+                    const int bb = orow / tl.T, tt = orow - bb * tl.T;
+                    rowoff[p] = orow < M ? (((bb * tl.H * tl.T + tt) << tl.dhs) + tc4) * 4 : (int)0x80000000;
+                }
+            }
+            bias_mfma(0);
+            __syncthreads();
+            for (int c = 0; c < TNC; ++c) {
+                const int cn = c + 1 < TNC ? c + 1 : c;                 // after the last chunk: a harmless reload
+                static_for<8>([&](auto ktc) __attribute__((always_inline)) {
+                    constexpr int kt = decltype(ktc)::value;
+                    tail_step(ktc, kt < 7 ? tail_soff(c, kt + 1) : tail_soff(cn, 0));
+                });
+                if constexpr (TAIL == 2) {
+                    const int which = c >> 1;                           // 128-column chunks never straddle q / k / v (d_model 256)
+                    crs = __builtin_amdgcn_make_buffer_rsrc(tl.C2 + (size_t)which * M * N, 0, M * N * 4, 0x00020000);
+                }
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    // one 32-column block at a time through the corner: its four read-backs have returned (their stores wait for
+                    // them) before the next block's writes are issued - the scheduler may not pull those writes up behind the
+                    // last read-back (seen wrong on the GPU: rows of the last read-back, when a co-resident block loaded the LDS)
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        f32x4 v;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = TAIL == 1 ? relu1(U[jj][4 * q + e]) : U[jj][4 * q + e];
+                        *(f32x4 *)&tp[r * 36 + 8 * q + 4 * h] = v;
+                    }
+                    int soff;
+                    if constexpr (TAIL == 1) soff = (TCH * c + 32 * jj) * 4;
+                    else {                                              // a 32-column block never straddles a head
+                        const int cc = (TCH * c + 32 * jj) & (N - 1), head = cc >> tl.dhs, e0 = cc - (head << tl.dhs);
+                        soff = (((head * tl.T) << tl.dhs) + e0) * 4;
+                    }
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const f32x4 v = *(const f32x4 *)&tp[(trow + 8 * p) * 36 + tc4];
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), crs, rowoff[p], soff, 0);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                bias_mfma(cn);
+            }
+        }
     }
     if constexpr (DIAG != 0) {
         if (diag != nullptr && lane == 0) {
@@ -992,6 +1131,36 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
             o[5] = stamp() - tbegin; o[6] = ktiles; o[7] = tbegin;
         }
     }
+}
+
+template <int NT, int PREC = 0, int A16 = 0, int DIAG = 0>     // PREC 1: bf16 MFMA operands (see gemm_nt_128), LDS rows of 16 bf16 padded to 48 B; 2: f16 hi|lo rows (80 B)
+__global__ __launch_bounds__(256, 2) void gemm_ln_rows(
+    const float *__restrict__ A, const float *__restrict__ W, const float *__restrict__ bias,
+    const float *__restrict__ res, const float *__restrict__ gamma, const float *__restrict__ beta,
+    float *__restrict__ out, int M, int K,
+    const float *__restrict__ score_w, const float *__restrict__ score_b, int num_classes,
+    int sigmoid, float *__restrict__ scores, unsigned long long *__restrict__ diag = nullptr) {
+    ln_rows_tiles<NT, PREC, A16, DIAG, 0>(A, W, bias, res, gamma, beta, out, M, K, score_w, score_b, num_classes, sigmoid, scores, diag,
+                                          LnTail{nullptr, nullptr, nullptr, 0, 0, 0});
+}
+
+// The exact-fp32 layer kernels of d_model 256: a gemm_ln_rows<8, 0> tile each, then the tail.
+//   layer_outproj_ln_fc1: h1 = LN1(att * Wo^T + bo + h0), hidden = relu(h1 * W1^T + b1)
+//   layer_fc2_ln_qkv:     h0' = LN2(hidden * W2^T + b2 + h1), q / k / v of the NEXT layer = h0' * Wqkv^T + bqkv
+__global__ __launch_bounds__(256, 2) void layer_outproj_ln_fc1(
+    const float *__restrict__ A, const float *__restrict__ W, const float *__restrict__ bias,
+    const float *__restrict__ res, const float *__restrict__ gamma, const float *__restrict__ beta,
+    float *__restrict__ out, int M, int K, const float *__restrict__ W1, const float *__restrict__ b1, float *__restrict__ hidden) {
+    ln_rows_tiles<8, 0, 0, 0, 1>(A, W, bias, res, gamma, beta, out, M, K, nullptr, nullptr, 0, 0, nullptr, nullptr,
+                                 LnTail{W1, b1, hidden, 0, 0, 0});
+}
+__global__ __launch_bounds__(256, 2) void layer_fc2_ln_qkv(
+    const float *__restrict__ A, const float *__restrict__ W, const float *__restrict__ bias,
+    const float *__restrict__ res, const float *__restrict__ gamma, const float *__restrict__ beta,
+    float *__restrict__ out, int M, int K, const float *__restrict__ Wqkv, const float *__restrict__ bqkv, float *__restrict__ qkv,
+    int T, int H, int dhs) {
+    ln_rows_tiles<8, 0, 0, 0, 2>(A, W, bias, res, gamma, beta, out, M, K, nullptr, nullptr, 0, 0, nullptr, nullptr,
+                                 LnTail{Wqkv, bqkv, qkv, T, H, dhs});
 }
 
 #ifdef VS_WITH_DIAG      // negative result kept for tools/ only: not in the product library
@@ -2410,6 +2579,35 @@ int vsk_linear_res_ln(const float *A, const float *W, const float *Wf, const flo
         default: return -1;
     }
 #undef VSK_LN_CASE
+    VSK_CHECK_LAUNCH();
+    return 0;
+}
+
+// Exact fp32, d_model 256, throughput batches: the two layer kernels with a register-fed second product (LnTail).
+// Their byte offsets into q / k / v are 32-bit: up to 2^20 rows (the caller keeps the stand-alone kernels beyond).
+bool vsk_layer_fused_supported(int M, int d) { return d == 256 && M > skinny_max_rows() && M <= (1 << 20); }
+
+int vsk_outproj_ln_fc1(const float *att, const float *Wo, const float *bo, const float *res, const float *gamma, const float *beta,
+                       float *h1, const float *W1, const float *b1, float *hidden, int M, int d, hipStream_t st) {
+    if (!vsk_layer_fused_supported(M, d)) return -1;
+    int blocks = persistent_blocks((M + 127) / 128);
+    if (blocks < 0) return (int)hipErrorInvalidDevice;
+    if (blocks > (M + 127) / 128) blocks = (M + 127) / 128;
+    hipLaunchKernelGGL(layer_outproj_ln_fc1, dim3(blocks), dim3(256), 0, st, att, Wo, bo, res, gamma, beta, h1, M, d, W1, b1, hidden);
+    VSK_CHECK_LAUNCH();
+    return 0;
+}
+
+int vsk_fc2_ln_qkv(const float *hidden, const float *W2, const float *b2, const float *res, const float *gamma, const float *beta,
+                   float *out, const float *Wqkv, const float *bqkv, float *qkv, int B, int T, int d, int H, hipStream_t st) {
+    const int M = B * T;
+    if (!vsk_layer_fused_supported(M, d) || H <= 0 || d % H || (d / H) % 32) return -1;      // a 32-column block within one head
+    int dhs = 5;                        // head dim 32, 64, 128 or 256
+    while ((1 << dhs) < d / H) ++dhs;
+    int blocks = persistent_blocks((M + 127) / 128);
+    if (blocks < 0) return (int)hipErrorInvalidDevice;
+    if (blocks > (M + 127) / 128) blocks = (M + 127) / 128;
+    hipLaunchKernelGGL(layer_fc2_ln_qkv, dim3(blocks), dim3(256), 0, st, hidden, W2, b2, res, gamma, beta, out, M, 4 * d, Wqkv, bqkv, qkv, T, H, dhs);
     VSK_CHECK_LAUNCH();
     return 0;
 }

@@ -116,6 +116,7 @@ const OptionName kOptions[] = {
     {"VS_GEMM_NWM2", &VskOptions::gemm_nwm2, 0},         {"VS_GEMM_NJ2", &VskOptions::gemm_nj2, 0},
     {"VS_ATTN_NW4", &VskOptions::attn_nw4, 0},           {"VS_ATTN_LP_SIMPLE", &VskOptions::attn_lp_simple, 0},
     {"VS_MLP_FUSION", &VskOptions::mlp_fusion, 0},       {"VS_MLP_ABL", &VskOptions::mlp_abl, 0},
+    {"VS_EXACT_UNFUSED", &VskOptions::exact_unfused, 0},
     {"VS_ATTN_LEGACY", &VskOptions::attn_legacy, 0},     {"VS_LP_STORE32", &VskOptions::lp_store32, 0},
     {"VS_LP_MLP_UNFUSED", &VskOptions::lp_mlp_unfused, 0}, {"VS_LP_TAIL_UNFUSED", &VskOptions::lp_tail_unfused, 0},
     {"VS_LP_QKV_UNFUSED", &VskOptions::lp_qkv_unfused, 0}, {"VS_LP_EMBED_UNFUSED", &VskOptions::lp_embed_unfused, 0},
@@ -481,6 +482,11 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
     // bf16 mode with bf16 q/k/v: every layer's tail kernel also projects its output rows to the NEXT layer's q/k/v, and
     // the embedding kernel to the first layer's
     const bool qkv_fused = mlp16 && qkv16 && !vsk_options().lp_qkv_unfused;
+    // exact fp32, d_model 256, throughput batches: out-projection + norm1 carries fc1, and fc2 + norm2 the NEXT layer's QKV, each
+    // fed from the registers that hold the rows it has just normalised (vs_kernels.hip: LnTail) - bit-identical to the four
+    // stand-alone kernels, which VS_EXACT_UNFUSED=1 brings back.  The first layer's QKV stays vsk_qkv.
+    const bool exact_fused = lbf == 0 && aprec == 0 && !embedded && !splitk && !opt.exact_unfused && vsk_layer_fused_supported(M, d) &&
+                             d % H == 0 && (d / H) % 32 == 0;
     bool have_qkv = false;                  // q/k/v of the layer about to run were written by the kernel before it
     const float *pe_rows = pk ? pk->pe_rows : (w->has_pe ? w->p(w->pe) : nullptr);
     // Embedding + positional table (simnet.py:211, 237-238)
@@ -592,6 +598,24 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
             continue;
         }
         have_qkv = false;
+        if (exact_fused) {
+            {   // recorded under fc1 / fc2: the stage table has no out-projection row then, and these two rows' FLOPs omit the
+                // out-projection and QKV shares (their TFLOP/s are understated, never overstated)
+                StageScope ps(VS_STAGE_FC1, st);
+                VS_LAUNCH(vsk_outproj_ln_fc1(att, w->p(P.wo), w->p(P.bo), h0, w->p(P.ln1g), w->p(P.ln1b), h1, w->p(P.w1), w->p(P.b1), ffn, M, d, st));
+            }
+            StageScope ps(VS_STAGE_FC2_LN, st);
+            if (last) {
+                VS_LAUNCH(vsk_linear_res_ln(ffn, w->p(P.w2), w->p(P.f_w2), w->p(P.b2), h1, w->p(P.ln2g), w->p(P.ln2b), dst, M, d, 4 * d,
+                                            w->p(w->final_w), w->p(w->final_b), D.num_classes, sig, scores, 0, st));
+            } else {
+                const LayerOff &N = w->layers[l + 1];
+                VS_LAUNCH(vsk_fc2_ln_qkv(ffn, w->p(P.w2), w->p(P.b2), h1, w->p(P.ln2g), w->p(P.ln2b), dst, w->p(N.wqkv), w->p(N.bqkv), qkv,
+                                         B, T, d, H, st));
+                have_qkv = true;
+            }
+            continue;
+        }
         // d_model > 256: plain GEMM + the row LayerNorm pass (faster than the fused wide kernel at every M; the
         // GEMM's output goes to a region of the workspace that is free at that point: q after the attention, att after fc1)
         const bool split_ln = d > 256 || embedded;      // (an embedded model's LayerNorm width is not d: the row pass knows it)
