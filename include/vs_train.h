@@ -181,6 +181,36 @@ int vs_pretrain_head_backward(const float *hidden, const float *logits, const ui
                               float *d_hidden, float *d_logits, float *d_vt_w, float *d_vt_b, void *workspace,
                               size_t workspace_bytes, void *stream);
 
+/* The same head on a PACKED ragged batch (the loss head of vs_train_forward_packed's outputs): hidden [Mtot,d] and logits
+ * [Mtot] hold the frames of B videos concatenated (video b = rows sum(lengths[:b]) ..., Mtot = sum(lengths)); there is no key
+ * mask and no padded row - video_transform, its wgrad and dgrad and every row pass run over Mtot rows.  Per video, over its
+ * own T_b frames: w = softmax_t(logits_t / temp); centering = (1 / ref_len) sum_t (w_t + 1e-9) log(w_t + 1e-9) (entropy) or
+ * ||w||_2 (norm); repelling = (||sum_t x^_t||^2 - sum_t ||x^_t||^2) / ref_len^2; pooled = sum_t w_t f_t; distillation as
+ * above.  ref_len >= max(lengths) is the width the reference would have padded the batch to: its mean over frames and its
+ * [T,T] mean divide by that width, masked frames counting as 0, so with ref_len = max(lengths) the three losses and every
+ * gradient are those of vs_pretrain_head_forward / _backward on the padded batch of the same videos.  With ref_len fixed a
+ * video's terms do not depend on the batch it is packed in; the batch enters through the mean over B only.
+ *   feats [Mtot,F]; head_state >= vs_pretrain_head_state_bytes_packed; workspace >= vs_pretrain_head_workspace_bytes_packed,
+ *   256-byte aligned.  d_hidden [Mtot,d], d_logits [Mtot].  Exact fp32.
+ * `lengths` is a HOST array (it sizes launches and scratch), `lengths_dev` the same values on the device: row offsets and the
+ * (video, 64-frame chunk) mapping are computed there, no host memory is read after the call returns.  lengths_dev that
+ * disagree with lengths cannot make a call write outside the buffers the host sized: a length is cut at max(lengths), rows
+ * beyond Mtot are cut (rows that no video covers are left unwritten).
+ * VS_ERR_INVALID (before any device access): NULL pointer, B <= 0, lengths[b] <= 0, ref_len < max(lengths), d % 32 != 0,
+ * F not in {256, 512, 768, 1024}, temp <= 0.  VS_ERR_WORKSPACE: short or unaligned workspace.  The byte counts are 0 on
+ * invalid input. */
+size_t vs_pretrain_head_state_bytes_packed(const int32_t *lengths, int32_t B, int32_t F);
+size_t vs_pretrain_head_workspace_bytes_packed(const int32_t *lengths, int32_t B, int32_t d, int32_t F);
+int vs_pretrain_head_forward_packed(const float *hidden, const float *logits, const int32_t *lengths, const int32_t *lengths_dev,
+                                    int32_t B, int32_t ref_len, const float *vid, const float *vt_w, const float *vt_b,
+                                    int32_t d, int32_t F, float temp, int32_t entropy_penalty, float *feats, void *head_state,
+                                    float *losses, void *stream);
+int vs_pretrain_head_backward_packed(const float *hidden, const float *logits, const int32_t *lengths, const int32_t *lengths_dev,
+                                     int32_t B, int32_t ref_len, const float *vid, const float *vt_w, const float *feats,
+                                     void *head_state, const float *d_losses, int32_t d, int32_t F, float temp,
+                                     int32_t entropy_penalty, float *d_hidden, float *d_logits, float *d_vt_w, float *d_vt_b,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* Per-kernel entry points for the parity tests (not needed by a binding). */
 
 /* softmax(q k^T * scale + keymask) with dropout p on the weights, times v; q,k,v head-major [B,H,T,dh]; out [B,T,H*dh];

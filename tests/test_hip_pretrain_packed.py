@@ -1,0 +1,405 @@
+"""GPU tests of PRETRAINING ON PACKED RAGGED BATCHES (include/vs_train.h: vs_pretrain_head_forward_packed / _backward_packed;
+pretrain._PretrainHeadPacked, PretrainModel.forward_packed, data.collate_fn_pretrain_packed, harness.pretrain_step_packed).
+
+Checkers: (1) the head's formulas restated per video in float64 torch, the [T,T] cosine matrix included; (2) float64 losses and
+gradients of the IMPORTED reference on the padded batch of the same videos (tests/golden/make_golden_pretrain_packed.py);
+(3) the padded step of the same module; (4) bit-equality of a video's gradient rows across batches; (5) guard bands around
+the buffers of a call whose device lengths disagree with the host's.
+
+Tolerances are those of tests/test_pretrain.py for the padded head and of tests/tolerances.py for the training path: nothing
+is added."""
+import ctypes as C
+import importlib
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN
+import tolerances as tol
+
+pytestmark = pytest.mark.gpu
+ATOL, RTOL = tol.TRAIN_GRAD_ATOL, tol.TRAIN_GRAD_RTOL
+TEMP = 0.4
+
+
+def _dev():
+    assert torch.cuda.is_available(), "these tests need a HIP device"
+    return torch.device("cuda:0")
+
+
+def _i32(values):
+    return (C.c_int32 * len(values))(*values)
+
+
+def _head():
+    return importlib.import_module("video-summarization_amd.pretrain")._PretrainHeadPacked
+
+
+# ---------------------------------------------------------------------------------------------
+# 1. the head kernels against the formulas in float64
+# ---------------------------------------------------------------------------------------------
+def _head_reference(hidden, logits, vid, lengths, W, b, temp, pen, ref_len):
+    """The packed head's contract (include/vs_train.h) per video in float64 torch; the repelling term in the reference's
+    own form, the [T,T] cosine matrix without its diagonal (simnet_pretrain.py:56-69), summed and divided by ref_len^2."""
+    import torch.nn.functional as F
+    feats = F.linear(hidden, W, b)
+    main, center, repel = [], [], []
+    row = 0
+    for i, T in enumerate(lengths):
+        f, s = feats[row:row + T], logits[row:row + T].reshape(T)
+        row += T
+        x = f / (f.norm(dim=1, keepdim=True) + 1e-9)
+        sim = (x @ x.t()) * (torch.eye(T, dtype=x.dtype) == 0).to(x.dtype)
+        repel.append(sim.sum() / float(ref_len * ref_len))
+        w = F.softmax(s / temp, dim=0)
+        if pen == "entropy":
+            center.append(((w + 1e-9) * torch.log(w + 1e-9)).sum() / float(ref_len))
+        else:
+            center.append(torch.norm(w))
+        pooled = (w.unsqueeze(0) @ f).squeeze(0)
+        main.append((-F.softmax(vid[i], dim=0) * torch.log(F.softmax(pooled, dim=0))).mean())
+    return torch.stack(main).mean(), torch.stack(center).mean(), torch.stack(repel).mean()
+
+
+HEAD_LENGTHS = ([150, 65, 64, 1], [333], [64, 63], [129, 128, 127, 2, 1])      # across the 64-frame chunk on both sides; one-frame videos
+HEAD_CASES = [(ls, d, pen, 512, 0) for ls in HEAD_LENGTHS for d in (128, 256, 512) for pen in ("entropy", "norm")]
+HEAD_CASES += [([150, 65, 64, 1], 256, "entropy", 256, 0), ([64, 63], 128, "norm", 1024, 0),
+               ([129, 128, 127, 2, 1], 256, "entropy", 512, 37)]               # F = 256, F = 1024, ref_len = max(lengths) + 37
+_HEAD_WANT = {}
+
+
+def _case_id(c):
+    ls, d, pen, Fo, extra = c
+    return "T%s-d%d-%s-F%d%s" % ("_".join(map(str, ls)), d, pen, Fo, "-ref+%d" % extra if extra else "")
+
+
+def _head_want(c):
+    """float64 inputs, losses and gradients of a case: computed once, shared by the two GEMM settings, never modified"""
+    key = _case_id(c)
+    if key not in _HEAD_WANT:
+        ls, d, pen, Fo, extra = c
+        M = sum(ls)
+        g = torch.Generator().manual_seed(M * 7 + d + Fo)
+        hidden = torch.randn(M, d, generator=g, dtype=torch.float64)
+        logits = torch.randn(M, 1, generator=g, dtype=torch.float64)
+        vid = torch.randn(len(ls), Fo, generator=g, dtype=torch.float64)
+        W = torch.randn(Fo, d, generator=g, dtype=torch.float64) / d ** 0.5
+        bias = 0.1 * torch.randn(Fo, generator=g, dtype=torch.float64)
+        leaves = [t.clone().requires_grad_(True) for t in (hidden, logits, W, bias)]
+        want = _head_reference(leaves[0], leaves[1], vid, ls, leaves[2], leaves[3], TEMP, pen, max(ls) + extra)
+        (want[0] + 0.5 * want[1] + 1.0 * want[2]).backward()
+        _HEAD_WANT[key] = ((hidden, logits, W, bias), vid, [w.item() for w in want], [t.grad for t in leaves])
+    return _HEAD_WANT[key]
+
+
+def _run_head_case(c):
+    ls, d, pen, Fo, extra = c
+    inputs, vid, want, want_grads = _head_want(c)
+    dl = [t.detach().float().to(_dev()).requires_grad_(True) for t in inputs]
+    got = _head().apply(dl[0], dl[1], vid.float().to(_dev()), ls, max(ls) + extra, dl[2], dl[3], TEMP, pen == "entropy")
+    (got[0] + 0.5 * got[1] + 1.0 * got[2]).backward()
+    torch.cuda.synchronize()
+    for i, name in enumerate(("distillation", "centering", "repelling")):
+        print("%s %s: %.9f (float64 %.9f)" % (_case_id(c), name, got[i].item(), want[i]))
+        assert abs(got[i].item() - want[i]) < 2e-6 * max(1.0, abs(want[i])), (name, got[i].item(), want[i])
+    for a, r, name in zip(dl, want_grads, ("d_hidden", "d_logits", "d_weight", "d_bias")):
+        assert a.grad is not None and a.grad.shape == r.shape and torch.isfinite(a.grad).all(), name
+        err = (a.grad.double().cpu() - r).abs().max().item()
+        scale = r.abs().max().item()
+        print("%s %s: err %.3e, max %.3e" % (_case_id(c), name, err, scale))
+        assert err <= 2e-5 * scale + 1e-9, "%s: err %.3e, max %.3e" % (name, err, scale)
+
+
+@pytest.fixture
+def tiled_gemms(vsa):
+    """VS_SKINNY_ROWS=0 pins the LDS-tiled GEMMs (video_transform's forward, dgrad and wgrad) that batches above the skinny
+    threshold take; these small batches get the latency kernels by default."""
+    vsa._lib.set_option("VS_SKINNY_ROWS", 0)
+    yield
+    vsa._lib.set_option("VS_SKINNY_ROWS", -1)
+
+
+@pytest.mark.parametrize("case", HEAD_CASES, ids=_case_id)
+def test_packed_head_kernels_match_float64_formulas(vsa, case):
+    """_PretrainHeadPacked (video_transform + repel + pooling + penalties + soft CE, forward and backward) against the
+    per-video formulas in float64, for the weighted sum of the three losses (pretrain.py:62); test_pretrain.py's bars."""
+    _run_head_case(case)
+
+
+@pytest.mark.parametrize("case", HEAD_CASES, ids=_case_id)
+def test_packed_head_kernels_on_tiled_gemms(vsa, case, tiled_gemms):
+    _run_head_case(case)
+
+
+# ---------------------------------------------------------------------------------------------
+# 2. the whole step against the imported reference (float64)
+# ---------------------------------------------------------------------------------------------
+def golden_cases():
+    with open(os.path.join(GOLDEN, "pretrain_packed_index.json")) as f:
+        return json.load(f)["cases"]
+
+
+def _golden_model(vsa, c):
+    m = vsa.PretrainModel(feature_dim=c["d"], num_heads=c["H"], num_layers=c["L"], dropout=0.3).eval()
+    m.encoder.load_state_dict(vsa.synth.make_state_dict(c["d"], c["L"], c["wseed"]), strict=True)
+    rng = np.random.Generator(np.random.PCG64(c["wseed"] + 1))                 # make_golden_pretrain_packed.head_weights
+    w = torch.from_numpy((rng.standard_normal((512, c["d"])) / np.sqrt(c["d"])).astype(np.float32))
+    b = torch.from_numpy((rng.standard_normal(512) * 0.1).astype(np.float32))
+    with torch.no_grad():
+        m.video_transform.weight.copy_(w)
+        m.video_transform.bias.copy_(b)
+    return m.to(_dev())
+
+
+def _golden_inputs(vsa, c):
+    """(padded x, mask, vid) - the recipe of make_golden_pretrain_packed.build_inputs"""
+    lengths = c["lengths"]
+    x = vsa.synth.make_features(len(lengths), max(lengths), c["xseed"], c["kind"], lengths)
+    mask = vsa.synth.padding_mask(x)
+    rng = np.random.Generator(np.random.PCG64(c["xseed"] + 100))
+    vid = torch.from_numpy(rng.standard_normal((len(lengths), 512)).astype(np.float32))
+    return x, mask, vid
+
+
+def _packed_step(m, c, x, mask, vid):
+    m.zero_grad(set_to_none=True)
+    xd = x[~mask].to(_dev()).requires_grad_(True)
+    main, center, repel = m.forward_packed(xd, vid.to(_dev()), c["lengths"], pen_met=c["pen"])
+    (main + 0.5 * center + 1. * repel).backward()
+    torch.cuda.synchronize()
+    grads = {"x": xd.grad}
+    grads.update({k: p.grad for k, p in m.named_parameters()})
+    return torch.stack([main, center, repel]).detach().double().cpu(), grads
+
+
+def _check_grads(z, grads, name, factor=1.0, want_grads=None):
+    """the checks of test_hip_train_packed._check_exact; want_grads: compare against these tensors instead of the golden rows"""
+    keys = json.loads(str(z["keys"]))
+    assert sorted(keys) == sorted(grads.keys())
+    worst = 0.0
+    for k in keys:
+        g = grads[k]
+        assert g is not None and torch.isfinite(g).all(), k
+        tot, nrm, gmax, ref32 = z["s:" + k]
+        if want_grads is None:
+            g2 = g.reshape(-1, g.shape[-1]) if g.dim() > 1 else g.reshape(1, -1)
+            rows = torch.from_numpy(z["r:" + k])
+            got, want = g2[rows.to(g2.device)].double().cpu(), torch.from_numpy(z["g:" + k]).double()
+            want_norm = nrm
+        else:
+            got, want = g.double().cpu(), want_grads[k].double().cpu()
+            want_norm = want.norm().item()
+        err = (got - want).abs().max().item()
+        print("%s %s: err %.3e, max|g| %.3e, norm %.6e (want %.6e; reference fp32 own err %.3e)" % (
+            name, k, err, gmax, g.double().norm().item(), want_norm, ref32))
+        assert err <= factor * ATOL and err <= factor * (RTOL * gmax + 1e-6), "%s: err %.3e, max|g| %.3e (reference fp32 own err %.3e)" % (k, err, gmax, ref32)
+        assert abs(g.double().norm().item() - want_norm) <= factor * (1e-4 * nrm + 1e-7), k
+        if want_grads is None:
+            assert abs(g.double().sum().item() - tot) <= 1e-3 * max(abs(tot), nrm) + 0.25 * RTOL * gmax * g.numel() ** 0.5 + 1e-7, k
+        worst = max(worst, err / gmax if gmax > 1e-6 else 0.0)
+    print("%s: worst gradient error relative to the tensor's max: %.2e" % (name, worst))
+
+
+@pytest.mark.parametrize("case", golden_cases(), ids=lambda c: c["name"])
+def test_packed_pretrain_step_matches_reference_golden(vsa, case):
+    """The three losses, dx on the valid frames and every parameter gradient (encoder and video_transform) of
+    PretrainModel.forward_packed against the reference's float64 run on the PADDED batch of the same videos."""
+    c = case
+    z = np.load(os.path.join(GOLDEN, c["name"] + ".npz"))
+    m = _golden_model(vsa, c)
+    losses, grads = _packed_step(m, c, *_golden_inputs(vsa, c))
+    assert m.encoder.last_train_dtype == "fp32"
+    want = torch.from_numpy(z["losses"])
+    print("%s: losses %s (float64 %s)" % (c["name"], losses.tolist(), want.tolist()))
+    assert (losses - want).abs().max().item() < 5e-6, (losses, want)
+    _check_grads(z, grads, c["name"])
+
+
+# ---------------------------------------------------------------------------------------------
+# 3. packed equals padded on the GPU
+# ---------------------------------------------------------------------------------------------
+def test_packed_step_equals_the_padded_step_of_the_same_module(vsa):
+    """forward_packed against forward(x_padded, vid, mask) of the same module on the pretrain_packed_ma inputs: each side
+    has its own fp32 error against the same truth, hence twice the bars of the golden test."""
+    c = [k for k in golden_cases() if k["name"] == "pretrain_packed_ma"][0]
+    z = np.load(os.path.join(GOLDEN, c["name"] + ".npz"))
+    m = _golden_model(vsa, c)
+    x, mask, vid = _golden_inputs(vsa, c)
+    lp, gp = _packed_step(m, c, x, mask, vid)
+    m.zero_grad(set_to_none=True)
+    xd = x.to(_dev()).requires_grad_(True)
+    main, center, repel = m(xd, vid.to(_dev()), mask.to(_dev()), pen_met=c["pen"])
+    (main + 0.5 * center + 1. * repel).backward()
+    torch.cuda.synchronize()
+    lq = torch.stack([main, center, repel]).detach().double().cpu()
+    gq = {"x": xd.grad[~mask.to(_dev())]}
+    gq.update({k: p.grad for k, p in m.named_parameters()})
+    for a, b in zip(lp.tolist(), lq.tolist()):
+        print("packed %.9f padded %.9f" % (a, b))
+        assert abs(a - b) <= 4e-6 * max(1.0, abs(b)), (a, b)
+    _check_grads(z, gp, "packed vs padded", factor=2.0, want_grads=gq)
+
+
+# ---------------------------------------------------------------------------------------------
+# 4. a video does not depend on its batch
+# ---------------------------------------------------------------------------------------------
+def test_a_videos_gradient_rows_do_not_depend_on_its_batch_mates(vsa):
+    """ref_len pinned: video a packed alone (B = 1) and with b (B = 2).  Its d_hidden / d_logits rows differ by the 1 / B of
+    the batch mean alone - doubling the B = 2 rows is exact (a power of two), so they are bit-equal."""
+    Ta, Tb, d, Fo, ref_len = 97, 65, 256, 512, 128
+    g = torch.Generator().manual_seed(97065)
+    hidden, logits = torch.randn(Ta + Tb, d, generator=g), torch.randn(Ta + Tb, 1, generator=g)
+    vid = torch.randn(2, Fo, generator=g)
+    W, bias = torch.randn(Fo, d, generator=g) / d ** 0.5, 0.1 * torch.randn(Fo, generator=g)
+    up = torch.tensor([1.0, 0.5, 1.0], device=_dev())
+
+    def run(rows, lengths, nvid, pen):
+        h = hidden[:rows].to(_dev()).requires_grad_(True)
+        s = logits[:rows].to(_dev()).requires_grad_(True)
+        losses = _head().apply(h, s, vid[:nvid].to(_dev()), lengths, ref_len, W.to(_dev()), bias.to(_dev()), TEMP, pen == "entropy")
+        dh, ds = torch.autograd.grad(losses, [h, s], grad_outputs=up)
+        return dh[:Ta], ds[:Ta]
+
+    for pen in ("entropy", "norm"):
+        dh1, ds1 = run(Ta, [Ta], 1, pen)
+        dh2, ds2 = run(Ta + Tb, [Ta, Tb], 2, pen)
+        torch.cuda.synchronize()
+        assert dh1.abs().max().item() > 0 and ds1.abs().max().item() > 0
+        assert torch.equal(ds1, 2.0 * ds2), (pen, (ds1 - 2.0 * ds2).abs().max().item())
+        assert torch.equal(dh1, 2.0 * dh2), (pen, (dh1 - 2.0 * dh2).abs().max().item())
+
+
+# ---------------------------------------------------------------------------------------------
+# 5. device lengths that disagree with the host's
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dev_lengths", [[1000, 1000], [40, 500], [1000, 1]])
+def test_device_lengths_beyond_the_host_lengths_cannot_write_outside_the_buffers(vsa, dev_lengths):
+    """The contract of include/vs_train.h: a length is cut at max(lengths), rows beyond Mtot are cut.  feats and head_state
+    are followed by guard bands of known bytes, which the call leaves intact (whatever status it returns)."""
+    lib, L = vsa._lib.load(), vsa._lib
+    lengths, d, Fo, guard = [70, 40], 128, 512, 4096
+    B, M = len(lengths), sum(lengths)
+    dev = _dev()
+    g = torch.Generator().manual_seed(11)
+    hidden, logits = torch.randn(M, d, generator=g).to(dev), torch.randn(M, generator=g).to(dev)
+    vid, W, bias = torch.randn(B, Fo, generator=g).to(dev), (torch.randn(Fo, d, generator=g) / d ** 0.5).to(dev), torch.zeros(Fo, device=dev)
+    feats_bytes = M * Fo * 4
+    state_bytes = lib.vs_pretrain_head_state_bytes_packed(_i32(lengths), B, Fo)
+    assert state_bytes > 0
+    feats = torch.full((feats_bytes + guard,), 0xA5, dtype=torch.uint8, device=dev)
+    state = torch.full((state_bytes + guard,), 0xA5, dtype=torch.uint8, device=dev)
+    losses = torch.full((3 + 64,), 7.0, dtype=torch.float32, device=dev)
+    dlen = torch.tensor(dev_lengths, dtype=torch.int32, device=dev)
+    rc = lib.vs_pretrain_head_forward_packed(hidden.data_ptr(), logits.data_ptr(), _i32(lengths), dlen.data_ptr(), B, max(lengths),
+                                             vid.data_ptr(), W.data_ptr(), bias.data_ptr(), d, Fo, TEMP, 1, feats.data_ptr(),
+                                             state.data_ptr(), losses.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert rc in (L.VS_OK, L.VS_ERR_INVALID, L.VS_ERR_HIP), rc
+    assert bool((feats[feats_bytes:] == 0xA5).all()) and bool((state[state_bytes:] == 0xA5).all())
+    assert bool((losses[3:] == 7.0).all())
+    # the backward under the same lengths: d_logits, d_hidden and the workspace keep their guard bands too
+    ws_bytes = lib.vs_pretrain_head_workspace_bytes_packed(_i32(lengths), B, d, Fo)
+    ws = torch.full((ws_bytes + guard,), 0xA5, dtype=torch.uint8, device=dev)
+    d_hidden = torch.full((M * d + 64,), 7.0, dtype=torch.float32, device=dev)
+    d_logits = torch.full((M + 64,), 7.0, dtype=torch.float32, device=dev)
+    d_w, d_b = torch.empty(Fo, d, device=dev), torch.empty(Fo, device=dev)
+    up = torch.tensor([1.0, 0.5, 1.0], device=dev)
+    rc = lib.vs_pretrain_head_backward_packed(hidden.data_ptr(), logits.data_ptr(), _i32(lengths), dlen.data_ptr(), B, max(lengths),
+                                              vid.data_ptr(), W.data_ptr(), feats.data_ptr(), state.data_ptr(), up.data_ptr(), d, Fo,
+                                              TEMP, 1, d_hidden.data_ptr(), d_logits.data_ptr(), d_w.data_ptr(), d_b.data_ptr(),
+                                              ws.data_ptr(), ws_bytes, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert rc in (L.VS_OK, L.VS_ERR_INVALID, L.VS_ERR_HIP), rc
+    assert bool((ws[ws_bytes:] == 0xA5).all()) and bool((state[state_bytes:] == 0xA5).all())
+    assert bool((d_hidden[M * d:] == 7.0).all()) and bool((d_logits[M:] == 7.0).all())
+
+
+# ---------------------------------------------------------------------------------------------
+# 6. the loop
+# ---------------------------------------------------------------------------------------------
+class _CountingSchedule:
+    def __init__(self):
+        self.calls = 0
+
+    def update(self):
+        self.calls += 1
+        return 1e-4
+
+
+def _pretrain_loop(vsa, native):
+    from torch.utils.data import DataLoader
+    harness = importlib.import_module("video-summarization_amd.harness")
+    data = importlib.import_module("video-summarization_amd.data")
+    lengths = [90, 71, 60, 33]
+    torch.manual_seed(4321)
+    m = vsa.PretrainModel(num_heads=4, feature_dim=256, num_layers=2, sparsity=0.5, dropout=0.2, num_classes=1,
+                          use_pos=True).to(_dev())                              # pretrain.py:33-36 passes sparsity
+    m.encoder.load_state_dict(vsa.synth.make_state_dict(256, 2, 3))
+    if native:
+        opt = vsa.Adam(m.encoder.parameters(), lr=1e-4, weight_decay=5e-4).attach(m)
+    else:
+        opt = torch.optim.Adam(m.encoder.parameters(), lr=1e-4, weight_decay=5e-4)          # the ENCODER's parameters only (:40)
+    scaler = torch.amp.GradScaler("cuda")
+    sched = _CountingSchedule()
+    features = vsa.synth.make_features(4, 90, 8, "pool5", lengths)
+    vid_rep = torch.randn(4, 512, generator=torch.Generator().manual_seed(2))
+    videos = [(features[i, :t].clone(), vid_rep[i]) for i, t in enumerate(lengths)]
+    loader = DataLoader(videos, shuffle=False, num_workers=0, collate_fn=data.collate_fn_pretrain_packed, batch_size=4)
+    losses = [harness.pretrain_step_packed(m, opt, sched, scaler, loader, _dev()) for _ in range(10)]
+    assert m.training and m.video_transform.weight.grad is not None            # the head's own Linear gets gradients too
+    assert sched.calls == 10                                                    # one update() per step
+    return losses, [p.detach().clone() for p in m.parameters()]
+
+
+def test_pretrain_step_packed_like_the_reference_loop(vsa):
+    """pretrain.py:49-86 in shape on a packed 4-video loader: autocast, main + 0.5 center + repel, an unmodified GradScaler,
+    torch.optim.Adam on the encoder's parameters, schedular.update() per step.  The loss falls; two runs from one torch seed
+    are bit-identical in losses and parameters (dropout on: HIP encoder + HIP head, ordered reductions)."""
+    l1, p1 = _pretrain_loop(vsa, native=False)
+    l2, p2 = _pretrain_loop(vsa, native=False)
+    print("losses", l1)
+    assert all(math.isfinite(v) for v in l1) and min(l1[-3:]) < l1[0], l1
+    assert l1 == l2 and all(torch.equal(a, b) for a, b in zip(p1, p2))
+
+
+def test_pretrain_step_packed_with_the_native_adam(vsa):
+    l1, _ = _pretrain_loop(vsa, native=True)
+    print("losses", l1)
+    assert all(math.isfinite(v) for v in l1) and min(l1[-3:]) < l1[0], l1
+
+
+# ---------------------------------------------------------------------------------------------
+# 7. a bf16 encoder under the exact head
+# ---------------------------------------------------------------------------------------------
+@pytest.fixture
+def lp_train_everywhere(vsa):
+    vsa._lib.set_option("VS_TRAIN_LP_MIN_ROWS", 0)
+    yield
+    vsa._lib.set_option("VS_TRAIN_LP_MIN_ROWS", -1)
+
+
+def test_bf16_encoder_under_the_exact_head(vsa, lp_train_everywhere):
+    """set_train_dtype("bf16") on pretrain_packed_ma: the encoder's Linears run on the bf16 pipe, the head stays exact fp32.
+    Losses at TRAIN_LP_LOSS_RTOL; the gradients next to the head (video_transform, final_layer) at TRAIN_LP_GRAD_RTOL."""
+    c = [k for k in golden_cases() if k["name"] == "pretrain_packed_ma"][0]
+    z = np.load(os.path.join(GOLDEN, c["name"] + ".npz"))
+    m = _golden_model(vsa, c)
+    m.encoder.set_train_dtype("bf16")
+    losses, grads = _packed_step(m, c, *_golden_inputs(vsa, c))
+    assert m.encoder.last_train_dtype == "bf16"
+    for got, want in zip(losses.tolist(), z["losses"].tolist()):
+        print("bf16 encoder: loss %.9f (float64 %.9f)" % (got, want))
+        assert abs(got - want) <= tol.TRAIN_LP_LOSS_RTOL * max(1.0, abs(want)), (got, want)
+    for k in ("video_transform.weight", "video_transform.bias", "encoder.final_layer.weight", "encoder.final_layer.bias"):
+        g = grads[k]
+        assert g is not None and torch.isfinite(g).all(), k
+        g2 = g.reshape(-1, g.shape[-1]) if g.dim() > 1 else g.reshape(1, -1)
+        rows = torch.from_numpy(z["r:" + k])
+        gmax = z["s:" + k][2]
+        err = (g2[rows.to(g2.device)].double().cpu() - torch.from_numpy(z["g:" + k]).double()).abs().max().item()
+        print("bf16 encoder: %s err %.3e, max|g| %.3e" % (k, err, gmax))
+        assert err <= tol.TRAIN_LP_GRAD_RTOL * gmax + 1e-6, "%s: err %.3e, max|g| %.3e" % (k, err, gmax)

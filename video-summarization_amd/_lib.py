@@ -57,7 +57,10 @@ TRAIN_EXPORTS = ("vs_train_prepare", "vs_train_saved_bytes", "vs_train_workspace
                  "vs_train_check_packed", "vs_train_saved_bytes_desc", "vs_train_saved_bytes_packed", "vs_train_workspace_bytes_packed",
                  "vs_train_forward_packed", "vs_train_backward_packed", "vs_mse_packed_loss_forward", "vs_mse_packed_loss_backward",
                  "vs_train_attention_packed_scratch_bytes", "vs_train_attention_forward_packed", "vs_train_attention_backward_packed",
-                 "vs_train_dropout_mask_attention_packed", "vs_train_saved_field_packed")
+                 "vs_train_dropout_mask_attention_packed", "vs_train_saved_field_packed",
+                 # the pretraining head on packed ragged batches
+                 "vs_pretrain_head_state_bytes_packed", "vs_pretrain_head_workspace_bytes_packed",
+                 "vs_pretrain_head_forward_packed", "vs_pretrain_head_backward_packed")
 # include/vs_segment.h (kernel temporal segmentation)
 SEGMENT_EXPORTS = ("vs_kts_workspace_bytes", "vs_kts_segment", "vs_kts_scatters")
 # include/vs_optim.h (the Adam step)
@@ -381,6 +384,17 @@ def load() -> C.CDLL:
         lib.vs_train_saved_field_packed.restype = C.c_int
         lib.vs_train_saved_field_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t),
                                                     C.POINTER(C.c_size_t)]
+        # ... and the pretraining head on them: (hidden, logits, lengths, lengths_dev, B, ref_len, vid, vt_w, ...)
+        lib.vs_pretrain_head_state_bytes_packed.restype = C.c_size_t
+        lib.vs_pretrain_head_state_bytes_packed.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        lib.vs_pretrain_head_workspace_bytes_packed.restype = C.c_size_t
+        lib.vs_pretrain_head_workspace_bytes_packed.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        lib.vs_pretrain_head_forward_packed.restype = C.c_int
+        lib.vs_pretrain_head_forward_packed.argtypes = ([C.c_void_p] * 4 + [C.c_int32] * 2 + [C.c_void_p] * 3 + [C.c_int32] * 2
+                                                        + [C.c_float, C.c_int32] + [C.c_void_p] * 4)
+        lib.vs_pretrain_head_backward_packed.restype = C.c_int
+        lib.vs_pretrain_head_backward_packed.argtypes = ([C.c_void_p] * 4 + [C.c_int32] * 2 + [C.c_void_p] * 5 + [C.c_int32] * 2
+                                                         + [C.c_float, C.c_int32] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p])
         # include/vs_segment.h
         lib.vs_kts_workspace_bytes.restype = C.c_size_t
         lib.vs_kts_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]

@@ -776,6 +776,83 @@ int vs_pretrain_head_backward(const float *hidden, const float *logits, const ui
     return VS_OK;
 }
 
+// ---- the head on a packed ragged batch ----
+namespace {
+struct HeadPacked { int Mtot = 0, tmax = 0, NC = 0; };      // NC: (video, 64-frame chunk) pairs
+bool head_width_ok(int F) { return F == 256 || F == 512 || F == 768 || F == 1024; }
+bool head_shape_ok(int d, int F) { return d > 0 && d % 32 == 0 && head_width_ok(F); }
+int head_packed_ctx(const int32_t *lengths, int32_t B, HeadPacked &hp) {
+    PackedCtx pc;
+    vs_model_desc none{};
+    if (int rc = packed_ctx(none, lengths, B, pc)) return rc;
+    hp.Mtot = pc.Mtot; hp.tmax = pc.tmax; hp.NC = 0;
+    for (int b = 0; b < B; ++b) hp.NC += (lengths[b] + 63) / 64;
+    return VS_OK;
+}
+}  // namespace
+
+size_t vs_pretrain_head_state_bytes_packed(const int32_t *lengths, int32_t B, int32_t F) {
+    HeadPacked hp;
+    if (!head_width_ok(F) || head_packed_ctx(lengths, B, hp) != VS_OK) return 0;
+    return align_floats(vsp_head_scratch_floats_packed(B, hp.Mtot, hp.NC, F)) * sizeof(float);
+}
+
+size_t vs_pretrain_head_workspace_bytes_packed(const int32_t *lengths, int32_t B, int32_t d, int32_t F) {
+    HeadPacked hp;
+    if (!head_shape_ok(d, F) || head_packed_ctx(lengths, B, hp) != VS_OK) return 0;
+    return head_work(1, hp.Mtot, d, F).total * sizeof(float);
+}
+
+static int head_packed_check(const int32_t *lengths, int32_t B, int32_t ref_len, int32_t d, int32_t F, float temp, HeadPacked &hp) {
+    if (int rc = head_packed_ctx(lengths, B, hp)) return rc;
+    if (ref_len < hp.tmax) return failf(VS_ERR_INVALID, "pretrain head: ref_len=%d is below max(lengths)=%d", ref_len, hp.tmax);
+    if (ref_len > (1 << 24)) return failf(VS_ERR_INVALID, "pretrain head: ref_len=%d too large", ref_len);
+    if (!head_shape_ok(d, F) || !(temp > 0.f))
+        return failf(VS_ERR_INVALID, "pretrain head: d=%d F=%d temp=%g unsupported (d %% 32 == 0, F in {256,512,768,1024}, temp > 0)", d, F, temp);
+    return VS_OK;
+}
+
+int vs_pretrain_head_forward_packed(const float *hidden, const float *logits, const int32_t *lengths, const int32_t *lengths_dev,
+                                    int32_t B, int32_t ref_len, const float *vid, const float *vt_w, const float *vt_b,
+                                    int32_t d, int32_t F, float temp, int32_t entropy_penalty, float *feats, void *head_state,
+                                    float *losses, void *stream) {
+    if (!hidden || !logits || !lengths || !lengths_dev || !vid || !vt_w || !vt_b || !feats || !head_state || !losses)
+        return failf(VS_ERR_INVALID, "pretrain head: NULL pointer");
+    HeadPacked hp;
+    if (int rc = head_packed_check(lengths, B, ref_len, d, F, temp, hp)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    VST_LAUNCH(vsk_linear(hidden, vt_w, nullptr, vt_b, feats, hp.Mtot, F, d, 0, nullptr, 1, 0, st));
+    VST_LAUNCH(vsp_head_forward_packed(feats, logits, lengths_dev, vid, B, hp.Mtot, hp.tmax, hp.NC, ref_len, F, 1.0f / temp,
+                                       entropy_penalty, (float *)head_state, losses, st));
+    return VS_OK;
+}
+
+int vs_pretrain_head_backward_packed(const float *hidden, const float *logits, const int32_t *lengths, const int32_t *lengths_dev,
+                                     int32_t B, int32_t ref_len, const float *vid, const float *vt_w, const float *feats,
+                                     void *head_state, const float *d_losses, int32_t d, int32_t F, float temp,
+                                     int32_t entropy_penalty, float *d_hidden, float *d_logits, float *d_vt_w, float *d_vt_b,
+                                     void *workspace, size_t workspace_bytes, void *stream) {
+    if (!hidden || !logits || !lengths || !lengths_dev || !vid || !vt_w || !feats || !head_state || !d_losses || !d_hidden ||
+        !d_logits || !d_vt_w || !d_vt_b || !workspace)
+        return failf(VS_ERR_INVALID, "pretrain head: NULL pointer");
+    HeadPacked hp;
+    if (int rc = head_packed_check(lengths, B, ref_len, d, F, temp, hp)) return rc;
+    const HeadWork W = head_work(1, hp.Mtot, d, F);
+    if (workspace_bytes < W.total * sizeof(float) || ((uintptr_t)workspace & 255))
+        return failf(VS_ERR_WORKSPACE, "pretrain head: workspace %zu bytes < %zu needed (256-byte aligned)", workspace_bytes, W.total * sizeof(float));
+    hipStream_t st = (hipStream_t)stream;
+    float *ws = (float *)workspace;
+    const int M = hp.Mtot;
+    VST_LAUNCH(vsp_head_backward_packed(feats, logits, lengths_dev, B, M, hp.tmax, hp.NC, ref_len, F, 1.0f / temp, entropy_penalty,
+                                        (float *)head_state, d_losses, ws + W.dfeats, d_logits, st));
+    // video_transform over the Mtot packed rows: weight / bias gradient, then the gradient of the hidden state
+    VST_LAUNCH(vst_wgrad(ws + W.dfeats, F, hidden, d, M, F, d, d_vt_w, nullptr, nullptr, d_vt_b, nullptr, nullptr, F, ws + W.wg, st));
+    VST_LAUNCH(vst_transpose(vt_w, ws + W.wt, F, d, st));
+    VST_HIP(hipMemsetAsync(ws + W.zeros, 0, (size_t)(d > F ? d : F) * sizeof(float), st));
+    VST_LAUNCH(vsk_linear(ws + W.dfeats, ws + W.wt, nullptr, ws + W.zeros, d_hidden, M, d, F, 0, nullptr, 1, 0, st));
+    return VS_OK;
+}
+
 int vs_train_attention_forward(const float *q, const float *k, const float *v, const uint8_t *key_pad_mask, float *out,
                                float *lse2, int32_t B, int32_t H, int32_t T, int32_t dh, float scale, uint64_t seed,
                                uint32_t site, float p, void *stream) {

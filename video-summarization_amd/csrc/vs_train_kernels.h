@@ -100,6 +100,16 @@ int vsp_head_backward(const float *feats, const float *scores, const uint8_t *ma
                       float inv_temp, int entropy_penalty, const float *scratch, const float *g_losses /*[3]*/,
                       float *d_feats, float *d_scores, hipStream_t st);
 
+// packed ragged batches: feats [Mtot,F], scores [Mtot], no mask; lengths_dev [B] (cut at tmax; rows beyond Mtot and chunks beyond
+// NC = sum ceil(T_b / 64), both as the host counted them, are cut); ref_len: the padded width the reference would divide by
+size_t vsp_head_scratch_floats_packed(int B, int Mtot, int NC, int F);
+int vsp_head_forward_packed(const float *feats, const float *scores, const int *lengths_dev, const float *vid, int B, int Mtot,
+                            int tmax, int NC, int ref_len, int F, float inv_temp, int entropy_penalty, float *scratch,
+                            float *losses /*[3]*/, hipStream_t st);
+int vsp_head_backward_packed(const float *feats, const float *scores, const int *lengths_dev, int B, int Mtot, int tmax, int NC,
+                             int ref_len, int F, float inv_temp, int entropy_penalty, float *scratch, const float *g_losses /*[3]*/,
+                             float *d_feats, float *d_scores, hipStream_t st);
+
 // ---- vs_train_gemm_rows.hip: A-stationary bf16 GEMM for K = 256 with a bf16 C (fc1 forward, fc2 input gradient) ----
 // epi 0: dropout(relu(.)) (seed, site, p); 1: gate (gate16 = the bf16-stored activation, scale); 2: relu; 3: q / k / v planes
 bool vst_gemm_rows16_supported(int M, int N, int K, bool any_rows = false);

@@ -212,6 +212,13 @@ def collate_fn_pretrain(batch):                              # dataset.py:139-14
     return pad_sequence(features, batch_first=True, padding_value=PAD_VALUE), torch.stack(vid_reps, dim=0)
 
 
+def collate_fn_pretrain_packed(batch):
+    """``collate_fn_pretrain`` without the padding: (features [sum T_i, 1024], vid_reps [B, 512], lengths) - the videos' frames
+    concatenated in batch order, for ``PretrainModel.forward_packed``."""
+    features, vid_reps = zip(*batch)
+    return torch.cat(features, dim=0), torch.stack(vid_reps, dim=0), [int(f.shape[0]) for f in features]
+
+
 # --------------------------------------------------------------------------------------------
 # the MI355X-side feed: packed ragged batches through a pinned ring
 # --------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """Training and evaluation harness: the counterparts of the reference's ``train_step`` (``src/train.py:111-131``, on packed
-ragged batches: ``train_step_packed``) and ``val_step`` (``src/train.py:134-152``).
+ragged batches: ``train_step_packed``), of ``pretrain.py``'s step (``src/pretrain.py:49-86``, on packed ragged batches:
+``pretrain_step_packed``) and of ``val_step`` (``src/train.py:134-152``).
 
 ``val_step(model, loader, device)`` keeps the reference's contract: ``loader`` yields
 ``(feature [1,T,1024], target [1,T], user)`` per video (reference ``collate_fn_test``,
@@ -39,6 +40,29 @@ def train_step_packed(model, optim, loader: Iterable, scaler, device):
         scaler.scale(loss).backward()
         scaler.step(optim)
         scaler.update()
+        total, n = total + loss.item(), n + 1
+    return total / max(n, 1)
+
+
+def pretrain_step_packed(model, optimizer, schedular, scaler, loader: Iterable, device):
+    """The reference's pretraining step (``src/pretrain.py:49-86``) on PACKED batches: ``loader`` yields ``(feature [sum T_i,
+    1024], vid_rep [B, 512], lengths)`` (``data.collate_fn_pretrain_packed``); no sentinel rows and no mask, the same losses
+    and gradients as the padded step (``PretrainModel.forward_packed``).  Any ``torch.optim`` optimizer or the native
+    ``Adam``; an unmodified ``GradScaler``; ``schedular.update()`` after every step unless ``schedular`` is None.  Returns the
+    mean loss over the batches."""
+    model.train()
+    total, n = 0.0, 0
+    for feature, vid_rep, lengths in loader:
+        feature, vid_rep = feature.to(device), vid_rep.to(device)
+        with torch.amp.autocast("cuda"):                                    # pretrain.py:59
+            main_loss, center_loss, repel_loss = model.forward_packed(feature, vid_rep, lengths)
+            loss = main_loss + center_loss * 0.5 + 1. * repel_loss          # pretrain.py:62
+        optimizer.zero_grad()
+        scaler.scale(loss).backward()
+        scaler.step(optimizer)
+        scaler.update()
+        if schedular is not None:
+            schedular.update()
         total, n = total + loss.item(), n + 1
     return total / max(n, 1)
 
