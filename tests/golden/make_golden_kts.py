@@ -18,7 +18,10 @@ sys.path.insert(0, os.path.dirname(HERE))
 import kts_ref  # noqa: E402
 
 # name: recipe.  fn: kts_seg (features -> K = X X^T in float32) | kts_segmentation | cpd_nonlin.
-# x: ("planted", n, D, shots, seed) | ("unstructured", n, D, seed); kernel: "dot" (float32 X X^T) | ("rbf", gamma) (float64)
+# x: ("planted", n, D, shots, seed) | ("unstructured", n, D, seed) | ("planted_int", n, D, shots, seed[, amp, noise]);
+# kernel: "dot" (float32 X X^T) | ("rbf", gamma) (float64)
+# The planted_int cases are exact: integer K with sum|K| < 2^24, so the reference's float32 prefix sums round nowhere
+# and the tests hold them with array_equal (the costs of kts_segmentation, which pass through log, at 1e-12).
 CASES = {
     "seg_planted_n60_d1024": dict(fn="kts_seg", x=("planted", 60, 1024, 4, 11), ncp=10, vmax=1.0),
     "seg_planted_n200_d1024": dict(fn="kts_seg", x=("planted", 200, 1024, 8, 12), ncp=20, vmax=1.0),
@@ -37,12 +40,30 @@ CASES = {
     "cpd_no_backtrack_n200": dict(fn="cpd_nonlin", x=("planted", 200, 1024, 6, 22), kernel="dot", ncp=12, backtrack=False),
     "cpd_out_scatters_n60": dict(fn="cpd_nonlin", x=("planted", 60, 1024, 3, 23), kernel="dot", ncp=5, backtrack=True,
                                  out_scatters=True),
+    "int_cpd_n1_ncp0": dict(fn="cpd_nonlin", x=("planted_int", 1, 32, 1, 61), kernel="dot", ncp=0, backtrack=True),
+    "int_cpd_n33": dict(fn="cpd_nonlin", x=("planted_int", 33, 32, 3, 62), kernel="dot", ncp=6, backtrack=True),
+    "int_cpd_ncp_n_minus_1_n65": dict(fn="cpd_nonlin", x=("planted_int", 65, 32, 4, 63), kernel="dot", ncp=64,
+                                      backtrack=True),
+    "int_cpd_all_inf_n60": dict(fn="cpd_nonlin", x=("planted_int", 60, 32, 3, 64), kernel="dot", ncp=5, lmin=10, lmax=10,
+                                backtrack=True),
+    "int_cpd_last_score_finite_n60": dict(fn="cpd_nonlin", x=("planted_int", 60, 32, 3, 65), kernel="dot", ncp=5, lmin=2,
+                                          lmax=12, backtrack=True),
+    "int_cpd_all_tie_n70": dict(fn="cpd_nonlin", x=("planted_int", 70, 32, 1, 66, 2, 0), kernel="dot", ncp=6, lmin=3,
+                                lmax=20, backtrack=True),
+    "int_cpd_out_scatters_n33": dict(fn="cpd_nonlin", x=("planted_int", 33, 32, 3, 67), kernel="dot", ncp=5,
+                                     backtrack=True, out_scatters=True),
+    "int_auto_lmin2_lmax50_desc15_n120": dict(fn="kts_segmentation", x=("planted_int", 120, 32, 5, 68), kernel="dot",
+                                              ncp=12, vmax=400.0, desc_rate=15, lmin=2, lmax=50),
 }
 
 
 def features(rec):
     if rec[0] == "planted":
         return kts_ref.planted(*rec[1:])
+    if rec[0] == "planted_int":
+        x = kts_ref.planted_int(*rec[1:])
+        assert np.abs(kts_ref.assert_exact(x)).sum() < 2 ** 24      # the reference sums a float32 K in float32
+        return x
     return kts_ref.unstructured(*rec[1:])
 
 

@@ -106,6 +106,32 @@ def planted(n, D, n_shots, seed, noise=0.5):
     return x.astype(np.float32)
 
 
+def planted_int(n, D, n_shots, seed, amp=2, noise=1):
+    """piecewise-constant integer centroids in [-amp, amp] plus integer noise in [-noise, noise] (float32 [n, D]): inputs
+    on which the Gram, the prefix sums, the scatter table and the dynamic program are exact in every summation order
+    (assert_exact).  Cuts come from 1..n-1, n_shots is clamped to n; noise = 0 with one shot gives identical frames."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n_shots = max(1, min(int(n_shots), n))
+    cuts = np.sort(rng.choice(np.arange(1, n), size=n_shots - 1, replace=False))
+    lab = np.searchsorted(cuts, np.arange(n), side="right")
+    cent = rng.integers(-amp, amp + 1, size=(n_shots, D))
+    x = cent[lab] + rng.integers(-noise, noise + 1, size=(n, D))
+    return x.astype(np.float32)
+
+
+def assert_exact(x):
+    """The premise of the bit-equality tests, checked: the float32 Gram of x equals the float64 one (every partial sum an
+    integer below 2^24), and the prefix sums of K stay integers below 2^53.  Returns K = X X^T in float64."""
+    x = np.asarray(x)
+    assert x.dtype == np.float32 and (x == np.rint(x)).all()
+    x64 = x.astype(np.float64)
+    K = x64 @ x64.T
+    assert np.array_equal(np.dot(x, x.T).astype(np.float64), K)
+    assert (np.abs(x64).sum(1).max() * np.abs(x64).max()) < 2.0 ** 24      # every partial sum of a dot product too
+    assert np.abs(K).max() < 2.0 ** 24 and np.abs(K).sum() < 2.0 ** 53
+    return K
+
+
 def unstructured(n, D, seed):
     rng = np.random.Generator(np.random.PCG64(seed))
     x = rng.standard_normal((n, D))

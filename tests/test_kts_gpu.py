@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import kts_ref
-from test_kts_host import CASES, case_kernel, golden, rel
+from test_kts_host import CASES, case_kernel, exact_case, golden, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -25,6 +25,9 @@ def seg():
 def test_every_golden_case(seg, name):
     c, z = CASES[name], golden()[1]
     x, K = case_kernel(c)
+    exact = exact_case(c)                  # integer inputs (kts_ref.assert_exact): bit-equal to the reference
+    if exact:
+        kts_ref.assert_exact(x)
     with contextlib.redirect_stdout(io.StringIO()):
         if c["fn"] == "kts_seg":
             cps = seg.kts_seg(x, c["ncp"], c["vmax"])                    # features in: the Gram on the GPU
@@ -40,10 +43,16 @@ def test_every_golden_case(seg, name):
                 g = z[name + "/scatters"]
                 assert sc[0].shape == g.shape and sc[0].dtype == np.float64
                 assert (np.tril(sc[0], -1) == 0).all()
-                assert np.abs(sc[0] - g).max() <= 5e-5 * np.abs(g).max()
+                if exact:
+                    np.testing.assert_array_equal(sc[0], g)
+                else:
+                    assert np.abs(sc[0] - g).max() <= 5e-5 * np.abs(g).max()
     assert cps.dtype == np.int64 and vals.dtype == np.float64
     np.testing.assert_array_equal(cps, z[name + "/cps"])
-    assert rel(vals, z[name + "/vals"]) <= 5e-5
+    if exact and c["fn"] == "cpd_nonlin":
+        np.testing.assert_array_equal(vals, z[name + "/vals"])
+    else:
+        assert rel(vals, z[name + "/vals"]) <= (1e-12 if exact else 5e-5)     # exact scores, then a log in the penalty
 
 
 def _restated_check(seg, x, ncp, vmax):

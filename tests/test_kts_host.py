@@ -23,7 +23,8 @@ def golden():
 
 def case_kernel(c):
     """The case's input as the reference saw it: K = X X^T in float32 (dot) or the float64 RBF kernel."""
-    x = kts_ref.planted(*c["x"][1:]) if c["x"][0] == "planted" else kts_ref.unstructured(*c["x"][1:])
+    gen = {"planted": kts_ref.planted, "planted_int": kts_ref.planted_int, "unstructured": kts_ref.unstructured}
+    x = gen[c["x"][0]](*c["x"][1:])
     if c.get("kernel", "dot") == "dot":
         return x, np.dot(x, x.T)
     return x, kts_ref.rbf(x, c["kernel"][1])
@@ -36,6 +37,11 @@ def rel(a, b):
     return float((np.abs(a[f] - b[f]) / np.maximum(np.abs(b[f]), 1e-300)).max()) if f.any() else 0.0
 
 
+def exact_case(c):
+    """planted_int recipes: every stage is exact on them (kts_ref.assert_exact), so they are held with array_equal."""
+    return c["x"][0] == "planted_int"
+
+
 CASES, _ = golden()
 
 
@@ -44,17 +50,26 @@ def test_restatement_matches_the_reference_goldens(name):
     c, z = CASES[name], golden()[1]
     x, K = case_kernel(c)
     K64 = np.asarray(K, dtype=np.float64)
+    exact = exact_case(c)
+    if exact:
+        assert np.array_equal(kts_ref.assert_exact(x), K64)
     if c["fn"] == "cpd_nonlin":
         cps, vals, _, _ = kts_ref.cpd_nonlin(K64, c["ncp"], c.get("lmin", 1), c.get("lmax", 100000), c["backtrack"])
         if c.get("out_scatters"):
             J = kts_ref.scatters(K64)
             g = z[name + "/scatters"]
-            assert np.abs(J - g).max() <= 5e-5 * np.abs(g).max()
+            if exact:
+                np.testing.assert_array_equal(J, g)
+            else:
+                assert np.abs(J - g).max() <= 5e-5 * np.abs(g).max()
     else:
         cps, vals, _, _ = kts_ref.kts_segmentation(K64, c["ncp"], c["vmax"], c.get("desc_rate", 1), c.get("lmin", 1),
                                                    c.get("lmax", 100000))
     np.testing.assert_array_equal(cps, z[name + "/cps"])
-    assert rel(vals, z[name + "/vals"]) <= 5e-5
+    if exact and c["fn"] == "cpd_nonlin":
+        np.testing.assert_array_equal(vals, z[name + "/vals"])
+    else:
+        assert rel(vals, z[name + "/vals"]) <= (1e-12 if exact else 5e-5)     # exact scores, then a log in the penalty
 
 
 def test_segment_header_is_plain_c99_and_declares_exactly_the_segment_exports(vsa):
