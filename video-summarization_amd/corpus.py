@@ -91,7 +91,8 @@ PackedScoreFn = Callable[[torch.Tensor, List[int]], torch.Tensor]           # (x
 
 def score_corpus(score_fn: ScoreFn, videos: Sequence[torch.Tensor], rank: int = 0, world: int = 1,
                  group=None, device=None, max_frames: int = 65536,
-                 packed_fn: Optional[PackedScoreFn] = None, force_collective: bool = False) -> Dict[int, torch.Tensor]:
+                 packed_fn: Optional[PackedScoreFn] = None, force_collective: bool = False,
+                 keep_on_device: bool = False) -> Dict[int, torch.Tensor]:
     """Scores every video once across `world` ranks and returns {video index: scores [T_i]} on EVERY
     rank (CPU tensors).  `score_fn` is `SimNet.score` on a GPU box.  With world == 1 no
     `torch.distributed` call is made (unless `force_collective`: the gather then runs over a one-rank group - how the
@@ -101,13 +102,17 @@ def score_corpus(score_fn: ScoreFn, videos: Sequence[torch.Tensor], rank: int = 
     The scores stay on the scorer's device until the end: the batches' outputs are concatenated, ONE indexed copy
     moves every valid frame into its row of the send buffer [n_max, t_max] (the index is built on the host from the
     lengths: two small uploads per call, none per video), ONE all_gather_into_tensor exchanges the shards and ONE
-    device-to-host copy brings the result back.  No video ids travel: every rank derives the same plan."""
+    device-to-host copy brings the result back.  No video ids travel: every rank derives the same plan.
+
+    `keep_on_device`: returns instead `(order, flat)` - this rank's video indices in ascending order and ONE tensor on
+    the scorer's device with their scores concatenated in that order - with no gather and no device-to-host copy
+    (what `evaluation.EvalSet.evaluate` consumes)."""
     lengths = [int(v.shape[0]) for v in videos]
     shards = plan_shards(lengths, world)
     mine = shards[rank]
     n_max = max((len(s) for s in shards), default=0)
     t_max = max(lengths) if lengths else 0
-    pending, src, dst = [], [], []
+    pending, src, dst, scored = [], [], [], []       # scored: the video of each entry of src / dst
     base = 0                                            # offset of the current batch in the concatenated outputs
     slot_of = {i: k for k, i in enumerate(mine)}
     for batch in bucket_batches(mine, lengths, max_frames, packed=packed_fn is not None):
@@ -125,10 +130,18 @@ def score_corpus(score_fn: ScoreFn, videos: Sequence[torch.Tensor], rank: int = 
             out = out2.reshape(-1)
             for b, i in enumerate(batch):
                 src.append(torch.arange(base + b * tb, base + b * tb + lengths[i]))
+        scored.extend(batch)
         for i in batch:
             dst.append(torch.arange(slot_of[i] * t_max, slot_of[i] * t_max + lengths[i]))
         pending.append(out)
         base += out.numel()
+    if keep_on_device:
+        order = sorted(mine)
+        if not pending:
+            return order, torch.zeros(0, dtype=torch.float32, device=device)
+        flat = pending[0] if len(pending) == 1 else torch.cat(pending)
+        src_of = dict(zip(scored, src))
+        return order, flat.index_select(0, torch.cat([src_of[i] for i in order]).to(flat.device))
     collective = world > 1 or force_collective
     if collective:
         import torch.distributed as dist

@@ -5,7 +5,8 @@ Same call surface as reference ``src/evaluation/compute_metrics.py:42`` ``eval_m
 maps video name -> a record with ``user_summary, user_scores, change_points, n_frames, picks``
 (reference ``data/dataset.py:146-154``).  The work (up-sampling, float32 shot means, 0/1 knapsack,
 F-score, Kendall tau / Spearman rho) runs in host C++ (``csrc/vs_eval.cpp``) through the C ABI of
-``include/vs_eval.h``; there is no Python fallback.
+``include/vs_eval.h``; there is no Python fallback.  ``EvalSet`` is the same evaluation from scores that are still
+on the device (``include/vs_eval_device.h``, ``csrc/vs_eval_device.hip``): opt-in, bit-equal results.
 """
 from __future__ import annotations
 
@@ -85,6 +86,24 @@ def evaluate_scores(predicted_scores, user_scores):
     return k.value, s.value
 
 
+def _video_record(r, keep, scores, u, eval_method, name):
+    """Fills one vs_eval_video from a reference user record (`scores` None: a record for EvalSet)."""
+    pos, cp = _i32(u.picks).reshape(-1), _i32(u.change_points)
+    us = np.ascontiguousarray(np.asarray(u.user_summary), dtype=np.int8)
+    uf = np.asarray(u.user_scores)
+    uf = np.ascontiguousarray(uf, dtype=np.float32 if uf.dtype == np.float32 else np.float64)
+    if uf.ndim != 2 or uf.shape[1] != int(u.n_frames):
+        raise ValueError("user_scores of %r has shape %r, n_frames %d" % (name, uf.shape, int(u.n_frames)))
+    if us.ndim != 2 or cp.ndim != 2 or cp.shape[1] != 2:
+        raise ValueError("user_summary / change_points of %r have shapes %r / %r" % (name, us.shape, cp.shape))
+    keep.append((scores, pos, cp, us, uf))
+    r.scores = _p(scores) if scores is not None else None
+    r.positions, r.change_points, r.user_summary, r.user_scores = _p(pos), _p(cp), _p(us), _p(uf)
+    r.n_scores, r.n_positions, r.n_frames, r.n_shots = (scores.size if scores is not None else pos.size), pos.size, int(u.n_frames), cp.shape[0]
+    r.n_users, r.user_len, r.n_score_users, r.use_max = us.shape[0], us.shape[1], uf.shape[0], 1 if eval_method == "max" else 0
+    r.user_scores_f32 = 1 if uf.dtype == np.float32 else 0
+
+
 def eval_videos(data, user_dict, eval_method="avg", max_threads=0):
     """The per-video results of eval_metrics: (f_score, kendall, spearman) arrays in the key order of `data`.
     ONE C call (vs_eval_corpus): every video and every (video, user) rank correlation runs on one bounded pool of host
@@ -95,19 +114,7 @@ def eval_videos(data, user_dict, eval_method="avg", max_threads=0):
     recs = (_lib.EvalVideo * max(n, 1))()
     keep = []                                       # the arrays the records point into
     for j, k in enumerate(keys):
-        u = user_dict[k]
-        sc, pos, cp = _f32(data[k]).reshape(-1), _i32(u.picks).reshape(-1), _i32(u.change_points)
-        us = np.ascontiguousarray(np.asarray(u.user_summary), dtype=np.int8)
-        uf = np.asarray(u.user_scores)
-        uf = np.ascontiguousarray(uf, dtype=np.float32 if uf.dtype == np.float32 else np.float64)      # float32 (the datasets' type) goes in as it is
-        if uf.ndim != 2 or uf.shape[1] != int(u.n_frames):
-            raise ValueError("user_scores of %r has shape %r, n_frames %d" % (k, uf.shape, int(u.n_frames)))
-        keep.append((sc, pos, cp, us, uf))
-        r = recs[j]
-        r.scores, r.positions, r.change_points, r.user_summary, r.user_scores = _p(sc), _p(pos), _p(cp), _p(us), _p(uf)
-        r.n_scores, r.n_positions, r.n_frames, r.n_shots = sc.size, pos.size, int(u.n_frames), cp.shape[0]
-        r.n_users, r.user_len, r.n_score_users, r.use_max = us.shape[0], us.shape[1], uf.shape[0], 1 if eval_method == "max" else 0
-        r.user_scores_f32 = 1 if uf.dtype == np.float32 else 0
+        _video_record(recs[j], keep, _f32(data[k]).reshape(-1), user_dict[k], eval_method, k)
     f, kt, sp = (np.empty(n, dtype=np.float64) for _ in range(3))
     _lib.check(lib.vs_eval_corpus(recs, n, int(max_threads), _p(f), _p(kt), _p(sp)))
     return f, kt, sp
@@ -120,3 +127,97 @@ def eval_metrics(data, user_dict):
         return float(np.mean(())), float(np.mean(())), float(np.mean(()))
     f, kt, sp = eval_videos(data, user_dict, "avg")
     return float(np.mean(f)), float(np.mean(kt)), float(np.mean(sp))
+
+
+class EvalSet:
+    """The keyshot evaluation of `eval_videos` from scores that are STILL ON THE DEVICE (include/vs_eval_device.h; opt-in).
+
+    `users`: a sequence or a dict of the reference's user records (`user_summary, user_scores, change_points, n_frames,
+    picks`).  Everything that does not depend on the scores is computed here, once, and uploaded; `evaluate` then runs
+    three kernels over the listed videos and returns the per-video (f_score, kendall, spearman) float64 arrays - bit
+    for bit what `eval_videos` gives for the same scores.  Scores must be finite.  `n_scores`: per video, the number of
+    scores `evaluate` will bring (default: one per pick)."""
+
+    def __init__(self, users, eval_method="avg", device=None, n_scores=None):
+        import torch
+        self._lib = _lib.load()
+        self.keys = list(users.keys()) if isinstance(users, dict) else list(range(len(users)))
+        self._index = {k: j for j, k in enumerate(self.keys)}
+        n = len(self.keys)
+        if n < 1:
+            raise ValueError("EvalSet needs at least one video")
+        if n_scores is not None and len(n_scores) != n:
+            raise ValueError("n_scores has %d entries, users %d" % (len(n_scores), n))
+        recs = (_lib.EvalVideo * n)()
+        keep = []
+        for j, k in enumerate(self.keys):
+            _video_record(recs[j], keep, None, users[k], eval_method, k)
+            if n_scores is not None:
+                recs[j].n_scores = int(n_scores[j])
+        self.n_scores = [int(recs[j].n_scores) for j in range(n)]
+        self.n_shots = [int(recs[j].n_shots) for j in range(n)]
+        self.device = torch.device(device) if device is not None else torch.device("cuda")
+        if self.device.index is None:
+            self.device = torch.device(self.device.type, torch.cuda.current_device())
+        self._handle = C.c_void_p()
+        self._workspace = None
+        self._need = (None, 0)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(self._lib.vs_eval_set_create(recs, n, C.c_void_p(stream), C.byref(self._handle)))
+
+    def close(self):
+        """Frees the set's host tables and device arrays (also done when the object is collected)."""
+        if getattr(self, "_handle", None):
+            self._lib.vs_eval_set_free(self._handle)
+            self._handle = None
+
+    __del__ = close
+
+    def evaluate(self, scores, videos=None, return_selected=False):
+        """scores: ONE device float32 tensor, the listed videos' scores concatenated, or a list of device tensors (one
+        per listed video).  videos: keys (dict) or indices of the videos, default all in the set's order.
+        -> (f_score, kendall, spearman) float64 [len(videos)]; with return_selected also the list of per-video int8
+        arrays [n_shots], 1 where the knapsack took the shot."""
+        import torch
+        keys = self.keys if videos is None else list(videos)
+        try:
+            ids = np.array([self._index[k] for k in keys], dtype=np.int32)
+        except KeyError as e:
+            raise ValueError("video %r is not in this EvalSet" % (e.args[0],))
+        if ids.size < 1:
+            raise ValueError("no videos listed")
+        if isinstance(scores, (list, tuple)):
+            if len(scores) != ids.size:
+                raise ValueError("%d score tensors for %d videos" % (len(scores), ids.size))
+            for t, j in zip(scores, ids):
+                if t.numel() != self.n_scores[j]:
+                    raise ValueError("video %r: %d scores, the set expects %d" % (self.keys[j], t.numel(), self.n_scores[j]))
+            scores = torch.cat([t.reshape(-1) for t in scores]) if len(scores) > 1 else scores[0].reshape(-1)
+        if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.device != self.device:
+            raise ValueError("scores must be float32 tensors on %s" % (self.device,))
+        want = sum(self.n_scores[j] for j in ids)
+        if scores.numel() != want:
+            raise ValueError("%d scores for videos that need %d" % (scores.numel(), want))
+        scores = scores.contiguous().view(-1)
+        lib = self._lib
+        key = ids.tobytes()
+        if self._need[0] != key:                      # an epoch loop lists the same videos every time
+            need = lib.vs_eval_set_workspace_bytes(self._handle, _p(ids), ids.size)
+            if need == 0:
+                _lib.check(_lib.VS_ERR_INVALID)
+            self._need = (key, need)
+        need = self._need[1]
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        f, kt, sp = (np.empty(ids.size, dtype=np.float64) for _ in range(3))
+        sel = np.empty(sum(self.n_shots[j] for j in ids), dtype=np.int8) if return_selected else None
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(lib.vs_eval_set_run(self._handle, C.c_void_p(scores.data_ptr()), _p(ids), ids.size, _p(f), _p(kt), _p(sp),
+                                           _p(sel) if sel is not None else None, C.c_void_p(self._workspace.data_ptr()),
+                                           self._workspace.numel(), C.c_void_p(stream)))
+        if not return_selected:
+            return f, kt, sp
+        cuts = np.cumsum([self.n_shots[j] for j in ids])[:-1]
+        return f, kt, sp, np.split(sel, cuts)

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 from typing import Iterable, Sequence
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -97,16 +98,46 @@ def evaluate_shard(scores, targets, users, order):
     return [loss, float(f.sum()), float(k.sum()), float(s.sum())]
 
 
+def evaluate_shard_device(eval_set, flat, targets, order):
+    """`evaluate_shard` from scores that never left the device: `flat` holds the scores of the videos `order`
+    (ascending indices into the EvalSet) concatenated.  The keyshot evaluation is `EvalSet.evaluate`; the per-video MSE
+    is taken on the device in float64 (one cumulative sum over the squared differences) and the four sums on the
+    host, in index order, in double."""
+    if not order:
+        return [0.0, 0.0, 0.0, 0.0]
+    f, k, s = eval_set.evaluate(flat, videos=[eval_set.keys[i] for i in order])
+    tgt = [targets[i].detach().reshape(-1) for i in order]
+    tgt = (torch.cat(tgt) if len(tgt) > 1 else tgt[0]).to(device=flat.device, dtype=torch.float32)
+    ends = torch.tensor([t.numel() for t in (targets[i] for i in order)], dtype=torch.int64).cumsum(0)
+    total = torch.cat([torch.zeros(1, dtype=torch.float64, device=flat.device), (flat - tgt).double().square().cumsum(0)])
+    ends_d = ends.to(flat.device)
+    starts_d = torch.cat([torch.zeros(1, dtype=torch.int64, device=flat.device), ends_d[:-1]])
+    per_video = ((total[ends_d] - total[starts_d]) / (ends_d - starts_d).double()).cpu()
+    loss = 0.0
+    for x in per_video.tolist():
+        loss += x
+    return [loss, float(np.sum(f)), float(np.sum(k)), float(np.sum(s))]
+
+
 @torch.no_grad()
 def val_step_batched(model, features: Sequence[torch.Tensor], targets: Sequence[torch.Tensor], users: Sequence,
-                     device, rank: int = 0, world: int = 1, group=None, max_frames: int = 65536):
-    """Same result as ``val_step`` over (features[i] [T_i,1024], targets[i] [T_i], users[i])."""
+                     device, rank: int = 0, world: int = 1, group=None, max_frames: int = 65536, eval_set=None):
+    """Same result as ``val_step`` over (features[i] [T_i,1024], targets[i] [T_i], users[i]).
+
+    ``eval_set``: an ``evaluation.EvalSet`` built over ``users`` (same order).  Each rank then evaluates the videos it
+    scored from the scores still on its device (no score all-gather, no score device-to-host copy), takes the MSE loss
+    there too, and only the all-reduce of the four sums stays.  F-score, tau and rho are the default path's bit for bit."""
     model.eval()
     # models with head dim 32 / 64 score PACKED batches (no sentinel padding, no mask; the same bits)
     can_pack = hasattr(model, "score_packed") and getattr(model, "_lib_dh", model.d_model // model.num_heads) in (32, 64, 128)
+    packed_fn = (lambda x, lens: model.score_packed(x, lens)) if can_pack else None
+    if eval_set is not None:
+        order, flat = score_corpus(lambda x, m: model.score(x, m), list(features), rank=rank, world=world, group=group,
+                                   device=device, max_frames=max_frames, packed_fn=packed_fn, keep_on_device=True)
+        sums = evaluate_shard_device(eval_set, flat, targets, order)
+        return _reduce_sums(sums, len(users), device, world, group)
     scores = score_corpus(lambda x, m: model.score(x, m), list(features), rank=rank, world=world, group=group,
-                          device=device, max_frames=max_frames,
-                          packed_fn=(lambda x, lens: model.score_packed(x, lens)) if can_pack else None)
+                          device=device, max_frames=max_frames, packed_fn=packed_fn)
     # every rank holds every video's scores; the (CPU) evaluation is sharded too: a rank evaluates the videos it
     # scored and the four sums are all-reduced (SURVEY.md §8(e)).  Sums run in a fixed per-rank order.
     lengths = [int(f.shape[0]) for f in features]
@@ -114,11 +145,16 @@ def val_step_batched(model, features: Sequence[torch.Tensor], targets: Sequence[
     order = sorted(mine)
 
     sums = evaluate_shard(scores, targets, users, order)
+    return _reduce_sums(sums, len(users), device, world, group)
+
+
+def _reduce_sums(sums, n_videos, device, world, group):
+    """All-reduce of a rank's [loss, F-score, tau, rho] sums, then the means over the corpus."""
     if world > 1:
         import torch.distributed as dist
         t = torch.tensor(sums, dtype=torch.float64,
                          device=device if (device is not None and dist.get_backend(group) == "nccl") else "cpu")
         dist.all_reduce(t, group=group)
         sums = t.tolist()
-    n = max(len(users), 1)
+    n = max(n_videos, 1)
     return sums[0] / n, sums[1] / n, sums[2] / n, sums[3] / n
