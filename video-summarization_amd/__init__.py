@@ -14,6 +14,9 @@ from .optim import Adam, AdamW  # noqa: F401
 from .data import collate_fn_pretrain_packed  # noqa: F401
 from .harness import pretrain_step_packed  # noqa: F401
 from .segmentation import get_segment_fn, kts_seg, kts_seg_batch  # noqa: F401
+from . import summary  # noqa: F401
+from .summary import summarize, summarize_scores  # noqa: F401
 
 __all__ = ["SimNet", "PretrainModel", "score_frames", "synth", "mse_with_mask_loss", "mse_packed_loss", "segmentation", "get_segment_fn", "kts_seg",
-           "kts_seg_batch", "optim", "Adam", "AdamW", "collate_fn_pretrain_packed", "pretrain_step_packed"]
+           "kts_seg_batch", "optim", "Adam", "AdamW", "collate_fn_pretrain_packed", "pretrain_step_packed", "summary", "summarize",
+           "summarize_scores"]

@@ -20,7 +20,7 @@ DIAG_LIB_PATH = os.path.join(HERE, "libvsscore_diag.so")
 SOURCES = ("vs_kernels.hip", "vs_attention.hip", "vs_attention_w64.hip", "vs_mlp_fused.hip", "vs_gemm_ring.hip", "vs_scorer.cpp", "vs_eval.cpp",
            "vs_train_kernels.hip", "vs_train_attention.hip", "vs_train_attention_bf16.hip", "vs_train_gemm_rows.hip", "vs_pretrain_kernels.hip",
            "vs_train.cpp", "vs_segment.hip", "vs_segment.cpp", "vs_optim.hip", "vs_attention_maps.hip",
-           "vs_eval_device.hip", "vs_eval_device.cpp")
+           "vs_eval_device.hip", "vs_eval_device.cpp", "vs_summary.hip", "vs_summary.cpp")
 ABI_VERSION = 3
 
 VS_OK, VS_ERR_INVALID, VS_ERR_WORKSPACE, VS_ERR_HIP = 0, 1, 2, 3
@@ -48,6 +48,8 @@ EVAL_EXPORTS = ("vs_eval_upsample", "vs_eval_knapsack", "vs_eval_generate_summar
                 "vs_eval_rank_correlation", "vs_eval_corpus")
 # include/vs_eval_device.h (the same evaluation from device-resident scores; opt-in)
 EVAL_DEVICE_EXPORTS = ("vs_eval_set_create", "vs_eval_set_free", "vs_eval_set_workspace_bytes", "vs_eval_set_run")
+# include/vs_summary.h (scores on the device in, the summary and its selected frames on the device out)
+SUMMARY_EXPORTS = ("vs_summarize_workspace_bytes", "vs_summarize")
 # include/vs_train.h
 TRAIN_EXPORTS = ("vs_train_prepare", "vs_train_saved_bytes", "vs_train_workspace_bytes", "vs_train_forward", "vs_train_backward",
                  "vs_mse_mask_loss_forward", "vs_mse_mask_loss_backward", "vs_train_attention_forward",
@@ -204,7 +206,7 @@ def load() -> C.CDLL:
                 "Run `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). "
                 "There is no PyTorch/CPU fallback for the scoring path." % path)
         lib = C.CDLL(path)
-        for name in EXPORTS + EVAL_EXPORTS + EVAL_DEVICE_EXPORTS + TRAIN_EXPORTS + SEGMENT_EXPORTS + OPTIM_EXPORTS + INSPECT_EXPORTS:
+        for name in EXPORTS + EVAL_EXPORTS + EVAL_DEVICE_EXPORTS + SUMMARY_EXPORTS + TRAIN_EXPORTS + SEGMENT_EXPORTS + OPTIM_EXPORTS + INSPECT_EXPORTS:
             if not hasattr(lib, name):
                 raise RuntimeError("libvsscore.so lacks symbol %s (stale build?)" % name)
         lib.vs_abi_version.restype = C.c_int
@@ -298,6 +300,12 @@ def load() -> C.CDLL:
         lib.vs_eval_set_run.restype = C.c_int
         lib.vs_eval_set_run.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
                                         + [C.c_size_t, C.c_void_p])
+        # include/vs_summary.h
+        lib.vs_summarize_workspace_bytes.restype = C.c_size_t
+        lib.vs_summarize_workspace_bytes.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_double]
+        lib.vs_summarize.restype = C.c_int
+        lib.vs_summarize.argtypes = ([C.c_int32] + [C.c_void_p] * 6 + [C.c_double] + [C.c_void_p] * 7
+                                     + [C.c_size_t, C.c_void_p])
         # include/vs_train.h
         lib.vs_train_prepare.restype = C.c_int
         lib.vs_train_prepare.argtypes = [C.c_void_p, C.c_void_p]

@@ -2,6 +2,7 @@
 // Three launches per run over the whole batch, no atomics (integer sums are order-free):
 //   eval_summary  one block per video:      float32 shot means in numpy's pairwise order, the double knapsack table row by
 //                                           row (only the bits K[i][w] != K[i-1][w] are kept), back-track, sumS, overlaps
+//                                           (the device functions live in vs_keyshot_device.h: the device summary shares them)
 //   eval_xrank    one block per video:      doubled average ranks of the pick runs, 2 * xtie, 4 * saa (weighted all-pairs counts)
 //   eval_pairs    one block per (video, user): dis, ntie, 4 * sab over the joint runs - the one O(m^2) kernel
 // Everything a result depends on is an exact integer or (shot means, knapsack table) the reference's own float32 / double
@@ -11,68 +12,13 @@
 
 #include "vs_device.h"
 #include "vs_eval_device_kernels.h"
+#include "vs_keyshot_device.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int NT = EV_NT;
-
-// frame f of the up-sampled prediction: the score of the pick that covers it, 0 past the last score
-__device__ __forceinline__ float frame_value(const int32_t *src, const float *sc, int f) {
-    const int p = src[f];
-    return p >= 0 ? sc[p] : 0.f;
-}
-
-// numpy's pairwise_sum below its recursion: n < 8 plain, n <= 128 eight strided partial sums.  EIGHT LANES (g = 0..7,
-// consecutive, all with the same arguments and so the same control flow) share the call: lane g carries partial sum g,
-// the eight are combined in numpy's order and every lane returns the same bits.
-__device__ float pairwise_leaf(const int32_t *src, const float *sc, int n, int g) {
-    if (n < 8) {
-        float res = 0.f;
-        for (int i = 0; i < n; ++i) res += frame_value(src, sc, i);
-        return res;
-    }
-    float r = frame_value(src, sc, g);
-    const int full = n - (n % 8);
-    int i;
-#pragma unroll 4
-    for (i = 8; i < full; i += 8) r += frame_value(src, sc, i + g);
-    const float r0 = __shfl(r, 0, 8), r1 = __shfl(r, 1, 8), r2 = __shfl(r, 2, 8), r3 = __shfl(r, 3, 8),
-                r4 = __shfl(r, 4, 8), r5 = __shfl(r, 5, 8), r6 = __shfl(r, 6, 8), r7 = __shfl(r, 7, 8);
-    float res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-    for (; i < n; ++i) res += frame_value(src, sc, i);
-    return res;
-}
-
-// np_pairwise_sum_f32 (vs_eval.cpp) without recursion: post-order walk of the same split tree (n2 = n / 2 rounded down
-// to a multiple of 8), by the same eight lanes as pairwise_leaf.  n <= 2^18 frames: at most 12 levels above the leaves.
-__device__ float pairwise_sum(const int32_t *src, const float *sc, int n, int g) {
-    if (n <= 128) return pairwise_leaf(src, sc, n, g);
-    int off[40], len[40];
-    bool seen[40];
-    float val[24];
-    int top = 0, vt = 0;
-    off[0] = 0; len[0] = n; seen[0] = false; top = 1;
-    while (top > 0) {
-        const int o = off[top - 1], l = len[top - 1];
-        if (l <= 128) {
-            --top;
-            val[vt++] = pairwise_leaf(src + o, sc, l, g);
-        } else if (seen[top - 1]) {
-            --top;
-            const float right = val[--vt], left = val[--vt];
-            val[vt++] = left + right;
-        } else {
-            seen[top - 1] = true;
-            int n2 = l / 2;
-            n2 -= n2 % 8;
-            off[top] = o + n2; len[top] = l - n2; seen[top] = false; ++top;     // right: walked second
-            off[top] = o;      len[top] = n2;     seen[top] = false; ++top;     // left: walked first
-        }
-    }
-    return val[0];
-}
 
 // sum of one int64 per thread over the block; the result is valid in thread 0.  buf: NT entries of LDS.
 __device__ long long block_sum(long long v, long long *buf) {
@@ -100,64 +46,16 @@ __global__ __launch_bounds__(EV_NT) void eval_summary(EvStatic S, EvRun R) {
     double *val = R.val + sl.shot_out;
     int8_t *sel = R.sel + sl.shot_out;
 
-    // shot means: float32 pairwise sum, float32 correctly rounded divide, NaN for an empty shot (generate_summary.py:42);
-    // eight lanes per shot
-    for (int s = t >> 3; s < n; s += NT / 8) {
-        const int a = lo[s], cnt = hi[s] - a;
-        const float m = cnt > 0 ? __fdiv_rn(pairwise_sum(src + a, sc, cnt, t & 7), (float)cnt) : __builtin_nanf("");
-        if ((t & 7) == 0) { val[s] = (double)m; sel[s] = 0; }
-    }
-
-    // knapsack rows (knapsack_implementation.py:11-21): parallel over w, rows in sequence
+    // shot means, knapsack rows and back-track: the device functions shared with the device summary (vs_keyshot_device.h)
+    vs_keyshot::shot_means(src, sc, lo, hi, n, val, sel);
     double *prev = sl.rows_off >= 0 ? R.rows + sl.rows_off : lds_rows;
     double *cur = prev + (sl.rows_off >= 0 ? W + 1 : EV_LDS_COLS);
     const int wpr = (W + 64) / 64;                            // 64-bit words of change bits per row
     unsigned long long *bits = (long long)n * wpr <= EV_LDS_BITS ? lds_bits : R.bits + sl.bits_off;     // read back by ONE thread
-    for (int w = t; w <= W; w += NT) prev[w] = 0.0;
-    __syncthreads();
-    for (int i = 1; i <= n; ++i) {
-        const int w_i = wt[i - 1];
-        const double v_i = val[i - 1];
-        for (int base = 0; base <= W; base += NT) {           // uniform trip count: every lane takes part in the ballot
-            const int w = base + t;
-            bool changed = false;
-            if (w <= W) {
-                double c = 0.0;                               // column 0 stays 0
-                if (w >= 1) {
-                    const double p = prev[w];
-                    if (w_i <= w) {
-                        const double take = v_i + prev[w - w_i];
-                        c = p > take ? p : take;              // Python max(a, b): a unless b > a, also with a NaN on either side
-                    } else {
-                        c = p;
-                    }
-                    changed = c != p;                         // a NaN differs from everything, itself included
-                }
-                cur[w] = c;
-            }
-            const unsigned long long mask = __ballot(changed);
-            const int word = (base >> 6) + (t >> 6);
-            if ((t & 63) == 0 && word < wpr) bits[(size_t)(i - 1) * wpr + word] = mask;
-        }
-        __syncthreads();
-        double *x = prev; prev = cur; cur = x;
-    }
-
-    // back-track (:23-28), one thread: a "taken" shot that does not fit carries a NEGATIVE capacity on, which indexes the
-    // row from its end (Python list semantics) and below -(W + 1) is the reference's IndexError
+    vs_keyshot::knapsack_rows(prev, cur, bits, wpr, wt, val, n, W);
     if (t == 0) {
-        long long sumS = 0, err = 0;
-        int w = W;
-        const int32_t *clip = S.shot_clip + V.shot_off;
-        for (int i = n; i > 0; --i) {
-            if (w < -(W + 1)) { err = 1; break; }
-            const int col = w < 0 ? w + W + 1 : w;
-            if ((bits[(size_t)(i - 1) * wpr + (col >> 6)] >> (col & 63)) & 1ull) {
-                sel[i - 1] = 1;
-                sumS += clip[i - 1];
-                w -= wt[i - 1];
-            }
-        }
+        long long sumS = 0;
+        const long long err = vs_keyshot::backtrack(bits, wpr, wt, S.shot_clip + V.shot_off, n, W, sel, &sumS);
         R.vidout[4 * (size_t)blockIdx.x + 0] = sumS;
         R.vidout[4 * (size_t)blockIdx.x + 1] = err;
     }
