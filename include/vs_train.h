@@ -166,7 +166,13 @@ int vs_mse_mask_loss_backward(const float *output, const float *target, const ui
  *   feats [B,T,F] (out: video_transform(hidden), kept for the backward), head_state >= vs_pretrain_head_state_bytes
  *   (out: per-video statistics, kept for the backward), losses [3] = (distillation, centering, repelling) batch means.
  * The repelling loss is evaluated as (||sum_t x^_t||^2 - sum_t ||x^_t||^2) / T^2 - the mean of the reference's
- * [T,T] cosine matrix without its diagonal, never materialised. */
+ * [T,T] cosine matrix without its diagonal, never materialised.
+ * A video whose frames are ALL masked gives what the reference gives: its distillation loss and its norm penalty are NaN
+ * (so are losses[0], losses[1] under the norm penalty, and after the backward its rows of d_hidden / d_logits and d_vt_w,
+ * d_vt_b), its entropy penalty and its repelling loss are 0; the other videos' rows of d_hidden / d_logits are not affected.
+ * VS_ERR_INVALID (before any device access): NULL pointer (key_pad_mask may be NULL), B <= 0, T <= 0, d <= 0 or d % 32 != 0,
+ * F not in {256, 512, 768, 1024}, temp <= 0.  VS_ERR_WORKSPACE (backward): short or unaligned workspace.  The byte counts
+ * are 0 when an argument is not positive. */
 size_t vs_pretrain_head_state_bytes(int32_t B, int32_t T, int32_t F);
 size_t vs_pretrain_head_workspace_bytes(int32_t B, int32_t T, int32_t d, int32_t F);
 int vs_pretrain_head_forward(const float *hidden, const float *logits, const uint8_t *key_pad_mask, const float *vid,

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from pretrain_ref import head_reference_packed as _head_reference, tiled_gemms      # noqa: F401  (tiled_gemms: a fixture)
 import tolerances as tol
 
 pytestmark = pytest.mark.gpu
@@ -42,29 +43,6 @@ def _head():
 # ---------------------------------------------------------------------------------------------
 # 1. the head kernels against the formulas in float64
 # ---------------------------------------------------------------------------------------------
-def _head_reference(hidden, logits, vid, lengths, W, b, temp, pen, ref_len):
-    """The packed head's contract (include/vs_train.h) per video in float64 torch; the repelling term in the reference's
-    own form, the [T,T] cosine matrix without its diagonal (simnet_pretrain.py:56-69), summed and divided by ref_len^2."""
-    import torch.nn.functional as F
-    feats = F.linear(hidden, W, b)
-    main, center, repel = [], [], []
-    row = 0
-    for i, T in enumerate(lengths):
-        f, s = feats[row:row + T], logits[row:row + T].reshape(T)
-        row += T
-        x = f / (f.norm(dim=1, keepdim=True) + 1e-9)
-        sim = (x @ x.t()) * (torch.eye(T, dtype=x.dtype) == 0).to(x.dtype)
-        repel.append(sim.sum() / float(ref_len * ref_len))
-        w = F.softmax(s / temp, dim=0)
-        if pen == "entropy":
-            center.append(((w + 1e-9) * torch.log(w + 1e-9)).sum() / float(ref_len))
-        else:
-            center.append(torch.norm(w))
-        pooled = (w.unsqueeze(0) @ f).squeeze(0)
-        main.append((-F.softmax(vid[i], dim=0) * torch.log(F.softmax(pooled, dim=0))).mean())
-    return torch.stack(main).mean(), torch.stack(center).mean(), torch.stack(repel).mean()
-
-
 HEAD_LENGTHS = ([150, 65, 64, 1], [333], [64, 63], [129, 128, 127, 2, 1])      # across the 64-frame chunk on both sides; one-frame videos
 HEAD_CASES = [(ls, d, pen, 512, 0) for ls in HEAD_LENGTHS for d in (128, 256, 512) for pen in ("entropy", "norm")]
 HEAD_CASES += [([150, 65, 64, 1], 256, "entropy", 256, 0), ([64, 63], 128, "norm", 1024, 0),
@@ -112,15 +90,6 @@ def _run_head_case(c):
         scale = r.abs().max().item()
         print("%s %s: err %.3e, max %.3e" % (_case_id(c), name, err, scale))
         assert err <= 2e-5 * scale + 1e-9, "%s: err %.3e, max %.3e" % (name, err, scale)
-
-
-@pytest.fixture
-def tiled_gemms(vsa):
-    """VS_SKINNY_ROWS=0 pins the LDS-tiled GEMMs (video_transform's forward, dgrad and wgrad) that batches above the skinny
-    threshold take; these small batches get the latency kernels by default."""
-    vsa._lib.set_option("VS_SKINNY_ROWS", 0)
-    yield
-    vsa._lib.set_option("VS_SKINNY_ROWS", -1)
 
 
 @pytest.mark.parametrize("case", HEAD_CASES, ids=_case_id)

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from pretrain_ref import head_reference as _head_reference, tiled_gemms      # noqa: F401  (tiled_gemms: a fixture)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEV = torch.device("cuda:0")
 
@@ -61,41 +63,7 @@ def test_repelling_loss_equals_the_materialised_form(vsa):
                 * (torch.eye(50) == 0).float()).mean(dim=1).mean().item()) < 1e-6
 
 
-def _head_reference(hidden, logits, vid, mask, W, b, temp, pen):
-    """The reference's formulas (simnet_pretrain.py:35-98) restated op for op in float64 torch, [T,T] matrix included."""
-    import torch.nn.functional as F
-    feats = F.linear(hidden, W, b)
-    x = feats * (mask == False).unsqueeze(2) if mask is not None else feats      # noqa: E712
-    x = x / (x.norm(dim=2, keepdim=True) + 1e-9)
-    T = x.shape[1]
-    sim = torch.matmul(x, x.transpose(1, 2)) * (torch.eye(T, dtype=x.dtype) == 0).to(x.dtype).unsqueeze(0)
-    repel = sim.mean(dim=1).mean()
-    sc = logits
-    if mask is not None:
-        sc = sc.masked_fill(mask.unsqueeze(2), float("-inf"))
-    mix = F.softmax(sc / temp, dim=1)
-    if pen == "entropy":
-        e = (mix + 1e-9) * torch.log(mix + 1e-9)
-        if mask is not None:
-            e = e.masked_fill(mask.unsqueeze(2), 0.)
-        center = e.mean(dim=1).mean()
-    else:
-        center = torch.norm(mix, dim=1).mean()
-    pooled = torch.matmul(mix.transpose(1, 2), feats).squeeze(1)
-    loss = (-F.softmax(vid, dim=1) * torch.log(F.softmax(pooled, dim=1))).mean()
-    return loss, center, repel
-
-
 HEAD_SHAPES = [(3, 150, 256, "entropy", True), (2, 64, 128, "norm", True), (1, 333, 512, "entropy", False), (4, 65, 256, "norm", False)]
-
-
-@pytest.fixture
-def tiled_gemms(vsa):
-    """VS_SKINNY_ROWS=0 pins the LDS-tiled GEMMs (video_transform's forward, dgrad and wgrad) that batches above the
-    skinny threshold take; these small batches get the latency kernels by default."""
-    vsa._lib.set_option("VS_SKINNY_ROWS", 0)
-    yield
-    vsa._lib.set_option("VS_SKINNY_ROWS", -1)
 
 
 @pytest.mark.gpu

@@ -167,6 +167,11 @@ __global__ __launch_bounds__(256) void head_final(const float *__restrict__ scor
         scratch[L.dce + (size_t)b * F + i] = expf(logp1) - p2;        // d CE_b / d pooled_i (before the 1/(B F) of the mean)
     }
     ce = block_sum(ce);
+    // every frame masked: the reference's softmax over -inf is NaN, and so are its pooled row, its distillation loss, its
+    // norm penalty and every gradient through them (entropy: masked_fill(mask, 0.) leaves 0).  The sums above saw w = 0.
+    const bool dead = !(Z > 0.f);
+    if (dead)
+        for (int i = tid; i < F; i += 256) scratch[L.dce + (size_t)b * F + i] = __builtin_nanf("");
     if (tid == 0) {
         float D = 0.f, cen = 0.f;
         for (int c = 0; c < L.nc; ++c) { D += part[(size_t)c * (2 * F + 4) + 2 * F]; cen += part[(size_t)c * (2 * F + 4) + 2 * F + 1]; }
@@ -176,6 +181,7 @@ __global__ __launch_bounds__(256) void head_final(const float *__restrict__ scor
         st[ST_CEN] = entropy ? cen / (float)T : sqrtf(cen);    // per-video centering value
         st[ST_R] = (S2 - D) / ((float)T * (float)T);           // per-video repel value
         st[ST_N - 1] = ce / (float)F;                          // per-video distillation loss
+        if (dead) { st[ST_N - 1] = __builtin_nanf(""); if (!entropy) st[ST_CEN] = __builtin_nanf(""); }
     }
 }
 
@@ -219,7 +225,8 @@ __global__ __launch_bounds__(256) void head_bwd_dots(const float *__restrict__ f
         const bool valid = !mk || !mk[t];
         const float w = valid ? expf(scores[(size_t)b * T + t] * inv_temp - m) / Z : 0.f;
         float dw = dot;
-        if (entropy) { if (valid) dw += gc / (float)T * (logf(w + EPS) + 1.0f); }
+        // (one fused multiply-add, spelled out: head_bwd_dots_pk must round the same way)
+        if (entropy) { if (valid) dw = __builtin_fmaf(gc / (float)T, logf(w + EPS) + 1.0f, dw); }
         else dw += gc * w / sqrtf(st[ST_W2]);
         if (lane == 0) { scratch[L.a + (size_t)b * T + t] = dw; racc += w * dw; }
     }
@@ -538,7 +545,9 @@ __global__ __launch_bounds__(256) void head_bwd_dots_pk(const float *__restrict_
         dot = wave_sum(dot);
         const float w = expf(scores[row] * inv_temp - m) / Z;
         float dw = dot;
-        if (entropy) dw += gc / A.tref * (logf(w + EPS) + 1.0f);
+        // fused like head_bwd_dots: left to the compiler this was a multiply and an add after the join with the norm branch,
+        // one rounding more than the padded kernel, and d_logits differed in the last bit under the entropy penalty
+        if (entropy) dw = __builtin_fmaf(gc / A.tref, logf(w + EPS) + 1.0f, dw);
         else dw += gc * w / sqrtf(st[ST_W2]);
         if (lane == 0) { scratch[L.a + row] = dw; racc += w * dw; }
     }
