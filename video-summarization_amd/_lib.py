@@ -20,7 +20,7 @@ DIAG_LIB_PATH = os.path.join(HERE, "libvsscore_diag.so")
 SOURCES = ("vs_kernels.hip", "vs_attention.hip", "vs_attention_w64.hip", "vs_mlp_fused.hip", "vs_gemm_ring.hip", "vs_scorer.cpp", "vs_eval.cpp",
            "vs_train_kernels.hip", "vs_train_attention.hip", "vs_train_attention_bf16.hip", "vs_train_gemm_rows.hip", "vs_pretrain_kernels.hip",
            "vs_train.cpp", "vs_segment.hip", "vs_segment.cpp", "vs_optim.hip", "vs_attention_maps.hip",
-           "vs_eval_device.hip", "vs_eval_device.cpp", "vs_summary.hip", "vs_summary.cpp")
+           "vs_eval_device.hip", "vs_eval_device.cpp", "vs_summary.hip", "vs_summary.cpp", "vs_batch.hip")
 ABI_VERSION = 3
 
 VS_OK, VS_ERR_INVALID, VS_ERR_WORKSPACE, VS_ERR_HIP = 0, 1, 2, 3
@@ -50,6 +50,8 @@ EVAL_EXPORTS = ("vs_eval_upsample", "vs_eval_knapsack", "vs_eval_generate_summar
 EVAL_DEVICE_EXPORTS = ("vs_eval_set_create", "vs_eval_set_free", "vs_eval_set_workspace_bytes", "vs_eval_set_run")
 # include/vs_summary.h (scores on the device in, the summary and its selected frames on the device out)
 SUMMARY_EXPORTS = ("vs_summarize_workspace_bytes", "vs_summarize")
+# include/vs_batch.h (the batches of a training epoch cut from a device-resident set)
+BATCH_EXPORTS = ("vs_batch_gather_packed", "vs_batch_gather_padded", "vs_batch_gather_rows")
 # include/vs_train.h
 TRAIN_EXPORTS = ("vs_train_prepare", "vs_train_saved_bytes", "vs_train_workspace_bytes", "vs_train_forward", "vs_train_backward",
                  "vs_mse_mask_loss_forward", "vs_mse_mask_loss_backward", "vs_train_attention_forward",
@@ -206,7 +208,7 @@ def load() -> C.CDLL:
                 "Run `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). "
                 "There is no PyTorch/CPU fallback for the scoring path." % path)
         lib = C.CDLL(path)
-        for name in EXPORTS + EVAL_EXPORTS + EVAL_DEVICE_EXPORTS + SUMMARY_EXPORTS + TRAIN_EXPORTS + SEGMENT_EXPORTS + OPTIM_EXPORTS + INSPECT_EXPORTS:
+        for name in EXPORTS + EVAL_EXPORTS + EVAL_DEVICE_EXPORTS + SUMMARY_EXPORTS + BATCH_EXPORTS + TRAIN_EXPORTS + SEGMENT_EXPORTS + OPTIM_EXPORTS + INSPECT_EXPORTS:
             if not hasattr(lib, name):
                 raise RuntimeError("libvsscore.so lacks symbol %s (stale build?)" % name)
         lib.vs_abi_version.restype = C.c_int
@@ -306,6 +308,15 @@ def load() -> C.CDLL:
         lib.vs_summarize.restype = C.c_int
         lib.vs_summarize.argtypes = ([C.c_int32] + [C.c_void_p] * 6 + [C.c_double] + [C.c_void_p] * 7
                                      + [C.c_size_t, C.c_void_p])
+        # include/vs_batch.h
+        lib.vs_batch_gather_packed.restype = C.c_int
+        lib.vs_batch_gather_packed.argtypes = ([C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 2 + [C.c_int32, C.c_int64, C.c_int32]
+                                               + [C.c_void_p] * 3)
+        lib.vs_batch_gather_padded.restype = C.c_int
+        lib.vs_batch_gather_padded.argtypes = ([C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 2 + [C.c_int32] * 3
+                                               + [C.c_float, C.c_int32] + [C.c_void_p] * 4)
+        lib.vs_batch_gather_rows.restype = C.c_int
+        lib.vs_batch_gather_rows.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         # include/vs_train.h
         lib.vs_train_prepare.restype = C.c_int
         lib.vs_train_prepare.argtypes = [C.c_void_p, C.c_void_p]

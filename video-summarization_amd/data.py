@@ -18,6 +18,11 @@ Two layers:
    batch i+1 overlapped with the kernels of batch i (side HIP stream, two device buffers) into
    ``SimNet.score_packed``.  ``val_step_from_dataset`` is ``val_step`` (``train.py:134-152``) from files to
    ``(loss, f_score, kendall, spearman)`` with that feed; a video's scores are the same bits as scoring it alone.
+
+3. **Device-resident training sets**: ``TrainSet`` / ``PretrainSet`` upload a training split once and cut every epoch's
+   shuffled batches on the device (``include/vs_batch.h``: one HIP launch per batch, one small plan upload per epoch, no
+   host synchronisation) - the same batches, in the same order, as ``DataLoader(ds, shuffle=True, ...)`` with the host
+   collates above (``epoch_plan``).
 """
 from __future__ import annotations
 
@@ -26,13 +31,14 @@ import os
 import queue
 import threading
 from pathlib import Path
-from typing import Dict, Iterator, List, Optional, Sequence, Tuple
+from typing import Dict, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from torch.nn.utils.rnn import pad_sequence
 from torch.utils.data import Dataset
 
+from . import _lib
 from .corpus import bucket_batches
 from .synth import IN_FEATURES, PAD_VALUE
 
@@ -410,3 +416,232 @@ def val_step_from_dataset(model, dataset: TSDataset, device, max_frames: int = 6
         user_dict[user.name] = user
     f_score, ktau, spr = eval_metrics(score_dict, user_dict)
     return loss / max(len(dataset), 1), f_score, ktau, spr
+
+
+# --------------------------------------------------------------------------------------------
+# device-resident training sets: the epoch's batches are cut on the GPU (include/vs_batch.h)
+# --------------------------------------------------------------------------------------------
+class EpochPlan(NamedTuple):
+    """One epoch's batches: per batch the video indices, their lengths, ``out_start`` (``[0, T_0, T_0 + T_1, ...]``, the
+    packed row offsets, ``len(batch) + 1`` entries) and ``t_max`` (the longest video: the padded width)."""
+    batches: List[List[int]]
+    lengths: List[List[int]]
+    out_start: List[List[int]]
+    t_max: List[int]
+
+
+def epoch_plan(lengths: Sequence[int], batch_size: int, shuffle: bool = True, drop_last: bool = False, generator=None) -> EpochPlan:
+    """The batches ``torch.utils.data.DataLoader(ds, shuffle=shuffle, batch_size=batch_size, drop_last=drop_last,
+    generator=generator)`` yields over a dataset of ``len(lengths)`` videos from the same generator state - the same order,
+    and the same draws consumed, so whatever draws from torch's generator afterwards (the model's dropout seeds) sees the
+    same state.  Pure host code.  The draws of one epoch, as the loader makes them:
+
+    1. the loader's base seed: one ``torch.empty((), dtype=torch.int64).random_(generator=generator)``;
+    2. ``shuffle=True`` without ``generator``: one more such draw from the default generator seeds a private generator, and
+       the order is its ``torch.randperm(n)``;
+       ``shuffle=True`` with ``generator``: the order is ``torch.randperm(n, generator=generator)`` - ``RandomSampler`` uses
+       the given generator as it is - and a second, empty-handed ``randperm`` is drawn from it when the sampler runs out
+       (here: at once; the loader draws it after its last batch, which only differs if something else draws from the same
+       generator in between);
+       ``shuffle=False``: no further draw, the order is ``0 .. n-1``.
+    """
+    n, bs = len(lengths), int(batch_size)
+    if bs < 1:
+        raise ValueError("batch_size must be >= 1, got %r" % (batch_size,))
+    lens = [int(t) for t in lengths]
+    torch.empty((), dtype=torch.int64).random_(generator=generator)                  # _BaseDataLoaderIter: _base_seed
+    if not shuffle:
+        order = list(range(n))
+    elif generator is None:
+        seed = int(torch.empty((), dtype=torch.int64).random_().item())              # RandomSampler.__iter__
+        order = torch.randperm(n, generator=torch.Generator().manual_seed(seed)).tolist()
+    else:
+        order = torch.randperm(n, generator=generator).tolist()
+        torch.randperm(n, generator=generator)                                       # ... [:num_samples % n], drawn and dropped
+    batches = [order[i: i + bs] for i in range(0, n, bs)]
+    if drop_last and batches and len(batches[-1]) < bs:
+        batches.pop()
+    blens = [[lens[v] for v in b] for b in batches]
+    starts = [[0] + np.cumsum(bl).tolist() for bl in blens]
+    return EpochPlan(batches, blens, starts, [max(bl) for bl in blens])
+
+
+class _ResidentSet:
+    """The videos' rows concatenated in device memory (``arena [N_total, d]``, ``video_start`` int64 ``[V + 1]``) and the
+    epoch iterator over them; ``TrainSet`` / ``PretrainSet`` add what travels with the rows."""
+
+    def __init__(self, features: Sequence, device):
+        device = torch.device("cuda" if device is None else device)
+        if device.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError("%s lives in the memory of a HIP device and is cut by HIP kernels: there is no CPU path "
+                               "(use the DataLoader with the host collates instead)" % type(self).__name__)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        feats = [_as_f32(f) for f in features]
+        if not feats:
+            raise ValueError("%s needs at least one video" % type(self).__name__)
+        d = int(feats[0].shape[1]) if feats[0].dim() == 2 else -1
+        for i, f in enumerate(feats):
+            if f.dim() != 2 or f.shape[1] != d or f.shape[0] < 1:
+                raise ValueError("video %d: expected features [T >= 1, %d], got %s" % (i, d, tuple(f.shape)))
+        self.device, self.d = device, d
+        self.lengths = [int(f.shape[0]) for f in feats]
+        self.video_start_host = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
+        self.arena = torch.cat(feats, dim=0).to(device)                               # the one upload of the features
+        self.video_start = torch.from_numpy(self.video_start_host).to(device)
+
+    def __len__(self) -> int:
+        return len(self.lengths)
+
+    def _upload_plan(self, plan: EpochPlan):
+        """The whole epoch's ``ids`` and ``out_start`` arrays in ONE int32 buffer ([ids_0 | out_start_0 | ids_1 | ...]),
+        copied from page-locked memory without blocking.  Returns (device buffer, element offset of each batch's ids, (the
+        stream of the copy, an event recorded behind it))."""
+        flat, offs = [], []
+        for b, s in zip(plan.batches, plan.out_start):
+            offs.append(len(flat))
+            flat.extend(b)
+            flat.extend(s)
+        host = torch.empty((max(len(flat), 1),), dtype=torch.int32, pin_memory=True)
+        host[:len(flat)] = torch.tensor(flat, dtype=torch.int32)
+        plan_dev = host.to(self.device, non_blocking=True)
+        stream = torch.cuda.current_stream(self.device)
+        ready = torch.cuda.Event()
+        ready.record(stream)
+        return plan_dev, offs, (stream, ready)
+
+    def _order_after_plan(self, plan_dev, uploaded):
+        """The plan went up on the stream that was current when ``epoch`` was called.  A batch drawn on ANOTHER stream (a
+        ``torch.cuda.stream(...)`` block around the loop body) waits on the device for that copy - no host wait - and tells
+        the allocator that the plan is in use there."""
+        stream, ready = uploaded
+        cur = torch.cuda.current_stream(self.device)
+        if cur != stream:
+            cur.wait_event(ready)
+            plan_dev.record_stream(cur)
+
+    def _gather(self, side, plan_dev, off, lengths, packed: bool, want_side: bool):
+        """One launch: the batch whose ids start at element ``off`` of ``plan_dev``.  Outputs from torch's allocator."""
+        lib = _lib.load()
+        B, rows, t_max = len(lengths), sum(lengths), max(lengths)
+        ids_ptr = plan_dev.data_ptr() + 4 * off
+        start_ptr = ids_ptr + 4 * B
+        dev = self.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if packed:
+            x = torch.empty((rows, self.d), dtype=torch.float32, device=dev)
+            y = torch.empty((rows,), dtype=torch.float32, device=dev) if want_side else None
+            _lib.check(lib.vs_batch_gather_packed(self.arena.data_ptr(), side.data_ptr() if want_side else None,
+                                                  self.video_start.data_ptr(), len(self), ids_ptr, start_ptr, B, rows, self.d,
+                                                  x.data_ptr(), y.data_ptr() if want_side else None, stream))
+            return x, y, None
+        x = torch.empty((B, t_max, self.d), dtype=torch.float32, device=dev)
+        y = torch.empty((B, t_max), dtype=torch.float32, device=dev) if want_side else None
+        mask = torch.empty((B, t_max), dtype=torch.uint8, device=dev)
+        _lib.check(lib.vs_batch_gather_padded(self.arena.data_ptr(), side.data_ptr() if want_side else None,
+                                              self.video_start.data_ptr(), len(self), ids_ptr, start_ptr, B, t_max, t_max,
+                                              float(PAD_VALUE), self.d, x.data_ptr(), y.data_ptr() if want_side else None,
+                                              mask.data_ptr(), stream))
+        return x, y, mask.view(torch.bool)
+
+    def _gather_rows(self, table, plan_dev, off, B):
+        lib = _lib.load()
+        out = torch.empty((B, table.shape[1]), dtype=torch.float32, device=self.device)
+        _lib.check(lib.vs_batch_gather_rows(table.data_ptr(), table.shape[0], plan_dev.data_ptr() + 4 * off, B, table.shape[1],
+                                            out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+        return out
+
+    def epoch(self, batch_size: int, shuffle: bool = True, drop_last: bool = False, generator=None, packed: bool = True):
+        """Iterates one epoch.  The plan (``epoch_plan``: the DataLoader's order and draws) is made and uploaded HERE, when
+        ``epoch`` is called - the point where ``iter(loader)`` and its first ``next`` draw; each ``next`` of the returned
+        iterator then enqueues one gather on the current stream and returns fresh tensors.  Nothing synchronises."""
+        plan = epoch_plan(self.lengths, batch_size, shuffle, drop_last, generator)
+        with torch.cuda.device(self.device):
+            plan_dev, offs, uploaded = self._upload_plan(plan) if plan.batches else (None, [], None)
+        return _Epoch(self._batches(plan, plan_dev, offs, uploaded, packed), plan)
+
+
+class _Epoch:
+    """The iterator ``epoch`` returns: ``len()`` is the number of batches, ``plan`` the ``EpochPlan`` behind them."""
+
+    def __init__(self, batches, plan: EpochPlan):
+        self._batches, self.plan = batches, plan
+
+    def __len__(self) -> int:
+        return len(self.plan.batches)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return next(self._batches)
+
+
+def _as_f32(a) -> torch.Tensor:
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.detach().to(device="cpu", dtype=torch.float32)
+
+
+class TrainSet(_ResidentSet):
+    """A fine-tuning train split in device memory: ``features[i] [T_i, 1024]`` and ``targets[i] [T_i]`` (arrays or tensors,
+    e.g. ``TSDataset.data`` / ``.target``) are concatenated and uploaded once.  ``epoch(...)`` yields what
+    ``DataLoader(ds, shuffle=True, batch_size=..., collate_fn=...)`` followed by ``.to(device)`` yields, batch for batch
+    and bit for bit:
+
+    - ``packed=True``: ``(feature [sum T, 1024], target [sum T], lengths)`` - ``collate_fn_train_packed``;
+    - ``packed=False``: ``(feature [B, Tmax, 1024], target [B, Tmax], mask bool [B, Tmax])`` - ``collate_fn_train`` and the
+      ``mask = feature[:, :, 0] == 1000`` of ``train.py:118`` (padding holds 1000 in every column and in the target).
+
+    HIP device only."""
+
+    def __init__(self, features: Sequence, targets: Sequence, device=None):
+        super().__init__(features, device)
+        tg = [_as_f32(t).reshape(-1) for t in targets]
+        if [int(t.numel()) for t in tg] != self.lengths:
+            raise ValueError("targets do not match the features: %r frames against %r" % ([int(t.numel()) for t in tg], self.lengths))
+        self.side = torch.cat(tg, dim=0).to(self.device)
+
+    @classmethod
+    def from_dataset(cls, dataset: TSDataset, device=None) -> "TrainSet":
+        return cls(dataset.data, dataset.target, device)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.arena, self.side, self.video_start))
+
+    def _batches(self, plan, plan_dev, offs, uploaded, packed):
+        for off, lengths in zip(offs, plan.lengths):
+            with torch.cuda.device(self.device):          # per batch: the consumer's current device is its own between them
+                self._order_after_plan(plan_dev, uploaded)
+                x, y, mask = self._gather(self.side, plan_dev, off, lengths, packed, True)
+            yield (x, y, list(lengths)) if packed else (x, y, mask)
+
+
+class PretrainSet(_ResidentSet):
+    """A pretraining set in device memory: ``features[i] [T_i, 1024]`` with ``vid_reps[i] [512]``.  ``epoch(...)`` yields
+    ``(feature [sum T, 1024], vid_rep [B, 512], lengths)`` (``collate_fn_pretrain_packed``) or, with ``packed=False``,
+    ``(feature [B, Tmax, 1024], vid_rep [B, 512], mask bool [B, Tmax])`` (``collate_fn_pretrain`` and ``pretrain.py:57``).
+    HIP device only."""
+
+    def __init__(self, features: Sequence, vid_reps: Sequence, device=None):
+        super().__init__(features, device)
+        reps = [_as_f32(r).reshape(-1) for r in vid_reps]
+        if len(reps) != len(self) or any(r.numel() != reps[0].numel() or r.numel() < 1 for r in reps):
+            raise ValueError("expected one video representation of one width per video (%d videos)" % len(self))
+        self.vid_reps = torch.stack(reps, dim=0).to(self.device)
+
+    @classmethod
+    def from_dataset(cls, dataset: PreTrainDataset, device=None) -> "PretrainSet":
+        return cls([f for f, _ in dataset.data], [r for _, r in dataset.data], device)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.arena, self.vid_reps, self.video_start))
+
+    def _batches(self, plan, plan_dev, offs, uploaded, packed):
+        for off, lengths in zip(offs, plan.lengths):
+            with torch.cuda.device(self.device):
+                self._order_after_plan(plan_dev, uploaded)
+                x, _, mask = self._gather(None, plan_dev, off, lengths, packed, False)
+                rep = self._gather_rows(self.vid_reps, plan_dev, off, len(lengths))
+            yield (x, rep, list(lengths)) if packed else (x, rep, mask)

@@ -1,6 +1,8 @@
 """Training and evaluation harness: the counterparts of the reference's ``train_step`` (``src/train.py:111-131``, on packed
 ragged batches: ``train_step_packed``), of ``pretrain.py``'s step (``src/pretrain.py:49-86``, on packed ragged batches:
-``pretrain_step_packed``) and of ``val_step`` (``src/train.py:134-152``).
+``pretrain_step_packed``) and of ``val_step`` (``src/train.py:134-152``).  ``train_epoch_resident`` / ``pretrain_epoch_resident``
+are the same epochs over a device-resident ``data.TrainSet`` / ``data.PretrainSet``: no loader, no host collate, no
+per-step ``loss.item()``.
 
 ``val_step(model, loader, device)`` keeps the reference's contract: ``loader`` yields
 ``(feature [1,T,1024], target [1,T], user)`` per video (reference ``collate_fn_test``,
@@ -22,7 +24,7 @@ import torch.nn.functional as F
 
 from .corpus import plan_shards, score_corpus
 from .evaluation import eval_metrics, eval_videos
-from .losses import mse_packed_loss
+from .losses import mse_packed_loss, mse_with_mask_loss
 
 
 def train_step_packed(model, optim, loader: Iterable, scaler, device):
@@ -66,6 +68,68 @@ def pretrain_step_packed(model, optimizer, schedular, scaler, loader: Iterable, 
             schedular.update()
         total, n = total + loss.item(), n + 1
     return total / max(n, 1)
+
+
+def _mean_of_steps(losses: torch.Tensor, n: int) -> float:
+    """The number the loader loops return: the steps' fp32 losses (ONE device-to-host copy) added in step order as Python
+    floats, divided by their count; 0.0 for an epoch without a batch."""
+    total = 0.0
+    for v in (losses.tolist() if n else []):
+        total += v
+    return total / max(n, 1)
+
+
+def train_epoch_resident(model, optim, train_set, scaler, batch_size, packed: bool = True, shuffle: bool = True,
+                         drop_last: bool = False):
+    """One fine-tuning epoch over a ``data.TrainSet``: the body of ``train_step_packed`` (``packed=False``: of the reference's
+    ``train_step`` with the padded forward and ``mse_with_mask_loss``) on batches cut on the device - the batches, order,
+    generator draws and therefore the result of ``DataLoader(ds, shuffle=shuffle, batch_size=batch_size, drop_last=drop_last)``
+    with the matching collate, bit for bit.  Each step's loss is stored in a device vector and read back once, after the
+    epoch.  Returns the mean loss over the batches."""
+    model.train()
+    batches = train_set.epoch(batch_size, shuffle=shuffle, drop_last=drop_last, packed=packed)
+    n = len(batches)
+    losses = torch.empty((n,), dtype=torch.float32, device=train_set.device)
+    for i, (feature, target, third) in enumerate(batches):
+        with torch.amp.autocast("cuda"):                                    # train.py:120
+            if packed:                                                      # third: lengths
+                pred, _ = model.forward_packed_train(feature, third)
+                loss = mse_packed_loss(pred, target, third)
+            else:                                                           # third: the padding mask of train.py:118
+                pred, _ = model(feature, third)
+                loss = mse_with_mask_loss(pred, target, third)              # train.py:122
+        optim.zero_grad()
+        scaler.scale(loss).backward()
+        scaler.step(optim)
+        scaler.update()
+        losses[i].copy_(loss.detach())
+    return _mean_of_steps(losses, n)
+
+
+def pretrain_epoch_resident(model, optimizer, schedular, scaler, pretrain_set, batch_size, packed: bool = True):
+    """One pretraining epoch over a ``data.PretrainSet``: the body of ``pretrain_step_packed`` (``packed=False``: the padded
+    ``PretrainModel.forward`` with the mask of ``pretrain.py:57``) on batches cut on the device, shuffled with
+    ``drop_last=True`` as ``pretrain.py:18-25`` builds its loader; ``schedular.update()`` after every step unless ``schedular``
+    is None.  Losses are read back once, after the epoch.  Returns the mean loss over the batches."""
+    model.train()
+    batches = pretrain_set.epoch(batch_size, shuffle=True, drop_last=True, packed=packed)
+    n = len(batches)
+    losses = torch.empty((n,), dtype=torch.float32, device=pretrain_set.device)
+    for i, (feature, vid_rep, third) in enumerate(batches):
+        with torch.amp.autocast("cuda"):                                    # pretrain.py:59
+            if packed:
+                main_loss, center_loss, repel_loss = model.forward_packed(feature, vid_rep, third)
+            else:
+                main_loss, center_loss, repel_loss = model(feature, vid_rep, third)
+            loss = main_loss + center_loss * 0.5 + 1. * repel_loss          # pretrain.py:62
+        optimizer.zero_grad()
+        scaler.scale(loss).backward()
+        scaler.step(optimizer)
+        scaler.update()
+        if schedular is not None:
+            schedular.update()
+        losses[i].copy_(loss.detach())
+    return _mean_of_steps(losses, n)
 
 
 @torch.no_grad()
