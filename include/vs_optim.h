@@ -82,6 +82,39 @@ int vs_adam_state_field(const vs_weights *w, int32_t tensor, int32_t which, size
 int vs_adam_step(vs_weights *w, const vs_model_params *params, const vs_model_grads *grads, void *state,
                  const vs_adam_cfg *cfg, const float *grad_scale, const float *found_inf, void *stream);
 
+/* ---- Clipping the global gradient norm (torch.nn.utils.clip_grad_norm_) without rewriting the gradients ----------------
+ * The Adam kernel divides every gradient by the device scalar `grad_scale`.  The calls below measure the norm of ALL
+ * gradients of a step and write, next to it, the divisor grad_scale / clip_coef: handing THAT scalar to vs_adam_step* as
+ * its grad_scale is the clipped step - one extra read of the gradients, no write.
+ *     out[0]  total norm of the unscaled gradients: sqrt(sum g^2) / grad_scale, or max |g| / grad_scale
+ *     out[1]  clip_coef = min(1, max_norm / (out[0] + 1e-6)) (torch's formula); exactly 1 when nothing is clipped
+ *     out[2]  grad_scale / clip_coef (1 / clip_coef without a scale); bit-equal to grad_scale whenever out[1] == 1
+ *     out[3]  0
+ * Squares are summed in double in a fixed order: the result is bitwise reproducible and does not depend on the grouping
+ * of the tensors into launches or on their alignment.  IEEE rules throughout (torch with error_if_nonfinite=False): an
+ * infinite norm gives clip_coef 0, a NaN norm NaN.  `grad_scale`: device scalar or NULL.  max_norm = +inf measures only.
+ * Launches: ceil(tensors / 64) + 1.  VS_ERR_INVALID (before any device access): NULL table / out / workspace, max_norm
+ * NaN or <= 0, unknown kind, n >= 2^32, workspace not 8-byte aligned.  VS_ERR_WORKSPACE: workspace too small. */
+typedef struct vs_grad_tensor { float *g; size_t n; } vs_grad_tensor;   /* g NULL or n 0: skipped; n < 2^32 */
+#define VS_GRAD_NORM_L2  0
+#define VS_GRAD_NORM_MAX 1
+
+/* host only; a non-zero multiple of 256, or 0 on invalid input (NULL table, n_tensors < 0, n >= 2^32) */
+size_t vs_grad_norm_workspace_bytes(const vs_grad_tensor *table, int32_t n_tensors);
+
+/* `table`: HOST array (read before the call returns); `out`: 4 device floats; `workspace`: device, caller-owned */
+int vs_grad_norm_tensors(const vs_grad_tensor *table, int32_t n_tensors, int32_t kind, double max_norm,
+                         const float *grad_scale, float *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The gradients of a handle: tensors in vs_model_params order with the handle's sizes, NULL gradient pointers skipped.
+ * The workspace is that of a vs_grad_tensor table with the same sizes.  Not for a handle that embeds a narrower model. */
+int vs_grad_norm(const vs_weights *w, const vs_model_grads *grads, int32_t kind, double max_norm,
+                 const float *grad_scale, float *out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* g *= *coef in place (`coef`: device scalar, e.g. out + 1); nothing is written when *coef == 1.  For a loop that keeps
+ * another optimizer: vs_grad_norm_tensors, then this. */
+int vs_grad_scale_tensors(const vs_grad_tensor *table, int32_t n_tensors, const float *coef, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ from .pretrain import PretrainModel  # noqa: F401
 from .losses import mse_packed_loss, mse_with_mask_loss  # noqa: F401
 from . import segmentation  # noqa: F401
 from . import optim  # noqa: F401
-from .optim import Adam, AdamW  # noqa: F401
+from .optim import Adam, AdamW, clip_grad_norm_, grad_norm  # noqa: F401
 from .data import PretrainSet, TrainSet, collate_fn_pretrain_packed, epoch_plan  # noqa: F401
 from .harness import pretrain_epoch_resident, pretrain_step_packed, train_epoch_resident  # noqa: F401
 from .segmentation import get_segment_fn, kts_seg, kts_seg_batch  # noqa: F401
@@ -18,5 +18,5 @@ from . import summary  # noqa: F401
 from .summary import summarize, summarize_scores  # noqa: F401
 
 __all__ = ["SimNet", "PretrainModel", "score_frames", "synth", "mse_with_mask_loss", "mse_packed_loss", "segmentation", "get_segment_fn", "kts_seg",
-           "kts_seg_batch", "optim", "Adam", "AdamW", "collate_fn_pretrain_packed", "pretrain_step_packed", "summary", "summarize",
+           "kts_seg_batch", "optim", "Adam", "AdamW", "clip_grad_norm_", "grad_norm", "collate_fn_pretrain_packed", "pretrain_step_packed", "summary", "summarize",
            "summarize_scores", "TrainSet", "PretrainSet", "epoch_plan", "train_epoch_resident", "pretrain_epoch_resident"]

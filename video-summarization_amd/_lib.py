@@ -71,10 +71,12 @@ TRAIN_EXPORTS = ("vs_train_prepare", "vs_train_saved_bytes", "vs_train_workspace
 # include/vs_segment.h (kernel temporal segmentation)
 SEGMENT_EXPORTS = ("vs_kts_workspace_bytes", "vs_kts_segment", "vs_kts_scatters")
 # include/vs_optim.h (the Adam step)
-OPTIM_EXPORTS = ("vs_adam_step_tensors", "vs_adam_state_bytes", "vs_adam_state_init", "vs_adam_state_field", "vs_adam_step")
+OPTIM_EXPORTS = ("vs_adam_step_tensors", "vs_adam_state_bytes", "vs_adam_state_init", "vs_adam_state_field", "vs_adam_step",
+                 "vs_grad_norm_workspace_bytes", "vs_grad_norm_tensors", "vs_grad_norm", "vs_grad_scale_tensors")
 # include/vs_inspect.h (attention maps on request)
 INSPECT_EXPORTS = ("vs_inspect_workspace_bytes", "vs_inspect_forward", "vs_attention_probs_workspace_bytes", "vs_attention_probs_f32")
 VS_ADAM_MAX_TENSORS = 64
+VS_GRAD_NORM_L2, VS_GRAD_NORM_MAX = 0, 1
 VS_KTS_FEATURES_F32, VS_KTS_KERNEL_F32, VS_KTS_KERNEL_F64 = 0, 1, 2
 VS_KTS_SCORES, VS_KTS_BACKTRACK, VS_KTS_AUTO = 0, 1, 2
 NUM_STAGES = 6
@@ -124,6 +126,10 @@ class AdamCfg(C.Structure):    # vs_adam_cfg (include/vs_optim.h)
 class AdamTensor(C.Structure):  # vs_adam_tensor
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("mirror", C.c_void_p),
                 ("step", C.c_void_p), ("n", C.c_size_t)]
+
+
+class GradTensor(C.Structure):  # vs_grad_tensor
+    _fields_ = [("g", C.c_void_p), ("n", C.c_size_t)]
 
 
 def hipcc_path() -> str:
@@ -449,6 +455,16 @@ def load() -> C.CDLL:
         lib.vs_adam_step.restype = C.c_int
         lib.vs_adam_step.argtypes = [C.c_void_p, C.POINTER(ModelParams), C.POINTER(ModelGrads), C.c_void_p, C.POINTER(AdamCfg),
                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.vs_grad_norm_workspace_bytes.restype = C.c_size_t
+        lib.vs_grad_norm_workspace_bytes.argtypes = [C.POINTER(GradTensor), C.c_int32]
+        lib.vs_grad_norm_tensors.restype = C.c_int
+        lib.vs_grad_norm_tensors.argtypes = [C.POINTER(GradTensor), C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.vs_grad_norm.restype = C.c_int
+        lib.vs_grad_norm.argtypes = [C.c_void_p, C.POINTER(ModelGrads), C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.vs_grad_scale_tensors.restype = C.c_int
+        lib.vs_grad_scale_tensors.argtypes = [C.POINTER(GradTensor), C.c_int32, C.c_void_p, C.c_void_p]
         # include/vs_inspect.h
         lib.vs_inspect_workspace_bytes.restype = C.c_size_t
         lib.vs_inspect_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]

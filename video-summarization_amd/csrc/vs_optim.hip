@@ -11,6 +11,10 @@
 // The step count t is read by every block of a tensor and advanced by ONE writer: the block that finishes last in the
 // launch (an agent-scope counter of blocks in `sync_word`, which that block also returns to zero).  Every other block
 // has read t before it counted itself, so there is no in-launch race and no second launch.
+//
+// Clipping the global gradient norm (further down): grad_sumsq_multi_tensor + grad_norm_finalize measure the norm of all
+// gradients and write grad_scale / clip_coef into a device scalar that adam_multi_tensor takes as its grad_scale - the
+// update kernel itself is unchanged; grad_scale_multi_tensor scales gradients in place for a loop with another optimizer.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -157,6 +161,148 @@ __global__ __launch_bounds__(NT) void adam_multi_tensor(const AdamTable tab, con
     }
 }
 
+// ---- the global gradient norm (clipping) ---------------------------------------------------------------------------
+// Same table-in-the-launch form and the same chunking as the Adam kernel.  A block reduces ONE chunk to ONE double and
+// stores it at the chunk's GLOBAL index in the caller's workspace; grad_norm_finalize, a second small launch, reduces those
+// and writes the four scalars of include/vs_optim.h.  Nothing is handed from block to block inside a launch (that would
+// need the release fence the note above prices), and because a partial depends on its chunk alone and the finalize order on
+// the chunk index alone, the norm does not depend on how the tensors were grouped into launches.
+//
+// The squares are accumulated in double from the element up: an fp32 x fp32 product is exact in double, so the only error
+// is the sum's (n 2^-53).  The element -> thread assignment is the same on the 16-byte path and on the element path, so the
+// bits do not depend on a tensor's alignment either.  fp64 FMA runs at half the fp32 VALU rate; at 4 bytes and one
+// multiply-add per element the kernel stays far below it.
+struct GradTable {
+    float *g[VS_ADAM_MAX_TENSORS];
+    unsigned n[VS_ADAM_MAX_TENSORS];
+    unsigned chunk0[VS_ADAM_MAX_TENSORS + 1];   // first block of tensor i; chunk0[count] = grid size
+    int count;
+    unsigned first;                             // global index of this launch's first chunk
+};
+
+__device__ __forceinline__ int table_find(const unsigned *chunk0, int count, unsigned blk) {
+    int lo = 0, hi = count;                     // chunk0[lo] <= blk < chunk0[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (chunk0[mid] <= blk) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// L2: a + b.  Max: the larger, a NaN wins (torch's norm propagates it; fmax would drop it).
+template <int KIND>
+__device__ __forceinline__ double norm_combine(double a, double b) {
+    if (KIND == VS_GRAD_NORM_L2) return a + b;
+    return a != a ? a : (b != b ? b : (a > b ? a : b));
+}
+
+template <int KIND>
+__device__ __forceinline__ void norm_take(double &acc, float x) {
+    const double d = (double)x;
+    if (KIND == VS_GRAD_NORM_L2) acc = fma(d, d, acc);      // d * d is exact: the same bits with or without contraction
+    else acc = norm_combine<KIND>(acc, fabs(d));
+}
+
+// lane, wave, block: a fixed order.  The result is valid in thread 0.
+template <int KIND>
+__device__ __forceinline__ double norm_block_reduce(double v, double *s_w) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = norm_combine<KIND>(v, __shfl_down(v, off, 64));
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        v = s_w[0];
+#pragma unroll
+        for (int w = 1; w < NT / 64; ++w) v = norm_combine<KIND>(v, s_w[w]);
+    }
+    return v;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(NT) void grad_sumsq_multi_tensor(const GradTable tab, double *partials) {
+    const unsigned blk = blockIdx.x;
+    const int ti = table_find(tab.chunk0, tab.count, blk);
+    const size_t base = (size_t)(blk - tab.chunk0[ti]) * CHUNK;
+    const unsigned n = tab.n[ti];
+    const unsigned len = (n - base) < (size_t)CHUNK ? (unsigned)(n - base) : CHUNK;
+    const float *g = tab.g[ti] + base;
+    const unsigned nv = len >> 2;
+    const bool vec = ((uintptr_t)g & 15u) == 0;
+    float4 G[VECS];
+#pragma unroll
+    for (int k = 0; k < VECS; ++k) {
+        const unsigned i = threadIdx.x + k * NT;
+        G[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);         // adds +0 / is never the larger: no effect on either norm
+        if (i < nv) {
+            if (vec) G[k] = reinterpret_cast<const float4 *>(g)[i];
+            else G[k] = make_float4(g[4 * i], g[4 * i + 1], g[4 * i + 2], g[4 * i + 3]);
+        }
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < VECS; ++k) {
+        norm_take<KIND>(acc, G[k].x);
+        norm_take<KIND>(acc, G[k].y);
+        norm_take<KIND>(acc, G[k].z);
+        norm_take<KIND>(acc, G[k].w);
+    }
+    if (threadIdx.x < (len & 3u)) norm_take<KIND>(acc, g[(nv << 2) + threadIdx.x]);   // the 0..3 elements behind the last vector
+    __shared__ double s_w[NT / 64];
+    acc = norm_block_reduce<KIND>(acc, s_w);
+    if (threadIdx.x == 0) partials[(size_t)tab.first + blk] = acc;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(NT) void grad_norm_finalize(const double *partials, unsigned count, double max_norm,
+                                                         const float *grad_scale, float *out) {
+    double acc = 0.0;
+    for (unsigned i = threadIdx.x; i < count; i += NT) acc = norm_combine<KIND>(acc, partials[i]);
+    __shared__ double s_w[NT / 64];
+    acc = norm_block_reduce<KIND>(acc, s_w);
+    if (threadIdx.x == 0) {
+        const float scale_f = grad_scale ? *grad_scale : 1.0f;
+        const double scale = (double)scale_f;
+        const double norm = (KIND == VS_GRAD_NORM_L2 ? sqrt(acc) : acc) / scale;
+        double coef = max_norm / (norm + 1e-6);             // torch.nn.utils.clip_grad_norm_'s formula ...
+        coef = coef < 1.0 ? coef : (coef != coef ? coef : 1.0);        // ... and its clamp(max = 1), which keeps a NaN
+        const float coef_f = (float)coef;
+        out[0] = (float)norm;
+        out[1] = coef_f;
+        out[2] = coef_f == 1.0f ? scale_f : (float)(scale / coef);     // the divisor of the Adam kernel: one rounding
+        out[3] = 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(NT) void grad_scale_multi_tensor(const GradTable tab, const float *coef) {
+    const float c = *coef;
+    if (c == 1.0f) return;                      // within the threshold: the gradients keep their bits, nothing is written
+    const unsigned blk = blockIdx.x;
+    const int ti = table_find(tab.chunk0, tab.count, blk);
+    const size_t base = (size_t)(blk - tab.chunk0[ti]) * CHUNK;
+    const unsigned n = tab.n[ti];
+    const unsigned len = (n - base) < (size_t)CHUNK ? (unsigned)(n - base) : CHUNK;
+    float *g = tab.g[ti] + base;
+    if (((uintptr_t)g & 15u) == 0) {
+        float4 *g4 = reinterpret_cast<float4 *>(g);
+        const unsigned nv = len >> 2;
+        float4 G[VECS];
+#pragma unroll
+        for (int k = 0; k < VECS; ++k) {
+            const unsigned i = threadIdx.x + k * NT;
+            if (i < nv) G[k] = g4[i];
+        }
+#pragma unroll
+        for (int k = 0; k < VECS; ++k) {
+            const unsigned i = threadIdx.x + k * NT;
+            if (i < nv) g4[i] = make_float4(G[k].x * c, G[k].y * c, G[k].z * c, G[k].w * c);
+        }
+        const unsigned i = (nv << 2) + threadIdx.x;
+        if (threadIdx.x < (len & 3u)) g[i] = g[i] * c;
+    } else {
+        for (unsigned i = threadIdx.x; i < len; i += NT) g[i] = g[i] * c;
+    }
+}
+
 int failf(int code, const char *fmt, ...) {
     char buf[384];
     va_list ap;
@@ -218,6 +364,88 @@ struct Launcher {
         tab.count = 0;
     }
 };
+
+// the same for the gradient-only kernels: norm partials (partials != NULL) or the in-place scale (coef != NULL)
+struct GradLauncher {
+    GradTable tab;
+    int kind;
+    double *partials;
+    const float *coef;
+    hipStream_t st;
+    hipError_t err = hipSuccess;
+
+    GradLauncher(int kind_, double *partials_, const float *coef_, void *stream)
+        : kind(kind_), partials(partials_), coef(coef_), st((hipStream_t)stream) {
+        tab.count = 0;
+        tab.chunk0[0] = 0;
+        tab.first = 0;
+    }
+    void add(float *g, size_t n) {
+        if (!g || n == 0) return;
+        if (tab.count == VS_ADAM_MAX_TENSORS) flush();
+        const int i = tab.count++;
+        tab.g[i] = g;
+        tab.n[i] = (unsigned)n;
+        tab.chunk0[i + 1] = tab.chunk0[i] + (unsigned)((n + CHUNK - 1) / CHUNK);
+    }
+    void flush() {
+        if (tab.count > 0 && err == hipSuccess) {
+            const dim3 grid(tab.chunk0[tab.count]), block(NT);
+            if (coef) hipLaunchKernelGGL(grad_scale_multi_tensor, grid, block, 0, st, tab, coef);
+            else if (kind == VS_GRAD_NORM_L2) hipLaunchKernelGGL(grad_sumsq_multi_tensor<VS_GRAD_NORM_L2>, grid, block, 0, st, tab, partials);
+            else hipLaunchKernelGGL(grad_sumsq_multi_tensor<VS_GRAD_NORM_MAX>, grid, block, 0, st, tab, partials);
+            err = hipGetLastError();
+        }
+        tab.first += tab.chunk0[tab.count];
+        tab.count = 0;
+    }
+    unsigned chunks() const { return tab.first + tab.chunk0[tab.count]; }
+};
+
+constexpr size_t GRAD_MAX_CHUNKS = (size_t)1 << 31;
+
+size_t grad_ws_bytes(size_t chunks) { return ((chunks > 0 ? chunks : 1) * sizeof(double) + 255) / 256 * 256; }
+
+// chunks of a table; (size_t)-1 when an entry is invalid
+size_t grad_table_chunks(const vs_grad_tensor *table, int32_t n_tensors, const char *who, bool report) {
+    size_t chunks = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        const vs_grad_tensor &t = table[i];
+        if (!t.g || t.n == 0) continue;
+        if (t.n >= ((size_t)1 << 32)) {
+            if (report) failf(VS_ERR_INVALID, "%s: tensor %d has %zu elements (< 2^32)", who, i, t.n);
+            return (size_t)-1;
+        }
+        chunks += (t.n + CHUNK - 1) / CHUNK;
+    }
+    if (chunks >= GRAD_MAX_CHUNKS) {
+        if (report) failf(VS_ERR_INVALID, "%s: %zu chunks of %u elements (< 2^31)", who, chunks, CHUNK);
+        return (size_t)-1;
+    }
+    return chunks;
+}
+
+int check_norm_args(const char *who, int32_t kind, double max_norm, const float *out, const void *workspace) {
+    if (!out) return failf(VS_ERR_INVALID, "%s: out is NULL", who);
+    if (!workspace) return failf(VS_ERR_INVALID, "%s: workspace is NULL", who);
+    if ((uintptr_t)workspace & 7u) return failf(VS_ERR_INVALID, "%s: workspace must be 8-byte aligned", who);
+    if (kind != VS_GRAD_NORM_L2 && kind != VS_GRAD_NORM_MAX) return failf(VS_ERR_INVALID, "%s: kind=%d (0 L2, 1 max)", who, kind);
+    if (!(max_norm > 0.0)) return failf(VS_ERR_INVALID, "%s: max_norm=%g invalid (> 0; +inf measures only)", who, max_norm);
+    return VS_OK;
+}
+
+int norm_finish(GradLauncher &ln, int32_t kind, double max_norm, const float *grad_scale, float *out) {
+    ln.flush();
+    if (ln.err == hipSuccess) {
+        if (kind == VS_GRAD_NORM_L2)
+            hipLaunchKernelGGL(grad_norm_finalize<VS_GRAD_NORM_L2>, dim3(1), dim3(NT), 0, ln.st, ln.partials, ln.chunks(), max_norm, grad_scale, out);
+        else
+            hipLaunchKernelGGL(grad_norm_finalize<VS_GRAD_NORM_MAX>, dim3(1), dim3(NT), 0, ln.st, ln.partials, ln.chunks(), max_norm, grad_scale, out);
+        ln.err = hipGetLastError();
+    }
+    if (ln.err != hipSuccess) return failf(VS_ERR_HIP, "grad norm launch failed: %s", hipGetErrorString(ln.err));
+    return VS_OK;
+}
 
 // ---- state of a handle: [sync word | 256 B] [step counts] [m of every tensor] [v of every tensor], 256-byte granules ----
 struct HandleTensor { size_t blob_off, n; };
@@ -377,6 +605,64 @@ int vs_adam_step(vs_weights *w, const vs_model_params *params, const vs_model_gr
     ++w->version;        // as vs_weights_update: every image family and the transposes are rebuilt on their next use
     vsw_mark(w, stream);
     if (ln.err != hipSuccess) return failf(VS_ERR_HIP, "adam launch failed: %s", hipGetErrorString(ln.err));
+    return VS_OK;
+}
+
+size_t vs_grad_norm_workspace_bytes(const vs_grad_tensor *table, int32_t n_tensors) {
+    if (n_tensors < 0 || !table) return 0;
+    const size_t chunks = grad_table_chunks(table, n_tensors, "vs_grad_norm_workspace_bytes", false);
+    return chunks == (size_t)-1 ? 0 : grad_ws_bytes(chunks);
+}
+
+int vs_grad_norm_tensors(const vs_grad_tensor *table, int32_t n_tensors, int32_t kind, double max_norm,
+                         const float *grad_scale, float *out, void *workspace, size_t workspace_bytes, void *stream) {
+    if (n_tensors < 0) return failf(VS_ERR_INVALID, "vs_grad_norm_tensors: n_tensors=%d", n_tensors);
+    if (!table) return failf(VS_ERR_INVALID, "vs_grad_norm_tensors: table is NULL");
+    if (int rc = check_norm_args("vs_grad_norm_tensors", kind, max_norm, out, workspace)) return rc;
+    const size_t chunks = grad_table_chunks(table, n_tensors, "vs_grad_norm_tensors", true);
+    if (chunks == (size_t)-1) return VS_ERR_INVALID;
+    if (workspace_bytes < grad_ws_bytes(chunks))
+        return failf(VS_ERR_WORKSPACE, "vs_grad_norm_tensors: workspace %zu bytes < %zu needed", workspace_bytes, grad_ws_bytes(chunks));
+    GradLauncher ln(kind, (double *)workspace, nullptr, stream);
+    for (int i = 0; i < n_tensors; ++i) ln.add(table[i].g, table[i].n);
+    return norm_finish(ln, kind, max_norm, grad_scale, out);
+}
+
+int vs_grad_norm(const vs_weights *w, const vs_model_grads *grads, int32_t kind, double max_norm, const float *grad_scale,
+                 float *out, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!w || !grads) return failf(VS_ERR_INVALID, "vs_grad_norm: weights/grads is NULL");
+    if (int rc = check_norm_args("vs_grad_norm", kind, max_norm, out, workspace)) return rc;
+    if (w->embedded())
+        return failf(VS_ERR_INVALID, "vs_grad_norm: the handle embeds a d_model=%d model in d_model=%d; use vs_grad_norm_tensors on the "
+                                     "caller's tensors", w->dn(), w->desc.d_model);
+    const int L = w->desc.num_layers, nt = handle_tensor_count(w);
+    if (L > 0 && !grads->layers) return failf(VS_ERR_INVALID, "vs_grad_norm: layers is NULL");
+    auto grad_of = [&](int i) -> float * {
+        if (i == 0) return grads->embed_w;
+        if (i == 1) return grads->embed_b;
+        if (i == 2 + 16 * L) return grads->final_w;
+        if (i == 3 + 16 * L) return grads->final_b;
+        return *layer_field(grads->layers[(i - 2) / 16], (i - 2) % 16);
+    };
+    size_t chunks = 0;
+    for (int i = 0; i < nt; ++i)
+        if (grad_of(i)) chunks += (handle_tensor(w, i).n + CHUNK - 1) / CHUNK;
+    if (workspace_bytes < grad_ws_bytes(chunks))
+        return failf(VS_ERR_WORKSPACE, "vs_grad_norm: workspace %zu bytes < %zu needed", workspace_bytes, grad_ws_bytes(chunks));
+    GradLauncher ln(kind, (double *)workspace, nullptr, stream);
+    for (int i = 0; i < nt; ++i) ln.add(grad_of(i), handle_tensor(w, i).n);
+    return norm_finish(ln, kind, max_norm, grad_scale, out);
+}
+
+int vs_grad_scale_tensors(const vs_grad_tensor *table, int32_t n_tensors, const float *coef, void *stream) {
+    if (n_tensors < 0) return failf(VS_ERR_INVALID, "vs_grad_scale_tensors: n_tensors=%d", n_tensors);
+    if (!table) return failf(VS_ERR_INVALID, "vs_grad_scale_tensors: table is NULL");
+    if (!coef) return failf(VS_ERR_INVALID, "vs_grad_scale_tensors: coef is NULL");
+    if (grad_table_chunks(table, n_tensors, "vs_grad_scale_tensors", true) == (size_t)-1) return VS_ERR_INVALID;
+    GradLauncher ln(VS_GRAD_NORM_L2, nullptr, coef, stream);
+    for (int i = 0; i < n_tensors; ++i) ln.add(table[i].g, table[i].n);
+    ln.flush();
+    if (ln.err != hipSuccess) return failf(VS_ERR_HIP, "grad scale launch failed: %s", hipGetErrorString(ln.err));
     return VS_OK;
 }
 

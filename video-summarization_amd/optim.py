@@ -17,10 +17,16 @@ on its next forward as it does after ``torch.optim.Adam``.
 State lives under torch's own keys (``step`` - a device fp32 scalar, as torch's fused / capturable form keeps it -
 ``exp_avg``, ``exp_avg_sq``), so ``state_dict()`` loads into ``torch.optim.Adam`` and the other way round.  There is
 no CPU path and no fallback to torch inside this class.
+
+Clipping the global gradient norm: ``Adam(..., max_grad_norm=1.0)`` measures the norm of every gradient of the step on
+the device (``vs_grad_norm_tensors``: squares summed in double) and hands ``grad_scale / clip_coef`` to the update kernel
+as its divisor - one extra read of the gradients, no write, nothing read by the host.  ``clip_grad_norm_`` / ``grad_norm``
+are the same kernels for a loop that keeps another optimizer.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, List, Optional
 
 import torch
@@ -30,7 +36,7 @@ from torch.optim import Optimizer
 from . import _lib
 from .simnet import SimNet
 
-__all__ = ["Adam", "AdamW"]
+__all__ = ["Adam", "AdamW", "clip_grad_norm_", "grad_norm"]
 
 
 def _pad64(n: int) -> int:
@@ -39,6 +45,116 @@ def _pad64(n: int) -> int:
 
 def _module_key(module: SimNet, device: torch.device):
     return (device,) + tuple((t.data_ptr(), t._version) for t in module._tensors())
+
+
+def _check_max_norm(max_norm) -> float:
+    if isinstance(max_norm, Tensor) or isinstance(max_norm, bool):
+        raise ValueError("max_norm must be a Python float (it is passed to the kernel with the launch), got %r" % (type(max_norm).__name__,))
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:
+        raise ValueError("Invalid max_norm: %r (> 0; float('inf') measures without clipping)" % (max_norm,))
+    return max_norm
+
+
+def _norm_kind(norm_type) -> int:
+    if not isinstance(norm_type, Tensor) and not isinstance(norm_type, (bool, str)):
+        try:
+            t = float(norm_type)
+        except (TypeError, ValueError):
+            t = None
+        if t == 2.0:
+            return _lib.VS_GRAD_NORM_L2
+        if t == math.inf:
+            return _lib.VS_GRAD_NORM_MAX
+    raise ValueError("norm_type %r is not implemented by the HIP kernel: 2.0 or float('inf')" % (norm_type,))
+
+
+class _ClipBuffers:
+    """The persistent device buffers of a clipping optimizer: the four result scalars and the per-chunk partials."""
+
+    def __init__(self, dev: torch.device):
+        self.dev = dev
+        self.out = torch.zeros((4,), dtype=torch.float32, device=dev)
+        self.ws: Optional[Tensor] = None
+        self.table = (_lib.GradTensor * 1)()
+
+    def measure(self, lib, grads, kind: int, max_norm: float, grad_scale: Optional[Tensor], stream) -> Tensor:
+        if len(grads) > len(self.table):
+            self.table = (_lib.GradTensor * len(grads))()
+        for e, g in zip(self.table, grads):
+            e.g, e.n = g.data_ptr(), g.numel()
+        need = lib.vs_grad_norm_workspace_bytes(self.table, len(grads))
+        if need == 0:
+            raise RuntimeError("a gradient has 2^32 elements or more")
+        if self.ws is None or self.ws.numel() < need:
+            self.ws = torch.empty((need,), dtype=torch.uint8, device=self.dev)
+        _lib.check(lib.vs_grad_norm_tensors(self.table, len(grads), kind, max_norm, None if grad_scale is None else grad_scale.data_ptr(),
+                                            self.out.data_ptr(), self.ws.data_ptr(), self.ws.numel(), stream))
+        return self.out
+
+
+def _dense_grads(parameters, who: str):
+    """the gradients of ``parameters`` for the free functions: HIP, fp32, dense, contiguous - or RuntimeError"""
+    if isinstance(parameters, Tensor):
+        parameters = [parameters]
+    grads, dev = [], None
+    for p in parameters:
+        g = p.grad
+        if g is None:
+            continue
+        if not p.is_cuda or not g.is_cuda:
+            raise RuntimeError("%s runs on the MI355X HIP kernel only: parameter of shape %s is on %s (there is no CPU path; use "
+                               "torch.nn.utils for CPU tensors)" % (who, tuple(p.shape), p.device))
+        if g.is_sparse:
+            raise RuntimeError("%s (HIP kernel) takes dense gradients, got a sparse one for a parameter of shape %s" % (who, tuple(p.shape)))
+        if g.dtype != torch.float32:
+            raise RuntimeError("%s (HIP kernel) takes fp32 gradients, got %s" % (who, g.dtype))
+        if not g.is_contiguous():
+            raise RuntimeError("%s (HIP kernel): the gradient of a parameter of shape %s is not contiguous - scaling a copy in place "
+                               "would silently leave it unclipped; make it contiguous first" % (who, tuple(p.shape)))
+        if dev is not None and g.device != dev:
+            raise RuntimeError("%s: gradients on %s and %s - one global norm needs one device" % (who, dev, g.device))
+        dev = g.device
+        grads.append(g)
+    return grads, dev
+
+
+def _measure(parameters, max_norm: float, norm_type, who: str):
+    kind = _norm_kind(norm_type)
+    grads, dev = _dense_grads(parameters, who)
+    if dev is None:
+        return None, None, None
+    lib = _lib.load()
+    buf = _ClipBuffers(dev)
+    with torch.cuda.device(dev):
+        out = buf.measure(lib, grads, kind, max_norm, None, torch.cuda.current_stream(dev).cuda_stream)
+    return out, buf, len(grads)
+
+
+@torch.no_grad()
+def grad_norm(parameters, norm_type=2.0) -> Tensor:
+    """``torch.nn.utils.get_total_norm`` of the gradients of ``parameters`` on the HIP kernel: the 0-dim fp32 device norm.
+    Nothing is read by the host."""
+    out, _, _ = _measure(parameters, math.inf, norm_type, "grad_norm")
+    return torch.zeros(()) if out is None else out[0]
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None) -> Tensor:
+    """``torch.nn.utils.clip_grad_norm_`` on the HIP kernels: norm launches (squares summed in double), one finalize, one
+    in-place scale that writes nothing when the norm is within ``max_norm``.  Returns the 0-dim fp32 device norm; the host
+    reads nothing, which is why ``error_if_nonfinite=True`` is refused.  ``foreach`` is accepted and has no meaning here.
+    With this library's ``Adam`` prefer ``Adam(max_grad_norm=...)``: it does not rewrite the gradients at all."""
+    if error_if_nonfinite:
+        raise ValueError("clip_grad_norm_(error_if_nonfinite=True) would read the norm on the host (a synchronisation): test the returned "
+                         "device tensor yourself, or use torch.nn.utils.clip_grad_norm_")
+    max_norm = _check_max_norm(max_norm)
+    out, buf, n = _measure(parameters, max_norm, norm_type, "clip_grad_norm_")
+    if out is None:
+        return torch.zeros(())
+    with torch.cuda.device(buf.dev):
+        _lib.check(_lib.load().vs_grad_scale_tensors(buf.table, n, out.data_ptr() + 4, torch.cuda.current_stream(buf.dev).cuda_stream))
+    return out[0]
 
 
 class _ModulePart:
@@ -77,12 +193,22 @@ class _GroupPlan:
 class Adam(Optimizer):
     """``torch.optim.Adam`` on the HIP multi-tensor kernel.  Same constructor; ``amsgrad``, ``maximize`` and
     ``differentiable`` are refused (not ignored); ``foreach`` / ``fused`` / ``capturable`` are accepted and have no
-    meaning here (the step is always one fused launch, the step count always a device tensor).  ``model=``: see ``attach``."""
+    meaning here (the step is always one fused launch, the step count always a device tensor).  ``model=``: see ``attach``.
+
+    ``max_grad_norm`` (keyword only, default None: off) clips the global norm of ALL gradients of a step, across every
+    param group, as ``torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm, grad_norm_type)`` before the
+    step would - inside ``step()``, with or without a ``GradScaler`` (before or after ``unscale_``), without rewriting
+    the gradients and without a host read.  ``grad_norm_type`` is 2.0 or ``inf``.  Both are attributes of the optimizer
+    (``optim.max_grad_norm`` may be rewritten between steps) and are NOT part of ``defaults`` / ``param_groups``: the key
+    set of ``state_dict()`` stays ``torch.optim.Adam``'s, so a checkpoint does not carry them - pass them again when the
+    optimizer is rebuilt.  After a clipped step ``optim.last_grad_norm`` is the 0-dim device tensor of the measured norm
+    (of the unscaled gradients), valid until the next step."""
 
     _step_supports_amp_scaling = True       # GradScaler.step: hand over grad_scale / found_inf, do not unscale or sync
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
-                 maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False, model=None):
+                 maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False, model=None,
+                 max_grad_norm=None, grad_norm_type=2.0):
         if amsgrad:
             raise ValueError("Adam(amsgrad=True) is not implemented by the HIP kernel (use torch.optim.Adam for it)")
         if maximize:
@@ -99,6 +225,9 @@ class Adam(Optimizer):
             raise ValueError("Invalid beta parameters: %r" % (betas,))
         if not 0.0 <= weight_decay:
             raise ValueError("Invalid weight_decay value: %r" % (weight_decay,))
+        if max_grad_norm is not None:
+            _check_max_norm(max_grad_norm)
+        _norm_kind(grad_norm_type)
         # the key set of torch.optim.Adam's groups, so a state_dict moves between the two classes
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=foreach,
                         capturable=True, differentiable=False, fused=fused, decoupled_weight_decay=bool(decoupled_weight_decay))
@@ -107,6 +236,10 @@ class Adam(Optimizer):
         self._plans: Dict[int, _GroupPlan] = {}
         self._module_state: Dict[SimNet, Tensor] = {}     # one vs_adam_state buffer per attached module
         self._sync_word: Optional[Tensor] = None
+        self.max_grad_norm = max_grad_norm
+        self.grad_norm_type = grad_norm_type
+        self.last_grad_norm: Optional[Tensor] = None
+        self._clip: Optional[_ClipBuffers] = None
         if model is not None:
             self.attach(model)
 
@@ -125,6 +258,10 @@ class Adam(Optimizer):
         self.__dict__.setdefault("_modules", [])
         self.__dict__.setdefault("_module_state", {})
         self.__dict__.setdefault("_sync_word", None)
+        self.__dict__.setdefault("max_grad_norm", None)
+        self.__dict__.setdefault("grad_norm_type", 2.0)
+        self.__dict__.setdefault("last_grad_norm", None)
+        self._clip = None
         self._plans = {}
 
     def load_state_dict(self, state_dict):
@@ -214,6 +351,53 @@ class Adam(Optimizer):
             plan.live.add(id(p))
         return plan
 
+    def _plan_of(self, gi: int, group) -> _GroupPlan:
+        plan = self._plans.get(gi)
+        if plan is None or plan.key != tuple(id(p) for p in group["params"]):
+            dev = self._device_of(group)          # every parameter: HIP device, fp32, contiguous (raises otherwise)
+            with torch.cuda.device(dev):
+                plan = self._plans[gi] = self._build_plan(gi, group, dev)
+            plan.dev = dev
+        return plan
+
+    # ---- clipping: the norm of every gradient of the step, and the divisor the update kernel takes ------------------
+    def _clip_divisor(self, lib, grad_scale, pre) -> int:
+        """Issues the norm launches over the gradients of ALL groups and returns the device address of
+        ``grad_scale / clip_coef``.  ``pre``: id(parameter) -> the (contiguous) gradient the step will read."""
+        max_norm = _check_max_norm(self.max_grad_norm)
+        kind = _norm_kind(self.grad_norm_type)
+        dev, grads = None, []
+        for gi, group in enumerate(self.param_groups):
+            if not group["params"]:
+                continue
+            plan = self._plan_of(gi, group)
+            if dev is not None and plan.dev != dev:
+                raise RuntimeError("Adam(max_grad_norm=...): the param groups are on %s and %s - one global norm needs one device"
+                                   % (dev, plan.dev))
+            dev = plan.dev
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if not p.is_cuda or p.dtype is not torch.float32:
+                    self._device_of(group)              # moved or cast since the plan was built: raises with the reason
+                if g.is_sparse:
+                    raise RuntimeError("Adam (HIP kernel) takes dense gradients, got a sparse one for a parameter of shape %s" % (tuple(p.shape),))
+                if not g.is_contiguous():
+                    g = g.contiguous()
+                pre[id(p)] = g
+                grads.append(g)
+        if dev is None:
+            raise RuntimeError("Adam(max_grad_norm=...): the optimizer has no parameters")
+        if grad_scale is not None and (grad_scale.device != dev or grad_scale.dtype != torch.float32):
+            raise RuntimeError("grad_scale / found_inf must be fp32 scalars on %s, got %s on %s" % (dev, grad_scale.dtype, grad_scale.device))
+        if self._clip is None or self._clip.dev != dev:
+            self._clip = _ClipBuffers(dev)
+        with torch.cuda.device(dev):
+            out = self._clip.measure(lib, grads, kind, max_norm, grad_scale, torch.cuda.current_stream(dev).cuda_stream)
+        self.last_grad_norm = out[0]
+        return out.data_ptr() + 8
+
     # ---- the step -----------------------------------------------------------------------------
     @torch.no_grad()
     def step(self, closure=None):
@@ -226,16 +410,13 @@ class Adam(Optimizer):
         found_inf = getattr(self, "found_inf", None)
         current = {}            # attached module -> its pack-cache key if the cache is current (write-through), else None
         touched = []
+        pre = {}                # clipping: id(parameter) -> the gradient that was measured (the one the kernel then reads)
+        divisor = self._clip_divisor(lib, grad_scale, pre) if self.max_grad_norm is not None else None
         for gi, group in enumerate(self.param_groups):
             params = group["params"]
             if not params:
                 continue
-            plan = self._plans.get(gi)
-            if plan is None or plan.key != tuple(id(p) for p in params):
-                dev = self._device_of(group)          # every parameter: HIP device, fp32, contiguous (raises otherwise)
-                with torch.cuda.device(dev):
-                    plan = self._plans[gi] = self._build_plan(gi, group, dev)
-                plan.dev = dev
+            plan = self._plan_of(gi, group)
             dev = plan.dev
             for t in (grad_scale, found_inf):
                 if t is not None and (t.device != dev or t.dtype != torch.float32):
@@ -244,6 +425,8 @@ class Adam(Optimizer):
             cfg = _lib.AdamCfg(float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
                                1 if group.get("decoupled_weight_decay", False) else 0, 0)
             gs, fi = (None if grad_scale is None else grad_scale.data_ptr()), (None if found_inf is None else found_inf.data_ptr())
+            if divisor is not None:
+                gs = divisor        # grad_scale / clip_coef: the kernel's division unscales and clips at once
             state, views, live, hold, f32 = self.state, plan.views, plan.live, [], torch.float32
 
             def grad_ptr(p):
@@ -251,13 +434,16 @@ class Adam(Optimizer):
                 g = p.grad
                 if g is None:
                     return None
-                if not p.is_cuda or p.dtype is not f32:
-                    self._device_of(group)              # moved or cast since the plan was built: raises with the reason
-                if g.is_sparse:
-                    raise RuntimeError("Adam (HIP kernel) takes dense gradients, got a sparse one for a parameter of shape %s" % (tuple(p.shape),))
-                if not g.is_contiguous():
-                    g = g.contiguous()
-                    hold.append(g)
+                if id(p) in pre:
+                    g = pre[id(p)]                      # checked (and made contiguous) when the norm was measured
+                else:
+                    if not p.is_cuda or p.dtype is not f32:
+                        self._device_of(group)              # moved or cast since the plan was built: raises with the reason
+                    if g.is_sparse:
+                        raise RuntimeError("Adam (HIP kernel) takes dense gradients, got a sparse one for a parameter of shape %s" % (tuple(p.shape),))
+                    if not g.is_contiguous():
+                        g = g.contiguous()
+                        hold.append(g)
                 if id(p) not in live:           # first gradient of this parameter: its state becomes visible, as in torch
                     s, m, v = views[p]
                     state[p] = {"step": s, "exp_avg": m, "exp_avg_sq": v}
@@ -316,6 +502,8 @@ class AdamW(Adam):
     """``torch.optim.AdamW``: decoupled weight decay (``p *= 1 - lr * weight_decay`` before the update), default 1e-2."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, foreach=None,
-                 maximize=False, capturable=False, differentiable=False, fused=None, model=None):
+                 maximize=False, capturable=False, differentiable=False, fused=None, model=None, max_grad_norm=None,
+                 grad_norm_type=2.0):
         super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
-                         differentiable=differentiable, fused=fused, decoupled_weight_decay=True, model=model)
+                         differentiable=differentiable, fused=fused, decoupled_weight_decay=True, model=model,
+                         max_grad_norm=max_grad_norm, grad_norm_type=grad_norm_type)
