@@ -64,6 +64,12 @@ typedef struct vs_dropout_cfg {
  * kernels are bf16-only: this mode runs the tiled GEMMs everywhere. */
 #define VS_TRAIN_FLAG_FP16 4u
 #define VS_TRAIN_FLAG_FP16_ALL (VS_TRAIN_FLAG_BF16 | VS_TRAIN_FLAG_FP16)
+/* Read by the PACKED calls only (vs_train_forward_packed / _backward_packed; padded calls ignore it): together with
+ * VS_TRAIN_FLAG_BF16_ATTENTION (and VS_TRAIN_FLAG_FP16) the packed attention runs on the 16-bit matrix pipe as well - head dim
+ * 32 / 64 / 128, above VS_TRAIN_LP_MIN_ROWS packed frames.  Without this bit a packed call accepts and ignores
+ * VS_TRAIN_FLAG_BF16_ATTENTION (its attention is exact fp32), as it always has.  q / k / v, dO and dq | dk | dv stay
+ * fp32-stored on the packed path; record and workspace sizes do not depend on the bit. */
+#define VS_TRAIN_FLAG_PACKED_LP_ATTENTION 8u
 
 /* Gradient destinations: the mirror of vs_layer_params / vs_model_params (nn.Linear layout [out, in]); every
  * pointer is a device buffer of the parameter's shape that the backward OVERWRITES (it does not accumulate). */
@@ -124,7 +130,10 @@ int vs_train_backward(vs_weights *w, const float *x, const uint8_t *key_pad_mask
  * Dropout: the row dropouts hash (seed, site, packed row, column); the attention weights hash (seed, site, head * Mtot +
  * packed row of the query, key index within the video).
  * Low precision: VS_TRAIN_FLAG_BF16_LINEAR (and VS_TRAIN_FLAG_FP16) apply as in the padded form, counted on Mtot rows; the
- * packed attention is exact fp32 - VS_TRAIN_FLAG_BF16_ATTENTION is accepted and ignored.
+ * packed attention is exact fp32 - VS_TRAIN_FLAG_BF16_ATTENTION alone is accepted and ignored - unless
+ * VS_TRAIN_FLAG_PACKED_LP_ATTENTION is set with it: then the attention products run on the bf16 / fp16 pipe too (head dim
+ * 32 / 64 / 128, Mtot above VS_TRAIN_LP_MIN_ROWS; vs_train_last_format() reports bit 1), from fp32-stored q / k / v and dO.  A
+ * video's attention bits are then those of the padded 16-bit kernels running that video alone (dropout off).
  * VS_ERR_INVALID: lengths[b] <= 0, a length above the positional table (each video starts at position 0, so max(lengths)
  * is what the table bounds, not Mtot), NULL lengths / lengths_dev.  (There is no class-token form of the training path.) */
 int vs_train_check_packed(const vs_model_desc *desc, const int32_t *lengths, int32_t B);      /* the checks above, from a description alone */
@@ -237,7 +246,8 @@ int vs_train_attention_dropout_bits(void *dbits, int32_t B, int32_t H, int32_t T
 /* vs_train_attention_forward / _backward on the bf16 matrix pipe (VS_TRAIN_FLAG_BF16_ATTENTION); dh in {32, 64, 128}; p > 0 needs
  * dbits (from vs_train_attention_dropout_bits with the same seed / site / p).  in16 != 0: q, k, v point to bf16 [B,H,T,dh]
  * planes, q already multiplied by scale * log2(e) - what the training forward stores when both low-precision flags are set
- * (results are bit-identical to the fp32-stored form, whose values the kernels round to the same bf16). */
+ * (results are bit-identical to the fp32-stored form, whose values the kernels round to the same bf16).  in16 & 64: the 16-bit
+ * type is IEEE fp16 (VS_TRAIN_FLAG_FP16's kernels) - operands, stored planes and the dO that enters delta. */
 int vs_train_attention_forward_bf16(const float *q, const float *k, const float *v, const uint8_t *key_pad_mask, float *out,
                                     float *lse2, int32_t B, int32_t H, int32_t T, int32_t dh, float scale, float p,
                                     const void *dbits, int32_t in16, void *stream);
@@ -258,6 +268,21 @@ int vs_train_attention_backward_packed(const float *q, const float *k, const flo
                                        const float *lse2, float *dqkv, const int32_t *lengths, const int32_t *lengths_dev,
                                        int32_t B, int32_t H, int32_t dh, float scale, uint64_t seed, uint32_t site, float p,
                                        void *scratch, size_t scratch_bytes, void *stream);
+/* The same two calls on the bf16 (f16 != 0: fp16) matrix pipe - the kernels of VS_TRAIN_FLAG_PACKED_LP_ATTENTION: dh in {32, 64,
+ * 128}, q / k / v / d_out / dqkv fp32 as above.  scratch >= vs_train_attention_packed_lp_scratch_bytes (256-byte aligned) holds the
+ * device plan, delta [H, Mtot] and both bit-packed copies of the keep words (2 * H * sum T_b * ceil(T_b / 32) words), which each call
+ * fills itself from (seed, site, p) - the decisions of vs_train_dropout_mask_attention_packed.  Checked before any device
+ * access: VS_ERR_INVALID for a NULL pointer, H <= 0, dh outside {32, 64, 128}, p outside [0, 1), NULL lengths, B <= 0 or a
+ * length <= 0; VS_ERR_WORKSPACE for a short or unaligned scratch.  The byte count is 0 on invalid input. */
+size_t vs_train_attention_packed_lp_scratch_bytes(const int32_t *lengths, int32_t B, int32_t H);
+int vs_train_attention_forward_packed_lp(const float *q, const float *k, const float *v, float *out, float *lse2,
+                                         const int32_t *lengths, const int32_t *lengths_dev, int32_t B, int32_t H, int32_t dh,
+                                         float scale, uint64_t seed, uint32_t site, float p, int32_t f16, void *scratch,
+                                         size_t scratch_bytes, void *stream);
+int vs_train_attention_backward_packed_lp(const float *q, const float *k, const float *v, const float *out, const float *d_out,
+                                          const float *lse2, float *dqkv, const int32_t *lengths, const int32_t *lengths_dev,
+                                          int32_t B, int32_t H, int32_t dh, float scale, uint64_t seed, uint32_t site, float p,
+                                          int32_t f16, void *scratch, size_t scratch_bytes, void *stream);
 /* keep masks of a packed batch's attention-weight dropout, exactly as those kernels (and the bit-packed copies of the full
  * path) draw them: video after video, [H, T_b, T_b] bytes each - H * sum T_b^2 bytes in all. */
 int vs_train_dropout_mask_attention_packed(uint8_t *keep, const int32_t *lengths, int32_t B, int32_t H, uint64_t seed,

@@ -8,7 +8,8 @@ and the loss head alone (``_PretrainHeadPacked`` against ``_PretrainHead`` on ra
 Batches: 64 videos of ``synth.corpus_lengths(64, seed)`` (100 to 650 frames) and the reference's B = 4 with
 ``synth.corpus_lengths(4, seed)``.  Models: A = M-A (H4 / d256 / L4), P = the ``pretrain.py`` default (H8 / d512 / L3).
 ``--dtypes``: exact fp32 and ``set_train_dtype("bf16")`` of the encoder (the head is exact fp32 in both forms and in every
-mode; in bf16 the PADDED attention runs on the bf16 matrix pipe and the packed one is exact fp32).
+mode; in bf16 the PADDED attention runs on the bf16 matrix pipe and the packed one is exact fp32).  ``bf16+attn``: bf16 with
+``packed_attention=True`` - the packed attention on the bf16 pipe as well.
 
 Each (model, dtype) runs in a child process of its own under a time limit; this process never opens the GPU.  A leg is timed
 as a host clock around `iters` steps that end in a device synchronisation, after 3 warm-up steps of the same shape; padded and
@@ -77,7 +78,7 @@ def leg():
     m = pkg.PretrainModel(feature_dim=d, num_heads=H, num_layers=L, sparsity=0.5, dropout=args.dropout, num_classes=1, use_pos=True)
     m.encoder.load_state_dict(pkg.synth.make_state_dict(d, L, 1234))
     m = m.to(dev).train()
-    m.encoder.set_train_dtype(dtype)
+    m.encoder.set_train_dtype(dtype.split("+")[0], packed_attention=dtype.endswith("+attn"))
 
     def timed(fn, iters):
         for _ in range(3):
@@ -122,7 +123,7 @@ def leg():
             main, center, repel = m.forward_packed(xp, vid, ls)
             m.zero_grad(set_to_none=True)
             (main + 0.5 * center + 1. * repel).backward()
-            ran["packed"] = m.encoder.last_train_dtype
+            ran["packed"] = m.encoder.last_train_dtype + ("+attn" if m.encoder.last_packed_attention_dtype != "fp32" else "")
 
         r = compare(padded_step, packed_step, iters)
         print(json.dumps(dict(r, B=B, what="step", ran=[ran["padded"], ran["packed"]])), flush=True)

@@ -7,7 +7,8 @@ ATen kernels - what the reference's nn.Module does on a GPU, minus its per-layer
     python tools/bench_train.py [--dropout 0.3] [--torch] [--optim {torch,torch-fused,native}]
 
 ``--packed``: training on packed ragged batches against the padded step on the SAME videos (lengths drawn with a fixed seed
-from ``synth.corpus_lengths``: 100 to 650 frames), forward + loss + backward, exact fp32 and bf16, at ``--batches`` (default
+from ``synth.corpus_lengths``: 100 to 650 frames), forward + loss + backward, exact fp32, bf16, bf16 Linears alone and bf16 with the
+opt-in packed bf16 attention (``bf16+attn``), at ``--batches`` (default
 the reference's 4, and 64).  Every timed leg runs in a child process of its own under a time limit; beside the times it prints
 the batch's fill sum T_i / (B Tmax) - the expected ratio of the Linears - and sum T_i^2 / (B Tmax^2), that of the attention,
 and the bytes of the activation record in both forms.
@@ -60,8 +61,9 @@ def packed_driver():
         print("B=%d  lengths %d..%d (seed %d)  rows %d packed / %d padded  fill sum T / (B Tmax) = %.3f  attention sum T^2 / (B Tmax^2) = %.3f"
               % (B, min(ls), tmax, args.seed, rows, B * tmax, fill, att), flush=True)
         # "bf16-linear": VS_TRAIN_FLAG_BF16_LINEAR alone in BOTH forms (exact attention) - what the packed form runs under
-        # set_train_dtype("bf16"), whose padded form has the bf16 attention kernels on top
-        for dtype in ("fp32", "bf16", "bf16-linear"):
+        # set_train_dtype("bf16"), whose padded form has the bf16 attention kernels on top.  "bf16+attn": the packed form with
+        # set_train_dtype("bf16", packed_attention=True) - bf16 Linears plus the packed bf16 attention - against the padded bf16 step
+        for dtype in ("fp32", "bf16", "bf16-linear", "bf16+attn"):
             res = {}
             for form in ("padded", "packed"):
                 cmd = [sys.executable, os.path.abspath(__file__), "--packed-leg", "%d,%s,%s" % (B, dtype, form), "--seed", str(args.seed),
@@ -120,9 +122,12 @@ if args.packed_leg:
         x[b, :n], target[b, :n] = xp[off:off + n], tp[off:off + n]
         off += n
     mask = x[:, :, 0] == 1000
-    m.set_train_dtype("bf16" if dtype == "bf16-linear" else dtype)
+    if dtype == "bf16+attn":
+        m.set_train_dtype("bf16", packed_attention=True)
+    else:
+        m.set_train_dtype("bf16" if dtype == "bf16-linear" else dtype)
     if dtype == "bf16-linear":
-        m._train_flags = lambda: pkg._lib.VS_TRAIN_FLAG_BF16_LINEAR
+        m._train_flags = lambda packed=False: pkg._lib.VS_TRAIN_FLAG_BF16_LINEAR
 
     def padded_step():
         pred, _ = m(x, mask)
@@ -140,7 +145,8 @@ if args.packed_leg:
     lib, handle = pkg._lib.load(), m._packed_weights(dev).handle
     record = (lib.vs_train_saved_bytes_packed(handle, (ctypes.c_int32 * B)(*ls), B) if form == "packed"
               else lib.vs_train_saved_bytes(handle, B, tmax))
-    print(json.dumps({"B": B, "dtype": dtype, "form": form, "ms": ms, "record": int(record), "ran": m.last_train_dtype}))
+    ran = m.last_train_dtype + ("+attn" if form == "packed" and m.last_packed_attention_dtype != "fp32" else "")
+    print(json.dumps({"B": B, "dtype": dtype, "form": form, "ms": ms, "record": int(record), "ran": ran}))
     sys.exit(0)
 
 for shape in args.shapes.split(","):

@@ -33,6 +33,7 @@ VS_FLAG_SPLITK = 32              # opt-in latency mode for reference-sized calls
 VS_TRAIN_FLAG_BF16_LINEAR = 1
 VS_TRAIN_FLAG_BF16_ATTENTION = 2
 VS_TRAIN_FLAG_FP16 = 4          # modifier: the 16-bit type is IEEE fp16 (the reference's own autocast type) instead of bf16
+VS_TRAIN_FLAG_PACKED_LP_ATTENTION = 8     # packed calls only: with BF16_ATTENTION, the packed attention on the 16-bit pipe too
 
 # every symbol include/vs_scorer.h declares
 EXPORTS = ("vs_abi_version", "vs_last_error", "vs_weights_pack", "vs_weights_free", "vs_weights_update", "vs_weights_set_norm_width", "vs_set_option",
@@ -65,6 +66,7 @@ TRAIN_EXPORTS = ("vs_train_prepare", "vs_train_saved_bytes", "vs_train_workspace
                  "vs_train_forward_packed", "vs_train_backward_packed", "vs_mse_packed_loss_forward", "vs_mse_packed_loss_backward",
                  "vs_train_attention_packed_scratch_bytes", "vs_train_attention_forward_packed", "vs_train_attention_backward_packed",
                  "vs_train_dropout_mask_attention_packed", "vs_train_saved_field_packed",
+                 "vs_train_attention_packed_lp_scratch_bytes", "vs_train_attention_forward_packed_lp", "vs_train_attention_backward_packed_lp",
                  # the pretraining head on packed ragged batches
                  "vs_pretrain_head_state_bytes_packed", "vs_pretrain_head_workspace_bytes_packed",
                  "vs_pretrain_head_forward_packed", "vs_pretrain_head_backward_packed")
@@ -416,6 +418,15 @@ def load() -> C.CDLL:
         lib.vs_train_attention_backward_packed.restype = C.c_int
         lib.vs_train_attention_backward_packed.argtypes = ([C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_float, C.c_uint64, C.c_uint32, C.c_float,
                                                                                              C.c_void_p, C.c_size_t, C.c_void_p])
+        # ... on the 16-bit pipe: (..., scale, seed, site, p, f16, scratch, scratch_bytes, stream)
+        lib.vs_train_attention_packed_lp_scratch_bytes.restype = C.c_size_t
+        lib.vs_train_attention_packed_lp_scratch_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        lib.vs_train_attention_forward_packed_lp.restype = C.c_int
+        lib.vs_train_attention_forward_packed_lp.argtypes = ([C.c_void_p] * 7 + [C.c_int32] * 3 + [C.c_float, C.c_uint64, C.c_uint32, C.c_float,
+                                                                                               C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p])
+        lib.vs_train_attention_backward_packed_lp.restype = C.c_int
+        lib.vs_train_attention_backward_packed_lp.argtypes = ([C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_float, C.c_uint64, C.c_uint32, C.c_float,
+                                                                                                C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p])
         lib.vs_train_dropout_mask_attention_packed.restype = C.c_int
         lib.vs_train_dropout_mask_attention_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32,
                                                                C.c_float, C.c_void_p]

@@ -86,12 +86,14 @@ RecordForm derive_form(const vs_weights *w, const vs_dropout_cfg *drop, int B, i
     // profiles/r04_lp_min_rows_sweep.txt - break-even at ~1280 frames, never slower; rounds 2-3 used the scoring path's 8192)
     f.lp = (drop && (drop->flags & VS_TRAIN_FLAG_BF16_LINEAR) && (long long)B * T > vsk_options().train_lp_min_rows) ? 1 : 0;
     // ... and (VS_TRAIN_FLAG_BF16_ATTENTION) the attention products of the forward and the backward (head dim 32 / 64 / 128)
-    // (packed ragged batches: the attention stays exact fp32 whatever the flag says - there is no packed bf16 form yet)
-    f.lpa = !packed && drop && (drop->flags & VS_TRAIN_FLAG_BF16_ATTENTION) && (long long)B * T > vsk_options().train_lp_min_rows &&
-            vst_attention_bf16_supported(w->desc.d_model / w->desc.num_heads);
+    // (packed ragged batches: the attention stays exact fp32 unless VS_TRAIN_FLAG_PACKED_LP_ATTENTION opts in as well - the
+    // padded rule counted on the packed rows, B * T = Mtot here; padded calls do not read that bit)
+    f.lpa = drop && (drop->flags & VS_TRAIN_FLAG_BF16_ATTENTION) && (!packed || (drop->flags & VS_TRAIN_FLAG_PACKED_LP_ATTENTION)) &&
+            (long long)B * T > vsk_options().train_lp_min_rows && vst_attention_bf16_supported(w->desc.d_model / w->desc.num_heads);
     // bf16 STORAGE of the tensors that are only ever bf16 matrix operands (VS_LP_STORE32 = 1 keeps them fp32: an A/B switch -
     // the kernels round the fp32-stored values to the same bf16, so every result is bit-identical either way)
-    f.qkv16 = f.lp && f.lpa && !vsk_options().lp_store32;     // q / k / v of the record are bf16 planes
+    // (packed: the packed 16-bit attention kernels read fp32-stored planes and an fp32 dO only)
+    f.qkv16 = !packed && f.lp && f.lpa && !vsk_options().lp_store32;     // q / k / v of the record are bf16 planes
     f.h16 = f.lp && !vsk_options().lp_store32;                // ... and so is the MLP hidden tensor (and, in the backward, its gradient)
     // ... which the A-stationary GEMM writes where it applies (K = d_model = 256, batches that fill the chip; VS_LP_MLP_UNFUSED = 1: the
     // tiled kernels, 2: the A-stationary kernel at every batch size - A/B and test switches)
@@ -362,7 +364,10 @@ static int forward_impl(const vs_weights *w, const float *x, const uint8_t *key_
         unsigned *dbits = p > 0.f ? (unsigned *)(sv + A.dbits) : nullptr;
         if (dbits && pc) VST_LAUNCH(vst_attention_dropout_bits_packed(dbits, pc->B, H, pc->tmax, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st, pk));
         else if (dbits) VST_LAUNCH(vst_attention_dropout_bits(dbits, B, H, T, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st));
-        if (pc)
+        if (pc && lpa)      // (the bit-packed keep words above are built whenever p > 0: the 16-bit kernels have no hash-per-element form)
+            VST_LAUNCH(vst_attention_fwd_bf16_packed(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, sv + A.att, sv + A.lse, H, d / H,
+                                                     scale, p, dbits, st, form.f16, pk));
+        else if (pc)
             VST_LAUNCH(vst_attention_fwd_packed(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, sv + A.att, sv + A.lse, H, d / H,
                                                 scale, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st, dbits, pk));
         else if (lpa)
@@ -425,7 +430,7 @@ static int backward_impl(vs_weights *w, const float *x, const uint8_t *key_pad_m
         form.lp = (fb & 1u) ? 1 : 0; form.lpa = (fb & 2u) != 0; form.qkv16 = (fb & 4u) != 0; form.h16 = (fb & 8u) != 0; form.rows16 = (fb & 16u) != 0;
         form.f16 = (fb & 32u) != 0;
         if ((form.qkv16 && !(form.lp && form.lpa)) || (form.h16 && !form.lp) || (form.rows16 && !form.h16) ||
-            (form.f16 && (form.rows16 || !(form.lp || form.lpa))) || (fb & 0x7fffffc0u) || (pc && form.lpa) ||
+            (form.f16 && (form.rows16 || !(form.lp || form.lpa))) || (fb & 0x7fffffc0u) || (pc && form.qkv16) ||
             (form.lpa && !vst_attention_bf16_supported(w->desc.d_model / w->desc.num_heads)) ||
             (form.rows16 && !vst_gemm_rows16_supported(B * T, 4 * w->desc.d_model, w->desc.d_model, true)))
             return failf(VS_ERR_INVALID, "vs_dropout_cfg.reserved = 0x%08x is not a record form this model / batch can have", fb);
@@ -505,7 +510,10 @@ static int backward_impl(vs_weights *w, const float *x, const uint8_t *key_pad_m
         // attention
         const float *qkv = sv + A.qkv;
         VST_LAUNCH(vst_head_rowdot(datt, sv + A.att, delta, M, T, H, d / H, st, qkv16 ? (1 | F) : lpa ? (2 | F) : 0));
-        if (pc)
+        if (pc && lpa)
+            VST_LAUNCH(vst_attention_bwd_bf16_packed(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, datt, sv + A.lse, delta, dqkv, H,
+                                                     d / H, scale, p, p > 0.f ? (const unsigned *)(sv + A.dbits) : nullptr, st, form.f16, pk));
+        else if (pc)
             VST_LAUNCH(vst_attention_bwd_packed(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, datt, sv + A.lse, delta, dqkv, H, d / H,
                                                 scale, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st,
                                                 p > 0.f ? (const unsigned *)(sv + A.dbits) : nullptr, pk));
@@ -676,6 +684,74 @@ int vs_train_attention_backward_packed(const float *q, const float *k, const flo
     VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
     VST_LAUNCH(vst_head_rowdot(d_out, out, delta, pc.Mtot, pc.Mtot, H, dh, st));
     VST_LAUNCH(vst_attention_bwd_packed(q, k, v, d_out, lse2, delta, dqkv, H, dh, scale, seed, site, p, st, nullptr, pk));
+    return VS_OK;
+}
+
+// ... and of the two 16-bit entry points: the device plan | delta [H][Mtot] | both bit-packed copies of the keep words
+namespace {
+struct PackedLpScratch { size_t delta, dbits, total; };      // floats
+PackedLpScratch packed_lp_scratch(const PackedCtx &pc, int H) {
+    PackedLpScratch S{};
+    S.delta = attention_packed_plan_floats(pc);
+    S.dbits = S.delta + align_floats((size_t)H * pc.Mtot);
+    S.total = S.dbits + align_floats(2 * (size_t)H * pc.words);
+    return S;
+}
+// the argument checks of the two entry points (before any device access); pc out
+int packed_lp_check(const int32_t *lengths, int32_t B, int32_t H, int32_t dh, float p, const void *scratch, size_t scratch_bytes,
+                    PackedCtx &pc) {
+    vs_model_desc none{};
+    if (H <= 0) return failf(VS_ERR_INVALID, "H=%d", H);
+    if (!vst_attention_bf16_supported(dh)) return failf(VS_ERR_INVALID, "head dim %d: the 16-bit attention kernels take 32 / 64 / 128", dh);
+    if (!(p >= 0.f && p < 1.f)) return failf(VS_ERR_INVALID, "dropout probability must be in [0, 1): p=%g", p);
+    if (int rc = packed_ctx(none, lengths, B, pc)) return rc;
+    const size_t need = packed_lp_scratch(pc, H).total * sizeof(float);
+    if (scratch_bytes < need || ((uintptr_t)scratch & 255))
+        return failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, need);
+    return VS_OK;
+}
+}  // namespace
+
+size_t vs_train_attention_packed_lp_scratch_bytes(const int32_t *lengths, int32_t B, int32_t H) {
+    PackedCtx pc;
+    vs_model_desc none{};
+    if (H <= 0 || packed_ctx(none, lengths, B, pc) != VS_OK) return 0;
+    return packed_lp_scratch(pc, H).total * sizeof(float);
+}
+
+int vs_train_attention_forward_packed_lp(const float *q, const float *k, const float *v, float *out, float *lse2,
+                                         const int32_t *lengths, const int32_t *lengths_dev, int32_t B, int32_t H, int32_t dh,
+                                         float scale, uint64_t seed, uint32_t site, float p, int32_t f16, void *scratch,
+                                         size_t scratch_bytes, void *stream) {
+    if (!q || !k || !v || !out || !lse2 || !lengths_dev || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
+    PackedCtx pc;
+    if (int rc = packed_lp_check(lengths, B, H, dh, p, scratch, scratch_bytes, pc)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const PackedLpScratch S = packed_lp_scratch(pc, H);
+    unsigned *dbits = p > 0.f ? (unsigned *)((float *)scratch + S.dbits) : nullptr;
+    VstPackedPlan pk{};
+    VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
+    if (dbits) VST_LAUNCH(vst_attention_dropout_bits_packed(dbits, B, H, pc.tmax, seed, site, p, st, pk));
+    VST_LAUNCH(vst_attention_fwd_bf16_packed(q, k, v, out, lse2, H, dh, scale, p, dbits, st, f16 != 0, pk));
+    return VS_OK;
+}
+
+int vs_train_attention_backward_packed_lp(const float *q, const float *k, const float *v, const float *out, const float *d_out,
+                                          const float *lse2, float *dqkv, const int32_t *lengths, const int32_t *lengths_dev,
+                                          int32_t B, int32_t H, int32_t dh, float scale, uint64_t seed, uint32_t site, float p,
+                                          int32_t f16, void *scratch, size_t scratch_bytes, void *stream) {
+    if (!q || !k || !v || !out || !d_out || !lse2 || !dqkv || !lengths_dev || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
+    PackedCtx pc;
+    if (int rc = packed_lp_check(lengths, B, H, dh, p, scratch, scratch_bytes, pc)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const PackedLpScratch S = packed_lp_scratch(pc, H);
+    float *delta = (float *)scratch + S.delta;
+    unsigned *dbits = p > 0.f ? (unsigned *)((float *)scratch + S.dbits) : nullptr;
+    VstPackedPlan pk{};
+    VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
+    if (dbits) VST_LAUNCH(vst_attention_dropout_bits_packed(dbits, B, H, pc.tmax, seed, site, p, st, pk));
+    VST_LAUNCH(vst_head_rowdot(d_out, out, delta, pc.Mtot, pc.Mtot, H, dh, st, 2 | (f16 ? VSK_F16 : 0)));      // dO enters delta as the kernels see it: rounded
+    VST_LAUNCH(vst_attention_bwd_bf16_packed(q, k, v, d_out, lse2, delta, dqkv, H, dh, scale, p, dbits, st, f16 != 0, pk));
     return VS_OK;
 }
 
@@ -892,7 +968,7 @@ int vs_train_attention_forward_bf16(const float *q, const float *k, const float 
     if (!q || !k || !v || !out || !lse2) return failf(VS_ERR_INVALID, "NULL pointer");
     if (B <= 0 || H <= 0 || T <= 0) return failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
     VST_LAUNCH(vst_attention_fwd_bf16(q, k, v, key_pad_mask, out, lse2, B, H, T, dh, scale, p, (const unsigned *)dbits,
-                                      (hipStream_t)stream, in16 ? 1 : 0));
+                                      (hipStream_t)stream, ((in16 & ~VSK_F16) ? 1 : 0) | (in16 & VSK_F16)));
     return VS_OK;
 }
 
@@ -903,9 +979,9 @@ int vs_train_attention_backward_bf16(const float *q, const float *k, const float
     if (!q || !k || !v || !out || !d_out || !lse2 || !dqkv || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
     if (B <= 0 || H <= 0 || T <= 0) return failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
     hipStream_t st = (hipStream_t)stream;
-    VST_LAUNCH(vst_head_rowdot(d_out, out, scratch, B * T, T, H, dh, st, 2));       // dO enters delta as the kernels see it: bf16
+    VST_LAUNCH(vst_head_rowdot(d_out, out, scratch, B * T, T, H, dh, st, 2 | (in16 & VSK_F16)));       // dO enters delta as the kernels see it: bf16 / f16
     VST_LAUNCH(vst_attention_bwd_bf16(q, k, v, key_pad_mask, d_out, lse2, scratch, dqkv, B, H, T, dh, scale, p,
-                                      (const unsigned *)dbits, st, in16 ? 1 : 0));
+                                      (const unsigned *)dbits, st, ((in16 & ~VSK_F16) ? 1 : 0) | (in16 & VSK_F16)));
     return VS_OK;
 }
 

@@ -30,10 +30,11 @@
 // the packed rows ([H][Mtot][DH], what vsk_qkv writes for B = 1, T = Mtot), lse2 / delta are [H][Mtot] and out / dO / dqkv
 // token-major over the packed rows.  A block takes (head, video, 128-row owner tile) from a work list built on the device
 // (plan_packed_train) and streams only that video's rows cu[b] .. cu[b+1]: the difference to the padded form is confined to
-// owner_tile() - where the block's rows, its keep words and its dropout row keys live - so a video's tile loops, LDS layout
+// owner_tile() (vs_train_attention_owner.h) - where the block's rows, its keep words and its dropout row keys live - so a video's tile loops, LDS layout
 // and summation order are those of the same video run alone.  No key mask: a packed batch has no padded rows.
 #include <atomic>
 
+#include "vs_train_attention_owner.h"
 #include "vs_train_device.h"
 #include "vs_train_kernels.h"
 
@@ -83,38 +84,6 @@ __device__ __forceinline__ f32x16 zero16() {
 #pragma unroll
     for (int t = 0; t < 16; ++t) z[t] = 0.f;
     return z;
-}
-
-// Where a block works.  Padded batches: (video * H + head, owner tile) from blockIdx, T the common length.  Packed ragged
-// batches: (head, video, owner tile) from the work list, T = that video's length.  plane: first row of the (video, head) in
-// the head-major planes (and in lse2 / delta; + query = the dropout row key); tok: first row of the video in the
-// token-major tensors; wbase: first word of the (video, head) in one bit-packed copy of the keep decisions, wall: words of
-// one copy (the key-major copy follows the query-major one).
-struct Owner { int T, b, hd, tile; size_t plane, tok, wbase, wall; };
-template <bool PACKED>
-__device__ __forceinline__ Owner owner_tile(int H, int T, const VstPackedPlan &pk) {
-    Owner o;
-    if constexpr (PACKED) {
-        const int wi = blockIdx.x / H, hd = blockIdx.x - wi * H;      // the heads of a tile side by side: the list's order is the grid's
-        const int b = pk.work[2 * wi];
-        o.hd = hd; o.b = b; o.tile = pk.work[2 * wi + 1];
-        if (b < 0) { o.T = 0; o.plane = o.tok = o.wbase = o.wall = 0; return o; }      // (device lengths gave fewer tiles than the host's)
-        const int r0 = pk.cu[b];
-        o.T = pk.cu[b + 1] - r0;
-        o.plane = (size_t)hd * pk.Mtot + r0;
-        o.tok = (size_t)r0;
-        o.wbase = (size_t)hd * pk.words + pk.bo[b];
-        o.wall = (size_t)H * pk.words;
-    } else {
-        const int nt = (T + 127) / 128, W = (T + 31) / 32;
-        const int bh = blockIdx.x / nt;
-        o.T = T; o.tile = blockIdx.x - bh * nt; o.b = bh / H; o.hd = bh - o.b * H;
-        o.plane = (size_t)bh * T;
-        o.tok = (size_t)o.b * T;
-        o.wbase = (size_t)bh * T * W;
-        o.wall = (size_t)gridDim.x / nt * T * W;
-    }
-    return o;
 }
 
 // S^T tile (lane = query): sum_c K[key][c] * Qs[query][c] + key bias; keys in rows

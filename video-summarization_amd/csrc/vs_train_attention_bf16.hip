@@ -19,6 +19,7 @@
 //   * dropout keep decisions come bit-packed from attn_dropout_bits (vs_train_attention.hip): one word per tile and lane.
 #include <atomic>
 
+#include "vs_train_attention_owner.h"
 #include "vs_train_device.h"
 #include "vs_train_kernels.h"
 
@@ -405,7 +406,10 @@ __global__ __launch_bounds__(256, DH == 128 ? 1 : 2) void attn_bwd_dkdv_bf16(
 #pragma unroll
     for (int db = 0; db < ND; ++db) { dk[db] = zero16b(); dv[db] = zero16b(); }
 
-    StagerB<DH, IN16, OUT16> sg;                                  // Q bf16 when IN16; dO bf16 when OUT16
+    // Q bf16 when IN16; dO bf16 when OUT16.  (F16 was missing here: under F16 = 1 an fp32-stored Q or dO was rounded to bf16
+    // and its bits multiplied as f16.  The fp16 training mode stores both as f16, so only its VS_LP_STORE32 = 1 form took that
+    // conversion.)
+    StagerB<DH, IN16, OUT16, F16> sg;
     auto side = [&](TileB<DH> &t, int q0) __attribute__((always_inline)) {
         if (tid < 64) {
             const int qi = q0 + tid;
@@ -495,6 +499,303 @@ __global__ __launch_bounds__(256, DH == 128 ? 1 : 2) void attn_bwd_dkdv_bf16(
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// PACKED ragged batches (VS_TRAIN_FLAG_PACKED_LP_ATTENTION): the three kernels above fed from the device work list of the
+// exact packed kernels (plan_packed_train, owner_tile<true>: vs_train_attention_owner.h).  q / k / v are the fp32 head-major
+// planes over the packed rows [H][Mtot][DH], lse2 / delta [H][Mtot], out / dO / dqkv fp32 token-major over the packed rows;
+// no key mask (the key bias is -inf for key >= T_b only); a video's streamed 64-row tiles start at its own first row; its
+// keep words are the (video, head) block at own.wbase of each packed copy, W_b = ceil(T_b / 32) words per row.
+// They are separate __global__ functions, not a PACKED parameter of the kernels above: routing the padded kernels through
+// a shared body moved the registers of 40 of their 120 instantiations, and those sit at their limits.  The difference is
+// confined to where a block's rows and keep words live: tile loops, LDS images, swizzles and the summation order of a video
+// are, line for line, those of the padded kernel running that video alone (fp32-stored operands, IN16 = OUT16 = false) -
+// tests/test_hip_train_packed_lp_attention.py holds the two to the same bits.  A change to one form belongs in the other.
+// ------------------------------------------------------------------------------------------
+template <int DH, bool DROP, int F16>
+__global__ __launch_bounds__(256, DH == 128 ? 1 : 2) void attn_fwd_train_bf16_packed(
+    const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v, float *__restrict__ out,
+    float *__restrict__ lse2, int H, float scale, float drop_scale, const unsigned *__restrict__ dbits, const VstPackedPlan pk) {
+    constexpr int NS = DH / 16, ND = DH / 32;
+    __shared__ __attribute__((aligned(16))) TileB<DH> lds[2];
+    const Owner own = owner_tile<true>(H, 0, pk);
+    if (own.T <= 0) return;
+    const int T = own.T, qt = own.tile, hd = own.hd;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int qi = qt * 128 + wave * 32 + r, qc = qi < T ? qi : T - 1;
+    const float sl2 = scale * 1.4426950408889634f;
+    const float *qb = q + own.plane * DH, *kb = k + own.plane * DH, *vb = v + own.plane * DH;
+
+    u32x4 qf[NS];
+    owner_frags<DH, F16>(qb + (size_t)qc * DH, sl2, h, qf);
+    f32x16 o[ND];
+#pragma unroll
+    for (int db = 0; db < ND; ++db) o[db] = zero16b();
+    float m_run = NEG_INF_B, l_run = 0.f;
+
+    StagerB<DH, false, false, F16> sg;
+    auto side = [&](TileB<DH> &t, int key0) __attribute__((always_inline)) {
+        if (tid < 64) t.s0[tid] = key0 + tid >= T ? NEG_INF_B : 0.f;
+    };
+    const int nkt = (T + 63) / 64, W = (T + 31) / 32;
+    const unsigned *bq = DROP ? dbits + own.wbase + (size_t)qc * W : nullptr;
+    const unsigned dsb = __builtin_bit_cast(unsigned, drop_scale);
+    unsigned kwn[2] = {0u, 0u};
+    if (DROP) load_kw(bq, 0, W, kwn);
+    sg.load(kb, DH, vb, DH, 0, T, 1.0f);
+    sg.store(lds[0]);
+    side(lds[0], 0);
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+        const TileB<DH> &t = lds[kt & 1];
+        const unsigned kw[2] = {kwn[0], kwn[1]};
+        if (DROP && kt + 1 < nkt) load_kw(bq, kt + 1, W, kwn);
+        if (kt + 1 < nkt) sg.load(kb, DH, vb, DH, 64 * (kt + 1), T, 1.0f);
+        f32x16 s[2];
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            s[n] = rows_init(&t.s0[32 * n], h);              // the key bias (0 / -inf) is the accumulator's initial value
+#pragma unroll
+            for (int ks = 0; ks < NS; ++ks) s[n] = mfma_lp<F16>(row_frag<DH>(t.a, 32 * n, ks, r, h), qf[ks], s[n]);
+        }
+        float mx = s[0][0];
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[n][e]);
+        mx = pair_max(mx);
+        const float m_new = fmaxf(m_run, mx);
+        const float m_use = m_new == NEG_INF_B ? 0.f : m_new;
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
+        float ls = 0.f;
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            const unsigned kwh = kw[n] >> (4 * h);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const float pe = __builtin_amdgcn_exp2f(s[n][e] - m_use);
+                ls += pe;
+                s[n][e] = !DROP ? pe : pe * keep_mul(kwh, (e & 3) + 8 * (e >> 2), dsb);
+            }
+        }
+        l_run = l_run * alpha + ls;
+        m_run = m_new;
+#pragma unroll
+        for (int db = 0; db < ND; ++db)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) o[db][e] *= alpha;
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                const u32x4 pf = pack_step<F16>(s[n], s2);
+#pragma unroll
+                for (int db = 0; db < ND; ++db) o[db] = mfma_lp<F16>(tr_frag<DH>(t.b, 32 * n + 16 * s2, db, lane), pf, o[db]);
+            }
+        if (kt + 1 < nkt) { sg.store(lds[(kt + 1) & 1]); side(lds[(kt + 1) & 1], 64 * (kt + 1)); }
+        __syncthreads();
+    }
+    const float l_tot = pair_sum(l_run);
+    const float inv = 1.0f / l_tot;
+    if (qi < T) {
+        float *op = out + (own.tok + qi) * (H * DH) + hd * DH;
+#pragma unroll
+        for (int db = 0; db < ND; ++db)
+#pragma unroll
+            for (int tg = 0; tg < 4; ++tg) {
+                f32x4 w;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) w[e] = o[db][4 * tg + e] * inv;
+                *(f32x4 *)(op + 32 * db + 8 * tg + 4 * h) = w;
+            }
+        if (h == 0) lse2[own.plane + qi] = m_run + log2f(l_tot);
+    }
+}
+
+template <int DH, bool DROP, int F16>
+__global__ __launch_bounds__(256, DH == 128 ? 1 : 2) void attn_bwd_dq_bf16_packed(
+    const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v, const float *__restrict__ dO,
+    const float *__restrict__ lse2, const float *__restrict__ delta, float *__restrict__ dqkv, int H, float scale,
+    float drop_scale, const unsigned *__restrict__ dbits, const VstPackedPlan pk) {
+    constexpr int NS = DH / 16, ND = DH / 32;
+    __shared__ __attribute__((aligned(16))) TileB<DH> lds[2];
+    const Owner own = owner_tile<true>(H, 0, pk);
+    if (own.T <= 0) return;
+    const int T = own.T, qt = own.tile, hd = own.hd, d = H * DH;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int qi = qt * 128 + wave * 32 + r, qc = qi < T ? qi : T - 1;
+    const float sl2 = scale * 1.4426950408889634f;
+    const float *qb = q + own.plane * DH, *kb = k + own.plane * DH, *vb = v + own.plane * DH;
+
+    u32x4 qf[NS], dof[NS];
+    owner_frags<DH, F16>(qb + (size_t)qc * DH, sl2, h, qf);
+    owner_frags<DH, F16>(dO + (own.tok + qc) * d + hd * DH, 1.0f, h, dof);
+    const float lq = lse2[own.plane + qc], dq_delta = delta[own.plane + qc];
+    f32x16 acc[ND];
+#pragma unroll
+    for (int db = 0; db < ND; ++db) acc[db] = zero16b();
+
+    StagerB<DH, false, false, F16> sg;
+    auto side = [&](TileB<DH> &t, int key0) __attribute__((always_inline)) {
+        if (tid < 64) t.s0[tid] = key0 + tid >= T ? NEG_INF_B : 0.f;
+    };
+    const int nkt = (T + 63) / 64, W = (T + 31) / 32;
+    const unsigned *bq = DROP ? dbits + own.wbase + (size_t)qc * W : nullptr;
+    const unsigned dsb = __builtin_bit_cast(unsigned, drop_scale);
+    unsigned kwn[2] = {0u, 0u};
+    if (DROP) load_kw(bq, 0, W, kwn);
+    sg.load(kb, DH, vb, DH, 0, T, 1.0f);
+    sg.store(lds[0]);
+    side(lds[0], 0);
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+        const TileB<DH> &t = lds[kt & 1];
+        const unsigned kw[2] = {kwn[0], kwn[1]};
+        if (DROP && kt + 1 < nkt) load_kw(bq, kt + 1, W, kwn);
+        if (kt + 1 < nkt) sg.load(kb, DH, vb, DH, 64 * (kt + 1), T, 1.0f);
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            f32x16 s = rows_init(&t.s0[32 * n], h), dp = zero16b();        // key bias = initial accumulator
+#pragma unroll
+            for (int ks = 0; ks < NS; ++ks) {
+                s = mfma_lp<F16>(row_frag<DH>(t.a, 32 * n, ks, r, h), qf[ks], s);
+                dp = mfma_lp<F16>(row_frag<DH>(t.b, 32 * n, ks, r, h), dof[ks], dp);
+            }
+            const unsigned kwh = kw[n] >> (4 * h);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float pe = __builtin_amdgcn_exp2f(s[i] - lq);
+                const float g = DROP ? fmaf(dp[i], keep_mul(kwh, (i & 3) + 8 * (i >> 2), dsb), -dq_delta) : dp[i] - dq_delta;
+                s[i] = pe * g;
+            }
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                const u32x4 dsf = pack_step<F16>(s, s2);
+#pragma unroll
+                for (int db = 0; db < ND; ++db) acc[db] = mfma_lp<F16>(tr_frag<DH>(t.a, 32 * n + 16 * s2, db, lane), dsf, acc[db]);
+            }
+        }
+        if (kt + 1 < nkt) { sg.store(lds[(kt + 1) & 1]); side(lds[(kt + 1) & 1], 64 * (kt + 1)); }
+        __syncthreads();
+    }
+    if (qi < T) {
+        float *op = dqkv + (own.tok + qi) * (3 * d) + hd * DH;
+#pragma unroll
+        for (int db = 0; db < ND; ++db)
+#pragma unroll
+            for (int tg = 0; tg < 4; ++tg) {
+                f32x4 w;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) w[e] = acc[db][4 * tg + e] * scale;
+                *(f32x4 *)(op + 32 * db + 8 * tg + 4 * h) = w;
+            }
+    }
+}
+
+template <int DH, bool DROP, int F16>
+__global__ __launch_bounds__(256, DH == 128 ? 1 : 2) void attn_bwd_dkdv_bf16_packed(
+    const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v, const float *__restrict__ dO,
+    const float *__restrict__ lse2, const float *__restrict__ delta, float *__restrict__ dqkv, int H, float scale,
+    float drop_scale, const unsigned *__restrict__ dbits, const VstPackedPlan pk) {
+    constexpr int NS = DH / 16, ND = DH / 32;
+    __shared__ __attribute__((aligned(16))) TileB<DH> lds[2];
+    const Owner own = owner_tile<true>(H, 0, pk);
+    if (own.T <= 0) return;
+    const int T = own.T, ktile = own.tile, hd = own.hd, d = H * DH;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int ki = ktile * 128 + wave * 32 + r, kc = ki < T ? ki : T - 1;
+    const float sl2 = scale * 1.4426950408889634f;
+    const float *qb = q + own.plane * DH, *kb = k + own.plane * DH, *vb = v + own.plane * DH;
+    const float *dob = dO + own.tok * d + hd * DH;          // row stride d
+
+    u32x4 kf[NS], vf[NS];
+    owner_frags<DH, F16>(kb + (size_t)kc * DH, 1.0f, h, kf);
+    owner_frags<DH, F16>(vb + (size_t)kc * DH, 1.0f, h, vf);
+    f32x16 dk[ND], dv[ND];
+#pragma unroll
+    for (int db = 0; db < ND; ++db) { dk[db] = zero16b(); dv[db] = zero16b(); }
+
+    StagerB<DH, false, false, F16> sg;
+    auto side = [&](TileB<DH> &t, int q0) __attribute__((always_inline)) {
+        if (tid < 64) {
+            const int qi = q0 + tid;
+            const bool ok = qi < T;
+            t.s0[tid] = ok ? -lse2[own.plane + qi] : NEG_INF_B;      // p = exp2(s - inf) = 0 on rows >= T
+            t.s1[tid] = ok ? -delta[own.plane + qi] : 0.f;
+        }
+    };
+    const int nqt = (T + 63) / 64, W = (T + 31) / 32;
+    const unsigned *bk = DROP ? dbits + own.wall + own.wbase + (size_t)kc * W : nullptr;     // the key-major copy
+    const unsigned dsb = __builtin_bit_cast(unsigned, drop_scale);
+    unsigned kwn[2] = {0u, 0u};
+    if (DROP) load_kw(bk, 0, W, kwn);
+    sg.load(qb, DH, dob, d, 0, T, sl2);
+    sg.store(lds[0]);
+    side(lds[0], 0);
+    __syncthreads();
+    for (int it = 0; it < nqt; ++it) {
+        const TileB<DH> &t = lds[it & 1];
+        const unsigned kw[2] = {kwn[0], kwn[1]};
+        if (DROP && it + 1 < nqt) load_kw(bk, it + 1, W, kwn);
+        if (it + 1 < nqt) sg.load(qb, DH, dob, d, 64 * (it + 1), T, sl2);
+#pragma unroll
+        for (int qblk = 0; qblk < 2; ++qblk) {
+            // S[query][key] - lse2[query] and (no dropout) dP[query][key] - delta[query]: the row constants are the initial
+            // accumulators.  With dropout the decision multiplies dP BEFORE delta leaves, so -delta joins in the fma below.
+            f32x16 s = rows_init(&t.s0[32 * qblk], h), dp = DROP ? zero16b() : rows_init(&t.s1[32 * qblk], h);
+#pragma unroll
+            for (int ks = 0; ks < NS; ++ks) {
+                s = mfma_lp<F16>(row_frag<DH>(t.a, 32 * qblk, ks, r, h), kf[ks], s);
+                dp = mfma_lp<F16>(row_frag<DH>(t.b, 32 * qblk, ks, r, h), vf[ks], dp);
+            }
+            const unsigned kwh = kw[qblk] >> (4 * h);
+            f32x16 pd;          // dropped-out probabilities (the B operand of dV)
+#pragma unroll
+            for (int tg = 0; tg < 4; ++tg) {
+                f32x4 dl = {0.f, 0.f, 0.f, 0.f};
+                if (DROP) dl = *(const f32x4 *)&t.s1[32 * qblk + 8 * tg + 4 * h];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int i = 4 * tg + e;
+                    const float pe = __builtin_amdgcn_exp2f(s[i]);
+                    if (DROP) {
+                        const float km = keep_mul(kwh, e + 8 * tg, dsb);
+                        pd[i] = pe * km;
+                        s[i] = pe * fmaf(dp[i], km, dl[e]);      // dS  (s1 holds -delta)
+                    } else {
+                        pd[i] = pe;
+                        s[i] = pe * dp[i];
+                    }
+                }
+            }
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                const u32x4 pdf = pack_step<F16>(pd, s2), dsf = pack_step<F16>(s, s2);
+#pragma unroll
+                for (int db = 0; db < ND; ++db) {
+                    dv[db] = mfma_lp<F16>(tr_frag<DH>(t.b, 32 * qblk + 16 * s2, db, lane), pdf, dv[db]);
+                    dk[db] = mfma_lp<F16>(tr_frag<DH>(t.a, 32 * qblk + 16 * s2, db, lane), dsf, dk[db]);
+                }
+            }
+        }
+        if (it + 1 < nqt) { sg.store(lds[(it + 1) & 1]); side(lds[(it + 1) & 1], 64 * (it + 1)); }
+        __syncthreads();
+    }
+    if (ki < T) {
+        float *op = dqkv + (own.tok + ki) * (3 * d) + hd * DH;
+        const float ln2 = 0.6931471805599453f;       // dK = scale * dS^T Q = (dS^T Qs) / log2(e)
+#pragma unroll
+        for (int db = 0; db < ND; ++db)
+#pragma unroll
+            for (int tg = 0; tg < 4; ++tg) {
+                f32x4 wk, wv;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { wk[e] = dk[db][4 * tg + e] * ln2; wv[e] = dv[db][4 * tg + e]; }
+                *(f32x4 *)(op + d + 32 * db + 8 * tg + 4 * h) = wk;
+                *(f32x4 *)(op + 2 * d + 32 * db + 8 * tg + 4 * h) = wv;
+            }
+    }
+}
+
 }  // namespace
 
 #define VSTB_LAUNCH(KERNEL_, DH_, DROP_, IN16_, ...)                                                            \
@@ -566,6 +867,47 @@ int vst_attention_bwd_bf16(const float *q, const float *k, const float *v, const
     VSTB_DISPATCH_B(attn_bwd_dkdv_bf16, q, k, v, mask, dO, lse2, delta, dqkv, H, T, scale, ds, dbits, B * H);
     VSK_CHECK_LAUNCH();
     VSTB_DISPATCH_B(attn_bwd_dq_bf16, q, k, v, mask, dO, lse2, delta, dqkv, H, T, scale, ds, dbits);
+    VSK_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- packed ragged batches: the packed kernels, fed from the device work list (vst_plan_packed); fp32-stored q / k / v / dO,
+// fp32 dqkv; dbits: the packed keep words (vst_attention_dropout_bits_packed), needed when p > 0 ----
+#define VSTB_PACKED_LAUNCH(KERNEL_, DH_, ...)                                                                   \
+    do {                                                                                                        \
+        if (drop && f16) hipLaunchKernelGGL((KERNEL_<DH_, true, 1>), grid, dim3(256), 0, st, __VA_ARGS__);      \
+        else if (drop) hipLaunchKernelGGL((KERNEL_<DH_, true, 0>), grid, dim3(256), 0, st, __VA_ARGS__);        \
+        else if (f16) hipLaunchKernelGGL((KERNEL_<DH_, false, 1>), grid, dim3(256), 0, st, __VA_ARGS__);        \
+        else hipLaunchKernelGGL((KERNEL_<DH_, false, 0>), grid, dim3(256), 0, st, __VA_ARGS__);                 \
+    } while (0)
+#define VSTB_PACKED_DISPATCH(KERNEL_, ...)                                                                      \
+    do {                                                                                                        \
+        const bool drop = p > 0.f;                                                                              \
+        if (dh == 32) VSTB_PACKED_LAUNCH(KERNEL_, 32, __VA_ARGS__);                                             \
+        else if (dh == 64) VSTB_PACKED_LAUNCH(KERNEL_, 64, __VA_ARGS__);                                        \
+        else if (dh == 128) VSTB_PACKED_LAUNCH(KERNEL_, 128, __VA_ARGS__);                                      \
+        else return -1;                                                                                         \
+    } while (0)
+
+int vst_attention_fwd_bf16_packed(const float *q, const float *k, const float *v, float *out, float *lse2, int H, int dh,
+                                  float scale, float p, const unsigned *dbits, hipStream_t st, bool f16, const VstPackedPlan &pk) {
+    if (p < 0.f || p >= 1.f || (p > 0.f && dbits == nullptr) || pk.nwork <= 0) return -1;
+    const float ds = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
+    const dim3 grid(H * pk.nwork);
+    VSTB_PACKED_DISPATCH(attn_fwd_train_bf16_packed, q, k, v, out, lse2, H, scale, ds, dbits, pk);
+    VSK_CHECK_LAUNCH();
+    return 0;
+}
+
+int vst_attention_bwd_bf16_packed(const float *q, const float *k, const float *v, const float *dO, const float *lse2,
+                                  const float *delta, float *dqkv, int H, int dh, float scale, float p, const unsigned *dbits,
+                                  hipStream_t st, bool f16, const VstPackedPlan &pk) {
+    if (p < 0.f || p >= 1.f || (p > 0.f && dbits == nullptr) || pk.nwork <= 0) return -1;
+    const float ds = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
+    const dim3 grid(H * pk.nwork);
+    VSTB_PACKED_DISPATCH(attn_bwd_dkdv_bf16_packed, q, k, v, dO, lse2, delta, dqkv, H, scale, ds, dbits, pk);
+    VSK_CHECK_LAUNCH();
+    VSTB_PACKED_DISPATCH(attn_bwd_dq_bf16_packed, q, k, v, dO, lse2, delta, dqkv, H, scale, ds, dbits, pk);
     VSK_CHECK_LAUNCH();
     return 0;
 }

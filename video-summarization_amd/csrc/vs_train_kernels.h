@@ -67,7 +67,7 @@ int vst_attention_bwd_bf16(const float *q, const float *k, const float *v, const
                            const float *lse2, const float *delta, float *dqkv, int B, int H, int T, int dh, float scale,
                            float p, const unsigned *dbits, hipStream_t st, int in16 = 0, int out16 = 0);      // in16: q (pre-scaled), k, v stored as bf16; out16: dqkv written as bf16
 // ---- packed ragged batches (vs_train_forward_packed): q, k, v head-major over the packed rows [H][Mtot][dh], lse2 / delta
-// [H][Mtot], out / dO / dqkv token-major over the packed rows; exact fp32 only ----
+// [H][Mtot], out / dO / dqkv token-major over the packed rows ----
 // The device plan: cu [B+1] row offsets | bo [B+1] keep-word offsets (video b: T_b * ceil(T_b / 32) words per head) |
 // work [nwork][2] (video, 128-row owner tile; video -1: nothing).  words = bo[B] as the host counted it.
 struct VstPackedPlan { const int *cu, *bo, *work; int nwork, Mtot; unsigned words; };
@@ -82,6 +82,13 @@ int vst_attention_fwd_packed(const float *q, const float *k, const float *v, flo
 int vst_attention_bwd_packed(const float *q, const float *k, const float *v, const float *dO, const float *lse2,
                              const float *delta, float *dqkv, int H, int dh, float scale, unsigned long long seed, unsigned site,
                              float p, hipStream_t st, const unsigned *dbits, const VstPackedPlan &pk);
+// the same two calls on the bf16 / fp16 matrix pipe (vs_train_attention_bf16.hip; head dim 32 / 64 / 128, VS_TRAIN_FLAG_PACKED_LP_ATTENTION):
+// fp32-stored q / k / v / dO, fp32 dqkv; p > 0 needs dbits (vst_attention_dropout_bits_packed); delta from vst_head_rowdot mode 2
+int vst_attention_fwd_bf16_packed(const float *q, const float *k, const float *v, float *out, float *lse2, int H, int dh,
+                                  float scale, float p, const unsigned *dbits, hipStream_t st, bool f16, const VstPackedPlan &pk);
+int vst_attention_bwd_bf16_packed(const float *q, const float *k, const float *v, const float *dO, const float *lse2,
+                                  const float *delta, float *dqkv, int H, int dh, float scale, float p, const unsigned *dbits,
+                                  hipStream_t st, bool f16, const VstPackedPlan &pk);
 int vst_attention_dropout_mask_video(uint8_t *keep, int H, int T, int Mtot, int row0, unsigned long long seed, unsigned site,
                                      float p, hipStream_t st);
 // test hook: keep[b,h,i,j] (bytes) of the attention-weight dropout, exactly as the two kernels above draw it

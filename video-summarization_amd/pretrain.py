@@ -199,7 +199,7 @@ class PretrainModel(nn.Module):
         """``forward`` on a RAGGED batch without padding: x [sum(lengths), 1024] = the videos' frames concatenated
         (``data.collate_fn_pretrain_packed``), video_representation [B, 512].  Returns the same triple (distillation,
         centering, repelling).  The encoder is ``SimNet.forward_packed_train`` (it follows ``set_train_dtype``; its packed
-        attention is exact fp32), the head below it ``_PretrainHeadPacked``, exact fp32 in every mode; no padded row is
+        attention is exact fp32 unless ``self.encoder.set_train_dtype(..., packed_attention=True)`` opted in), the head below it ``_PretrainHeadPacked``, exact fp32 in every mode; no padded row is
         computed in either, forward or backward.
 
         Equality with the padded step: the reference pads a batch to its longest video with the 1000.0 sentinel and masks

@@ -245,7 +245,8 @@ class _TrainForwardPacked(torch.autograd.Function):
         ctx.save_for_backward(x, dev_len, saved)
         ctx.module, ctx.cfg, ctx.packed, ctx.packed_key = module, (float(p_embed), float(p), int(seed), int(tflags), fmt), packed, module._packed_key
         ctx.lengths = tuple(lengths)
-        module._note_train_arithmetic(int(tflags) & ~_lib.VS_TRAIN_FLAG_BF16_ATTENTION, fmt, M)
+        module._note_train_arithmetic(int(tflags) & ~(_lib.VS_TRAIN_FLAG_BF16_ATTENTION | _lib.VS_TRAIN_FLAG_PACKED_LP_ATTENTION), fmt, M)
+        module._last_packed_attention_dtype = ("fp16" if (fmt & 32) else "bf16") if (fmt & 2) else "fp32"
         ctx.set_materialize_grads(False)
         return scores, (hidden[..., :module.d_model] if module._plan else hidden)
 
@@ -375,6 +376,8 @@ class SimNet(nn.Module):
         self.latency_mode = False         # opt-in (set_latency_mode): split-K kernels for one reference-sized video per call
         self._train_dtype = "fp32"        # set_train_dtype("bf16"): the training path's counterpart of the reference's autocast
         self.last_train_dtype = None      # what the last training forward actually computed in ("fp32" / "bf16" / "fp16")
+        self._packed_attention = False    # set_train_dtype(..., packed_attention=True): packed batches' attention on the 16-bit pipe too
+        self._last_packed_attention_dtype = "fp32"
         self._packed: Optional[_Packed] = None
         self._packed_key = None
         self._packed_shape = None
@@ -753,7 +756,7 @@ class SimNet(nn.Module):
                           "low-precision training kernels apply above VS_TRAIN_LP_MIN_ROWS frames per batch (see "
                           "SimNet.last_train_dtype after any training forward)" % (self._train_dtype, frames), RuntimeWarning)
 
-    def set_train_dtype(self, value: str) -> "SimNet":
+    def set_train_dtype(self, value: str, packed_attention: bool = False) -> "SimNet":
         """Arithmetic of the TRAINING path's matrix products (forward Linears, dgrad and wgrad GEMMs): 'fp32' (default:
         exact fp32 MFMA, gradients at 1e-6 of the float64 truth) or 'bf16' - the counterpart of the reference's
         ``with amp.autocast():`` (train.py:120, pretrain.py:59): operands rounded to bf16, fp32 accumulation, and - as
@@ -768,14 +771,29 @@ class SimNet(nn.Module):
         reaches these kernels as a scaled ``d_scores``, an overflow surfaces as inf / NaN gradients and GradScaler skips
         the step and halves the scale.
         Packed ragged batches (``forward_packed_train``): the Linears, dgrad and wgrad follow this setting; the packed attention
-        is exact fp32 in every mode."""
+        is exact fp32 in every mode unless ``packed_attention=True`` is given with 'bf16' / 'fp16': then its products run on that
+        16-bit pipe as well (head dim 32 / 64 / 128, above VS_TRAIN_LP_MIN_ROWS packed frames; q / k / v and the attention
+        gradients stay fp32-stored; ``last_packed_attention_dtype`` says what a packed forward really ran).  Opt-in: the
+        default leaves every packed step bit-identical to what it was.  With 'fp32' the keyword has no effect."""
         if value not in ("fp32", "bf16", "fp16"):
             raise ValueError("train dtype must be 'fp32', 'bf16' or 'fp16', got %r" % (value,))
+        packed_attention = bool(packed_attention) and value != "fp32"
+        if packed_attention and self._lib_dh not in (32, 64, 128):
+            raise ValueError("%s attention needs head_dim in %s, got %d" % (value, (32, 64, 128), self._lib_dh))
         self._train_dtype = value
+        self._packed_attention = packed_attention
         return self
 
-    def _train_flags(self) -> int:
+    @property
+    def last_packed_attention_dtype(self) -> str:
+        """Arithmetic of the attention products of the last ``forward_packed_train`` ('fp32' / 'bf16' / 'fp16'), from the format
+        word the library published for it; 'fp32' before any."""
+        return self._last_packed_attention_dtype
+
+    def _train_flags(self, packed: bool = False) -> int:
         tflags = (_lib.VS_TRAIN_FLAG_BF16_LINEAR | _lib.VS_TRAIN_FLAG_BF16_ATTENTION) if self._train_dtype in ("bf16", "fp16") else 0
+        if packed and tflags and self._packed_attention:
+            tflags |= _lib.VS_TRAIN_FLAG_PACKED_LP_ATTENTION
         return tflags | (_lib.VS_TRAIN_FLAG_FP16 if self._train_dtype == "fp16" else 0)
 
     def forward_packed_train(self, x: Tensor, lengths):
@@ -787,8 +805,10 @@ class SimNet(nn.Module):
         zero to every gradient, so with ``losses.mse_packed_loss`` the step equals the padded one.  With dropout off a
         video's outputs are bit-identical to running it alone.  Dropout is active iff ``self.training`` (seed drawn like
         ``forward``'s).  ``set_train_dtype("bf16" | "fp16")`` runs the Linears, dgrad and wgrad in low precision above
-        VS_TRAIN_LP_MIN_ROWS packed frames; the packed ATTENTION stays exact fp32 in every mode (``last_train_dtype`` names
-        the arithmetic of the Linears).  Every head dim of the padded training path; embedded shapes work; no class token."""
+        VS_TRAIN_LP_MIN_ROWS packed frames; the packed ATTENTION stays exact fp32 unless ``set_train_dtype(...,
+        packed_attention=True)`` opted in (head dim 32 / 64 / 128; ``last_train_dtype`` names the arithmetic of the Linears,
+        ``last_packed_attention_dtype`` that of the attention).  Every head dim of the padded training path; embedded shapes
+        work; no class token."""
         if self.use_cls:
             raise NotImplementedError("packed batches are not available with use_cls=True")
         if not x.is_cuda:
@@ -806,7 +826,7 @@ class SimNet(nn.Module):
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if (p > 0.0 or p_embed > 0.0) else 0
         params = [t for t in self._tensors() if isinstance(t, nn.Parameter)]
         x32 = x if x.dtype == torch.float32 else x.float()
-        return _TrainForwardPacked.apply(self, x32, lengths, p, p_embed, seed, self._train_flags(), *params)
+        return _TrainForwardPacked.apply(self, x32, lengths, p, p_embed, seed, self._train_flags(packed=True), *params)
 
     @torch.no_grad()
     def forward_packed(self, x: Tensor, lengths, want_hidden: bool = True):
