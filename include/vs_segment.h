@@ -55,6 +55,59 @@ int vs_kts_segment(const void *x, int32_t input, int32_t d, const int32_t *cu, i
 int vs_kts_scatters(const void *x, int32_t input, int32_t d, int32_t n, double *scatters, void *workspace,
                     size_t workspace_bytes, void *stream);
 
+/* ---- cosine and Gaussian kernels; the Gram of a ragged batch in one launch --------------------------------------------
+ * x is float [n][d].  g_ij = the fp32 matrix-pipe dot product of rows i and j (the fma chain over k ascending),
+ * s_i = sum_k x_ik^2 accumulated in double in a fixed order.
+ *   DOT:    K_ij = g_ij.
+ *   COSINE: inv_i = s_i > 0 ? 1 / sqrt(s_i) : 0 (double); K_ij = float(clamp((double)g_ij * inv_i * inv_j, -1, 1)) for
+ *           i != j; K_ii = s_i > 0 ? 1 : 0.  An all-zero frame has a zero row and column.
+ *   RBF:    K_ij = float(exp(-gamma * max(0, s_i + s_j - 2 (double)g_ij))), exp in double; K_ii = 1.
+ * K is symmetric bit for bit (both halves are stored from one accumulator), and a video's K does not depend on the
+ * videos it is batched with, on its place among them, or on the call. */
+#define VS_KTS_GRAM_DOT 0
+#define VS_KTS_GRAM_COSINE 1
+#define VS_KTS_GRAM_RBF 2
+
+typedef struct vs_kts_kernel {
+    int32_t kind;      /* VS_KTS_GRAM_* */
+    int32_t reserved;  /* 0 */
+    double gamma;      /* RBF only: finite and > 0; ignored by the other kinds */
+} vs_kts_kernel;
+
+/* Device bytes vs_kts_gram needs (0: invalid arguments, see vs_last_error()). */
+size_t vs_kts_gram_workspace_bytes(const int32_t *cu, int32_t batch, int32_t d);
+
+/* The kernel matrices of a ragged batch: one row-norm pre-pass (cosine / rbf) and ONE Gram launch for all videos, operands
+ * read straight from x (no padded copy).  x: device float [cu[batch]][d]; cu: host [batch + 1]; kern: host.
+ * K_out: device float, video v = n_v * n_v dense values after those of v - 1 - the VS_KTS_KERNEL_F32 input layout.
+ * Stream-ordered: enqueues on `stream` and returns; no copy to or from host memory, no synchronisation. */
+int vs_kts_gram(const void *x, int32_t d, const int32_t *cu, int32_t batch, const vs_kts_kernel *kern, float *K_out,
+                void *workspace, size_t workspace_bytes, void *stream);
+
+/* vs_kts_workspace_bytes / vs_kts_segment with the kernel of the Gram chosen by `kern` (host, not NULL).  Same contracts
+ * otherwise; `input` must be VS_KTS_FEATURES_F32 (a kernel matrix has its kernel already: VS_ERR_INVALID).  The Gram
+ * comes from the one-launch kernel above for all three kinds.  kind = VS_KTS_GRAM_DOT here computes the same g_ij as
+ * vs_kts_segment where the fp32 Gram is exact; on data whose fp32 Gram rounds it is NOT bound to vs_kts_segment's bits
+ * (that path sums a zero-padded copy on another GEMM's tiling). */
+size_t vs_kts_workspace_bytes_k(const int32_t *cu, int32_t batch, int32_t d, int32_t input, const int32_t *ncp, int32_t mode,
+                                const vs_kts_kernel *kern);
+int vs_kts_segment_k(const void *x, int32_t input, int32_t d, const int32_t *cu, int32_t batch, const int32_t *ncp,
+                     const int32_t *lmin, const int32_t *lmax, const double *vmax, const double *desc_rate, int32_t mode,
+                     const vs_kts_kernel *kern, int64_t *cps, int32_t *n_cps, double *scores, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
+/* Replaces: eval_score(K, cps) (cpd_auto.py) for every video of a ragged batch: the sum of the scatters of the segments
+ * that the given change points cut, each scatter evaluated as the scatter table of vs_kts_segment evaluates it and added
+ * left to right in double - the additions of the dynamic program along that path, so the value is bit-equal to the
+ * cpd_nonlin score of its own change points.  x / input / d as vs_kts_segment; kern (host, NULL = DOT) chooses the
+ * kernel of a VS_KTS_FEATURES_F32 input and is ignored for the two kernel-matrix inputs.  cps: host int64, video v's
+ * n_cps[v] change points after those of v - 1 (strictly increasing, in 1 .. n_v - 1, else VS_ERR_INVALID); n_cps: host
+ * [batch].  scores_out: host double [batch].  workspace: at least vs_kts_workspace_bytes_k(cu, batch, d, input, n_cps,
+ * VS_KTS_SCORES, kern) bytes (vs_kts_workspace_bytes for a kernel-matrix input is enough).  Synchronises `stream`. */
+int vs_kts_eval_score(const void *x, int32_t input, int32_t d, const vs_kts_kernel *kern, const int32_t *cu, int32_t batch,
+                      const int64_t *cps, const int32_t *n_cps, double *scores_out, void *workspace, size_t workspace_bytes,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

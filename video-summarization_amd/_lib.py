@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(HERE, "libvsscore.so")
 DIAG_LIB_PATH = os.path.join(HERE, "libvsscore_diag.so")
 SOURCES = ("vs_kernels.hip", "vs_attention.hip", "vs_attention_w64.hip", "vs_mlp_fused.hip", "vs_gemm_ring.hip", "vs_scorer.cpp", "vs_eval.cpp",
            "vs_train_kernels.hip", "vs_train_attention.hip", "vs_train_attention_bf16.hip", "vs_train_gemm_rows.hip", "vs_pretrain_kernels.hip",
-           "vs_train.cpp", "vs_segment.hip", "vs_segment.cpp", "vs_optim.hip", "vs_attention_maps.hip",
+           "vs_train.cpp", "vs_segment.hip", "vs_segment_gram.hip", "vs_segment.cpp", "vs_optim.hip", "vs_attention_maps.hip",
            "vs_eval_device.hip", "vs_eval_device.cpp", "vs_summary.hip", "vs_summary.cpp", "vs_batch.hip")
 ABI_VERSION = 3
 
@@ -71,7 +71,9 @@ TRAIN_EXPORTS = ("vs_train_prepare", "vs_train_saved_bytes", "vs_train_workspace
                  "vs_pretrain_head_state_bytes_packed", "vs_pretrain_head_workspace_bytes_packed",
                  "vs_pretrain_head_forward_packed", "vs_pretrain_head_backward_packed")
 # include/vs_segment.h (kernel temporal segmentation)
-SEGMENT_EXPORTS = ("vs_kts_workspace_bytes", "vs_kts_segment", "vs_kts_scatters")
+SEGMENT_EXPORTS = ("vs_kts_workspace_bytes", "vs_kts_segment", "vs_kts_scatters",
+                   # cosine / Gaussian kernels, the one-launch ragged Gram, the score of given change points
+                   "vs_kts_gram_workspace_bytes", "vs_kts_gram", "vs_kts_workspace_bytes_k", "vs_kts_segment_k", "vs_kts_eval_score")
 # include/vs_optim.h (the Adam step)
 OPTIM_EXPORTS = ("vs_adam_step_tensors", "vs_adam_state_bytes", "vs_adam_state_init", "vs_adam_state_field", "vs_adam_step",
                  "vs_grad_norm_workspace_bytes", "vs_grad_norm_tensors", "vs_grad_norm", "vs_grad_scale_tensors")
@@ -81,6 +83,7 @@ VS_ADAM_MAX_TENSORS = 64
 VS_GRAD_NORM_L2, VS_GRAD_NORM_MAX = 0, 1
 VS_KTS_FEATURES_F32, VS_KTS_KERNEL_F32, VS_KTS_KERNEL_F64 = 0, 1, 2
 VS_KTS_SCORES, VS_KTS_BACKTRACK, VS_KTS_AUTO = 0, 1, 2
+VS_KTS_GRAM_DOT, VS_KTS_GRAM_COSINE, VS_KTS_GRAM_RBF = 0, 1, 2
 NUM_STAGES = 6
 
 
@@ -128,6 +131,10 @@ class AdamCfg(C.Structure):    # vs_adam_cfg (include/vs_optim.h)
 class AdamTensor(C.Structure):  # vs_adam_tensor
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("mirror", C.c_void_p),
                 ("step", C.c_void_p), ("n", C.c_size_t)]
+
+
+class KtsKernel(C.Structure):   # vs_kts_kernel (include/vs_segment.h)
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("gamma", C.c_double)]
 
 
 class GradTensor(C.Structure):  # vs_grad_tensor
@@ -453,6 +460,19 @@ def load() -> C.CDLL:
         lib.vs_kts_scatters.restype = C.c_int
         lib.vs_kts_scatters.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.c_void_p]
+        lib.vs_kts_gram_workspace_bytes.restype = C.c_size_t
+        lib.vs_kts_gram_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        lib.vs_kts_gram.restype = C.c_int
+        lib.vs_kts_gram.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(KtsKernel), C.c_void_p, C.c_void_p,
+                                    C.c_size_t, C.c_void_p]
+        lib.vs_kts_workspace_bytes_k.restype = C.c_size_t
+        lib.vs_kts_workspace_bytes_k.argtypes = lib.vs_kts_workspace_bytes.argtypes + [C.POINTER(KtsKernel)]
+        lib.vs_kts_segment_k.restype = C.c_int
+        lib.vs_kts_segment_k.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
+                                         + [C.c_int32, C.POINTER(KtsKernel)] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p])
+        lib.vs_kts_eval_score.restype = C.c_int
+        lib.vs_kts_eval_score.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.POINTER(KtsKernel), C.c_void_p, C.c_int32]
+                                          + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p])
         # include/vs_optim.h
         lib.vs_adam_step_tensors.restype = C.c_int
         lib.vs_adam_step_tensors.argtypes = [C.POINTER(AdamTensor), C.c_int32, C.POINTER(AdamCfg), C.c_void_p, C.c_void_p,

@@ -2,6 +2,7 @@
 // and the host end of the model selection (penalty and argmin in double, the reference's expression order).
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -49,6 +50,10 @@ struct Plan {
     std::vector<KtsVideo> vids;
     int64_t vids_off = 0, bias_off = 0, xpad_off = 0, total = 0;
     int32_t n_max = 0, m_max = 0, d_pad = 0;
+    // the one-launch Gram (the *_k entry points): its video table and the row norms, after everything else
+    std::vector<KtsGramVideo> gvids;
+    int64_t gvids_off = 0, nrm_off = 0;
+    int32_t tiles = 0;
 };
 
 // Checks everything that needs no GPU and lays out the workspace.  Returns VS_OK or VS_ERR_INVALID (message set).
@@ -156,32 +161,78 @@ int table(const void *x, int32_t input, int32_t d, const int32_t *cu, const Plan
     return VS_OK;
 }
 
-}  // namespace
 
-extern "C" {
-
-size_t vs_kts_workspace_bytes(const int32_t *cu, int32_t batch, int32_t d, int32_t input, const int32_t *ncp, int32_t mode) {
-    Plan P;
-    if (make_plan(cu, batch, d, input, ncp, nullptr, nullptr, mode, P) != VS_OK) return 0;
-    return (size_t)P.total;
+int check_kernel(const vs_kts_kernel *kern) {
+    if (!kern) return fail(VS_ERR_INVALID, "kern is NULL");
+    if (kern->kind != VS_KTS_GRAM_DOT && kern->kind != VS_KTS_GRAM_COSINE && kern->kind != VS_KTS_GRAM_RBF)
+        return fail(VS_ERR_INVALID, "kern->kind=%d is not a VS_KTS_GRAM_* kind", kern->kind);
+    if (kern->reserved != 0) return fail(VS_ERR_INVALID, "kern->reserved=%d must be 0", kern->reserved);
+    if (kern->kind == VS_KTS_GRAM_RBF && !(std::isfinite(kern->gamma) && kern->gamma > 0.0))
+        return fail(VS_ERR_INVALID, "kern->gamma=%g must be finite and > 0 for VS_KTS_GRAM_RBF", kern->gamma);
+    return VS_OK;
 }
 
-int vs_kts_segment(const void *x, int32_t input, int32_t d, const int32_t *cu, int32_t batch, const int32_t *ncp,
-                   const int32_t *lmin, const int32_t *lmax, const double *vmax, const double *desc_rate, int32_t mode,
-                   int64_t *cps, int32_t *n_cps, double *scores, void *workspace, size_t workspace_bytes, void *stream) {
-    Plan P;
-    if (int rc = make_plan(cu, batch, d, input, ncp, lmin, lmax, mode, P)) return rc;
-    if (!x || !cps || !n_cps || !scores) return fail(VS_ERR_INVALID, "x / cps / n_cps / scores is NULL");
-    if (mode == VS_KTS_AUTO) {
-        if (!vmax) return fail(VS_ERR_INVALID, "vmax is NULL (needed by VS_KTS_AUTO)");
-        for (int32_t b = 0; b < batch; ++b)
-            if (desc_rate && !(desc_rate[b] > 0)) return fail(VS_ERR_INVALID, "video %d: desc_rate=%g must be > 0", b, desc_rate[b]);
+// the Gram launch's table for videos whose K lies at k_off[b] with row stride ldk[b]; appends its workspace at `off`
+int plan_gram(const int32_t *cu, int32_t batch, Plan &P, int64_t off) {
+    P.gvids.assign(batch, KtsGramVideo{});
+    int64_t tiles = 0;
+    for (int32_t b = 0; b < batch; ++b) {
+        KtsGramVideo &G = P.gvids[b];
+        G.n = cu[b + 1] - cu[b];
+        G.row0 = cu[b];
+        G.tile0 = (int32_t)tiles;
+        const int64_t t = (G.n + KTS_GRAM_TILE - 1) / KTS_GRAM_TILE;
+        tiles += t * (t + 1) / 2;
+        if (tiles > INT32_MAX) return fail(VS_ERR_INVALID, "the batch has more than 2^31 Gram tiles");
     }
-    if (!workspace || workspace_bytes < (size_t)P.total)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    if (int rc = table(x, input, d, cu, P, ws, st)) return rc;
+    P.tiles = (int32_t)tiles;
+    P.gvids_off = off; off = align256(off + (int64_t)batch * (int64_t)sizeof(KtsGramVideo));
+    P.nrm_off = off; off = align256(off + (int64_t)cu[batch] * 8);
+    P.total = off;
+    return VS_OK;
+}
+
+// row norms (cosine / rbf), the table, the one Gram launch: all enqueued, nothing copied from host memory
+int gram_k(const float *x, int32_t d, int32_t rows, const vs_kts_kernel &kern, const Plan &P, char *ws, void *kbase,
+           hipStream_t st) {
+    KTS_LAUNCH(vsk_kts_put(P.gvids.data(), P.gvids.size() * sizeof(KtsGramVideo), ws + P.gvids_off, st));
+    double *nrm = nullptr;
+    if (kern.kind != VS_KTS_GRAM_DOT) {
+        nrm = (double *)(ws + P.nrm_off);
+        KTS_LAUNCH(vsk_kts_row_norms(x, d, rows, kern.kind == VS_KTS_GRAM_COSINE, nrm, st));
+    }
+    KTS_LAUNCH(vsk_kts_gram(x, d, (const KtsGramVideo *)(ws + P.gvids_off), (int)P.gvids.size(), P.tiles, kern.kind,
+                            kern.gamma, nrm, kbase, st));
+    return VS_OK;
+}
+
+// make_plan for a *_k entry point: features only, the Gram of every video where the scatter stage reads it
+int make_plan_k(const int32_t *cu, int32_t batch, int32_t d, int32_t input, const int32_t *ncp, const int32_t *lmin,
+                const int32_t *lmax, int32_t mode, const vs_kts_kernel *kern, Plan &P) {
+    if (int rc = check_kernel(kern)) return rc;
+    if (input == VS_KTS_KERNEL_F32 || input == VS_KTS_KERNEL_F64)
+        return fail(VS_ERR_INVALID, "a kernel-matrix input has its kernel already: kern needs VS_KTS_FEATURES_F32");
+    if (int rc = make_plan(cu, batch, d, input, ncp, lmin, lmax, mode, P)) return rc;
+    if (int rc = plan_gram(cu, batch, P, P.total)) return rc;
+    for (int32_t b = 0; b < batch; ++b) {
+        P.gvids[b].ldk = P.vids[b].ldk;
+        P.gvids[b].k_off = P.vids[b].k_off;
+    }
+    return VS_OK;
+}
+
+// features -> scatter table through the one-launch Gram
+int table_k(const float *x, int32_t d, const int32_t *cu, const vs_kts_kernel &kern, const Plan &P, char *ws, hipStream_t st) {
+    const int B = (int)P.vids.size();
+    KTS_LAUNCH(vsk_kts_put(P.vids.data(), P.vids.size() * sizeof(KtsVideo), ws, st));
+    if (int rc = gram_k(x, d, cu[B], kern, P, ws, ws, st)) return rc;
+    KTS_LAUNCH(vsk_kts_scatter_table((const KtsVideo *)ws, B, P.n_max, ws, ws, 0, st));
+    return VS_OK;
+}
+
+// everything of vs_kts_segment after the scatter table: the dynamic program, the model selection, the back-tracking
+int finish_segment(Plan &P, int32_t batch, const double *vmax, const double *desc_rate, int32_t mode, int64_t *cps,
+                   int32_t *n_cps, double *scores, char *ws, hipStream_t st) {
     const KtsVideo *dv = (const KtsVideo *)ws;
     KTS_LAUNCH(vsk_kts_dp_init(dv, batch, P.n_max, ws, st));
     for (int32_t k = 1; k <= P.m_max; ++k) KTS_LAUNCH(vsk_kts_dp_step(dv, batch, P.n_max, k, ws, st));
@@ -231,6 +282,35 @@ int vs_kts_segment(const void *x, int32_t input, int32_t d, const int32_t *cu, i
     return VS_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+size_t vs_kts_workspace_bytes(const int32_t *cu, int32_t batch, int32_t d, int32_t input, const int32_t *ncp, int32_t mode) {
+    Plan P;
+    if (make_plan(cu, batch, d, input, ncp, nullptr, nullptr, mode, P) != VS_OK) return 0;
+    return (size_t)P.total;
+}
+
+int vs_kts_segment(const void *x, int32_t input, int32_t d, const int32_t *cu, int32_t batch, const int32_t *ncp,
+                   const int32_t *lmin, const int32_t *lmax, const double *vmax, const double *desc_rate, int32_t mode,
+                   int64_t *cps, int32_t *n_cps, double *scores, void *workspace, size_t workspace_bytes, void *stream) {
+    Plan P;
+    if (int rc = make_plan(cu, batch, d, input, ncp, lmin, lmax, mode, P)) return rc;
+    if (!x || !cps || !n_cps || !scores) return fail(VS_ERR_INVALID, "x / cps / n_cps / scores is NULL");
+    if (mode == VS_KTS_AUTO) {
+        if (!vmax) return fail(VS_ERR_INVALID, "vmax is NULL (needed by VS_KTS_AUTO)");
+        for (int32_t b = 0; b < batch; ++b)
+            if (desc_rate && !(desc_rate[b] > 0)) return fail(VS_ERR_INVALID, "video %d: desc_rate=%g must be > 0", b, desc_rate[b]);
+    }
+    if (!workspace || workspace_bytes < (size_t)P.total)
+        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    if (int rc = table(x, input, d, cu, P, ws, st)) return rc;
+    return finish_segment(P, batch, vmax, desc_rate, mode, cps, n_cps, scores, ws, st);
+}
+
 int vs_kts_scatters(const void *x, int32_t input, int32_t d, int32_t n, double *scatters, void *workspace,
                     size_t workspace_bytes, void *stream) {
     const int32_t cu[2] = {0, n}, zero = 0;
@@ -244,6 +324,118 @@ int vs_kts_scatters(const void *x, int32_t input, int32_t d, int32_t n, double *
     if (int rc = table(x, input, d, cu, P, ws, st)) return rc;
     KTS_LAUNCH(vsk_kts_scatters_out((const KtsVideo *)ws, n, ws, scatters, st));
     KTS_HIP(hipStreamSynchronize(st));                        // the plan's host copy of the descriptors ends here
+    return VS_OK;
+}
+
+size_t vs_kts_gram_workspace_bytes(const int32_t *cu, int32_t batch, int32_t d) {
+    const vs_kts_kernel dot = {VS_KTS_GRAM_DOT, 0, 0.0};
+    Plan P;
+    std::vector<int32_t> zeros(batch > 0 ? batch : 0, 0);
+    if (!cu || batch <= 0) { fail(VS_ERR_INVALID, "cu is NULL or batch=%d is not positive", batch); return 0; }
+    if (make_plan_k(cu, batch, d, VS_KTS_FEATURES_F32, zeros.data(), nullptr, nullptr, VS_KTS_SCORES, &dot, P) != VS_OK)
+        return 0;                                            // the same checks of cu / d as every other entry point
+    if (plan_gram(cu, batch, P, 0) != VS_OK) return 0;
+    return (size_t)P.total;
+}
+
+int vs_kts_gram(const void *x, int32_t d, const int32_t *cu, int32_t batch, const vs_kts_kernel *kern, float *K_out,
+                void *workspace, size_t workspace_bytes, void *stream) {
+    Plan P;
+    if (!cu || batch <= 0) return fail(VS_ERR_INVALID, "cu is NULL or batch=%d is not positive", batch);
+    std::vector<int32_t> zeros(batch, 0);
+    if (int rc = make_plan_k(cu, batch, d, VS_KTS_FEATURES_F32, zeros.data(), nullptr, nullptr, VS_KTS_SCORES, kern, P)) return rc;
+    if (!x || !K_out) return fail(VS_ERR_INVALID, "x / K_out is NULL");
+    if (int rc = plan_gram(cu, batch, P, 0)) return rc;
+    int64_t k_off = 0;
+    for (int32_t b = 0; b < batch; ++b) {                    // dense, one video after the other
+        KtsGramVideo &G = P.gvids[b];
+        G.ldk = G.n;
+        G.k_off = k_off;
+        k_off += (int64_t)G.n * G.n * 4;
+    }
+    if (!workspace || workspace_bytes < (size_t)P.total)
+        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+    return gram_k((const float *)x, d, cu[batch], *kern, P, (char *)workspace, K_out, (hipStream_t)stream);
+}
+
+size_t vs_kts_workspace_bytes_k(const int32_t *cu, int32_t batch, int32_t d, int32_t input, const int32_t *ncp, int32_t mode,
+                                const vs_kts_kernel *kern) {
+    Plan P;
+    if (make_plan_k(cu, batch, d, input, ncp, nullptr, nullptr, mode, kern, P) != VS_OK) return 0;
+    return (size_t)P.total;
+}
+
+int vs_kts_segment_k(const void *x, int32_t input, int32_t d, const int32_t *cu, int32_t batch, const int32_t *ncp,
+                     const int32_t *lmin, const int32_t *lmax, const double *vmax, const double *desc_rate, int32_t mode,
+                     const vs_kts_kernel *kern, int64_t *cps, int32_t *n_cps, double *scores, void *workspace,
+                     size_t workspace_bytes, void *stream) {
+    Plan P;
+    if (int rc = make_plan_k(cu, batch, d, input, ncp, lmin, lmax, mode, kern, P)) return rc;
+    if (!x || !cps || !n_cps || !scores) return fail(VS_ERR_INVALID, "x / cps / n_cps / scores is NULL");
+    if (mode == VS_KTS_AUTO) {
+        if (!vmax) return fail(VS_ERR_INVALID, "vmax is NULL (needed by VS_KTS_AUTO)");
+        for (int32_t b = 0; b < batch; ++b)
+            if (desc_rate && !(desc_rate[b] > 0)) return fail(VS_ERR_INVALID, "video %d: desc_rate=%g must be > 0", b, desc_rate[b]);
+    }
+    if (!workspace || workspace_bytes < (size_t)P.total)
+        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    if (int rc = table_k((const float *)x, d, cu, *kern, P, ws, st)) return rc;
+    return finish_segment(P, batch, vmax, desc_rate, mode, cps, n_cps, scores, ws, st);
+}
+
+int vs_kts_eval_score(const void *x, int32_t input, int32_t d, const vs_kts_kernel *kern, const int32_t *cu, int32_t batch,
+                      const int64_t *cps, const int32_t *n_cps, double *scores_out, void *workspace, size_t workspace_bytes,
+                      void *stream) {
+    const vs_kts_kernel dot = {VS_KTS_GRAM_DOT, 0, 0.0};
+    const bool feats = input == VS_KTS_FEATURES_F32;
+    if (!n_cps) return fail(VS_ERR_INVALID, "n_cps is NULL");
+    Plan P;
+    if (feats) {
+        if (int rc = make_plan_k(cu, batch, d, input, n_cps, nullptr, nullptr, VS_KTS_SCORES, kern ? kern : &dot, P)) return rc;
+    } else if (int rc = make_plan(cu, batch, d, input, n_cps, nullptr, nullptr, VS_KTS_SCORES, P)) {
+        return rc;                                           // n_cps > n - 1 is refused here: n >= (ncp + 1) lmin
+    }
+    int64_t total_cps = 0;
+    for (int32_t b = 0; b < batch; ++b) total_cps += n_cps[b];
+    if (!x || !scores_out || (total_cps && !cps)) return fail(VS_ERR_INVALID, "x / cps / scores_out is NULL");
+    std::vector<int32_t> c32((size_t)total_cps + 1);
+    int64_t at = 0;
+    for (int32_t b = 0; b < batch; ++b) {
+        const int32_t n = P.vids[b].n;
+        int64_t prev = 0;
+        for (int32_t i = 0; i < n_cps[b]; ++i, ++at) {
+            const int64_t c = cps[at];
+            if (c <= prev || c > n - 1)
+                return fail(VS_ERR_INVALID, "video %d: change point %d = %lld must be in 1 .. n - 1 = %d and above the one before it",
+                            b, i, (long long)c, n - 1);
+            c32[(size_t)at] = (int32_t)c;
+            prev = c;
+        }
+    }
+    if (!workspace || workspace_bytes < (size_t)P.total)
+        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    if (feats) {
+        if (int rc = table_k((const float *)x, d, cu, kern ? *kern : dot, P, ws, st)) return rc;
+    } else if (int rc = table(x, input, d, cu, P, ws, st)) {
+        return rc;
+    }
+    if (total_cps) KTS_LAUNCH(vsk_kts_put(c32.data(), (size_t)total_cps * 4, ws + P.vids[0].c_off, st));
+    KTS_LAUNCH(vsk_kts_eval((const KtsVideo *)ws, batch, ws, st));
+    // every video's s_off is (m + 1) doubles after the one before: gather the first of each on the host
+    int64_t n_scores = 0;
+    for (const KtsVideo &V : P.vids) n_scores += V.m + 1;
+    std::vector<double> s((size_t)n_scores);
+    KTS_HIP(hipMemcpyAsync(s.data(), ws + P.vids[0].s_off, (size_t)n_scores * 8, hipMemcpyDeviceToHost, st));
+    KTS_HIP(hipStreamSynchronize(st));
+    int64_t si = 0;
+    for (int32_t b = 0; b < batch; ++b) {
+        scores_out[b] = s[(size_t)si];
+        si += P.vids[b].m + 1;
+    }
     return VS_OK;
 }
 

@@ -5,6 +5,10 @@ Drop-in for the reference's ``segmentations`` package (``create_segments.get_seg
 scores / costs.  The scatter table and the dynamic program run in fp64 on the HIP kernels of ``csrc/vs_segment.hip``
 (C ABI ``include/vs_segment.h``); the Gram of ``kts_seg`` is fp32 on the matrix pipe.  There is no CPU path: without a
 HIP device every KTS call raises, as the scorer does.
+
+Beyond the reference: ``kernel="cosine"`` / ``"rbf"`` in ``kts_seg`` / ``kts_seg_batch`` (the reference's TODO "be sure to
+normalize frame features"), ``gram`` (the kernel matrices of a ragged batch in one launch, ``csrc/vs_segment_gram.hip``),
+and ``cpd_auto.py``'s helpers ``eval_score`` / ``eval_cost`` / ``estimate_vmax`` / ``centering``.
 """
 from __future__ import annotations
 
@@ -16,7 +20,7 @@ import torch
 from . import _lib
 
 __all__ = ["cpd_nonlin", "kts_segmentation", "kts_seg", "kts_seg_batch", "uniform_seg", "get_segment_fn",
-           "shots_from_change_points"]
+           "shots_from_change_points", "gram", "eval_score", "eval_cost", "estimate_vmax", "centering"]
 
 _LMAX = 100000
 
@@ -27,6 +31,18 @@ def _device(x):
     if not torch.cuda.is_available():
         raise RuntimeError("KTS segmentation runs on the MI355X HIP kernels only (no CPU path for the segmentation)")
     return torch.device("cuda", torch.cuda.current_device())
+
+
+def _kernel_device(x, kernel):
+    """_device for a kernel of the Gram.  "cosine" and "rbf" exist on the HIP kernels only, so without a HIP device they
+    are what every kernel but "dot" is in the reference: not implemented (NotImplementedError is a RuntimeError, the
+    type "dot" raises there)."""
+    try:
+        return _device(x)
+    except RuntimeError as e:
+        if kernel == "dot":
+            raise
+        raise NotImplementedError("kernel=%r: %s" % (kernel, e)) from None
 
 
 def _on_device(x, dtype, dev):
@@ -58,8 +74,27 @@ def _check_args(n, m, lmin, lmax):
         raise ValueError("needs lmax >= lmin >= 1 (lmin=%d lmax=%d)" % (lmin, lmax))
 
 
-def _segment(x, input_kind, lengths, ncp, mode, lmin=None, lmax=None, vmax=None, desc_rate=None):
-    """One vs_kts_segment call over a packed batch on x's device.  Returns (cps list, scores list) as numpy."""
+_KINDS = {"dot": _lib.VS_KTS_GRAM_DOT, "cosine": _lib.VS_KTS_GRAM_COSINE, "rbf": _lib.VS_KTS_GRAM_RBF}
+
+
+def _kernel_desc(kernel, gamma, D):
+    """vs_kts_kernel of (kernel, gamma): NotImplementedError for an unknown name, ValueError for a gamma that the kernel
+    does not take or that is not finite and > 0.  gamma=None with "rbf" is 1 / D."""
+    if kernel not in _KINDS:
+        raise NotImplementedError
+    if gamma is not None and kernel != "rbf":
+        raise ValueError("gamma is a parameter of kernel='rbf' only (got kernel=%r)" % (kernel,))
+    g = 0.0
+    if kernel == "rbf":
+        g = 1.0 / D if gamma is None else float(gamma)
+        if not (np.isfinite(g) and g > 0):
+            raise ValueError("gamma=%r must be finite and > 0" % (gamma,))
+    return _lib.KtsKernel(_KINDS[kernel], 0, g)
+
+
+def _segment(x, input_kind, lengths, ncp, mode, lmin=None, lmax=None, vmax=None, desc_rate=None, kern=None):
+    """One vs_kts_segment call (vs_kts_segment_k with a kernel descriptor) over a packed batch on x's device.  Returns
+    (cps list, scores list) as numpy."""
     lib = _lib.load()
     B = len(lengths)
     cu = _i32(np.concatenate([[0], np.cumsum(lengths)]))
@@ -69,7 +104,10 @@ def _segment(x, input_kind, lengths, ncp, mode, lmin=None, lmax=None, vmax=None,
     vm = _f64(vmax if vmax is not None else [0.0] * B)
     dr = _f64(desc_rate if desc_rate is not None else [1.0] * B)
     d = int(x.shape[-1]) if input_kind == _lib.VS_KTS_FEATURES_F32 else 0
-    nbytes = lib.vs_kts_workspace_bytes(_p(cu), B, d, input_kind, _p(ncp), mode)
+    if kern is None:
+        nbytes = lib.vs_kts_workspace_bytes(_p(cu), B, d, input_kind, _p(ncp), mode)
+    else:
+        nbytes = lib.vs_kts_workspace_bytes_k(_p(cu), B, d, input_kind, _p(ncp), mode, C.byref(kern))
     if nbytes == 0:
         _lib.check(_lib.VS_ERR_INVALID)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
@@ -77,8 +115,12 @@ def _segment(x, input_kind, lengths, ncp, mode, lmin=None, lmax=None, vmax=None,
     n_cps = np.zeros(B, dtype=np.int32)
     scores = np.zeros(int(ncp.sum()) + B, dtype=np.float64)
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    _lib.check(lib.vs_kts_segment(x.data_ptr(), input_kind, d, _p(cu), B, _p(ncp), _p(lmin), _p(lmax), _p(vm), _p(dr), mode,
-                                  _p(cps), _p(n_cps), _p(scores), ws.data_ptr(), nbytes, stream))
+    if kern is None:
+        _lib.check(lib.vs_kts_segment(x.data_ptr(), input_kind, d, _p(cu), B, _p(ncp), _p(lmin), _p(lmax), _p(vm), _p(dr), mode,
+                                      _p(cps), _p(n_cps), _p(scores), ws.data_ptr(), nbytes, stream))
+    else:
+        _lib.check(lib.vs_kts_segment_k(x.data_ptr(), input_kind, d, _p(cu), B, _p(ncp), _p(lmin), _p(lmax), _p(vm), _p(dr), mode,
+                                        C.byref(kern), _p(cps), _p(n_cps), _p(scores), ws.data_ptr(), nbytes, stream))
     out_c, out_s, ci, si = [], [], 0, 0
     for b in range(B):
         m = int(ncp[b])
@@ -159,34 +201,125 @@ def _features(features, dev):
     return f
 
 
-def kts_seg(features, num_seg: int, v_max: float, kernel: str = "dot"):
-    """create_segments.kts_seg: change points (int64) of X [n, D] under the dot kernel K = X X^T (not normalised)."""
-    if kernel != "dot":
-        raise NotImplementedError
-    return kts_seg_batch([features], num_seg, v_max)[0]
+def _width(f):
+    shape = f.shape if hasattr(f, "shape") else np.asarray(f).shape
+    return int(shape[-1]) if len(shape) else 1
 
 
-def kts_seg_batch(features_list, num_seg, v_max, lmin=1, lmax=_LMAX):
-    """kts_seg over a ragged corpus in one pass: one Gram per video, then the scatter tables and every dynamic-program
-    step for all videos together.  num_seg / v_max: one value, or one per video.  Returns a list of int64 arrays, each
-    equal to kts_seg of that video alone."""
-    feats = list(features_list)
-    if not feats:
-        return []
-    dev = _device(feats[0])
-    fs = [_features(f, dev) for f in feats]
+def _packed(features_list, kernel="dot"):
+    """(packed x [sum n, D] on the device, lengths) of a list of [n, D] feature arrays."""
+    dev = _kernel_device(features_list[0], kernel)
+    fs = [_features(f, dev) for f in features_list]
     D = fs[0].shape[1]
     if any(f.shape[1] != D for f in fs):
         raise ValueError("every video needs the same feature width")
-    B = len(fs)
+    return (torch.cat(fs, 0) if len(fs) > 1 else fs[0]), [int(f.shape[0]) for f in fs]
+
+
+def gram(features_list, kernel: str = "dot", gamma=None):
+    """The kernel matrices of a ragged list of videos, one Gram launch for all of them: a list of device float32 [n, n]
+    tensors (one array in: one tensor out).  kernel: "dot" (K = X X^T), "cosine" (rows normalised, an all-zero frame
+    gives a zero row and column) or "rbf" (exp(-gamma |x_i - x_j|^2), gamma=None: 1 / D).  K is symmetric bit for bit
+    and a video's K does not depend on the videos around it."""
+    single = not isinstance(features_list, (list, tuple))
+    feats = [features_list] if single else list(features_list)
+    if not feats:
+        return []
+    kern = _kernel_desc(kernel, gamma, _width(feats[0]))
+    x, lengths = _packed(feats, kernel)
+    lib = _lib.load()
+    B = len(lengths)
+    cu = _i32(np.concatenate([[0], np.cumsum(lengths)]))
+    nbytes = lib.vs_kts_gram_workspace_bytes(_p(cu), B, int(x.shape[1]))
+    if nbytes == 0:
+        _lib.check(_lib.VS_ERR_INVALID)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    out = torch.empty(sum(n * n for n in lengths), dtype=torch.float32, device=x.device)
+    _lib.check(lib.vs_kts_gram(x.data_ptr(), int(x.shape[1]), _p(cu), B, C.byref(kern), out.data_ptr(), ws.data_ptr(), nbytes,
+                               torch.cuda.current_stream(x.device).cuda_stream))
+    ws.record_stream(torch.cuda.current_stream(x.device))
+    Ks, at = [], 0
+    for n in lengths:
+        Ks.append(out[at:at + n * n].view(n, n))
+        at += n * n
+    return Ks[0] if single else Ks
+
+
+def kts_seg(features, num_seg: int, v_max: float, kernel: str = "dot", gamma=None):
+    """create_segments.kts_seg: change points (int64) of X [n, D].  kernel="dot": K = X X^T, not normalised (the
+    reference's only kernel); "cosine" / "rbf": see gram.  Any other name raises NotImplementedError, as the reference
+    does, and so do "cosine" / "rbf" where there is no HIP device; gamma with a kernel other than "rbf" is a ValueError."""
+    if kernel not in _KINDS:
+        raise NotImplementedError
+    return kts_seg_batch([features], num_seg, v_max, kernel=kernel, gamma=gamma)[0]
+
+
+def kts_seg_batch(features_list, num_seg, v_max, lmin=1, lmax=_LMAX, kernel: str = "dot", gamma=None):
+    """kts_seg over a ragged corpus in one pass: the Grams, then the scatter tables and every dynamic-program step for all
+    videos together.  num_seg / v_max: one value, or one per video.  Returns a list of int64 arrays, each equal to
+    kts_seg of that video alone.  kernel="dot" runs one exact-fp32 GEMM per video; "cosine" / "rbf" run the one-launch
+    ragged Gram (vs_kts_segment_k)."""
+    feats = list(features_list)
+    if kernel not in _KINDS:
+        raise NotImplementedError
+    if gamma is not None and kernel != "rbf":
+        raise ValueError("gamma is a parameter of kernel='rbf' only (got kernel=%r)" % (kernel,))
+    if not feats:
+        return []
+    kern = None if kernel == "dot" else _kernel_desc(kernel, gamma, _width(feats[0]))
+    x, lengths = _packed(feats, kernel)
+    B = len(lengths)
     per = lambda v: list(v) if np.ndim(v) else [v] * B
     ncp, vmax, lmin, lmax = [int(v) for v in per(num_seg)], [float(v) for v in per(v_max)], per(lmin), per(lmax)
-    lengths = [int(f.shape[0]) for f in fs]
     for n, m, lo, hi in zip(lengths, ncp, lmin, lmax):
         _check_args(n, m, int(lo), int(hi))
-    x = torch.cat(fs, 0) if B > 1 else fs[0]
-    cps, _ = _segment(x, _lib.VS_KTS_FEATURES_F32, lengths, ncp, _lib.VS_KTS_AUTO, lmin, lmax, vmax)
+    cps, _ = _segment(x, _lib.VS_KTS_FEATURES_F32, lengths, ncp, _lib.VS_KTS_AUTO, lmin, lmax, vmax, kern=kern)
     return cps
+
+
+def eval_score(K, cps):
+    """cpd_auto.eval_score: the unnormalised empirical score (sum of the kernelised scatters of the segments) of the given
+    change points, from the scatter table on the device - bit-equal to cpd_nonlin's score of its own change points."""
+    t, kind = _kernel_input(K)
+    n = int(t.shape[0])
+    c = np.ascontiguousarray(np.asarray(list(cps), dtype=np.int64).reshape(-1))
+    m = int(c.size)
+    if m and (c[0] < 1 or c[-1] > n - 1 or (np.diff(c) <= 0).any()):
+        raise ValueError("change points must be strictly increasing in 1 .. n - 1 = %d (got %s)" % (n - 1, c.tolist()))
+    lib = _lib.load()
+    cu, ncp = _i32([0, n]), _i32([m])
+    nbytes = lib.vs_kts_workspace_bytes(_p(cu), 1, 0, kind, _p(ncp), _lib.VS_KTS_SCORES)
+    if nbytes == 0:
+        _lib.check(_lib.VS_ERR_INVALID)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
+    out = np.zeros(1, dtype=np.float64)
+    cbuf = c if m else np.zeros(1, dtype=np.int64)
+    _lib.check(lib.vs_kts_eval_score(t.data_ptr(), kind, 0, None, _p(cu), 1, _p(cbuf), _p(ncp), _p(out), ws.data_ptr(), nbytes,
+                                     torch.cuda.current_stream(t.device).cuda_stream))
+    return float(out[0])
+
+
+def eval_cost(K, cps, score, vmax):
+    """cpd_auto.eval_cost: score / N + the penalty of len(cps) change points, host arithmetic in the reference's order."""
+    N = np.shape(K)[0]
+    penalty = (vmax * len(cps) / (2.0 * N)) * (np.log(float(N) / len(cps)) + 1)
+    return score / float(N) + penalty
+
+
+def centering(K):
+    """cpd_auto.centering: K - row means - column means + the mean of the row means (K symmetric)."""
+    if isinstance(K, torch.Tensor):
+        mean_rows = K.mean(1, keepdim=True)
+        return K - mean_rows - mean_rows.T + mean_rows.mean()
+    K = np.asarray(K)
+    mean_rows = np.mean(K, 1)[:, np.newaxis]
+    return K - mean_rows - mean_rows.T + np.mean(mean_rows)
+
+
+def estimate_vmax(K_stable):
+    """cpd_auto.estimate_vmax: trace(centering(K) / n) of a stable segment's kernel = the scatter of the whole segment
+    over n, which is eval_score with no change point."""
+    return eval_score(K_stable, []) / np.shape(K_stable)[0]
 
 
 def uniform_seg(n_frames: int, sec_per_seg: int = 2, fps: int = 2):

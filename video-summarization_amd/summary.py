@@ -124,11 +124,11 @@ def _score_on_device(model, feats, dev, max_frames):
 
 
 def summarize(model, features, n_frames=None, picks=None, change_points=None, num_seg=None, v_max=1.0, proportion=0.15,
-              max_frames=65536):
+              max_frames=65536, kernel="dot", gamma=None):
     """The summaries of new videos end to end.  features: list of [T_i, 1024]; picks (default arange(T_i)) and n_frames
     (default T_i) as in the reference's records; change_points: per video [n_shots, 2], or None: the shots then come
-    from ONE kts_seg_batch(features, min(num_seg, T_i - 1), v_max) and shots_from_change_points.  The scores never visit
-    the host.  -> list of ``Summary``."""
+    from ONE kts_seg_batch(features, min(num_seg, T_i - 1), v_max, kernel=kernel, gamma=gamma) and
+    shots_from_change_points.  The scores never visit the host.  -> list of ``Summary``."""
     import torch
     from . import segmentation
     model.eval()
@@ -143,7 +143,8 @@ def summarize(model, features, n_frames=None, picks=None, change_points=None, nu
             if num_seg is None:
                 raise ValueError("summarize needs change_points or num_seg (the number of KTS change points)")
             per = list(num_seg) if np.ndim(num_seg) else [num_seg] * len(T)
-            cps = segmentation.kts_seg_batch(feats, [min(int(m), t - 1) for m, t in zip(per, T)], v_max)
+            cps = segmentation.kts_seg_batch(feats, [min(int(m), t - 1) for m, t in zip(per, T)], v_max, kernel=kernel,
+                                             gamma=gamma)
             change_points = [segmentation.shots_from_change_points(c, nf, p) for c, nf, p in zip(cps, n_frames, picks)]
     return summarize_scores(flat, change_points, n_frames, picks, proportion, n_scores=T)
 
