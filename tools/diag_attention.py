@@ -56,7 +56,7 @@ def run(B, H, T, dh=64):
     tot = d[:, 8]
     print("B=%d H=%d T=%d: stamped %.4f ms (%.1f TF), product kernel %.4f ms (%.1f TF = %.3f of 157.3); %d blocks x 8 waves, %d tiles per block"
           % (B, H, T, ms, fl / ms / 1e9, ms_p, fl / ms_p / 1e9, fl / ms_p / 1e9 / 157.3, nblk, nt))
-    mf_tile = 130.0                      # MFMAs per wave and 64-key tile (2 x (1 bias + 32 S' + 32 P.V))
+    mf_tile = 128.0                      # MFMAs per wave and 64-key tile (2 x (32 S' + 32 P.V); the row bias is a C operand)
     print("   cycles per wave: total med %.0f (min %.0f max %.0f); ideal = 2 waves/SIMD x %d tiles x %d MFMAs x 64 = %.0f -> MFMA share %.3f"
           % (tot.median().item(), tot.min().item(), tot.max().item(), nt, mf_tile, 2 * nt * mf_tile * 64, 2 * nt * mf_tile * 64 / tot.median().item()))
     for i in (12, 0, 1, 2, 3, 4, 5, 6, 7):
@@ -67,8 +67,8 @@ def run(B, H, T, dh=64):
             per.min().item(), per.max().item()))
     fixed = (d[:, 0] + d[:, 12] + d[:, 7]).median().item()
     loop = (d[:, 1:7].sum(1)).median().item()
-    print("   fixed per block (Q fetch + prologue + epilogue) %.0f cycles = %.2f %% ; tile loop %.0f cycles = %.0f per tile (2 x 65 MFMAs x 64 x 2 waves = %.0f)"
-          % (fixed, 100 * fixed / tot.median().item(), loop, loop / nt, 2 * 65 * 64 * 2))
+    print("   fixed per block (Q fetch + prologue + epilogue) %.0f cycles = %.2f %% ; tile loop %.0f cycles = %.0f per tile (%d MFMAs x 64 x 2 waves = %.0f)"
+          % (fixed, 100 * fixed / tot.median().item(), loop, loop / nt, mf_tile, mf_tile * 64 * 2))
     t0, t1 = d[:, 9], d[:, 10]
     base = t0.min()
     life = (t1 - t0) / 100

@@ -1237,8 +1237,10 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_lp_pipe(
 // or not.  So this kernel is built to issue as few VALU instructions per MFMA as possible:
 //  * K/V tiles arrive through buffer loads whose per-tile offset is a scalar (no address VALU, and the
 //    hardware bounds check zero-fills the ragged tail);
-//  * the running row max m is folded into the product: S' = [K,1]*[Q,-m]^T costs one extra MFMA per
-//    32-key block and replaces the accumulator zero-init and the 16 subtracts before exp2;
+//  * the running row max m is folded into the product: a 16-register block holds -m per lane and is the C
+//    operand of a block's first S' MFMA (S' = K*Q^T - m); it replaces the accumulator zero-init and the 16
+//    subtracts before exp2, costs no instruction per block, and is rewritten only in the rare fix-up (round 8;
+//    until then a bias MFMA [K,1]*[Q,-m]^T per block produced the same bits);
 //  * deferred max: m is only raised (and O, l rescaled) when a block's max exceeds it by more than
 //    2^8 — exact in fp32 (p <= 256 instead of <= 1) and almost never taken after the first block;
 //  * the key-mask bias (0/-inf) is added only on tiles that have masked keys or the ragged tail.
@@ -1246,7 +1248,10 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_lp_pipe(
 // exp2, row sum) runs between them; then O^T += V_b^T * P_b^T with the V operands prefetched into
 // registers.  K/V tiles of 64 keys are double-buffered in LDS; global loads of tile t+2 and LDS writes
 // of tile t+1 ride in the MFMA stream of tile t.  NW waves per block (8: one block per CU, all
-// blocks take the same time; 4: for short videos).
+// blocks take the same time; 4: for short videos).  8-wave blocks run the loop two tiles per iteration, so
+// the buffer parity and every LDS address are immediates; a block's maximum is a tree of 7 v_max3 + 1 v_max
+// (tests/test_attention_fp32_schedule.py counts the emitted loop: 128 MFMAs, 104 other vector instructions
+// per tile).
 // ------------------------------------------------------------------------------------------
 // VARLEN (packed ragged batches, vs_scorer_forward_packed): the videos' frames are concatenated ([Mtot, .] rows,
 // video b = rows cu[b] .. cu[b+1]), q/k/v are head-major over the packed rows ([H][Mtot][DH]) and the grid is
@@ -1255,6 +1260,32 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_lp_pipe(
 // diag[(block * NW + wave) * 16 + ..]: 0 prologue, 1 barrier A, 2 half-step A (S' of block 1 || softmax of block 0),
 // 3 P.V of block 0, 4 barrier B, 5 half-step B, 6 P.V of block 1, 7 epilogue, 8 total cycles, 9 / 10 wall clock
 // (100 MHz) at wave start / end, 11 tiles, 12 Q fetch (inside 0)
+// The maxima of attn_fwd_pipe's block maximum, as the instructions themselves: from fmaxf hipcc re-associates the tree
+// and quiets inputs it cannot prove canonical with an extra v_max_f32 x, x each (13 instructions for 16 values, and 5 for
+// the exchange between the half-waves).  No NaN reaches these (S' is finite or -inf), so the instructions' own
+// semantics are fmaxf's.  Their inputs are MFMA results that are more than a dozen MFMAs old where they are read.
+__device__ __forceinline__ float max3f(float a, float b, float c) {
+    float d;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
+}
+__device__ __forceinline__ float max2f(float a, float b) {
+    float d;
+    asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+}
+__device__ __forceinline__ float pair_max2f(float x) {      // pair_max (vs_device.h) on max2f
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    auto pr = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return max2f(__builtin_bit_cast(float, (unsigned)pr[0]), __builtin_bit_cast(float, (unsigned)pr[1]));
+}
+// D = A * B + C with D in registers of its own (C stays live): hipcc otherwise copies C into D first, 16 moves
+__device__ __forceinline__ f32x16 mfma32_keep_c(float a, float b, const f32x16 &c) {
+    f32x16 d;
+    asm("v_mfma_f32_32x32x2_f32 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
+}
+
 template <int DH, bool HAS_MASK, int NW, bool VARLEN = false, int DIAG = 0>
 __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_pipe(
     const float *__restrict__ Q, const float *__restrict__ Kg, const float *__restrict__ Vg,
@@ -1327,8 +1358,14 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_pipe(
         for (int t = 0; t < 16; ++t) o[d][t] = 0.f;
     // m_run: running max (log2 units) actually applied to O and l; -inf until the first live key.
     // m_use(m) = m, or 0 while m is still -inf (keeps exp2 arguments finite-or--inf, never inf-inf).
-    float m_run = NEG_INF, l_run = 0.f;
-    const float ones_a = h == 0 ? 1.0f : 0.0f;      // A operand of the bias step: adds B[0][q] to every key row
+    // u_run = m_use(m_run) and thr_run = m_run + THR are kept beside m_run: all three change only in the fix-up.
+    float m_run = NEG_INF, l_run = 0.f, u_run = 0.f, thr_run = NEG_INF;
+    // Row bias: -u_run in all 16 registers, the C operand of a block's first S' MFMA.  Rewritten only where m_run
+    // changes (fix-up).  The value is what the bias MFMA of earlier versions produced, 1*(-m) + 0*(-m) + 0: +0.0f
+    // for m = 0, never -0.0f, so the first accumulation rounds as it always did.
+    f32x16 cbias;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) cbias[t] = 0.f;
 
     // ---- staging: buffer loads (scalar per-tile offset, zero fill beyond T), then LDS writes ----
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(
@@ -1346,19 +1383,20 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_pipe(
     auto gload_k = [&](int i, int tile) __attribute__((always_inline)) { pk[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, voff[i], tile * (KT * DH * 4), 0)); };
     auto gload_v = [&](int i, int tile) __attribute__((always_inline)) { pv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, voff[i], tile * (KT * DH * 4), 0)); };
     auto gload_m = [&](int tile) __attribute__((always_inline)) {      // key-mask bias of key (tid & 63): 0 or -inf (also for keys >= T)
-        const int key = tile * KT + (tid & (KT - 1));
+        // Without a mask only the last tile's bias is ever read (MASKED is set for that tile alone), so every tile
+        // stages the last tile's: the same values where they are used, and nothing to compute per tile.
+        const int key = (HAS_MASK ? tile : ntiles - 1) * KT + (tid & (KT - 1));
         float pmv = key >= T ? NEG_INF : 0.f;
         if (HAS_MASK) pmv = mask[(size_t)b * T + (key < T ? key : T - 1)] != 0 ? NEG_INF : pmv;
         pm = pmv;
     };
-    auto stage_k = [&](int i, int buf) __attribute__((always_inline)) {
-        const int idx = tid + NT * i;
-        *(f32x4 *)&smem[buf * 2 * TILE + (idx / (DH / 4)) * LD + (idx % (DH / 4)) * 4] = pk[i];
-    };
-    auto stage_v = [&](int i, int buf) __attribute__((always_inline)) {
-        const int idx = tid + NT * i;
-        *(f32x4 *)&smem[buf * 2 * TILE + TILE + (idx / (DH / 4)) * LD + (idx % (DH / 4)) * 4] = pv[i];
-    };
+    // LDS position of this thread's first staged float4 inside a tile; float4 i lies i * SROW floats further on
+    // (NT threads cover NT / (DH / 4) whole key rows), so with the buffer a constant every address is base + immediate
+    static_assert(NT % (DH / 4) == 0, "a staging pass covers whole key rows");
+    constexpr int SROW = (NT / (DH / 4)) * LD;
+    float *const sdst = smem + (tid / (DH / 4)) * LD + (tid % (DH / 4)) * 4;
+    auto stage_k = [&](int i, int buf) __attribute__((always_inline)) { *(f32x4 *)&sdst[buf * 2 * TILE + i * SROW] = pk[i]; };
+    auto stage_v = [&](int i, int buf) __attribute__((always_inline)) { *(f32x4 *)&sdst[buf * 2 * TILE + TILE + i * SROW] = pv[i]; };
 
     // ---- softmax state of the block in flight ----
     float sm_mx = 0.f, sm_psum = 0.f;
@@ -1377,7 +1415,10 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_pipe(
 #pragma unroll
             for (int t = 0; t < 16; ++t) o[d][t] *= alpha;
         l_run *= alpha;
-        m_run = m_new;
+        m_run = m_new; u_run = u_new; thr_run = m_new + THR;
+        const float nb = 0.0f - u_new;                          // +0.0f for u_new = 0 (see cbias)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) cbias[t] = nb;
     };
     // One unit of block-b softmax work, issued between two MFMAs of block b+1's S'.  sv = S' of block b
     // (biased by -m_bias), MASKED: add the key-mask bias first.
@@ -1390,17 +1431,17 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_pipe(
             for (int e = 0; e < 4; ++e) sv[4 * U + e] += bv[e];
         }
         if constexpr (U == 4) {
-            sm_mx = fmaxf(fmaxf(sv[0], sv[1]), sv[2]);
-#pragma unroll
-            for (int t = 3; t < 15; t += 2) sm_mx = fmaxf(fmaxf(sm_mx, sv[t]), sv[t + 1]);
-            sm_mx = fmaxf(sm_mx, sv[15]);
+            // 16-way maximum as a tree of three-input maxima (7 + one two-input): max is exact and associative here
+            // (no NaN: S' is finite or -inf), so any grouping gives the same value
+            const float a0 = max3f(sv[0], sv[1], sv[2]), a1 = max3f(sv[3], sv[4], sv[5]), a2 = max3f(sv[6], sv[7], sv[8]);
+            const float a3 = max3f(sv[9], sv[10], sv[11]), a4 = max3f(sv[12], sv[13], sv[14]);
+            sm_mx = max2f(max3f(a0, a1, a2), max3f(a3, a4, sv[15]));
         }
         if constexpr (U == 5) {
-            const float raw_max = pair_max(sm_mx) + m_bias;      // -inf if every key so far is masked
-            const float u_run = (m_run == NEG_INF) ? 0.f : m_run;
-            const bool fix = (m_bias != u_run) || (raw_max > m_run + THR) || (m_run == NEG_INF && raw_max != NEG_INF);
+            const float raw_max = pair_max2f(sm_mx) + m_bias;    // -inf if every key so far is masked
+            // raw_max > thr_run covers the first live block too: thr_run is -inf while m_run is, and raw_max is never NaN
+            const bool fix = (m_bias != u_run) || (raw_max > thr_run);
             if (__builtin_expect(__any(fix), 0)) fixup(sv, m_bias, raw_max);
-            sm_psum = 0.f;
         }
         if constexpr (U >= 8 && U < 16) {
             constexpr int k = U - 8;
@@ -1408,30 +1449,33 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_pipe(
             for (int e = 0; e < 2; ++e) {
                 const float pe_ = __builtin_amdgcn_exp2f(sv[2 * k + e]);
                 sv[2 * k + e] = pe_;
-                sm_psum += pe_;
+                // the row sum starts at its first term: 0.f + p is p bit for bit (v_exp_f32 returns +0 or a normal number)
+                if (k == 0 && e == 0) sm_psum = pe_; else sm_psum += pe_;
             }
         }
         if constexpr (U == 16) l_run += pair_sum(sm_psum);
     };
-    // MFMA stream of one half-step:  s_out = [K_blk,1]*[Q,-m_bias]^T  (1 + 4*NJ MFMAs), with between
-    // consecutive MFMAs: one V operand of block (Vsrc,vblk) into vreg, one softmax unit of s_in, and
-    // (STAGE) the LDS writes of tile t+1 / buffer loads of tile t+2.
-    auto half_step = [&](const float *Ksrc, int blk, f32x16 &s_out, float m_bias_out, f32x16 &s_in, float m_bias_in,
+    // This lane's fragment positions inside a tile; the tile, buffer and block offsets on top are compile-time constants.
+    const float *const kfrag = smem + r * LD + 4 * h;
+    const float *const vfrag = smem + 4 * h * LD + r;
+    // MFMA stream of one half-step:  s_out = K_blk*Q^T - u_run  (4*NJ MFMAs, the row bias enters as the C operand
+    // of the first), with between consecutive MFMAs: one V operand of block (Vsrc,vblk) into vreg, one softmax unit
+    // of s_in, and (STAGE) the LDS writes of tile t+1 / buffer loads of tile t+2.  Ksrc, Vsrc, mb are smem + constant.
+    auto half_step = [&](const float *Ksrc, int blk, f32x16 &s_out, f32x16 &s_in, float m_bias_in,
                          const float *mb, const float *Vsrc, int vblk, auto masked_tag, auto stage_tag, int nbuf, int ntile) __attribute__((always_inline)) {
         constexpr bool STAGE = decltype(stage_tag)::value;
         constexpr int NSLOT = 4 * NJ, R = 32 / NSLOT;      // softmax units per MFMA slot (DH=64: 1, DH=32: 2)
         static_assert(NSLOT == 16 * ND, "one V operand per MFMA slot");
-        const float *kp = Ksrc + (32 * blk + r) * LD + 4 * h;
-        const float *vp = Vsrc + (32 * vblk + 4 * h) * LD + r;
+        const float *kp = kfrag + ((Ksrc - smem) + 32 * blk * LD);
+        const float *vp = vfrag + ((Vsrc - smem) + 32 * vblk * LD);
         f32x4 ka[2];
         ka[0] = *(const f32x4 *)kp;
-        const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        s_out = MFMA32(ones_a, -m_bias_out, zero);
-        __builtin_amdgcn_sched_barrier(0);
+        const f32x16 c0 = cbias;                           // the bias this block starts with (a fix-up may rewrite cbias)
         static_for<NSLOT>([&](auto ic) {
             constexpr int i = decltype(ic)::value, j = i / 4, st = i % 4;
             if constexpr (st == 0 && j + 1 < NJ) ka[(j + 1) & 1] = *(const f32x4 *)(kp + 8 * (j + 1));
-            s_out = MFMA32(ka[j & 1][st], qreg[4 * j + st], s_out);
+            if constexpr (i == 0) s_out = mfma32_keep_c(ka[0][0], qreg[0], c0);      // the row bias -u_run is the C operand
+            else s_out = MFMA32(ka[j & 1][st], qreg[4 * j + st], s_out);
             {
                 constexpr int t = i / ND, d = i % ND;
                 vreg[i] = vp[((t & 3) + 8 * (t >> 2)) * LD + 32 * d];
@@ -1446,12 +1490,16 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_pipe(
                     if constexpr (U == 17 + 2 * F4) gload_m(ntile);
                 }
             });
+            // The compiler does not know that mfma32_keep_c reads its C registers for 16 passes: keep them alive (and
+            // so unwritten) until the next MFMA has issued behind it.  The fix-up, which rewrites cbias, comes later.
+            if constexpr (i == 1) asm volatile("" :: "v"(c0));
             __builtin_amdgcn_sched_barrier(0);
         });
     };
     // softmax alone (last block of the video: nothing left to overlap with)
     auto softmax_only = [&](f32x16 &sv, float m_bias, const float *mb, const float *Vsrc, int vblk, auto masked_tag) __attribute__((always_inline)) {
-        const float *vp = Vsrc + (32 * vblk + 4 * h) * LD + r;
+        const float *vp = vfrag + ((Vsrc - smem) + 32 * vblk * LD);
+        __builtin_amdgcn_sched_barrier(0);     // max3f / max2f stay behind the P.V MFMAs that follow this block's S'
 #pragma unroll
         for (int i = 0; i < 16 * ND; ++i) vreg[i] = vp[(((i / ND) & 3) + 8 * ((i / ND) >> 2)) * LD + 32 * (i % ND)];
         static_for<32>([&](auto uc) { sm_unit(uc, sv, m_bias, mb, masked_tag); });
@@ -1494,16 +1542,18 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_pipe(
 
     // One 64-key tile.  LAST (the video's final tile) is peeled out of the loop so that the loop body has
     // no branch besides the rare fix-up: a branch there costs 64 accumulator-register copies per tile.
-    auto tile_step = [&](int t, auto masked_tag, auto last_tag) __attribute__((always_inline)) {
+    // In 8-wave blocks the LDS buffer (t & 1) is a compile-time constant - the loop below runs two tiles per
+    // iteration - so every LDS address of the tile is a per-lane base that never changes plus an immediate.
+    auto tile_step = [&](int t, auto buf_tag, auto masked_tag, auto last_tag) __attribute__((always_inline)) {
         constexpr bool LAST = decltype(last_tag)::value;
-        const int buf = t & 1;
+        const int buf = buf_tag;               // std::integral_constant (a constant after inlining) or t & 1
         const float *Ks = smem + buf * 2 * TILE, *Vs = Ks + TILE;
         const float *Kn = smem + (buf ^ 1) * 2 * TILE;
         __syncthreads();                       // everyone is done with buffer buf^1 (tile t-1)
         lap(1);
         // S' of block (t,1)  ||  softmax of block (t,0), LDS writes of tile t+1, loads of tile t+2
-        mb_nxt = (m_run == NEG_INF) ? 0.f : m_run;
-        half_step(Ks, 1, s_nxt, mb_nxt, s_cur, mb_cur, mbs + buf * KT, Vs, 0, masked_tag, std::integral_constant<bool, !LAST>{},
+        mb_nxt = u_run;
+        half_step(Ks, 1, s_nxt, s_cur, mb_cur, mbs + buf * KT, Vs, 0, masked_tag, std::integral_constant<bool, !LAST>{},
                   buf ^ 1, t + 2 < ntiles ? t + 2 : ntiles - 1);
         lap(2);
         pv_acc(s_cur);
@@ -1512,8 +1562,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_pipe(
         lap(4);
         if constexpr (!LAST) {
             // S' of block (t+1,0)  ||  softmax of block (t,1)
-            mb_cur = (m_run == NEG_INF) ? 0.f : m_run;
-            half_step(Kn, 0, s_cur, mb_cur, s_nxt, mb_nxt, mbs + buf * KT + 32, Vs, 1, masked_tag, std::false_type{}, 0, 0);
+            mb_cur = u_run;
+            half_step(Kn, 0, s_cur, s_nxt, mb_nxt, mbs + buf * KT + 32, Vs, 1, masked_tag, std::false_type{}, 0, 0);
         } else {
             softmax_only(s_nxt, mb_nxt, mbs + buf * KT + 32, Vs, 1, masked_tag);
         }
@@ -1522,10 +1572,32 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_pipe(
         lap(6);
     };
     lap(0);
-    // without a mask only the ragged last tile carries dead keys
-    for (int t = 0; t + 1 < ntiles; ++t) tile_step(t, std::integral_constant<bool, HAS_MASK>{}, std::false_type{});
-    if (HAS_MASK || (T % KT) != 0) tile_step(ntiles - 1, std::true_type{}, std::true_type{});
-    else                           tile_step(ntiles - 1, std::false_type{}, std::true_type{});
+    constexpr std::integral_constant<int, 0> B0{};
+    constexpr std::integral_constant<int, 1> B1{};
+    constexpr std::integral_constant<bool, HAS_MASK> MK{};
+    const bool dead_keys = HAS_MASK || (T % KT) != 0;      // without a mask only the ragged last tile carries dead keys
+    int t = 0;
+    if constexpr (NW != 8) {
+        // 4-wave blocks stage twice the float4s per thread and have no registers left for the second copy of the
+        // loop body: one tile per iteration, the buffer a run-time value
+        for (; t + 1 < ntiles; ++t) tile_step(t, t & 1, MK, std::false_type{});
+        if (dead_keys) tile_step(t, t & 1, std::true_type{}, std::true_type{});
+        else           tile_step(t, t & 1, std::false_type{}, std::true_type{});
+    } else {
+        for (; t + 2 < ntiles; t += 2) {           // steady state: two tiles per iteration, neither is the last
+            tile_step(t, B0, MK, std::false_type{});
+            tile_step(t + 1, B1, MK, std::false_type{});
+        }
+        // remainder: one tile (the last, in buffer 0) or two (one more steady tile, then the last in buffer 1)
+        if (t + 2 == ntiles) {
+            tile_step(t, B0, MK, std::false_type{});
+            if (dead_keys) tile_step(t + 1, B1, std::true_type{}, std::true_type{});
+            else           tile_step(t + 1, B1, std::false_type{}, std::true_type{});
+        } else {
+            if (dead_keys) tile_step(t, B0, std::true_type{}, std::true_type{});
+            else           tile_step(t, B0, std::false_type{}, std::true_type{});
+        }
+    }
 
     // ---- epilogue: O^T[d][q] / l -> out[b, q, head*DH + d], through the wave-private LDS corner so that
     // every store instruction writes whole 128-byte lines (DH/4 lanes per row) ----
