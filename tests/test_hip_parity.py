@@ -637,6 +637,37 @@ def test_attention_bf16_stored_w64_operand_layout_is_exact_on_a_permutation(vsa,
 
 
 @pytest.mark.gpu
+def test_w64_masked_long_on_a_second_device(vsa, lp_linear_everywhere):
+    """The masked one-wave-per-SIMD kernel needs more dynamic LDS than a launch may use by default once the key-bias table
+    has 65 tiles (T = 4160: the smallest such shape), and that limit is a per-DEVICE attribute of the kernel
+    (csrc/vs_launch.h: vsk_raise_lds).  It used to be raised once per process: the second device's launch failed.  One
+    process, device 0 then device 1: both succeed with the same bits."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("one device visible: the per-device LDS limit needs two")
+    synth = vsa.synth
+    T = 4160
+    sd = synth.make_state_dict(256, 1, 311, trained_like=True)
+    x = synth.make_features(1, T, 312, "pool5")
+    mask = torch.zeros(1, T, dtype=torch.bool)
+    mask[:, T - 30:] = True
+    outs = []
+    try:
+        vsa._lib.set_option("VS_ATTN_W64", 1)
+        for dev in (torch.device("cuda:0"), torch.device("cuda:1")):
+            m = vsa.SimNet(num_heads=4, d_model=256, num_layers=1, sparsity=0.0, dropout=0.0)
+            m.load_state_dict(sd, strict=True)
+            m = m.to(dev).eval().set_compute_dtype("bf16")
+            with torch.no_grad():
+                logits = m(x.to(dev), mask.to(dev))[0]
+            torch.cuda.synchronize(dev)
+            outs.append(logits.cpu())
+    finally:
+        vsa._lib.set_option("VS_ATTN_W64", -1)
+    assert torch.isfinite(outs[0][:, :T - 30]).all()
+    assert torch.equal(outs[0], outs[1])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("T", [64, 127, 320, 1024])
 def test_attention_bf16_stored_logits_beyond_2_to_the_14(vsa, T):
     """The 8-wave bf16 kernel carries its row constant through a bf16 operand, i.e. rounded to a bf16 grid point; it used to

@@ -4,6 +4,7 @@
 //   attn_fwd_lp(_pipe)  opt-in low-precision matrix pipes: bf16 operands, or fp32 emulated with f16 hi+lo halves
 #include "vs_device.h"
 #include "vs_kernels.h"
+#include "vs_launch.h"
 
 namespace {
 
@@ -1655,12 +1656,11 @@ int vsk_diag_attention_lp(const float *q, const float *k, const float *v, float 
     dim3 g(8 * ((BH + 7) / 8) * nq);
     const float sl2 = scale * 1.4426950408889634f;
     if (prec >= 100) {      // timing ablations of the bf16 kernel (no stamps): prec = 100 + ABL
-#define VSK_ABL(A_) case A_: hipLaunchKernelGGL((attn_fwd_lp_pipe<64, 8, 1, false, true, 0, A_>), g, dim3(512), 0, st, q, k, v, nullptr, out, H, T, sl2, BH, nullptr, nullptr, 0, nullptr); break;
-        switch (prec - 100) {
-            VSK_ABL(0) VSK_ABL(1) VSK_ABL(2) VSK_ABL(3) VSK_ABL(4) VSK_ABL(5) VSK_ABL(7) VSK_ABL(16) VSK_ABL(17) VSK_ABL(19)
-            default: return -1;
-        }
-#undef VSK_ABL
+        if (!vsk_pick_int<0, 1, 2, 3, 4, 5, 7, 16, 17, 19>(prec - 100, [&](auto ABL) {
+                hipLaunchKernelGGL((attn_fwd_lp_pipe<64, 8, 1, false, true, 0, ABL()>), g, dim3(512), 0, st, q, k, v, nullptr, out, H, T,
+                                   sl2, BH, nullptr, nullptr, 0, nullptr);
+            }))
+            return -1;
         VSK_CHECK_LAUNCH();
         return (int)g.x;
     }
@@ -1697,16 +1697,14 @@ int vsk_attention(const float *q, const float *k, const float *v, const uint8_t 
         const bool wide = !vsk_options().attn_nw4 && r8 * 100 <= r4 * 105;
         const int nq = wide ? r8 / 256 : r4 / 128;
         dim3 g(8 * ((BH + 7) / 8) * nq), blk(wide ? 512 : 256);
-#define VSK_ATTN(DH_, MASK_, NW_) \
-    hipLaunchKernelGGL((attn_fwd_pipe<DH_, MASK_, NW_, false>), g, blk, 0, st, q, k, v, mask, out, H, T, sl2, BH, nullptr, nullptr, 0, nullptr)
-        if (dh == 32) {
-            if (mask) { if (wide) VSK_ATTN(32, true, 8); else VSK_ATTN(32, true, 4); }
-            else      { if (wide) VSK_ATTN(32, false, 8); else VSK_ATTN(32, false, 4); }
-        } else {
-            if (mask) { if (wide) VSK_ATTN(64, true, 8); else VSK_ATTN(64, true, 4); }
-            else      { if (wide) VSK_ATTN(64, false, 8); else VSK_ATTN(64, false, 4); }
-        }
-#undef VSK_ATTN
+        vsk_pick_int<32, 64>(dh, [&](auto DH) {
+            vsk_pick_bool(mask != nullptr, [&](auto MASK) {
+                vsk_pick_int<4, 8>(wide ? 8 : 4, [&](auto NW) {
+                    hipLaunchKernelGGL((attn_fwd_pipe<DH(), MASK(), NW(), false>), g, blk, 0, st, q, k, v, mask, out, H, T, sl2, BH,
+                                       nullptr, nullptr, 0, nullptr);
+                });
+            });
+        });
     }
     else if (dh == 128)
         hipLaunchKernelGGL((attn_fwd<128, 1>), grid, dim3(256), 0, st, q, k, v, mask, out, H, T, sl2, BH);
@@ -1729,6 +1727,8 @@ int vsk_attention_splitkv(const float *q, const float *k, const float *v, const 
     return 0;
 }
 
+static constexpr int row(int dh, int nw) { return 16 * dh + nw; }      // (head dim, 4 or 8 waves) as one pick key
+
 // packed ragged batch: q/k/v [H][Mtot][dh] head-major over the packed rows, cu [B+1] row offsets, work[nwork] =
 // (video, query tile of 32*nw rows); exact fp32, head dim 32 / 64
 int vsk_attention_packed(const float *q, const float *k, const float *v, float *out, int H, int Mtot, int dh,
@@ -1739,40 +1739,38 @@ int vsk_attention_packed(const float *q, const float *k, const float *v, float *
         return vsk_attention_bf16_w64_packed(q, k, v, out, H, Mtot, cu, work, nwork, st);
     dim3 grid(nwork, H);
     const int2 *wk = (const int2 *)work;
-#define VSK_ATTN_PX(DH_, NW_) \
-    hipLaunchKernelGGL((attn_fwd_pipe<DH_, false, NW_, true>), grid, dim3(64 * NW_), 0, st, q, k, v, nullptr, out, H, 0, sl2, 0, cu, wk, Mtot, nullptr)
-#define VSK_ATTN_PE(DH_, NW_, P_) \
-    hipLaunchKernelGGL((attn_fwd_lp_pipe<DH_, NW_, P_, true>), grid, dim3(64 * NW_), 0, st, q, k, v, nullptr, out, H, 0, sl2, 0, cu, wk, Mtot)
-#define VSK_ATTN_P16(DH_, NW_) \
-    hipLaunchKernelGGL((attn_fwd_lp_pipe<DH_, NW_, 1, true, true>), grid, dim3(64 * NW_), 0, st, q, k, v, nullptr, out, H, 0, sl2, 0, cu, wk, Mtot)
-    if (prec == (1 | VSK_STORE16)) {      // bf16 q (pre-scaled) / k / v in, bf16 out
-        if (dh == 64 && nw == 8) VSK_ATTN_P16(64, 8);
-        else if (dh == 64 && nw == 4) VSK_ATTN_P16(64, 4);
-        else if (dh == 32 && nw == 4) VSK_ATTN_P16(32, 4);
-        else return -1;
-    } else if (prec == 2) {
-        if (dh == 64 && nw == 8) VSK_ATTN_PE(64, 8, 2);
-        else if (dh == 64 && nw == 4) VSK_ATTN_PE(64, 4, 2);
-        else if (dh == 32 && nw == 4) VSK_ATTN_PE(32, 4, 2);
-        else return -1;
-    } else if (prec == 1) {
-        if (dh == 128 && nw == 8) VSK_ATTN_PE(128, 8, 1);       // head dim 128 (round 4), fp32 q / k / v in HBM
-        else if (dh == 64 && nw == 8) VSK_ATTN_PE(64, 8, 1);
-        else if (dh == 64 && nw == 4) VSK_ATTN_PE(64, 4, 1);
-        else if (dh == 32 && nw == 4) VSK_ATTN_PE(32, 4, 1);
-        else return -1;
-    } else {
-        if (dh == 128 && nw == 4)       // exact fp32, head dim 128 (M-B): 128-row work items through the non-pipelined kernel
-            hipLaunchKernelGGL((attn_fwd<128, 1, true>), grid, dim3(256), 0, st, q, k, v, nullptr, out, H, 0, sl2, 0, cu, wk, Mtot);
-        else if (dh == 64 && nw == 8) VSK_ATTN_PX(64, 8);
-        else if (dh == 64 && nw == 4) VSK_ATTN_PX(64, 4);
-        else if (dh == 32 && nw == 8) VSK_ATTN_PX(32, 8);
-        else if (dh == 32 && nw == 4) VSK_ATTN_PX(32, 4);
-        else return -1;
-    }
-#undef VSK_ATTN_PX
-#undef VSK_ATTN_PE
-#undef VSK_ATTN_P16
+    // the supported (head dim, waves per block) rows of each precision; what is not listed has no kernel: -1
+    if (nw != 4 && nw != 8) return -1;
+    const int r = row(dh, nw);
+    bool found;
+    if (prec == (1 | VSK_STORE16))      // bf16 q (pre-scaled) / k / v in, bf16 out
+        found = vsk_pick_int<row(64, 8), row(64, 4), row(32, 4)>(r, [&](auto ROW) {
+            constexpr int DH = ROW() / 16, NW = ROW() % 16;
+            hipLaunchKernelGGL((attn_fwd_lp_pipe<DH, NW, 1, true, true>), grid, dim3(64 * NW), 0, st, q, k, v, nullptr, out, H, 0, sl2, 0,
+                               cu, wk, Mtot);
+        });
+    else if (prec == 2)                 // fp16x3 on fp32 q / k / v
+        found = vsk_pick_int<row(64, 8), row(64, 4), row(32, 4)>(r, [&](auto ROW) {
+            constexpr int DH = ROW() / 16, NW = ROW() % 16;
+            hipLaunchKernelGGL((attn_fwd_lp_pipe<DH, NW, 2, true>), grid, dim3(64 * NW), 0, st, q, k, v, nullptr, out, H, 0, sl2, 0, cu,
+                               wk, Mtot);
+        });
+    else if (prec == 1)                 // bf16 on fp32 q / k / v in HBM; head dim 128: round 4
+        found = vsk_pick_int<row(128, 8), row(64, 8), row(64, 4), row(32, 4)>(r, [&](auto ROW) {
+            constexpr int DH = ROW() / 16, NW = ROW() % 16;
+            hipLaunchKernelGGL((attn_fwd_lp_pipe<DH, NW, 1, true>), grid, dim3(64 * NW), 0, st, q, k, v, nullptr, out, H, 0, sl2, 0, cu,
+                               wk, Mtot);
+        });
+    else                                // exact fp32; head dim 128 (M-B): 128-row work items through the non-pipelined kernel
+        found = vsk_pick_int<row(128, 4), row(64, 8), row(64, 4), row(32, 8), row(32, 4)>(r, [&](auto ROW) {
+            constexpr int DH = ROW() / 16, NW = ROW() % 16;
+            if constexpr (DH == 128)
+                hipLaunchKernelGGL((attn_fwd<128, 1, true>), grid, dim3(256), 0, st, q, k, v, nullptr, out, H, 0, sl2, 0, cu, wk, Mtot);
+            else
+                hipLaunchKernelGGL((attn_fwd_pipe<DH, false, NW, true>), grid, dim3(64 * NW), 0, st, q, k, v, nullptr, out, H, 0, sl2, 0,
+                                   cu, wk, Mtot, nullptr);
+        });
+    if (!found) return -1;
     VSK_CHECK_LAUNCH();
     return 0;
 }
@@ -1796,32 +1794,24 @@ int vsk_attention_bf16(const float *q, const float *k, const float *v, const uin
         VSK_CHECK_LAUNCH();
         return 0;
     }
-#define VSK_ATTN_LP(KERN_, P_)                                                                                           \
-    if (dh == 64 && wide)                                                                                                \
-        hipLaunchKernelGGL((KERN_<64, 8, P_>), grid, dim3(512), 0, st, q, k, v, mask, out, H, T, sl2, BH);               \
-    else if (dh == 64)                                                                                                   \
-        hipLaunchKernelGGL((KERN_<64, 4, P_>), grid, dim3(256), 0, st, q, k, v, mask, out, H, T, sl2, BH);               \
-    else if (dh == 32)                                                                                                   \
-        hipLaunchKernelGGL((KERN_<32, 4, P_>), grid, dim3(256), 0, st, q, k, v, mask, out, H, T, sl2, BH);               \
-    else                                                                                                                 \
+    const bool io16 = prec == (1 | VSK_STORE16);      // bf16 q (pre-scaled) / k / v in, bf16 out: the pipelined kernel only
+    if (io16 && dh == 64 && wide && vsk_options().attn_w64) {      // one wave per SIMD, 4 waves x 64 query rows (vs_attention_w64.hip)
+        const int rc = vsk_attention_bf16_w64(q, k, v, mask, out, B, H, T, st);
+        if (rc != -1) return rc;
+    }
+    // (head dim, waves per block): 8 waves at head dim 64 only
+    if (!vsk_pick_int<row(64, 8), row(64, 4), row(32, 4)>(row(dh, wide ? 8 : 4), [&](auto ROW) {
+            constexpr int DH = ROW() / 16, NW = ROW() % 16;
+            if (io16) {
+                hipLaunchKernelGGL((attn_fwd_lp_pipe<DH, NW, 1, false, true>), grid, dim3(64 * NW), 0, st, q, k, v, mask, out, H, T, sl2, BH);
+                return;
+            }
+            vsk_pick_int<1, 2>(prec == 2 ? 2 : 1, [&](auto P) {
+                if (simple) hipLaunchKernelGGL((attn_fwd_lp<DH, NW, P()>), grid, dim3(64 * NW), 0, st, q, k, v, mask, out, H, T, sl2, BH);
+                else hipLaunchKernelGGL((attn_fwd_lp_pipe<DH, NW, P()>), grid, dim3(64 * NW), 0, st, q, k, v, mask, out, H, T, sl2, BH);
+            });
+        }))
         return -1;
-    if (prec == (1 | VSK_STORE16)) {      // bf16 q (pre-scaled) / k / v in, bf16 out: the pipelined kernel only
-        if (dh == 64 && wide && vsk_options().attn_w64) {      // one wave per SIMD, 4 waves x 64 query rows (vs_attention_w64.hip)
-            const int rc = vsk_attention_bf16_w64(q, k, v, mask, out, B, H, T, st);
-            if (rc != -1) return rc;
-        }
-        if (dh == 64 && wide)
-            hipLaunchKernelGGL((attn_fwd_lp_pipe<64, 8, 1, false, true>), grid, dim3(512), 0, st, q, k, v, mask, out, H, T, sl2, BH);
-        else if (dh == 64)
-            hipLaunchKernelGGL((attn_fwd_lp_pipe<64, 4, 1, false, true>), grid, dim3(256), 0, st, q, k, v, mask, out, H, T, sl2, BH);
-        else if (dh == 32)
-            hipLaunchKernelGGL((attn_fwd_lp_pipe<32, 4, 1, false, true>), grid, dim3(256), 0, st, q, k, v, mask, out, H, T, sl2, BH);
-        else
-            return -1;
-    } else
-    if (simple) { if (prec == 2) { VSK_ATTN_LP(attn_fwd_lp, 2) } else { VSK_ATTN_LP(attn_fwd_lp, 1) } }
-    else        { if (prec == 2) { VSK_ATTN_LP(attn_fwd_lp_pipe, 2) } else { VSK_ATTN_LP(attn_fwd_lp_pipe, 1) } }
-#undef VSK_ATTN_LP
     VSK_CHECK_LAUNCH();
     return 0;
 }

@@ -21,10 +21,9 @@
 // ds_read_b128, V^T fragments by ds_read_b64_tr_b16, the S' accumulator registers packed pairwise ARE the B operand of
 // the second product.  Softmax: P = exp2(S') against a row constant c kept >= max - 1 (raised to max + 6 when a P
 // reaches 2: OR test on the packed P; rare path), l from the rounded P on the matrix pipe.
-#include <atomic>
-
 #include "vs_device.h"
 #include "vs_kernels.h"
+#include "vs_launch.h"
 
 // The instruction stream itself is generated (tools/gen_attn_w64.py -> vs_attention_w64_asm.inc): hipcc, given the
 // 512-register budget, moves the S' accumulators through v_accvgpr_read / write around every exp2.
@@ -232,32 +231,24 @@ int vsk_attention_bf16_w64(const void *q, const void *k, const void *v, const ui
     dim3 grid(8 * ((BH + 7) / 8) * nq);
     if (mask != nullptr) {
         // key-bias table of the whole row + one flag byte per tile behind the 48 KiB of K / V ring: beyond the 64 KiB a
-        // launch may use by default, so the limit of this kernel is raised once (gfx950: 160 KiB per workgroup)
+        // launch may use by default, so the limit of this kernel is raised once per device (gfx950: 160 KiB per workgroup)
         const size_t dyn = (size_t)ntiles * 64 * sizeof(float) + (size_t)((ntiles + 15) / 16 * 16);
         if (dyn > 96 * 1024 || ntiles > 2048) return -1;
-        static std::atomic<int> raised{0};
-        if (!raised.load(std::memory_order_acquire)) {
-            if (hipFuncSetAttribute((const void *)attn_fwd_bf16_w64<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) {
-                (void)hipGetLastError();
-                return -1;
-            }
-            raised.store(1, std::memory_order_release);
+        if (vsk_raise_lds<attn_fwd_bf16_w64<false, true>>(96 * 1024) != 0) {
+            (void)hipGetLastError();
+            return -1;
         }
         hipLaunchKernelGGL((attn_fwd_bf16_w64<false, true>), grid, dim3(256), dyn, st, (const h16 *)q, (const h16 *)k, (const h16 *)v,
                            mask, (h16 *)out, H, T, BH, nullptr, nullptr, 0, 1);
     } else {
-#ifdef VS_WITH_DIAG
-#define VS_W64_LAUNCH_ABL(A_) case A_: hipLaunchKernelGGL((attn_fwd_bf16_w64<false, false, A_>), grid, dim3(256), 256, st, (const h16 *)q, (const h16 *)k, (const h16 *)v, nullptr, (h16 *)out, H, T, BH, nullptr, nullptr, 0, 0); break;
-        switch (vsk_options().attn_w64_abl) {
-            VS_W64_LAUNCH_ABL(1) VS_W64_LAUNCH_ABL(2) VS_W64_LAUNCH_ABL(4) VS_W64_LAUNCH_ABL(8) VS_W64_LAUNCH_ABL(14) VS_W64_LAUNCH_ABL(15) VS_W64_LAUNCH_ABL(512) VS_W64_LAUNCH_ABL(1024)
-            default:
+#ifdef VS_WITH_DIAG     // timing ablations (generated by tools/gen_attn_w64.py --abl): wrong values by construction
+        if (!vsk_pick_int<1, 2, 4, 8, 14, 15, 512, 1024>(vsk_options().attn_w64_abl, [&](auto ABL) {
+                hipLaunchKernelGGL((attn_fwd_bf16_w64<false, false, ABL()>), grid, dim3(256), 256, st, (const h16 *)q, (const h16 *)k,
+                                   (const h16 *)v, nullptr, (h16 *)out, H, T, BH, nullptr, nullptr, 0, 0);
+            }))
 #endif
         hipLaunchKernelGGL((attn_fwd_bf16_w64<false, false>), grid, dim3(256), 256, st, (const h16 *)q, (const h16 *)k, (const h16 *)v,
                            nullptr, (h16 *)out, H, T, BH, nullptr, nullptr, 0, vsk_options().attn_w64_checked ? 1 : 0);
-#ifdef VS_WITH_DIAG
-        }
-#undef VS_W64_LAUNCH_ABL
-#endif
     }
     VSK_CHECK_LAUNCH();
     return 0;

@@ -14,10 +14,9 @@
 // A lane fetches FOUR consecutive k of its row with one 16-byte LDS read (k = 8*g + 4*h + s,
 // s = 0..3) and feeds them to four MFMA steps; step s therefore contracts k in {8g+s, 8g+4+s}.
 // The k order inside a sum is irrelevant as long as A and B use the same one.
-#include <atomic>
-
 #include "vs_train_device.h"     // dropout hash (vs_device.h comes with it)
 #include "vs_kernels.h"
+#include "vs_launch.h"
 
 namespace {
 
@@ -2175,22 +2174,9 @@ int vsk_sum_parts_pe(const float *parts, int nsplit, const float *bias, const fl
     VSK_CHECK_LAUNCH();
     return 0;
 }
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute: set it once per (kernel, device).  `done` is
-// the call site's own per-device flag array (one per kernel instantiation).
-enum { VSK_MAX_DEVICES = 64 };
-static int allow_big_lds_on_device(const void *kernel, std::atomic<unsigned char> *done) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipErrorInvalidDevice;
-    if (dev >= 0 && dev < VSK_MAX_DEVICES && done[dev].load(std::memory_order_acquire)) return 0;
-    const int rc = (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 1028 * 4);
-    if (rc == 0 && dev >= 0 && dev < VSK_MAX_DEVICES) done[dev].store(1, std::memory_order_release);
-    return rc;
-}
-#define VSK_ALLOW_BIG_LDS(kernel_)                                          \
-    ([]() -> int {                                                          \
-        static std::atomic<unsigned char> done_[VSK_MAX_DEVICES];           \
-        return allow_big_lds_on_device((const void *)(kernel_), done_);     \
-    }())
+// the most dynamic LDS a skinny2 kernel is launched with (K >= 1024): above the 64 KiB default, so its limit is raised to
+// this once per device (vsk_raise_lds), whatever the K of the first call
+static const size_t SKINNY2_LDS_MAX = skinny2_lds(1024);
 
 // LPP: the PREC of the 16-bit-operand branch - 1 bf16, 3 f16 (the training path's fp16 mode; bf16 flag | VSK_F16)
 template <int EPI, int LPP = 1>
@@ -2202,7 +2188,7 @@ static int launch_gemm(const float *A, const float *W, const float *Wf, const fl
     const bool kw64 = K % 64 == 0 && K >= 512;
     if (bf16 == 2 && Wf != nullptr && M <= skinny_max_rows() && N % 32 == 0 && K % 128 == 0) {
         // fp16x3 latency kernels (Wf is then the pack_fragments_f16x3 copy)
-        if (const int attr_rc = VSK_ALLOW_BIG_LDS((skinny2_gemm<EPI, 2>))) return attr_rc;
+        if (const int attr_rc = vsk_raise_lds<skinny2_gemm<EPI, 2>>(SKINNY2_LDS_MAX)) return attr_rc;
         dim3 grid((M + 31) / 32, (N + 127) / 128);
         hipLaunchKernelGGL((skinny2_gemm<EPI, 2>), grid, dim3(256), skinny2_lds(K), st, A, Wf, bias, C, M, N, K, pe, T, H, dh, ea);
         VSK_CHECK_LAUNCH();
@@ -2280,7 +2266,7 @@ static int launch_gemm(const float *A, const float *W, const float *Wf, const fl
         return 0;
     }
     if (Wf != nullptr && M <= skinny_max_rows() && N % 32 == 0 && K % 128 == 0) {
-        if (const int attr_rc = VSK_ALLOW_BIG_LDS((skinny2_gemm<EPI, 0>))) return attr_rc;
+        if (const int attr_rc = vsk_raise_lds<skinny2_gemm<EPI, 0>>(SKINNY2_LDS_MAX)) return attr_rc;
         dim3 grid((M + 31) / 32, (N + 127) / 128);
         hipLaunchKernelGGL((skinny2_gemm<EPI, 0>), grid, dim3(256), skinny2_lds(K), st, A, Wf, bias, C, M, N, K, pe, T, H, dh, ea);
         VSK_CHECK_LAUNCH();
@@ -2469,20 +2455,17 @@ int vsk_linear_res_ln(const float *A, const float *W, const float *Wf, const flo
                       const float *gamma, const float *beta, float *out, int M, int N, int K,
                       const float *score_w, const float *score_b, int num_classes, int sigmoid,
                       float *scores, int bf16, hipStream_t st) {
+    // every branch: the kernel's width parameter is N / 32 (N / 64 in the last), picked as a constant (vs_launch.h)
     if (bf16 == 2 && Wf != nullptr && M <= skinny_max_rows() && N <= 256 && N % 32 == 0 && K % 128 == 0) {
         const int blocks = (M + 31) / 32;       // fp16x3 latency kernel (Wf: pack_fragments_f16x3 copy)
-#define VSK_SLN3_CASE(NW_)                                                                                 \
-    case NW_: {                                                                                            \
-        if (const int attr_rc = VSK_ALLOW_BIG_LDS((skinny2_ln<NW_, 2>))) return attr_rc;                   \
-        hipLaunchKernelGGL((skinny2_ln<NW_, 2>), dim3(blocks), dim3(64 * NW_), skinny2_lds(K), st, A, Wf, bias, res, \
-                           gamma, beta, out, M, K, score_w, score_b, num_classes, sigmoid, scores);        \
-        break;                                                                                             \
-    }
-        switch (N / 32) {
-            VSK_SLN3_CASE(2) VSK_SLN3_CASE(4) VSK_SLN3_CASE(6) VSK_SLN3_CASE(8)
-            default: return -1;
-        }
-#undef VSK_SLN3_CASE
+        int rc = 0;
+        if (!vsk_pick_int<2, 4, 6, 8>(N / 32, [&](auto NW) {
+                if ((rc = vsk_raise_lds<skinny2_ln<NW(), 2>>(SKINNY2_LDS_MAX)) != 0) return;
+                hipLaunchKernelGGL((skinny2_ln<NW(), 2>), dim3(blocks), dim3(64 * NW()), skinny2_lds(K), st, A, Wf, bias, res, gamma, beta,
+                                   out, M, K, score_w, score_b, num_classes, sigmoid, scores);
+            }))
+            return -1;
+        if (rc) return rc;
         VSK_CHECK_LAUNCH();
         return 0;
     }
@@ -2494,55 +2477,41 @@ int vsk_linear_res_ln(const float *A, const float *W, const float *Wf, const flo
         int blocks = persistent_blocks((M + 127) / 128);
         if (blocks < 0) return (int)hipErrorInvalidDevice;
         if (blocks > (M + 127) / 128) blocks = (M + 127) / 128;
-#define VSK_LNB_CASE(NT_)                                                                                   \
-    case NT_:                                                                                               \
-        if (bf16 == 2)                                                                                      \
-            hipLaunchKernelGGL((gemm_ln_rows<NT_, 2>), dim3(blocks), dim3(256), 0, st, A, W, bias, res, gamma, \
-                               beta, out, M, K, score_w, score_b, num_classes, sigmoid, scores);            \
-        else if (a16)                                                                                       \
-            hipLaunchKernelGGL((gemm_ln_rows<NT_, 1, 1>), dim3(blocks), dim3(256), 0, st, A, W, bias, res, gamma, \
-                               beta, out, M, K, score_w, score_b, num_classes, sigmoid, scores);            \
-        else                                                                                                \
-            hipLaunchKernelGGL((gemm_ln_rows<NT_, 1>), dim3(blocks), dim3(256), 0, st, A, W, bias, res, gamma, \
-                               beta, out, M, K, score_w, score_b, num_classes, sigmoid, scores);            \
-        break;
-        switch (N / 32) {
-            VSK_LNB_CASE(2) VSK_LNB_CASE(4) VSK_LNB_CASE(6) VSK_LNB_CASE(8)
-            default: return -1;
-        }
-#undef VSK_LNB_CASE
+        if (!vsk_pick_int<2, 4, 6, 8>(N / 32, [&](auto NT) {
+                if (bf16 == 2)
+                    hipLaunchKernelGGL((gemm_ln_rows<NT(), 2>), dim3(blocks), dim3(256), 0, st, A, W, bias, res, gamma, beta, out, M, K,
+                                       score_w, score_b, num_classes, sigmoid, scores);
+                else if (a16)
+                    hipLaunchKernelGGL((gemm_ln_rows<NT(), 1, 1>), dim3(blocks), dim3(256), 0, st, A, W, bias, res, gamma, beta, out, M, K,
+                                       score_w, score_b, num_classes, sigmoid, scores);
+                else
+                    hipLaunchKernelGGL((gemm_ln_rows<NT(), 1>), dim3(blocks), dim3(256), 0, st, A, W, bias, res, gamma, beta, out, M, K,
+                                       score_w, score_b, num_classes, sigmoid, scores);
+            }))
+            return -1;
         VSK_CHECK_LAUNCH();
         return 0;
     }
     if (Wf != nullptr && M <= skinny_max_rows() && N <= 256 && N % 32 == 0 && K % 128 == 0) {
         const int blocks = (M + 31) / 32;
-#define VSK_SLN2_CASE(NW_)                                                                                 \
-    case NW_: {                                                                                            \
-        if (const int attr_rc = VSK_ALLOW_BIG_LDS((skinny2_ln<NW_, 0>))) return attr_rc;                   \
-        hipLaunchKernelGGL((skinny2_ln<NW_, 0>), dim3(blocks), dim3(64 * NW_), skinny2_lds(K), st, A, Wf, bias, res, \
-                           gamma, beta, out, M, K, score_w, score_b, num_classes, sigmoid, scores);        \
-        break;                                                                                             \
-    }
-        switch (N / 32) {
-            VSK_SLN2_CASE(2) VSK_SLN2_CASE(4) VSK_SLN2_CASE(6) VSK_SLN2_CASE(8)
-            default: return -1;
-        }
-#undef VSK_SLN2_CASE
+        int rc = 0;
+        if (!vsk_pick_int<2, 4, 6, 8>(N / 32, [&](auto NW) {
+                if ((rc = vsk_raise_lds<skinny2_ln<NW(), 0>>(SKINNY2_LDS_MAX)) != 0) return;
+                hipLaunchKernelGGL((skinny2_ln<NW(), 0>), dim3(blocks), dim3(64 * NW()), skinny2_lds(K), st, A, Wf, bias, res, gamma, beta,
+                                   out, M, K, score_w, score_b, num_classes, sigmoid, scores);
+            }))
+            return -1;
+        if (rc) return rc;
         VSK_CHECK_LAUNCH();
         return 0;
     }
     if (M <= skinny_max_rows() && N <= 256 && N % 32 == 0 && K % 128 == 0) {
         const int blocks = (M + 31) / 32;
-#define VSK_SLN_CASE(NW_)                                                                          \
-    case NW_:                                                                                      \
-        hipLaunchKernelGGL(skinny_ln<NW_>, dim3(blocks), dim3(64 * NW_), 0, st, A, W, bias, res, gamma, \
-                           beta, out, M, K, score_w, score_b, num_classes, sigmoid, scores);       \
-        break;
-        switch (N / 32) {
-            VSK_SLN_CASE(2) VSK_SLN_CASE(4) VSK_SLN_CASE(6) VSK_SLN_CASE(8)
-            default: return -1;
-        }
-#undef VSK_SLN_CASE
+        if (!vsk_pick_int<2, 4, 6, 8>(N / 32, [&](auto NW) {
+                hipLaunchKernelGGL(skinny_ln<NW()>, dim3(blocks), dim3(64 * NW()), 0, st, A, W, bias, res, gamma, beta, out, M, K, score_w,
+                                   score_b, num_classes, sigmoid, scores);
+            }))
+            return -1;
         VSK_CHECK_LAUNCH();
         return 0;
     }
@@ -2550,35 +2519,24 @@ int vsk_linear_res_ln(const float *A, const float *W, const float *Wf, const flo
         int blocks = persistent_blocks((M + 127) / 128);
         if (blocks < 0) return (int)hipErrorInvalidDevice;
         if (blocks > (M + 127) / 128) blocks = (M + 127) / 128;
-#define VSK_LNR_CASE(NT_)                                                                             \
-    case NT_:                                                                                         \
-        hipLaunchKernelGGL((gemm_ln_rows<NT_, 0>), dim3(blocks), dim3(256), 0, st, A, W, bias, res, gamma, \
-                           beta, out, M, K, score_w, score_b, num_classes, sigmoid, scores);          \
-        break;
-        switch (N / 32) {
-            VSK_LNR_CASE(2) VSK_LNR_CASE(4) VSK_LNR_CASE(6) VSK_LNR_CASE(8)
-            default: return -1;
-        }
-#undef VSK_LNR_CASE
+        if (!vsk_pick_int<2, 4, 6, 8>(N / 32, [&](auto NT) {
+                hipLaunchKernelGGL((gemm_ln_rows<NT(), 0>), dim3(blocks), dim3(256), 0, st, A, W, bias, res, gamma, beta, out, M, K,
+                                   score_w, score_b, num_classes, sigmoid, scores);
+            }))
+            return -1;
         VSK_CHECK_LAUNCH();
         return 0;
     }
     const int blocks = (M + 63) / 64;
-#define VSK_LN_CASE(NB_)                                                                                  \
-    case NB_:                                                                                             \
-        if (bf16 == 2)                                                                                    \
-            hipLaunchKernelGGL((gemm_res_ln<NB_, 2>), dim3(blocks), dim3(256), 0, st, A, W, bias, res, gamma, \
-                               beta, out, M, K, score_w, score_b, num_classes, sigmoid, scores);          \
-        else                                                                                              \
-            hipLaunchKernelGGL((gemm_res_ln<NB_, 0>), dim3(blocks), dim3(256), 0, st, A, W, bias, res, gamma, \
-                               beta, out, M, K, score_w, score_b, num_classes, sigmoid, scores);          \
-        break;
-    switch (N / 64) {
-        VSK_LN_CASE(1) VSK_LN_CASE(2) VSK_LN_CASE(3) VSK_LN_CASE(4)
-        VSK_LN_CASE(5) VSK_LN_CASE(6) VSK_LN_CASE(7) VSK_LN_CASE(8)
-        default: return -1;
-    }
-#undef VSK_LN_CASE
+    if (!vsk_pick_int<1, 2, 3, 4, 5, 6, 7, 8>(N / 64, [&](auto NB) {
+            if (bf16 == 2)
+                hipLaunchKernelGGL((gemm_res_ln<NB(), 2>), dim3(blocks), dim3(256), 0, st, A, W, bias, res, gamma, beta, out, M, K,
+                                   score_w, score_b, num_classes, sigmoid, scores);
+            else
+                hipLaunchKernelGGL((gemm_res_ln<NB(), 0>), dim3(blocks), dim3(256), 0, st, A, W, bias, res, gamma, beta, out, M, K,
+                                   score_w, score_b, num_classes, sigmoid, scores);
+        }))
+        return -1;
     VSK_CHECK_LAUNCH();
     return 0;
 }

@@ -41,8 +41,7 @@
 // SIMD (NWV = 4, two 128-row tiles per CU) takes 106 us against 79.
 #include "vs_device.h"
 #include "vs_kernels.h"
-
-#include <atomic>
+#include "vs_launch.h"
 
 namespace {
 
@@ -690,19 +689,6 @@ constexpr size_t EMBED_LDS = (size_t)3 * MLP_IMG + 4 * MLP_D * sizeof(float);
 
 constexpr size_t MLP_LDS = (size_t)3 * MLP_IMG + (MLP_HID + 10 * MLP_D) * sizeof(float);      // 134 KiB
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is per DEVICE: set once per (kernel instantiation, device)
-template <bool TAIL, int NWV, int ABL>
-int allow_lds() {
-    static std::atomic<unsigned char> done[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipErrorInvalidDevice;
-    if (dev >= 0 && dev < 64 && done[dev].load(std::memory_order_acquire)) return 0;
-    const int rc = (int)hipFuncSetAttribute((const void *)mlp_fused_bf16<TAIL, NWV, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)MLP_LDS);
-    if (rc == 0 && dev >= 0 && dev < 64) done[dev].store(1, std::memory_order_release);
-    return rc;
-}
-
 }  // namespace
 
 size_t vsk_mlp_bf16_image_bytes(int d) { return d == MLP_D ? (size_t)MLP_CHUNKS * MLP_IMG : 0; }
@@ -739,22 +725,14 @@ int vsk_embed_bf16(const float *x, const void *img, const float *bias, const flo
     const EmbedArgs ea{x, K, bias, pe, T};
     const QkvArgs qa = next ? QkvArgs{(const unsigned char *)next->img, next->bqkv, (h16 *)next->qkv16, next->T, next->H, d / next->H, next->qscale}
                             : QkvArgs{nullptr, nullptr, nullptr, 1, 1, d, 1.0f};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipErrorInvalidDevice;
-#define VSK_EMBED_LAUNCH(W_)                                                                                            \
-    do {                                                                                                                \
-        static std::atomic<unsigned char> done[64];      /* hipFuncAttributeMaxDynamicSharedMemorySize is per DEVICE */  \
-        if (!(dev >= 0 && dev < 64 && done[dev].load(std::memory_order_acquire))) {                                     \
-            const int rc = (int)hipFuncSetAttribute((const void *)embed_qkv_bf16<W_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EMBED_LDS); \
-            if (rc) return rc;                                                                                          \
-            if (dev >= 0 && dev < 64) done[dev].store(1, std::memory_order_release);                                    \
-        }                                                                                                               \
-        const int ntiles = (M + 32 * W_ - 1) / (32 * W_);                                                               \
-        hipLaunchKernelGGL(embed_qkv_bf16<W_>, dim3(ntiles < cus ? ntiles : cus), dim3(64 * W_), EMBED_LDS, st, ea, qa,  \
-                           (const unsigned char *)img, out, M);                                                         \
-    } while (0)
-    if (vsk_fused_half_tiles(M, cus)) VSK_EMBED_LAUNCH(4); else VSK_EMBED_LAUNCH(8);
-#undef VSK_EMBED_LAUNCH
+    int rc = 0;
+    vsk_pick_int<4, 8>(vsk_fused_half_tiles(M, cus) ? 4 : 8, [&](auto NWV) {
+        if ((rc = vsk_raise_lds<embed_qkv_bf16<NWV()>>(EMBED_LDS)) != 0) return;
+        const int ntiles = (M + 32 * NWV() - 1) / (32 * NWV());
+        hipLaunchKernelGGL(embed_qkv_bf16<NWV()>, dim3(ntiles < cus ? ntiles : cus), dim3(64 * NWV()), EMBED_LDS, st, ea, qa,
+                           (const unsigned char *)img, out, M);
+    });
+    if (rc) return rc;
     VSK_CHECK_LAUNCH();
     return 0;
 }
@@ -785,31 +763,26 @@ int vsk_mlp_bf16(const float *h, const void *att16, const float *bo, const float
     const TailArgs ta{(const h16 *)att16, h, bo, gamma1, beta1};
     const QkvArgs qa = next ? QkvArgs{(const unsigned char *)next->img, next->bqkv, (h16 *)next->qkv16, next->T, next->H, d / next->H, next->qscale}
                             : QkvArgs{nullptr, nullptr, nullptr, 1, 1, d, 1.0f};
-#define VSK_MLP_LAUNCH(T_, W_, A_)                                                                                     \
-    do {                                                                                                               \
-        if (const int rc = allow_lds<T_, W_, A_>()) return rc;                                                         \
-        const int ntiles = (M + 32 * W_ - 1) / (32 * W_);                                                              \
-        hipLaunchKernelGGL((mlp_fused_bf16<T_, W_, A_>), dim3(ntiles < cus ? ntiles : cus), dim3(64 * W_), MLP_LDS, st, h, ta, qa, \
-                           (const unsigned char *)img, b1, b2, gamma, beta, out, M, score_w, score_b, num_classes, sigmoid, scores); \
-    } while (0)
+    int rc = 0;
+    auto launch = [&](auto TAIL, auto NWV, auto ABL) {
+        if ((rc = vsk_raise_lds<mlp_fused_bf16<TAIL(), NWV(), ABL()>>(MLP_LDS)) != 0) return;
+        const int ntiles = (M + 32 * NWV() - 1) / (32 * NWV());
+        hipLaunchKernelGGL((mlp_fused_bf16<TAIL(), NWV(), ABL()>), dim3(ntiles < cus ? ntiles : cus), dim3(64 * NWV()), MLP_LDS, st, h, ta,
+                           qa, (const unsigned char *)img, b1, b2, gamma, beta, out, M, score_w, score_b, num_classes, sigmoid, scores);
+    };
 #ifdef VS_WITH_DIAG
-    switch (vsk_options().mlp_abl) {       // timing-only ablations of the MLP-block kernel (tools/bench_mlp_fused.py)
-        case 0: break;
-        case 1: VSK_MLP_LAUNCH(false, 8, 1); VSK_CHECK_LAUNCH(); return 0;
-        case 2: VSK_MLP_LAUNCH(false, 8, 2); VSK_CHECK_LAUNCH(); return 0;
-        case 3: VSK_MLP_LAUNCH(false, 8, 3); VSK_CHECK_LAUNCH(); return 0;
-        case 4: VSK_MLP_LAUNCH(false, 8, 4); VSK_CHECK_LAUNCH(); return 0;
-        case 5: VSK_MLP_LAUNCH(false, 8, 5); VSK_CHECK_LAUNCH(); return 0;
-        case 7: VSK_MLP_LAUNCH(false, 8, 7); VSK_CHECK_LAUNCH(); return 0;
-        default: VSK_MLP_LAUNCH(false, 8, 8); VSK_CHECK_LAUNCH(); return 0;
+    if (const int abl = vsk_options().mlp_abl) {       // timing-only ablations of the MLP-block kernel (tools/bench_mlp_fused.py)
+        const bool own = (abl >= 1 && abl <= 5) || abl == 7;       // every other value runs ablation 8
+        vsk_pick_int<1, 2, 3, 4, 5, 7, 8>(own ? abl : 8, [&](auto ABL) { launch(std::false_type{}, vsk_int<8>{}, ABL); });
+        if (rc) return rc;
+        VSK_CHECK_LAUNCH();
+        return 0;
     }
 #endif
-    if (vsk_fused_half_tiles(M, cus)) {
-        if (att16 != nullptr) VSK_MLP_LAUNCH(true, 4, 0); else VSK_MLP_LAUNCH(false, 4, 0);
-    } else {
-        if (att16 != nullptr) VSK_MLP_LAUNCH(true, 8, 0); else VSK_MLP_LAUNCH(false, 8, 0);
-    }
-#undef VSK_MLP_LAUNCH
+    vsk_pick_bool(att16 != nullptr, [&](auto TAIL) {
+        vsk_pick_int<4, 8>(vsk_fused_half_tiles(M, cus) ? 4 : 8, [&](auto NWV) { launch(TAIL, NWV, vsk_int<0>{}); });
+    });
+    if (rc) return rc;
     VSK_CHECK_LAUNCH();
     return 0;
 }

@@ -32,8 +32,7 @@
 // (plan_packed_train) and streams only that video's rows cu[b] .. cu[b+1]: the difference to the padded form is confined to
 // owner_tile() (vs_train_attention_owner.h) - where the block's rows, its keep words and its dropout row keys live - so a video's tile loops, LDS layout
 // and summation order are those of the same video run alone.  No key mask: a packed batch has no padded rows.
-#include <atomic>
-
+#include "vs_launch.h"
 #include "vs_train_attention_owner.h"
 #include "vs_train_device.h"
 #include "vs_train_kernels.h"
@@ -533,39 +532,25 @@ __global__ __launch_bounds__(256) void rows_dropout_mask(uint8_t *__restrict__ k
 
 }  // namespace
 
-// dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize, a per-DEVICE attribute: set once per
-// (kernel instantiation, device) - `done` is the call site's own flag array
-static int allow_lds(const void *kernel, size_t bytes, std::atomic<unsigned char> *done) {
-    if (bytes <= 64 * 1024) return 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipErrorInvalidDevice;
-    if (dev >= 0 && dev < 64 && done[dev].load(std::memory_order_acquire)) return 0;
-    const int rc = (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (rc == 0 && dev >= 0 && dev < 64) done[dev].store(1, std::memory_order_release);
-    return rc;
+// One launch of a kernel of this file: two staged tiles of dynamic LDS; above 64 KiB (head dim 128 up) the kernel's
+// per-device limit is raised first (vs_launch.h).  Returns that raise's code, 0 once launched.
+template <int DH, auto Kernel, class... Args>
+static int launch_tiles(dim3 grid, hipStream_t st, Args... args) {
+    constexpr size_t lds_bytes = 2 * sizeof(TileLds<DH>);
+    if (const int rc = vsk_raise_lds<Kernel>(lds_bytes)) return rc;
+    hipLaunchKernelGGL(Kernel, grid, dim3(256), lds_bytes, st, args...);
+    return 0;
 }
-
-#define VST_ATTN_LAUNCH(KERNEL_, PK_, DH_, DROP_, ...)                                                          \
-    do {                                                                                                        \
-        static std::atomic<unsigned char> done_[64];                                                            \
-        constexpr size_t lds_bytes_ = 2 * sizeof(TileLds<DH_>);                                                 \
-        if (const int rc_ = allow_lds((const void *)KERNEL_<DH_, DROP_, PK_>, lds_bytes_, done_)) return rc_;   \
-        hipLaunchKernelGGL((KERNEL_<DH_, DROP_, PK_>), grid, dim3(256), lds_bytes_, st, __VA_ARGS__);           \
-    } while (0)
-#define VST_ATTN_DH(KERNEL_, PK_, DH_, ...)                                                                     \
-    do {                                                                                                        \
-        if (!(p > 0.f)) VST_ATTN_LAUNCH(KERNEL_, PK_, DH_, 0, __VA_ARGS__);                                     \
-        else if (dbits != nullptr) VST_ATTN_LAUNCH(KERNEL_, PK_, DH_, 2, __VA_ARGS__);                          \
-        else VST_ATTN_LAUNCH(KERNEL_, PK_, DH_, 1, __VA_ARGS__);                                                \
-    } while (0)
-#define VST_ATTN_DISPATCH(KERNEL_, PK_, ...)      /* PK_: packed ragged batch (work list) */                    \
-    do {                                                                                                        \
-        if (dh == 32) VST_ATTN_DH(KERNEL_, PK_, 32, __VA_ARGS__);                                               \
-        else if (dh == 64) VST_ATTN_DH(KERNEL_, PK_, 64, __VA_ARGS__);                                          \
-        else if (dh == 128) VST_ATTN_DH(KERNEL_, PK_, 128, __VA_ARGS__);                                        \
-        else if (dh == 256) VST_ATTN_DH(KERNEL_, PK_, 256, __VA_ARGS__);      /* round 4: correctness first (1 wave / SIMD, spills) */ \
-        else return -1;                                                                                         \
-    } while (0)
+// rc = f(DH, DROP) with both as constants; DROP 0: p == 0, 2: bit-packed keep words given, 1: hashed per element.
+// -1: no kernel for this head dim.
+template <class F>
+static int pick_dh_drop(int dh, float p, const unsigned *dbits, F &&f) {
+    const int drop = !(p > 0.f) ? 0 : dbits != nullptr ? 2 : 1;
+    int rc = 0;
+    // head dim 256, round 4: correctness first (1 wave / SIMD, spills)
+    const bool found = vsk_pick_int<32, 64, 128, 256>(dh, [&](auto DH) { vsk_pick_int<0, 1, 2>(drop, [&](auto DROP) { rc = f(DH, DROP); }); });
+    return found ? rc : -1;
+}
 
 size_t vst_attention_dropout_bits_words(int B, int H, int T) { return 2 * (size_t)B * H * T * ((T + 31) / 32); }
 
@@ -612,7 +597,10 @@ int vst_attention_fwd_packed(const float *q, const float *k, const float *v, flo
     if (p < 0.f || p >= 1.f || pk.nwork <= 0) return -1;
     const dim3 grid(H * pk.nwork);
     const uint8_t *mask = nullptr;
-    VST_ATTN_DISPATCH(attn_fwd_train, true, q, k, v, mask, out, lse2, H, 0, scale, seed, site, p, dbits, pk);
+    if (const int rc = pick_dh_drop(dh, p, dbits, [&](auto DH, auto DROP) {
+            return launch_tiles<DH(), attn_fwd_train<DH(), DROP(), true>>(grid, st, q, k, v, mask, out, lse2, H, 0, scale, seed, site, p, dbits, pk);
+        }))
+        return rc;
     VSK_CHECK_LAUNCH();
     return 0;
 }
@@ -623,9 +611,15 @@ int vst_attention_bwd_packed(const float *q, const float *k, const float *v, con
     if (p < 0.f || p >= 1.f || pk.nwork <= 0) return -1;
     const dim3 grid(H * pk.nwork);
     const uint8_t *mask = nullptr;
-    VST_ATTN_DISPATCH(attn_bwd_dkdv, true, q, k, v, mask, dO, lse2, delta, dqkv, H, 0, scale, seed, site, p, dbits, pk);
+    if (const int rc = pick_dh_drop(dh, p, dbits, [&](auto DH, auto DROP) {
+            return launch_tiles<DH(), attn_bwd_dkdv<DH(), DROP(), true>>(grid, st, q, k, v, mask, dO, lse2, delta, dqkv, H, 0, scale, seed, site, p, dbits, pk);
+        }))
+        return rc;
     VSK_CHECK_LAUNCH();
-    VST_ATTN_DISPATCH(attn_bwd_dq, true, q, k, v, mask, dO, lse2, delta, dqkv, H, 0, scale, seed, site, p, dbits, pk);
+    if (const int rc = pick_dh_drop(dh, p, dbits, [&](auto DH, auto DROP) {
+            return launch_tiles<DH(), attn_bwd_dq<DH(), DROP(), true>>(grid, st, q, k, v, mask, dO, lse2, delta, dqkv, H, 0, scale, seed, site, p, dbits, pk);
+        }))
+        return rc;
     VSK_CHECK_LAUNCH();
     return 0;
 }
@@ -646,7 +640,10 @@ int vst_attention_fwd(const float *q, const float *k, const float *v, const uint
                       hipStream_t st, const unsigned *dbits) {
     if (p < 0.f || p >= 1.f) return -1;
     const dim3 grid(B * H * ((T + 127) / 128));
-    VST_ATTN_DISPATCH(attn_fwd_train, false, q, k, v, mask, out, lse2, H, T, scale, seed, site, p, dbits, VstPackedPlan{});
+    if (const int rc = pick_dh_drop(dh, p, dbits, [&](auto DH, auto DROP) {
+            return launch_tiles<DH(), attn_fwd_train<DH(), DROP(), false>>(grid, st, q, k, v, mask, out, lse2, H, T, scale, seed, site, p, dbits, VstPackedPlan{});
+        }))
+        return rc;
     VSK_CHECK_LAUNCH();
     return 0;
 }
@@ -656,9 +653,15 @@ int vst_attention_bwd(const float *q, const float *k, const float *v, const uint
                       unsigned long long seed, unsigned site, float p, hipStream_t st, const unsigned *dbits) {
     if (p < 0.f || p >= 1.f) return -1;
     const dim3 grid(B * H * ((T + 127) / 128));
-    VST_ATTN_DISPATCH(attn_bwd_dkdv, false, q, k, v, mask, dO, lse2, delta, dqkv, H, T, scale, seed, site, p, dbits, VstPackedPlan{});
+    if (const int rc = pick_dh_drop(dh, p, dbits, [&](auto DH, auto DROP) {
+            return launch_tiles<DH(), attn_bwd_dkdv<DH(), DROP(), false>>(grid, st, q, k, v, mask, dO, lse2, delta, dqkv, H, T, scale, seed, site, p, dbits, VstPackedPlan{});
+        }))
+        return rc;
     VSK_CHECK_LAUNCH();
-    VST_ATTN_DISPATCH(attn_bwd_dq, false, q, k, v, mask, dO, lse2, delta, dqkv, H, T, scale, seed, site, p, dbits, VstPackedPlan{});
+    if (const int rc = pick_dh_drop(dh, p, dbits, [&](auto DH, auto DROP) {
+            return launch_tiles<DH(), attn_bwd_dq<DH(), DROP(), false>>(grid, st, q, k, v, mask, dO, lse2, delta, dqkv, H, T, scale, seed, site, p, dbits, VstPackedPlan{});
+        }))
+        return rc;
     VSK_CHECK_LAUNCH();
     return 0;
 }

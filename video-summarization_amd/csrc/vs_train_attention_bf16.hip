@@ -17,8 +17,7 @@
 //   * row constants enter as the accumulator's initial value where the row index is the accumulator's row (-lse2, -delta in
 //     the key-owner kernel);
 //   * dropout keep decisions come bit-packed from attn_dropout_bits (vs_train_attention.hip): one word per tile and lane.
-#include <atomic>
-
+#include "vs_launch.h"
 #include "vs_train_attention_owner.h"
 #include "vs_train_device.h"
 #include "vs_train_kernels.h"
@@ -510,6 +509,7 @@ __global__ __launch_bounds__(256, DH == 128 ? 1 : 2) void attn_bwd_dkdv_bf16(
 // confined to where a block's rows and keep words live: tile loops, LDS images, swizzles and the summation order of a video
 // are, line for line, those of the padded kernel running that video alone (fp32-stored operands, IN16 = OUT16 = false) -
 // tests/test_hip_train_packed_lp_attention.py holds the two to the same bits.  A change to one form belongs in the other.
+// DESIGN.md section 32 has the later measurement (a shared per-tile step moved all 156 kernels) and the rule it gives.
 // ------------------------------------------------------------------------------------------
 template <int DH, bool DROP, int F16>
 __global__ __launch_bounds__(256, DH == 128 ? 1 : 2) void attn_fwd_train_bf16_packed(
@@ -798,26 +798,13 @@ __global__ __launch_bounds__(256, DH == 128 ? 1 : 2) void attn_bwd_dkdv_bf16_pac
 
 }  // namespace
 
-#define VSTB_LAUNCH(KERNEL_, DH_, DROP_, IN16_, ...)                                                            \
-    do {                                                                                                        \
-        if (f16) hipLaunchKernelGGL((KERNEL_<DH_, DROP_, IN16_, 1>), grid, dim3(256), 0, st, __VA_ARGS__);      \
-        else hipLaunchKernelGGL((KERNEL_<DH_, DROP_, IN16_, 0>), grid, dim3(256), 0, st, __VA_ARGS__);          \
-    } while (0)
-#define VSTB_DISPATCH2(KERNEL_, DH_, ...)                                                                       \
-    do {                                                                                                        \
-        if (drop && in16) VSTB_LAUNCH(KERNEL_, DH_, true, true, __VA_ARGS__);                                   \
-        else if (drop) VSTB_LAUNCH(KERNEL_, DH_, true, false, __VA_ARGS__);                                     \
-        else if (in16) VSTB_LAUNCH(KERNEL_, DH_, false, true, __VA_ARGS__);                                     \
-        else VSTB_LAUNCH(KERNEL_, DH_, false, false, __VA_ARGS__);                                              \
-    } while (0)
-#define VSTB_DISPATCH(KERNEL_, ...)                                                                             \
-    do {                                                                                                        \
-        const bool drop = p > 0.f;                                                                              \
-        if (dh == 32) VSTB_DISPATCH2(KERNEL_, 32, __VA_ARGS__);                                                 \
-        else if (dh == 64) VSTB_DISPATCH2(KERNEL_, 64, __VA_ARGS__);                                            \
-        else if (dh == 128) VSTB_DISPATCH2(KERNEL_, 128, __VA_ARGS__);                                          \
-        else return -1;                                                                                         \
-    } while (0)
+// f(DH, DROP, F16) with the three as constants (vs_launch.h); false: no kernel for this head dim
+template <class F>
+static bool pick_form(int dh, bool drop, bool f16, F &&f) {
+    return vsk_pick_int<32, 64, 128>(dh, [&](auto DH) {
+        vsk_pick_bool(drop, [&](auto DROP) { vsk_pick_bool(f16, [&](auto F16) { f(DH, DROP, F16); }); });
+    });
+}
 
 bool vst_attention_bf16_supported(int dh) { return dh == 32 || dh == 64 || dh == 128; }
 
@@ -829,31 +816,16 @@ int vst_attention_fwd_bf16(const float *q, const float *k, const float *v, const
     in16 &= ~VSK_F16;
     const float ds = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
     const dim3 grid(B * H * ((T + 127) / 128));
-    VSTB_DISPATCH(attn_fwd_train_bf16, q, k, v, mask, out, lse2, H, T, scale, ds, dbits);
+    if (!pick_form(dh, p > 0.f, f16, [&](auto DH, auto DROP, auto F16) {
+            vsk_pick_bool(in16 != 0, [&](auto IN16) {
+                hipLaunchKernelGGL((attn_fwd_train_bf16<DH(), DROP(), IN16(), F16()>), grid, dim3(256), 0, st, q, k, v, mask, out,
+                                   lse2, H, T, scale, ds, dbits);
+            });
+        }))
+        return -1;
     VSK_CHECK_LAUNCH();
     return 0;
 }
-
-#define VSTB_LAUNCH_B(KERNEL_, DH_, DROP_, IN16_, OUT16_, ...)                                                  \
-    do {                                                                                                        \
-        if (f16) hipLaunchKernelGGL((KERNEL_<DH_, DROP_, IN16_, OUT16_, 1>), grid, dim3(256), 0, st, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL_<DH_, DROP_, IN16_, OUT16_, 0>), grid, dim3(256), 0, st, __VA_ARGS__);  \
-    } while (0)
-#define VSTB_DISPATCH_B3(KERNEL_, DH_, DROP_, ...)                                                              \
-    do {                                                                                                        \
-        if (in16 && out16) VSTB_LAUNCH_B(KERNEL_, DH_, DROP_, true, true, __VA_ARGS__);                         \
-        else if (in16) VSTB_LAUNCH_B(KERNEL_, DH_, DROP_, true, false, __VA_ARGS__);                            \
-        else if (out16) VSTB_LAUNCH_B(KERNEL_, DH_, DROP_, false, true, __VA_ARGS__);                           \
-        else VSTB_LAUNCH_B(KERNEL_, DH_, DROP_, false, false, __VA_ARGS__);                                     \
-    } while (0)
-#define VSTB_DISPATCH_B(KERNEL_, ...)                                                                           \
-    do {                                                                                                        \
-        const bool drop = p > 0.f;                                                                              \
-        if (dh == 32) { if (drop) VSTB_DISPATCH_B3(KERNEL_, 32, true, __VA_ARGS__); else VSTB_DISPATCH_B3(KERNEL_, 32, false, __VA_ARGS__); } \
-        else if (dh == 64) { if (drop) VSTB_DISPATCH_B3(KERNEL_, 64, true, __VA_ARGS__); else VSTB_DISPATCH_B3(KERNEL_, 64, false, __VA_ARGS__); } \
-        else if (dh == 128) { if (drop) VSTB_DISPATCH_B3(KERNEL_, 128, true, __VA_ARGS__); else VSTB_DISPATCH_B3(KERNEL_, 128, false, __VA_ARGS__); } \
-        else return -1;                                                                                         \
-    } while (0)
 
 // out16: dqkv is written as bf16 [M][3 d] (2-byte elements) instead of fp32
 int vst_attention_bwd_bf16(const float *q, const float *k, const float *v, const uint8_t *mask, const float *dO,
@@ -864,37 +836,38 @@ int vst_attention_bwd_bf16(const float *q, const float *k, const float *v, const
     in16 &= ~VSK_F16;
     const float ds = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
     const dim3 grid(B * H * ((T + 127) / 128));
-    VSTB_DISPATCH_B(attn_bwd_dkdv_bf16, q, k, v, mask, dO, lse2, delta, dqkv, H, T, scale, ds, dbits, B * H);
+    // f(DH, DROP, IN16, OUT16, F16)
+    auto pick = [&](auto &&f) {
+        return pick_form(dh, p > 0.f, f16, [&](auto DH, auto DROP, auto F16) {
+            vsk_pick_bool(in16 != 0, [&](auto IN16) { vsk_pick_bool(out16 != 0, [&](auto OUT16) { f(DH, DROP, IN16, OUT16, F16); }); });
+        });
+    };
+    if (!pick([&](auto DH, auto DROP, auto IN16, auto OUT16, auto F16) {
+            hipLaunchKernelGGL((attn_bwd_dkdv_bf16<DH(), DROP(), IN16(), OUT16(), F16()>), grid, dim3(256), 0, st, q, k, v, mask, dO,
+                               lse2, delta, dqkv, H, T, scale, ds, dbits, B * H);
+        }))
+        return -1;
     VSK_CHECK_LAUNCH();
-    VSTB_DISPATCH_B(attn_bwd_dq_bf16, q, k, v, mask, dO, lse2, delta, dqkv, H, T, scale, ds, dbits);
+    pick([&](auto DH, auto DROP, auto IN16, auto OUT16, auto F16) {
+        hipLaunchKernelGGL((attn_bwd_dq_bf16<DH(), DROP(), IN16(), OUT16(), F16()>), grid, dim3(256), 0, st, q, k, v, mask, dO, lse2,
+                           delta, dqkv, H, T, scale, ds, dbits);
+    });
     VSK_CHECK_LAUNCH();
     return 0;
 }
 
 // ---- packed ragged batches: the packed kernels, fed from the device work list (vst_plan_packed); fp32-stored q / k / v / dO,
 // fp32 dqkv; dbits: the packed keep words (vst_attention_dropout_bits_packed), needed when p > 0 ----
-#define VSTB_PACKED_LAUNCH(KERNEL_, DH_, ...)                                                                   \
-    do {                                                                                                        \
-        if (drop && f16) hipLaunchKernelGGL((KERNEL_<DH_, true, 1>), grid, dim3(256), 0, st, __VA_ARGS__);      \
-        else if (drop) hipLaunchKernelGGL((KERNEL_<DH_, true, 0>), grid, dim3(256), 0, st, __VA_ARGS__);        \
-        else if (f16) hipLaunchKernelGGL((KERNEL_<DH_, false, 1>), grid, dim3(256), 0, st, __VA_ARGS__);        \
-        else hipLaunchKernelGGL((KERNEL_<DH_, false, 0>), grid, dim3(256), 0, st, __VA_ARGS__);                 \
-    } while (0)
-#define VSTB_PACKED_DISPATCH(KERNEL_, ...)                                                                      \
-    do {                                                                                                        \
-        const bool drop = p > 0.f;                                                                              \
-        if (dh == 32) VSTB_PACKED_LAUNCH(KERNEL_, 32, __VA_ARGS__);                                             \
-        else if (dh == 64) VSTB_PACKED_LAUNCH(KERNEL_, 64, __VA_ARGS__);                                        \
-        else if (dh == 128) VSTB_PACKED_LAUNCH(KERNEL_, 128, __VA_ARGS__);                                      \
-        else return -1;                                                                                         \
-    } while (0)
-
 int vst_attention_fwd_bf16_packed(const float *q, const float *k, const float *v, float *out, float *lse2, int H, int dh,
                                   float scale, float p, const unsigned *dbits, hipStream_t st, bool f16, const VstPackedPlan &pk) {
     if (p < 0.f || p >= 1.f || (p > 0.f && dbits == nullptr) || pk.nwork <= 0) return -1;
     const float ds = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
     const dim3 grid(H * pk.nwork);
-    VSTB_PACKED_DISPATCH(attn_fwd_train_bf16_packed, q, k, v, out, lse2, H, scale, ds, dbits, pk);
+    if (!pick_form(dh, p > 0.f, f16, [&](auto DH, auto DROP, auto F16) {
+            hipLaunchKernelGGL((attn_fwd_train_bf16_packed<DH(), DROP(), F16()>), grid, dim3(256), 0, st, q, k, v, out, lse2, H, scale,
+                               ds, dbits, pk);
+        }))
+        return -1;
     VSK_CHECK_LAUNCH();
     return 0;
 }
@@ -905,9 +878,16 @@ int vst_attention_bwd_bf16_packed(const float *q, const float *k, const float *v
     if (p < 0.f || p >= 1.f || (p > 0.f && dbits == nullptr) || pk.nwork <= 0) return -1;
     const float ds = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
     const dim3 grid(H * pk.nwork);
-    VSTB_PACKED_DISPATCH(attn_bwd_dkdv_bf16_packed, q, k, v, dO, lse2, delta, dqkv, H, scale, ds, dbits, pk);
+    if (!pick_form(dh, p > 0.f, f16, [&](auto DH, auto DROP, auto F16) {
+            hipLaunchKernelGGL((attn_bwd_dkdv_bf16_packed<DH(), DROP(), F16()>), grid, dim3(256), 0, st, q, k, v, dO, lse2, delta, dqkv,
+                               H, scale, ds, dbits, pk);
+        }))
+        return -1;
     VSK_CHECK_LAUNCH();
-    VSTB_PACKED_DISPATCH(attn_bwd_dq_bf16_packed, q, k, v, dO, lse2, delta, dqkv, H, scale, ds, dbits, pk);
+    pick_form(dh, p > 0.f, f16, [&](auto DH, auto DROP, auto F16) {
+        hipLaunchKernelGGL((attn_bwd_dq_bf16_packed<DH(), DROP(), F16()>), grid, dim3(256), 0, st, q, k, v, dO, lse2, delta, dqkv, H,
+                           scale, ds, dbits, pk);
+    });
     VSK_CHECK_LAUNCH();
     return 0;
 }
