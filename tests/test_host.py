@@ -310,12 +310,15 @@ def test_no_kernel_touches_scratch_inside_its_innermost_mfma_loop(vsa, tmp_path)
 
 def test_every_documented_switch_is_a_known_option_and_unknown_names_are_refused(vsa):
     """include/vs_scorer.h names the A/B switches vs_set_option accepts; each must be known to the library (value -1 =
-    back to the environment / built-in default: a no-op here), a misspelt one must be an error, not a silent no-op."""
+    back to the environment / built-in default: a no-op here), a misspelt one - or a removed one - must be an error, not a silent no-op."""
     hdr = open(os.path.join(ROOT, "include", "vs_scorer.h")).read()
     block = hdr[hdr.index("A/B and test switches"):hdr.index("int vs_set_option")]
     names = sorted(set(re.findall(r"\bVS_[A-Z0-9_]+\b", block)) - {"VS_SCORER_H"})
     assert "VS_LP_STORE32" in names and "VS_LP_EMBED_UNFUSED" in names and "VS_LP_MIN_ROWS_FUSED" in names and len(names) >= 15
     for n in names:
         vsa._lib.set_option(n, -1)
-    with pytest.raises(RuntimeError, match="unknown option"):
-        vsa._lib.set_option("VS_LP_STORE_32", 1)
+    # a misspelt name, and the six switches whose kernels and forced block shapes were removed
+    for n in ("VS_LP_STORE_32", "VS_ATTN_LP_SIMPLE", "VS_MLP_FUSION", "VS_ATTN_LEGACY", "VS_GEMM_NWM2", "VS_GEMM_NJ2", "VS_ATTN_NW4"):
+        assert n not in names
+        with pytest.raises(RuntimeError, match="unknown option"):
+            vsa._lib.set_option(n, 1)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device-code diff of two csrc trees: is every kernel the compiler emits the same, instruction for instruction?
 
-    python tools/device_code_diff.py A_CSRC B_CSRC [--diag] [--jobs N] [--only FILE ...]
+    python tools/device_code_diff.py A_CSRC B_CSRC [--diag] [--jobs N] [--only FILE ...] [--rename 'PATTERN=REPLACEMENT']
 
 Compiles every .hip file of both trees for gfx950 with the library's own flags (_lib._build) plus
 ``-S --cuda-device-only``, cuts the text of each kernel symbol out of the assembly, drops comments, renumbers each
@@ -12,6 +12,9 @@ A host-side refactor must print zero differences and the same symbol set; one di
 slipped in.  ``--diag`` compiles with -DVS_WITH_DIAG; both trees then need the generated ablation includes of the
 one-wave-per-SIMD attention kernel (``python tools/gen_attn_w64.py --abl 1,2,4,8,14,15,512,1024`` writes them into
 the repository's csrc; copy them to an exported tree).
+
+``--rename`` is for a change that renames kernels without touching them (a template parameter removed): tree A's mangled
+kernel names are rewritten with ``re.sub(PATTERN, REPLACEMENT, name)`` wherever they occur in A's assembly, before matching.
 
 Exit status 0: identical.  1: a difference, or a file that did not compile.
 """
@@ -82,10 +85,19 @@ def kernels(asm):
     return out
 
 
-def tree(csrc, extra, jobs, only):
+def renamed(asm, pattern, repl):
+    """the assembly with every kernel symbol `name` replaced by re.sub(pattern, repl, name)"""
+    for name in re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", asm, re.M):
+        asm = asm.replace(name, re.sub(pattern, repl, name))
+    return asm
+
+
+def tree(csrc, extra, jobs, only, rename=None):
     srcs = sorted(f for f in os.listdir(csrc) if f.endswith(".hip") and (not only or f in only))
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(max_workers=jobs) as pool:
         asms = list(pool.map(lambda s: device_asm(csrc, s, extra, tmp), srcs))
+    if rename:
+        asms = [renamed(a, *rename.split("=", 1)) for a in asms]
     return {s: kernels(a) for s, a in zip(srcs, asms)}
 
 
@@ -96,10 +108,11 @@ def main():
     ap.add_argument("--diag", action="store_true", help="compile with -DVS_WITH_DIAG")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--only", nargs="*", default=[], metavar="FILE", help="compare these .hip files only")
+    ap.add_argument("--rename", metavar="PATTERN=REPLACEMENT", help="rewrite tree A's kernel names with this regular expression first")
     args = ap.parse_args()
     extra = ["-DVS_WITH_DIAG"] if args.diag else []
     try:
-        a, b = tree(args.a_csrc, extra, args.jobs, args.only), tree(args.b_csrc, extra, args.jobs, args.only)
+        a, b = tree(args.a_csrc, extra, args.jobs, args.only, args.rename), tree(args.b_csrc, extra, args.jobs, args.only)
     except RuntimeError as e:
         print(e)
         return 1

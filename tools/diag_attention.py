@@ -141,37 +141,6 @@ def run_lp(B, H, T, prec, dh=64):
     print("   wave lifetime med %.1f us -> in-wave clock %.2f GHz; kernel %.1f us" % (life.median().item(), tot.median().item() / life.median().item() / 1e3, ms * 1e3))
 
 
-def run_abl(B, H, T, dh=64):
-    """timing-only ablations of the bf16 kernel (results are wrong by construction)"""
-    q, k, v = (torch.randn(B, H, T, dh, device=dev) for _ in range(3))
-    scale = (H * dh) ** -0.5
-    q = (q * (scale * 1.4426950408889634)).to(torch.bfloat16)        # the bf16 mode's QKV epilogue stores q pre-scaled
-    k, v = k.to(torch.bfloat16), v.to(torch.bfloat16)
-    out = torch.empty(B, T, H * dh, device=dev, dtype=torch.bfloat16)
-    st = torch.cuda.current_stream().cuda_stream
-    fl = 4.0 * B * H * T * T * dh
-    names = {0: "full kernel", 1: "no staging", 2: "no barriers", 3: "no staging, no barriers", 4: "fragment reads pinned to tile 0",
-             5: "no staging, pinned reads", 7: "no staging, no barriers, pinned reads", 16: "no fragment reads (one fragment for all)",
-             17: "no staging, no fragment reads", 19: "no staging, no barriers, no fragment reads"}
-    warm()
-    for abl in (0, 1, 2, 3, 4, 5, 7, 16, 17, 19):
-        for _ in range(3):
-            rc = lib.vs_diag_attention_lp(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, T, scale, 100 + abl, None, st)
-            assert rc > 0, rc
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            lib.vs_diag_attention_lp(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, T, scale, 100 + abl, None, st)
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / 20
-        print("bf16 B=%d H=%d T=%d  ABL %2d %-44s %.4f ms  %.0f TF" % (B, H, T, abl, names[abl], ms, fl / ms / 1e9))
-
-
-if len(sys.argv) > 1 and sys.argv[1] == "abl":
-    run_abl(8, 4, 8192)
-    run_abl(64, 4, 1024)
-    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "lp":
     for prec in (1, 2):
         run_lp(8, 4, 8192, prec)

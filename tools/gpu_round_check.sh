@@ -40,13 +40,12 @@ VS_BENCH_D=1024 python tools/bench_long.py 64 1024 fp32,bf16,fp16x3 > $OUT/bench
 VS_MLP_ABLS=1,2,4,7,8 python tools/bench_mlp_fused.py > $OUT/mlp_fused_ablations.txt 2>&1
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof_long_bf16 -- python3 $ROOT/tools/bench_long.py 8 8192 bf16 > /dev/null 2>&1 )
 bash tools/pmc_cmd.sh $OUT/pmc_summary_long_bf16.txt tools/bench_long.py 8 8192 bf16 > /dev/null 2>&1
-# round 3: the other bench workloads, wide models, attention timelines / ablations / issue probe, raw PMC of the bf16 attention
+# round 3: the other bench workloads, wide models, attention timelines / issue probe, raw PMC of the bf16 attention
 python bench.py --full --workload corpus --steps 20 --warmup 3 > $OUT/bench_corpus.json 2> $OUT/bench_corpus.err
 python bench.py --full --workload long --steps 20 --warmup 3 > $OUT/bench_long.json 2> $OUT/bench_long.err
 python tools/bench_wide.py > $OUT/bench_wide.txt 2>&1
 python tools/bench_mb_modes.py > $OUT/mb_modes.txt 2>&1
 python tools/diag_attention.py > $OUT/attention_timeline_exact.txt 2>&1
-python tools/diag_attention.py abl > $OUT/attn_bf16_ablations.txt 2>&1
 ./tools/valu_probe > $OUT/valu_probe.txt 2>&1 || true
 # round 3, second half: the bf16-operand GEMM, M-B / wide models in bf16 mode (kernel trace + PMC), the bf16 training step
 python tools/bench_gemm16.py > $OUT/gemm16.txt 2>&1

@@ -159,8 +159,8 @@ def needs_build() -> bool:
 def build(force: bool = False, verbose: bool = False, diag: bool = False) -> str:
     """Cross-compiles the HIP sources for gfx950 into the in-tree ``libvsscore.so``
     (works without a GPU).  Returns the library path.  ``diag=True`` builds ``libvsscore_diag.so`` instead: the same
-    sources with ``-DVS_WITH_DIAG`` (stamped GEMM instantiations, the fused-MLP negative result, the non-pipelined
-    attention) for ``tools/`` only - the product library does not carry them."""
+    sources with ``-DVS_WITH_DIAG`` (stamped GEMM and attention instantiations, the timing ablations of the bf16
+    layer-tail and one-wave-per-SIMD attention kernels) for ``tools/`` only - the product library does not carry them."""
     if diag:
         return _build(DIAG_LIB_PATH, ["-DVS_WITH_DIAG"], verbose)
     if not force and not needs_build():

@@ -1,7 +1,7 @@
 // vs_attention.hip — gfx950 attention kernels of the frame-importance scorer (reference simnet.py:155-161):
-//   attn_fwd            exact fp32, head dim 128 (and the A/B baseline for 32/64)
+//   attn_fwd            exact fp32, head dim 128
 //   attn_fwd_pipe       exact fp32, software-pipelined, head dim 32/64 (the default path)
-//   attn_fwd_lp(_pipe)  opt-in low-precision matrix pipes: bf16 operands, or fp32 emulated with f16 hi+lo halves
+//   attn_fwd_lp_pipe    opt-in low-precision matrix pipes: bf16 operands, or fp32 emulated with f16 hi+lo halves
 #include "vs_device.h"
 #include "vs_kernels.h"
 #include "vs_launch.h"
@@ -343,275 +343,27 @@ __global__ __launch_bounds__(512) void attn_fwd_splitkv(
 }
 
 // ------------------------------------------------------------------------------------------
-// Attention on the bf16 matrix pipe (opt-in, VS_FLAG_BF16_ATTENTION; long videos): the same
-// flash-style walk and operand trick as attn_fwd, but both products run as
-// v_mfma_f32_32x32x16_bf16 (16x the fp32 MFMA rate).  Q*scale, K, V and the probabilities P are
-// rounded to bf16 (round-to-nearest-even, v_cvt_pk_bf16_f32) on their way into the MFMA; scores,
-// softmax statistics and the output accumulate in fp32.  Inputs and output stay fp32 in HBM.
-//   S^T = K * Q^T : A = K[key r][d = 16s+8h+j] (one ds_read_b128 of the bf16 tile), B = Q in registers.
-//   O^T = V^T * P^T: B = registers 8s..8s+7 of the S^T accumulator packed pairwise — element j of
-//   lane half h is key 16s + 8(j>>2) + 4h + (j&3) — and A = V^T[d r][those keys], two ds_read_b64
-//   of the TRANSPOSED bf16 V tile, which the staging writes (4 keys of one d packed per b64 store).
-// The row sums l are a third "V" block of ones (the matrix pipe has slack, the VALU does not); the running
-// max is deferred (raised only on a jump > 2^8, so the O/l rescale almost never runs); K/V tiles arrive by
-// buffer loads with scalar offsets, are rounded once into a double-buffered LDS tile, one barrier per tile.
-// Measured (T=8192, B=8, M-A): 750 TFLOP/s; per 64-key tile and wave 20 MFMAs (640 cycles) + 32 v_exp_f32
-// (quarter rate, 512 cycles) + ~100 VALU - and the SIMD issues them one after the other, so the exp2 of the
-// softmax, not the matrix pipe, bounds this kernel at head dim 64.
+// Attention on the low-precision matrix pipes (opt-in; long videos), software-pipelined: the same flash-style walk
+// and operand trick as attn_fwd, but both products run as 32x32x16 MFMAs on 16-bit operands (16x the fp32 MFMA
+// rate); scores, softmax statistics and the output accumulate in fp32.
+// PREC 1 (bf16, VS_FLAG_BF16_ATTENTION): Q*scale, K, V and the probabilities P are rounded to bf16
+// (round-to-nearest-even, v_cvt_pk_bf16_f32) on their way into v_mfma_f32_32x32x16_bf16.
 // NOT within the 1e-4 fp32 bar of the reference: tests/test_hip_parity.py states its tolerance.
-// ------------------------------------------------------------------------------------------
 // PREC 2 ("fp16x3", VS_FLAG_F16X3_ATTENTION) EMULATES the fp32 products on the f16 pipe instead: every operand
 // (q*scale, k, v, p) is split into f16 hi + lo halves (split_f16) kept in two LDS planes / register sets, and
 // each product is three MFMAs (lo*hi, hi*lo, hi*hi; fp32 accumulate) - 56 MFMAs of 32 cycles per 64-key tile
 // where the fp32 kernel needs 132 of 64 cycles - with results inside the fp32 path's own 1e-4 bar.
-template <int DH, int NW, int PREC>       // NW waves per block, 32 query rows each; PREC 1: bf16, 2: f16 hi+lo
-__global__ __launch_bounds__(64 * NW, 2) void attn_fwd_lp(
-    const float *__restrict__ Q, const float *__restrict__ Kg, const float *__restrict__ Vg,
-    const uint8_t *__restrict__ mask, float *__restrict__ out, int H, int T, float scale_log2e, int BH) {
-    constexpr int KT = 64, NS = DH / 16, ND = DH / 32, NT = 64 * NW, QB = 32 * NW;
-    constexpr int NP = PREC == 2 ? 2 : 1;          // operand planes (hi, lo)
-    constexpr int LDK = DH + 8;                    // 16-bit elements per K row: 36 (DH 64) / 20 (DH 32) dwords, b128 reads conflict-free
-    constexpr int LDV = KT + 4;                    // 16-bit elements per V^T row: 34 dwords, b64 reads conflict-free
-    constexpr int D4 = DH / 4;                     // float4 per key row
-    constexpr int KPT = KT * D4 / NT;              // keys per thread in the staging, one float4 of d each
-    static_assert(KPT == 2 || KPT == 4, "staging packs 2 or 4 keys per V^T store");
-    constexpr float THR = 8.0f;                    // deferred max: the applied max is raised only on a jump > 2^8
-    typedef unsigned short h16;
-    // K tile, V^T tile and key-mask bias, double-buffered: tile t+1 is written while tile t is consumed,
-    // one block barrier per tile
-    __shared__ __attribute__((aligned(16))) h16 Kb[2][NP][KT * LDK];
-    __shared__ __attribute__((aligned(16))) h16 Vt[2][NP][DH * LDV];
-    __shared__ __attribute__((aligned(16))) float mb[2][KT];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    int bh, qt;
-    if (!attn_block_map((T + QB - 1) / QB, BH, bh, qt)) return;
-    const int b = bh / H, head = bh - b * H;
-    const size_t base = (size_t)bh * T * DH;
-    const int q0 = qt * QB + 32 * wave;
-    const float NEG_INF = -__builtin_inff();
-
-    // two floats -> one packed pair per plane
-    auto pack = [&](float x0, float x1, unsigned (&pl)[NP]) __attribute__((always_inline)) {
-        if constexpr (PREC == 2) split_f16(x0, x1, pl[0], pl[1]);
-        else pl[0] = pack_bf16(x0, x1);
-    };
-    auto mma = [&](const u32x4 &a, const u32x4 &bq, const f32x16 &c) __attribute__((always_inline)) -> f32x16 {
-        if constexpr (PREC == 2) return MFMA_F16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, bq), c);
-        else return MFMA_BF16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq), c);
-    };
-    // acc += A * B over the planes: hi*hi (+ lo*hi + hi*lo, small terms first)
-    auto mma_planes = [&](const u32x4 (&a)[NP], const u32x4 (&bq)[NP], f32x16 &c) __attribute__((always_inline)) {
-        if constexpr (PREC == 2) {
-            c = mma(a[1], bq[0], c);
-            c = mma(a[0], bq[1], c);
-        }
-        c = mma(a[0], bq[0], c);
-    };
-
-    // Q fragments (B operand): Q[q][16s + 8h + j] * scale*log2(e)
-    u32x4 qreg[NS][NP];
-    {
-        int qr = q0 + r; qr = qr < T ? qr : T - 1;
-        const float *qp = Q + base + (size_t)qr * DH + 8 * h;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const f32x4 v0 = *(const f32x4 *)(qp + 16 * s), v1 = *(const f32x4 *)(qp + 16 * s + 4);
-            unsigned pl[4][NP];
-            pack(v0[0] * scale_log2e, v0[1] * scale_log2e, pl[0]);
-            pack(v0[2] * scale_log2e, v0[3] * scale_log2e, pl[1]);
-            pack(v1[0] * scale_log2e, v1[1] * scale_log2e, pl[2]);
-            pack(v1[2] * scale_log2e, v1[3] * scale_log2e, pl[3]);
-#pragma unroll
-            for (int p = 0; p < NP; ++p)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) qreg[s][p][e] = pl[e][p];
-        }
-    }
-    // o[0..ND-1] = O^T blocks; o[ND] = the row sums l, as the product of P with a block of ones
-    // (the matrix pipe has slack, the VALU does not; and l then sums exactly the rounded P the output uses)
-    f32x16 o[ND + 1];
-#pragma unroll
-    for (int d = 0; d <= ND; ++d)
-#pragma unroll
-        for (int t = 0; t < 16; ++t) o[d][t] = 0.f;
-    float m_run = NEG_INF;                         // the max actually applied to O and l (log2 units)
-    constexpr unsigned ONE2 = PREC == 2 ? 0x3C003C00u : 0x3F803F80u;        // (1.0, 1.0) in f16 / bf16
-    const u32x4 ones_u = {ONE2, ONE2, ONE2, ONE2};
-
-    // staging: thread (d4 = tid % D4, kq = tid / D4) owns keys KPT*kq .. +KPT-1 at d = 4*d4 .. +3.
-    // Buffer loads: the per-tile offset is a scalar, rows beyond T read as zero (and are masked below).
-    const int d4 = tid % D4, kq = tid / D4;
-    const int ntiles = (T + KT - 1) / KT;
-    const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Kg + base), 0, T * DH * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Vg + base), 0, T * DH * 4, 0x00020000);
-    int voff[KPT];
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) voff[i] = ((KPT * kq + i) * DH + 4 * d4) * 4;
-    f32x4 pk[KPT], pv[KPT];
-    float pm = 0.f;
-    auto gload = [&](int tile) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < KPT; ++i) {
-            pk[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, voff[i], tile * (KT * DH * 4), 0));
-            pv[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(vrs, voff[i], tile * (KT * DH * 4), 0));
-        }
-        if (tid < KT) {                             // key-mask bias of key tile*KT + tid: 0 or -inf (also beyond T)
-            const int key = tile * KT + tid;
-            float pmv = key >= T ? NEG_INF : 0.f;
-            if (mask != nullptr) pmv = mask[(size_t)b * T + (key < T ? key : T - 1)] != 0 ? NEG_INF : pmv;
-            pm = pmv;
-        }
-    };
-    auto stage = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < KPT; ++i) {
-            unsigned p0[NP], p1[NP];
-            pack(pk[i][0], pk[i][1], p0);
-            pack(pk[i][2], pk[i][3], p1);
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                u32x2 u; u[0] = p0[p]; u[1] = p1[p];
-                *(u32x2 *)&Kb[buf][p][(KPT * kq + i) * LDK + 4 * d4] = u;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if constexpr (KPT == 4) {
-                unsigned p0[NP], p1[NP];
-                pack(pv[0][e], pv[1][e], p0);
-                pack(pv[2][e], pv[3][e], p1);
-#pragma unroll
-                for (int p = 0; p < NP; ++p) {
-                    u32x2 u; u[0] = p0[p]; u[1] = p1[p];
-                    *(u32x2 *)&Vt[buf][p][(4 * d4 + e) * LDV + 4 * kq] = u;
-                }
-            } else {
-                unsigned p0[NP];
-                pack(pv[0][e], pv[1][e], p0);
-#pragma unroll
-                for (int p = 0; p < NP; ++p) *(unsigned *)&Vt[buf][p][(4 * d4 + e) * LDV + 2 * kq] = p0[p];
-            }
-        }
-        if (tid < KT) mb[buf][tid] = pm;
-    };
-    gload(0);
-    stage(0);
-    if (ntiles > 1) gload(1);
-    __syncthreads();
-
-    for (int tile = 0; tile < ntiles; ++tile) {
-        const int cur = tile & 1;
-        const bool masked_tile = mask != nullptr || (tile + 1) * KT > T;
-        // ---- S^T = K * Q^T ----
-        f32x16 s[2];
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int t = 0; t < 16; ++t) s[n][t] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < NS; ++ks)
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                u32x4 ka[NP];
-#pragma unroll
-                for (int p = 0; p < NP; ++p) ka[p] = *(const u32x4 *)&Kb[cur][p][(32 * n + r) * LDK + 16 * ks + 8 * h];
-                mma_planes(ka, qreg[ks], s[n]);
-            }
-        // ---- V^T fragments of this tile (A of O^T): reads in flight under the softmax ----
-        u32x4 va[2][2][ND][NP];
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int d = 0; d < ND; ++d)
-#pragma unroll
-                    for (int p = 0; p < NP; ++p) {
-                        const h16 *vp = &Vt[cur][p][(32 * d + r) * LDV + 32 * n + 16 * ks + 4 * h];
-                        const u32x2 lo = *(const u32x2 *)vp, hi = *(const u32x2 *)(vp + 8);
-                        va[n][ks][d][p][0] = lo[0]; va[n][ks][d][p][1] = lo[1]; va[n][ks][d][p][2] = hi[0]; va[n][ks][d][p][3] = hi[1];
-                    }
-        // ---- tile t+1 into the other LDS buffer, tile t+2 into registers (under the MFMAs / softmax) ----
-        if (tile + 1 < ntiles) stage(cur ^ 1);
-        if (tile + 2 < ntiles) gload(tile + 2);
-        if (masked_tile) {
-#pragma unroll
-            for (int n = 0; n < 2; ++n)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 bv = *(const f32x4 *)&mb[cur][32 * n + 8 * g + 4 * h];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) s[n][4 * g + e] += bv[e];
-                }
-        }
-        // ---- online softmax with a deferred max, one query per lane pair (l, l^32) ----
-        float mx = __builtin_fmaxf(__builtin_fmaxf(s[0][0], s[0][1]), s[1][0]);
-        mx = __builtin_fmaxf(mx, s[1][1]);
-#pragma unroll
-        for (int t = 2; t < 16; t += 2) {
-            mx = __builtin_fmaxf(__builtin_fmaxf(mx, s[0][t]), s[0][t + 1]);
-            mx = __builtin_fmaxf(__builtin_fmaxf(mx, s[1][t]), s[1][t + 1]);
-        }
-        mx = pair_max(mx);
-        const bool raise = mx > m_run + THR || (m_run == NEG_INF && mx != NEG_INF);
-        if (__builtin_expect(__any(raise), 0)) {   // first live tile, or a jump > 2^THR: rare, wave-uniform branch
-            const float m_new = raise ? mx : m_run;
-            const float u_new = (m_new == NEG_INF) ? 0.f : m_new;
-            const float alpha = __builtin_amdgcn_exp2f(m_run - u_new);    // 1 for lanes that keep their max; 0 from -inf
-#pragma unroll
-            for (int d = 0; d <= ND; ++d)
-#pragma unroll
-                for (int t = 0; t < 16; ++t) o[d][t] *= alpha;
-            m_run = m_new;
-        }
-        const float m_use = (m_run == NEG_INF) ? 0.f : m_run;           // p = exp2(s - m_use) <= 2^THR
-        const f32x2 mm = {m_use, m_use};
-        // ---- O^T += V^T * P^T, l += 1 * P^T ----
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                u32x4 pf[NP];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const f32x2 sv = {s[n][8 * ks + 2 * j], s[n][8 * ks + 2 * j + 1]};
-                    const f32x2 dv = sv - mm;
-                    unsigned pl[NP];
-                    pack(__builtin_amdgcn_exp2f(dv[0]), __builtin_amdgcn_exp2f(dv[1]), pl);
-#pragma unroll
-                    for (int p = 0; p < NP; ++p) pf[p][j] = pl[p];
-                }
-#pragma unroll
-                for (int d = 0; d < ND; ++d) mma_planes(va[n][ks][d], pf, o[d]);
-#pragma unroll
-                for (int p = NP - 1; p >= 0; --p) o[ND] = mma(ones_u, pf[p], o[ND]);
-            }
-        __syncthreads();
-    }
-
-    // ---- epilogue: O^T[d][q] / l -> out[b, q, head*DH + d]; 4 consecutive d per 16-B store ----
-    const int q = q0 + r;
-    if (q < T) {
-        const float inv = 1.0f / o[ND][0];
-        float *op = out + ((size_t)b * T + q) * (H * DH) + head * DH;
-#pragma unroll
-        for (int d = 0; d < ND; ++d)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = o[d][4 * g + e] * inv;
-                *(f32x4 *)(op + 32 * d + 8 * g + 4 * h) = v;
-            }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// attn_fwd_lp, software-pipelined (the default for the bf16 / fp16x3 modes): attn_fwd_lp keeps every wave in
-// the same phase (the per-tile barrier aligns them), so the matrix pipe idles during the softmax and the VALU
-// during the products.  Here K runs one tile ahead of V: iteration t issues the MFMAs of S(t+1) = K(t+1) Q^T
+//   S^T = K * Q^T : A = K[key r][d = 16s+8h+j] (one ds_read_b128 of the 16-bit tile), B = Q in registers.
+//   O^T = V^T * P^T: B = registers 8s..8s+7 of the S^T accumulator packed pairwise — element j of
+//   lane half h is key 16s + 8(j>>2) + 4h + (j&3) — and A = V^T[d r][those keys], two ds_read_b64
+//   of the TRANSPOSED 16-bit V tile, which the staging writes (4 keys of one d packed per b64 store).
+// The row sums l are a third "V" block of ones (the matrix pipe has slack, the VALU does not); the running
+// max is deferred (raised only on a jump > 2^8, so the O/l rescale almost never runs); K/V tiles arrive by
+// buffer loads with scalar offsets and are rounded once into their LDS tiles.  At head dim 64 the exp2 of the
+// softmax (32 v_exp_f32 per 64-key tile and wave, quarter rate), not the matrix pipe, bounds the kernel.
+// Pipeline: with one barrier per tile and nothing else, every wave is in the same phase, so the matrix pipe idles
+// during the softmax and the VALU during the products (DESIGN section 9 measured that form).  Here K runs one
+// tile ahead of V: iteration t issues the MFMAs of S(t+1) = K(t+1) Q^T
 // with the softmax of tile t (max3 chain, deferred-max check, exp2, hi/lo split) sliced between them, then the
 // MFMAs of O += V(t)^T P(t)^T (+ row sums) with the staging of K(t+2) / V(t+1) (split, LDS writes) and the
 // buffer loads of K(t+3) / V(t+2) between them.  One barrier per tile; K and V double-buffered in LDS, the
@@ -633,10 +385,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_lp(
 // (the QKV epilogue / the out-projection do the rounding this kernel / that kernel would do anyway: same bits)
 // DIAG (diagnostic library only): per-wave stamps, diag[(block * NW + wave) * 16 + ..]: 0 prologue, 1 phase A (S(t+1) ||
 // softmax(t)), 2 phase B (P.V + row sums || staging), 3 barrier, 7 epilogue, 8 total, 9 / 10 wall clock, 11 tiles
-// ABL (diagnostic library only, timing ablations with WRONG results): 1 no staging inside the loop (no global loads,
-// no LDS writes), 2 no block barriers inside the loop, 4 no fragment reads inside the loop (LDS offsets pinned to tile 0
-// and hoistable), 8 no softmax work (P fragments constant)
-template <int DH, int NW, int PREC, bool VARLEN = false, bool IO16 = false, int DIAG = 0, int ABL = 0>       // VARLEN: packed ragged batches, see attn_fwd_pipe
+template <int DH, int NW, int PREC, bool VARLEN = false, bool IO16 = false, int DIAG = 0>       // NW waves per block, 32 query rows each; VARLEN: packed ragged batches, see attn_fwd_pipe
 __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_lp_pipe(
     const float *__restrict__ Q, const float *__restrict__ Kg, const float *__restrict__ Vg,
     const uint8_t *__restrict__ mask, float *__restrict__ out, int H, int T, float scale_log2e, int BH,
@@ -1083,11 +832,9 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_lp_pipe(
     constexpr int NSLOT_B = 4 * (ND * NPROD + NP);
     constexpr int NITEM = KPT + 4 + 2, SB = NSLOT_B / NITEM > 0 ? NSLOT_B / NITEM : 1;    // staging items, slot stride
 
-    u32x4 abl_frag = {0u, 0u, 0u, 0u};
-    if constexpr ((ABL & 16) != 0) abl_frag = *(const u32x4 *)&Kb[0][0][r * LDK + 8 * h];
     // one iteration: s_in = S(t) (complete), s_out <- S(t+1)
     auto iteration = [&](int t, f32x16 (&s_in)[2], float &cb_in, f32x16 (&s_out)[2], float &cb_out) __attribute__((always_inline)) {
-        const int cur = (ABL & 4) ? 0 : t % NBUF, nxt = (ABL & 4) ? 0 : (t + 1) % NBUF;                  // V(t) / K(t+1) live here
+        const int cur = t % NBUF, nxt = (t + 1) % NBUF;                  // V(t) / K(t+1) live here
         if (mask != nullptr || (t + 1) * KT > T) {       // masked / ragged tile: key-mask bias first (rare)
             const float *mp = mb[t % NMB];
 #pragma unroll
@@ -1108,16 +855,6 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_lp_pipe(
         // the first MFMA and every V fragment of tile t during phase A, so no MFMA waits for an LDS read issued one
         // gap earlier (round 2: `s_waitcnt lgkmcnt(0)` in front of every MFMA).  Otherwise: one fragment ahead.
         u32x4 ka[NKF][NP], va[NVF][NP];
-        if constexpr ((ABL & 16) != 0) {
-#pragma unroll
-            for (int g = 0; g < NKF; ++g)
-#pragma unroll
-                for (int p = 0; p < NP; ++p) ka[g][p] = abl_frag;
-#pragma unroll
-            for (int g = 0; g < NVF; ++g)
-#pragma unroll
-                for (int p = 0; p < NP; ++p) va[g][p] = abl_frag;
-        } else
         if constexpr (FULLPF) {
 #pragma unroll
             for (int g = 0; g < NS * 2; ++g) k_frag(nxt, g % NS, g / NS, ka[g]);
@@ -1135,24 +872,24 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_lp_pipe(
             } else {
                 constexpr int ks = (w - 1) / NPROD, pr = (w - 1) % NPROD, g = n * NS + ks;       // fragment index: block-major
                 if constexpr (!FOLD && w == 1) s_out[n] = zero16;
-                if constexpr (!(ABL & 16) && !FULLPF && pr == 0 && g + 1 < NS * 2) k_frag(nxt, (g + 1) % NS, (g + 1) / NS, ka[(g + 1) & 1]);
+                if constexpr (!FULLPF && pr == 0 && g + 1 < NS * 2) k_frag(nxt, (g + 1) % NS, (g + 1) / NS, ka[(g + 1) & 1]);
                 mma_prod(std::integral_constant<int, pr>{}, ka[FULLPF ? g : (g & 1)], qreg[ks], s_out[n]);
             }
-            if constexpr (!(ABL & 16) && FULLPF && i >= NBIAS && i - NBIAS < NVF) {
+            if constexpr (FULLPF && i >= NBIAS && i - NBIAS < NVF) {
                 constexpr int f = i - NBIAS;
                 v_frag(cur, f / ND / 2, (f / ND) % 2, f % ND, va[f]);
             }
             static_for<RA>([&](auto rc) {
                 constexpr int U = i * RA + decltype(rc)::value;
-                if constexpr (U < NU && !(ABL & 8)) sm_unit(std::integral_constant<int, U>{}, s_in, cb_in);
+                if constexpr (U < NU) sm_unit(std::integral_constant<int, U>{}, s_in, cb_in);
             });
             __builtin_amdgcn_sched_barrier(0);
         });
         lap(1);
         if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the pieces requested in phase B(t-1) have landed
-        if constexpr (STAG && !(ABL & 2)) { __syncthreads(); lap(3); }  // the partner wave of this SIMD changes phase too
+        if constexpr (STAG) { __syncthreads(); lap(3); }  // the partner wave of this SIMD changes phase too
         // ---- phase B: O += V(t)^T P(t)^T and the row sums; staging of K(t+KAHEAD), V(t+VAHEAD), loads of the tiles after ----
-        if constexpr (!FULLPF && !(ABL & 16)) v_frag(cur, 0, 0, 0, va[0]);
+        if constexpr (!FULLPF) v_frag(cur, 0, 0, 0, va[0]);
         __builtin_amdgcn_sched_barrier(0);
         static_for<NSLOT_B>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
@@ -1160,7 +897,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_lp_pipe(
             constexpr int g = i / PER, w = i % PER, n = g / 2, ks = g % 2;
             if constexpr (w < ND * NPROD) {
                 constexpr int d = w / NPROD, pr = w % NPROD, f = g * ND + d;       // fragment index
-                if constexpr (!(ABL & 16) && !FULLPF && pr == 0 && f + 1 < 4 * ND)
+                if constexpr (!FULLPF && pr == 0 && f + 1 < 4 * ND)
                     v_frag(cur, (f + 1) / ND / 2, ((f + 1) / ND) % 2, (f + 1) % ND, va[(f + 1) & 1]);
                 mma_prod(std::integral_constant<int, pr>{}, va[FULLPF ? f : (f & 1)], pf[n][ks], o[d]);
             } else {
@@ -1169,10 +906,10 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_lp_pipe(
             }
             if constexpr (DMA) {
                 // K(t+KAHEAD) and V(t+VAHEAD) straight into their LDS tiles, as early in the phase as possible
-                if constexpr (!(ABL & 1) && i == 0) dma_issue(t + KAHEAD, t + VAHEAD, true, true);
-                if constexpr (!(ABL & 1) && i == 4) { stage_m((t + KAHEAD) % NMB); gload_m(t + KAHEAD + 1); }
+                if constexpr (i == 0) dma_issue(t + KAHEAD, t + VAHEAD, true, true);
+                if constexpr (i == 4) { stage_m((t + KAHEAD) % NMB); gload_m(t + KAHEAD + 1); }
             } else
-            if constexpr (!(ABL & 1) && i % SB == SB - 1 && i / SB < NITEM) {
+            if constexpr (i % SB == SB - 1 && i / SB < NITEM) {
                 constexpr int item = i / SB;
                 if constexpr (item < KPT) stage_k1(item, (t + KAHEAD) % NBUF);
                 else if constexpr (item < KPT + 4) stage_v1(item - KPT, (t + VAHEAD) % NBUF);
@@ -1182,7 +919,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_lp_pipe(
             __builtin_amdgcn_sched_barrier(0);
         });
         lap(2);
-        if constexpr (!(ABL & 2)) __syncthreads();
+        __syncthreads();
         lap(3);
     };
 
@@ -1655,15 +1392,6 @@ int vsk_diag_attention_lp(const float *q, const float *k, const float *v, float 
     const int BH = B * H, nq = (T + 255) / 256;
     dim3 g(8 * ((BH + 7) / 8) * nq);
     const float sl2 = scale * 1.4426950408889634f;
-    if (prec >= 100) {      // timing ablations of the bf16 kernel (no stamps): prec = 100 + ABL
-        if (!vsk_pick_int<0, 1, 2, 3, 4, 5, 7, 16, 17, 19>(prec - 100, [&](auto ABL) {
-                hipLaunchKernelGGL((attn_fwd_lp_pipe<64, 8, 1, false, true, 0, ABL()>), g, dim3(512), 0, st, q, k, v, nullptr, out, H, T,
-                                   sl2, BH, nullptr, nullptr, 0, nullptr);
-            }))
-            return -1;
-        VSK_CHECK_LAUNCH();
-        return (int)g.x;
-    }
     if (prec == 1)
         hipLaunchKernelGGL((attn_fwd_lp_pipe<64, 8, 1, false, true, 1>), g, dim3(512), 0, st, q, k, v, nullptr, out, H, T, sl2, BH,
                            nullptr, nullptr, 0, diag);
@@ -1682,19 +1410,11 @@ int vsk_attention(const float *q, const float *k, const float *v, const uint8_t 
     const float sl2 = vsk_attention_qscale(scale);
     const int BH = B * H;
     dim3 grid(8 * ((BH + 7) / 8) * ((T + 127) / 128));
-#ifdef VS_WITH_DIAG     // A/B switch for tools/ (diagnostic library only): the non-pipelined kernel at head dim 32 / 64
-    const bool legacy = vsk_options().attn_legacy != 0;
-    if (dh == 32 && legacy)
-        hipLaunchKernelGGL((attn_fwd<32, 2>), grid, dim3(256), 0, st, q, k, v, mask, out, H, T, sl2, BH);
-    else if (dh == 64 && legacy)
-        hipLaunchKernelGGL((attn_fwd<64, 2>), grid, dim3(256), 0, st, q, k, v, mask, out, H, T, sl2, BH);
-    else
-#endif
     if (dh == 32 || dh == 64) {
         // 8-wave blocks (one per CU, 256 query rows) unless the ragged tail would waste more rows than
         // 4-wave blocks (two per CU, 128 query rows) do
         const int r8 = (T + 255) / 256 * 256, r4 = (T + 127) / 128 * 128;
-        const bool wide = !vsk_options().attn_nw4 && r8 * 100 <= r4 * 105;
+        const bool wide = r8 * 100 <= r4 * 105;
         const int nq = wide ? r8 / 256 : r4 / 128;
         dim3 g(8 * ((BH + 7) / 8) * nq), blk(wide ? 512 : 256);
         vsk_pick_int<32, 64>(dh, [&](auto DH) {
@@ -1781,9 +1501,8 @@ int vsk_attention_bf16(const float *q, const float *k, const float *v, const uin
     const int BH = B * H;
     // 8-wave blocks (256 query rows share one staged K/V tile) unless the ragged tail would waste too many rows
     const int r8 = (T + 255) / 256 * 256, r4 = (T + 127) / 128 * 128;
-    const bool wide = dh == 64 && !vsk_options().attn_nw4 && r8 * 100 <= r4 * 105;
+    const bool wide = dh == 64 && r8 * 100 <= r4 * 105;
     dim3 grid(8 * ((BH + 7) / 8) * (wide ? r8 / 256 : r4 / 128));
-    const bool simple = vsk_options().attn_lp_simple != 0;      // A/B switch for tools/, not a fallback
     if (dh == 128) {     // head dim 128 (M-B): bf16 only, 8-wave blocks only (fp16x3 does not fit the register file: 48 spills)
         if (prec != 1 && prec != (1 | VSK_STORE16)) return -1;
         dim3 g128(8 * ((BH + 7) / 8) * (r8 / 256));
@@ -1807,8 +1526,7 @@ int vsk_attention_bf16(const float *q, const float *k, const float *v, const uin
                 return;
             }
             vsk_pick_int<1, 2>(prec == 2 ? 2 : 1, [&](auto P) {
-                if (simple) hipLaunchKernelGGL((attn_fwd_lp<DH, NW, P()>), grid, dim3(64 * NW), 0, st, q, k, v, mask, out, H, T, sl2, BH);
-                else hipLaunchKernelGGL((attn_fwd_lp_pipe<DH, NW, P()>), grid, dim3(64 * NW), 0, st, q, k, v, mask, out, H, T, sl2, BH);
+                hipLaunchKernelGGL((attn_fwd_lp_pipe<DH, NW, P()>), grid, dim3(64 * NW), 0, st, q, k, v, mask, out, H, T, sl2, BH);
             });
         }))
         return -1;

@@ -83,11 +83,6 @@ int vsk_diag_attention_lp(const float *q, const float *k, const float *v, float 
                           int prec, unsigned long long *diag, hipStream_t st);
 int vsk_diag_gemm(const float *A, const float *W, const float *bias, float *C, int M, int N, int K,
                   int grid, unsigned long long *diag, hipStream_t st);
-// fc1 + ReLU + fc2 + residual + LayerNorm (+ score head) in one kernel; d_model == 256 only (-1 otherwise)
-int vsk_mlp_fused(const float *H1, const float *W1, const float *b1, const float *W2, const float *b2,
-                  const float *gamma, const float *beta, float *out, int M, int d,
-                  const float *score_w, const float *score_b, int num_classes, int sigmoid, float *scores,
-                  hipStream_t st);
 // bf16 mode, d_model == 256: fc1 + ReLU + fc2 + residual + LayerNorm (+ score head) as one kernel whose hidden
 // activations stay in registers (vs_mlp_fused.hip) - and, when the attention output is stored as bf16 (att16 != nullptr),
 // the out-projection + residual + norm1 in front of it as well (h is then the layer input, else h = h1).
@@ -143,10 +138,6 @@ struct VskOptions {
     int train_lp_min_rows;// VS_TRAIN_LP_MIN_ROWS (default 1024): frames per batch above which a low-precision TRAINING request is honoured
                           // (profiles/r04_lp_min_rows_sweep.txt: break-even at ~1280 frames, 1.1x at 2560, 1.7x at 8192)
     int lp_min_rows_fused;// VS_LP_MIN_ROWS_FUSED (default 256): the same threshold where the fused bf16 layer kernels apply
-    int gemm_nwm2;        // VS_GEMM_NWM2     128x128 four-wave GEMM blocks only
-    int gemm_nj2;         // VS_GEMM_NJ2      128-column GEMM tiles only
-    int attn_nw4;         // VS_ATTN_NW4      4-wave attention blocks only
-    int attn_lp_simple;   // VS_ATTN_LP_SIMPLE phase-aligned low-precision attention
     int attn_w64;         // VS_ATTN_W64      (default 1) bf16-stored head-dim-64 attention on the one-wave-per-SIMD kernel (0: the 8-wave kernel, A/B)
     int lp_store32;       // VS_LP_STORE32    bf16 mode keeps q/k/v, the attention output and the MLP hidden tensor fp32 in HBM (A/B)
     int lp_mlp_unfused;   // VS_LP_MLP_UNFUSED bf16 mode runs fc1 and fc2 + LayerNorm as two kernels (A/B)
@@ -155,10 +146,8 @@ struct VskOptions {
     int lp_tile256;       // VS_LP_TILE256     the fused bf16 layer kernels always use 256-row tiles / 8-wave blocks (A/B)
     int lp_embed_unfused; // VS_LP_EMBED_UNFUSED bf16 mode runs the embedding as the generic GEMM + the first QKV kernel (A/B)
     int exact_unfused;    // VS_EXACT_UNFUSED  exact fp32, d_model 256: out-projection + norm1, fc1, fc2 + norm2 and QKV as four kernels (A/B, bit-identity tests)
-    int mlp_fusion;       // VS_MLP_FUSION    (diagnostic builds only)
-    int mlp_abl;          // VS_MLP_ABL       (diagnostic builds only)
+    int mlp_abl;          // VS_MLP_ABL       (diagnostic builds only) timing ablation of the bf16 layer-tail kernel's MLP part (vs_mlp_fused.hip)
     int attn_w64_checked; // VS_ATTN_W64_CHECKED the one-wave-per-SIMD attention skips its optimistic pass (every tile checked; A/B and test pin)
-    int attn_legacy;      // VS_ATTN_LEGACY   (diagnostic builds only)
     int attn_w64_abl;     // VS_ATTN_W64_ABL  (diagnostic builds only) timing ablation of the one-wave-per-SIMD attention
 };
 VskOptions &vsk_options();

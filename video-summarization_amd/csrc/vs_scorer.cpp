@@ -113,11 +113,8 @@ namespace {
 struct OptionName { const char *name; int VskOptions::*field; int dflt; };
 const OptionName kOptions[] = {
     {"VS_SKINNY_ROWS", &VskOptions::skinny_rows, 16384}, {"VS_LP_MIN_ROWS", &VskOptions::lp_min_rows, 8192},
-    {"VS_GEMM_NWM2", &VskOptions::gemm_nwm2, 0},         {"VS_GEMM_NJ2", &VskOptions::gemm_nj2, 0},
-    {"VS_ATTN_NW4", &VskOptions::attn_nw4, 0},           {"VS_ATTN_LP_SIMPLE", &VskOptions::attn_lp_simple, 0},
-    {"VS_MLP_FUSION", &VskOptions::mlp_fusion, 0},       {"VS_MLP_ABL", &VskOptions::mlp_abl, 0},
-    {"VS_EXACT_UNFUSED", &VskOptions::exact_unfused, 0},
-    {"VS_ATTN_LEGACY", &VskOptions::attn_legacy, 0},     {"VS_LP_STORE32", &VskOptions::lp_store32, 0},
+    {"VS_MLP_ABL", &VskOptions::mlp_abl, 0},             {"VS_EXACT_UNFUSED", &VskOptions::exact_unfused, 0},
+    {"VS_LP_STORE32", &VskOptions::lp_store32, 0},
     {"VS_LP_MLP_UNFUSED", &VskOptions::lp_mlp_unfused, 0}, {"VS_LP_TAIL_UNFUSED", &VskOptions::lp_tail_unfused, 0},
     {"VS_LP_QKV_UNFUSED", &VskOptions::lp_qkv_unfused, 0}, {"VS_LP_EMBED_UNFUSED", &VskOptions::lp_embed_unfused, 0},
     {"VS_LP_MIN_ROWS_FUSED", &VskOptions::lp_min_rows_fused, 256}, {"VS_LP_TILE256", &VskOptions::lp_tile256, 0},
@@ -447,7 +444,7 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
     // 4-wave blocks below half a chip of 256-row tiles: 0.36 ms at 320 rows, 0.43 ms from 1k to 8k rows): 256 rows)
     const VskOptions &opt = vsk_options();
     const bool fused_ok = !embedded && vsk_mlp_bf16_supported(d) && (pk ? pk->prec == 1 : (flags & VS_FLAG_BF16_ATTENTION) != 0) &&
-                          !opt.lp_store32 && !opt.lp_mlp_unfused && !opt.attn_lp_simple;
+                          !opt.lp_store32 && !opt.lp_mlp_unfused;
     const int lp_min_rows = fused_ok && opt.lp_min_rows_fused < opt.lp_min_rows ? opt.lp_min_rows_fused
                                                                                : opt.lp_min_rows;    // tests / tools pin the bf16 tiled kernels with 0
     const int lbf = (flags & VS_FLAG_F16X3_LINEAR) ? 2 : ((flags & VS_FLAG_BF16_LINEAR) && M > lp_min_rows) ? 1 : 0;
@@ -468,7 +465,7 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
     const int aprec = pk ? pk->prec : (flags & VS_FLAG_F16X3_ATTENTION) ? 2 : (flags & VS_FLAG_BF16_ATTENTION) ? 1 : 0;
     // (d_model > 256 - M-B and wider - has no bf16-storage consumers: its LayerNorm GEMMs are the plain bf16 GEMM + the
     // row pass, which read fp32, and the head-dim-128 attention reads fp32 q / k / v: fp32 storage there)
-    const bool qkv16 = lbf == 1 && aprec == 1 && d <= 256 && !embedded && !vsk_options().lp_store32 && !vsk_options().attn_lp_simple;
+    const bool qkv16 = lbf == 1 && aprec == 1 && d <= 256 && !embedded && !vsk_options().lp_store32;
     const bool ffn16 = lbf == 1 && d <= 256 && !embedded && !vsk_options().lp_store32;
     const bool mlp16 = lbf == 1 && !embedded && vsk_mlp_bf16_supported(d) && !vsk_options().lp_mlp_unfused && !vsk_options().lp_store32;
     // d_model > 256 in bf16 mode with a bf16 attention: the bf16-OPERAND GEMM (vs_gemm_ring.hip).  Every Linear after the
@@ -633,20 +630,6 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
             VS_LAUNCH(vsk_linear_res_ln(att, w->p(P.wo), w->p(lnbf == 2 ? P.h_wo : P.f_wo), w->p(P.bo), h0, w->p(P.ln1g), w->p(P.ln1b), h1, M, d, d,
                                         nullptr, nullptr, 0, 0, nullptr, qkv16 ? (1 | VSK_STORE16) : lnbf, st));
         }
-#ifdef VS_WITH_DIAG     // diagnostic library only (tools/): the measured-slower fused MLP kernel
-        // Opt-in alternative (VS_MLP_FUSION=1, d_model = 256): fc1 + ReLU + fc2 + residual + norm2 (+ score head)
-        // as ONE kernel with the activations kept in registers (reported under the fc2 stage).  Bit-identical
-        // to the two-kernel path but measured 6 % slower: its ~506 registers per lane allow one
-        // wave per SIMD only, so nothing covers the weight loads' issue stalls.
-        const bool fused = d == 256 && vsk_options().mlp_fusion != 0 && M > vsk_skinny_max_rows() && !lbf;
-        if (fused) {
-            StageScope ps(VS_STAGE_FC2_LN, st);
-            VS_LAUNCH(vsk_mlp_fused(h1, w->p(P.w1), w->p(P.b1), w->p(P.w2), w->p(P.b2), w->p(P.ln2g), w->p(P.ln2b), dst, M, d,
-                                    last ? w->p(w->final_w) : nullptr, last ? w->p(w->final_b) : nullptr,
-                                    D.num_classes, sig, last ? scores : nullptr, st));
-            continue;
-        }
-#endif
         // bf16 mode, d_model 256, throughput batches: the whole MLP block as one kernel (hidden activations in registers)
         if (mlp16) {
             StageScope ps(VS_STAGE_FC2_LN, st);
