@@ -1,0 +1,23 @@
+"""CPU: the scoring forward's plan (csrc/vs_forward_plan.h) - which kernels a forward runs, as a pure function
+of the model's shape, the call and the switches.  tests/cabi/forward_plan_demo.cpp includes that header alone and is built with
+the host C++17 compiler under AddressSanitizer and UBSan: a table of named cases gives the expected plan and reaches every
+enumerator of every plan enum, each A/B switch flips exactly the fields DESIGN.md section 10 names, and over a grid of shapes,
+flags, switches and call forms the plan's invariants hold and every invalid combination is refused with its documented message."""
+import os
+import shutil
+import subprocess
+
+from conftest import ROOT
+
+
+def test_forward_plan_as_plain_cxx17_under_sanitizers(tmp_path):
+    cxx = shutil.which("g++")
+    assert cxx, "g++ not found"
+    exe = str(tmp_path / "forward_plan_demo")
+    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                            "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "video-summarization_amd", "csrc"),
+                            "-I" + os.path.join(ROOT, "include"),
+                            os.path.join(ROOT, "tests", "cabi", "forward_plan_demo.cpp"), "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-2000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0 and run.stdout == "OK\n", (run.stdout, run.stderr[-2000:])

@@ -278,7 +278,6 @@ __global__ __launch_bounds__(256) void to_bf16(const float *__restrict__ src, h1
 
 }  // namespace
 
-bool vsk_gemm16_supported(int M, int N, int K) { return M > 0 && N > 0 && N % 32 == 0 && K >= 32 && K % 32 == 0; }
 
 // epi: 0 bias, 1 bias + ReLU, 3 bias + q/k/v head-major scatter (T, H, dh; q additionally times qscale when c16).
 // A16 [M, K], W16 [N, K] bf16 row-major, 16-byte aligned; C fp32 [M, N] (c16 = 0) or bf16 (c16 = 1).

@@ -4,12 +4,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vs_forward_plan.h"      // VskOptions, the mode words, vsk_*_supported
+
 // bf16 != 0: operands rounded to bf16 for the matrix pipe (opt-in; fp32 storage, bias, accumulation, LayerNorm)
 // bf16 == (1 | VSK_STORE16): additionally the tensors that are ONLY ever consumed as bf16 matrix operands live in HBM
 // as bf16: C of vsk_qkv and of vsk_linear(relu), A of vsk_linear_res_ln, q/k/v/out of the bf16 attention.  The
 // rounding happens in the producer instead of the consumer: same bits, half the bytes.
-enum { VSK_STORE16 = 16, VSK_A16 = 32, VSK_F16 = 64 };      // VSK_A16 (training path): A of vsk_linear is stored as bf16;
-// VSK_F16 (training path's fp16 mode): the 16-bit type of this call - operands, stored C, stored A - is IEEE f16, not bf16
+// (VSK_STORE16, VSK_A16, VSK_F16: vs_forward_plan.h)
 // Wf: the weight in fragment-major order (vsk_pack_fragments) or nullptr; enables the packed latency kernels
 int vsk_linear(const float *A, const float *W, const float *Wf, const float *bias, float *C, int M, int N, int K,
                int relu, const float *pe, int T, int bf16, hipStream_t st);
@@ -51,7 +52,6 @@ int vsk_linear_res_ln(const float *A, const float *W, const float *Wf, const flo
 // the next Linear - bit-identical to the two stand-alone kernels (-1: shape outside these kernels).
 //   vsk_outproj_ln_fc1: h1 = LN(att * Wo^T + bo + res), hidden [M, 4d] = relu(h1 * W1^T + b1)
 //   vsk_fc2_ln_qkv:     out = LN(hidden * W2^T + b2 + res), qkv = out * Wqkv^T + bqkv as vsk_qkv writes it (M = B * T)
-bool vsk_layer_fused_supported(int M, int d);
 int vsk_outproj_ln_fc1(const float *att, const float *Wo, const float *bo, const float *res, const float *gamma, const float *beta,
                        float *h1, const float *W1, const float *b1, float *hidden, int M, int d, hipStream_t st);
 int vsk_fc2_ln_qkv(const float *hidden, const float *W2, const float *b2, const float *res, const float *gamma, const float *beta,
@@ -88,7 +88,6 @@ int vsk_diag_gemm(const float *A, const float *W, const float *bias, float *C, i
 // the out-projection + residual + norm1 in front of it as well (h is then the layer input, else h = h1).
 // img: the per-chunk LDS images of Wo, W1, W2 made by vsk_pack_mlp_bf16 (vsk_mlp_bf16_image_bytes(d) bytes, 256-byte
 // aligned; 0 = this d_model has no fused kernel).
-bool vsk_mlp_bf16_supported(int d);
 size_t vsk_mlp_bf16_image_bytes(int d);
 int vsk_pack_mlp_bf16(const float *Wo, const float *W1, const float *W2, void *img, int d, hipStream_t st);
 // next != nullptr: the kernel also projects the rows it produced to the NEXT layer's q * qscale / k / v (bf16, head-major:
@@ -130,33 +129,13 @@ int vsk_insert_cls(const float *e, const float *cls, const uint8_t *mask, float 
                    hipStream_t st);
 int vsk_skinny_max_rows();      // rows up to which the skinny (latency) kernels are used
 
-// A/B and test switches (DESIGN.md "Environment switches").  Read from the environment ONCE, when the library is
-// first used; afterwards only vs_set_option() changes them, so no forward pays a getenv.
-struct VskOptions {
-    int skinny_rows;      // VS_SKINNY_ROWS   (default 16384)
-    int lp_min_rows;      // VS_LP_MIN_ROWS   (default 8192)
-    int train_lp_min_rows;// VS_TRAIN_LP_MIN_ROWS (default 1024): frames per batch above which a low-precision TRAINING request is honoured
-                          // (profiles/r04_lp_min_rows_sweep.txt: break-even at ~1280 frames, 1.1x at 2560, 1.7x at 8192)
-    int lp_min_rows_fused;// VS_LP_MIN_ROWS_FUSED (default 256): the same threshold where the fused bf16 layer kernels apply
-    int attn_w64;         // VS_ATTN_W64      (default 1) bf16-stored head-dim-64 attention on the one-wave-per-SIMD kernel (0: the 8-wave kernel, A/B)
-    int lp_store32;       // VS_LP_STORE32    bf16 mode keeps q/k/v, the attention output and the MLP hidden tensor fp32 in HBM (A/B)
-    int lp_mlp_unfused;   // VS_LP_MLP_UNFUSED bf16 mode runs fc1 and fc2 + LayerNorm as two kernels (A/B)
-    int lp_tail_unfused;  // VS_LP_TAIL_UNFUSED bf16 mode runs the out-projection + norm1 as its own kernel in front of the fused MLP (A/B)
-    int lp_qkv_unfused;   // VS_LP_QKV_UNFUSED  bf16 mode runs every layer's QKV projection as its own kernel (A/B)
-    int lp_tile256;       // VS_LP_TILE256     the fused bf16 layer kernels always use 256-row tiles / 8-wave blocks (A/B)
-    int lp_embed_unfused; // VS_LP_EMBED_UNFUSED bf16 mode runs the embedding as the generic GEMM + the first QKV kernel (A/B)
-    int exact_unfused;    // VS_EXACT_UNFUSED  exact fp32, d_model 256: out-projection + norm1, fc1, fc2 + norm2 and QKV as four kernels (A/B, bit-identity tests)
-    int mlp_abl;          // VS_MLP_ABL       (diagnostic builds only) timing ablation of the bf16 layer-tail kernel's MLP part (vs_mlp_fused.hip)
-    int attn_w64_checked; // VS_ATTN_W64_CHECKED the one-wave-per-SIMD attention skips its optimistic pass (every tile checked; A/B and test pin)
-    int attn_w64_abl;     // VS_ATTN_W64_ABL  (diagnostic builds only) timing ablation of the one-wave-per-SIMD attention
-};
+// A/B and test switches: struct VskOptions, vs_forward_plan.h
 VskOptions &vsk_options();
 // per-device cache of the CU count (one process may drive several GPUs)
 int vsk_device_cus();
 
 // ---- vs_gemm_ring.hip: bf16 x bf16 operands from HBM (wide models' bf16 mode) ----
 // epi: 0 bias, 1 bias + ReLU, 3 bias + q/k/v head-major scatter (q additionally times qscale when c16)
-bool vsk_gemm16_supported(int M, int N, int K);
 int vsk_gemm16(const void *A16, const void *W16, const float *bias, void *C, int M, int N, int K, int epi, int c16,
                int T, int H, int dh, float qscale, hipStream_t st);
 int vsk_to_bf16(const float *src, void *dst, size_t n, hipStream_t st);

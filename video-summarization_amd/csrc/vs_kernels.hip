@@ -2283,11 +2283,10 @@ int vsk_linear_res_ln(const float *A, const float *W, const float *Wf, const flo
 
 // Exact fp32, d_model 256, throughput batches: the two layer kernels with a register-fed second product (LnTail).
 // Their byte offsets into q / k / v are 32-bit: up to 2^20 rows (the caller keeps the stand-alone kernels beyond).
-bool vsk_layer_fused_supported(int M, int d) { return d == 256 && M > skinny_max_rows() && M <= (1 << 20); }
 
 int vsk_outproj_ln_fc1(const float *att, const float *Wo, const float *bo, const float *res, const float *gamma, const float *beta,
                        float *h1, const float *W1, const float *b1, float *hidden, int M, int d, hipStream_t st) {
-    if (!vsk_layer_fused_supported(M, d)) return -1;
+    if (!vsk_layer_fused_supported(M, d, skinny_max_rows())) return -1;
     int blocks = persistent_blocks((M + 127) / 128);
     if (blocks < 0) return (int)hipErrorInvalidDevice;
     if (blocks > (M + 127) / 128) blocks = (M + 127) / 128;
@@ -2299,7 +2298,7 @@ int vsk_outproj_ln_fc1(const float *att, const float *Wo, const float *bo, const
 int vsk_fc2_ln_qkv(const float *hidden, const float *W2, const float *b2, const float *res, const float *gamma, const float *beta,
                    float *out, const float *Wqkv, const float *bqkv, float *qkv, int B, int T, int d, int H, hipStream_t st) {
     const int M = B * T;
-    if (!vsk_layer_fused_supported(M, d) || H <= 0 || d % H || (d / H) % 32) return -1;      // a 32-column block within one head
+    if (!vsk_layer_fused_supported(M, d, skinny_max_rows()) || H <= 0 || d % H || (d / H) % 32) return -1;      // a 32-column block within one head
     int dhs = 5;                        // head dim 32, 64, 128 or 256
     while ((1 << dhs) < d / H) ++dhs;
     int blocks = persistent_blocks((M + 127) / 128);

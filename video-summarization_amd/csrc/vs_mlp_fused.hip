@@ -737,7 +737,7 @@ int vsk_embed_bf16(const float *x, const void *img, const float *bias, const flo
     return 0;
 }
 
-bool vsk_mlp_bf16_supported(int d) { return d == MLP_D; }
+static_assert(MLP_D == 256, "vsk_mlp_bf16_supported (vs_forward_plan.h) names this kernel's d_model");
 
 size_t vsk_qkv_bf16_image_bytes(int d) { return d == MLP_D ? (size_t)MLP_NCHQ * MLP_IMG : 0; }
 

@@ -385,7 +385,6 @@ struct PackedInfo {
     const int *cu;           // device [B+1] row offsets
     const int *work;         // device [nwork][2] (video, query tile)
     int nwork, nw;           // query tile = 32*nw rows
-    int prec;                // attention arithmetic: 0 exact fp32, 2 fp16x3
 };
 
 // vs_inspect_forward: after the QKV stage of every selected layer the attention-map kernels READ that layer's q / k planes
@@ -407,126 +406,137 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
     if (!w || !x || !scores) return fail(VS_ERR_INVALID, "weights/x/scores is NULL");
     if (B <= 0 || T <= 0) return fail(VS_ERR_INVALID, "B=%d T=%d", B, T);
     const vs_model_desc &D = w->desc;
-    if (!pk && w->has_pe && T > D.max_len)
-        return fail(VS_ERR_INVALID, "T=%d exceeds the positional table (max_len=%d)", T, D.max_len);
-    if (cls && pk) return fail(VS_ERR_INVALID, "packed batches have no class-token form");
     const int Tf = T;                   // frames per video (rows of x, positional rows)
-    if (cls) T += 1;                    // sequence length the encoder sees
-    if ((long long)B * T > (1ll << 30)) return fail(VS_ERR_INVALID, "B*T too large");
-    if ((flags & VS_FLAG_BF16_LINEAR) && (flags & VS_FLAG_F16X3_LINEAR))
-        return fail(VS_ERR_INVALID, "VS_FLAG_BF16_LINEAR and VS_FLAG_F16X3_LINEAR are exclusive");
-    if ((flags & (VS_FLAG_BF16_ATTENTION | VS_FLAG_F16X3_ATTENTION)) && D.d_model / D.num_heads != 32 && D.d_model / D.num_heads != 64 &&
-        !((flags & VS_FLAG_BF16_ATTENTION) && D.d_model / D.num_heads == 128))
-        return fail(VS_ERR_INVALID, "VS_FLAG_BF16_ATTENTION needs head_dim 32, 64 or 128, VS_FLAG_F16X3_ATTENTION 32 or 64 (got %d)", D.d_model / D.num_heads);
-    if ((flags & VS_FLAG_BF16_ATTENTION) && (flags & VS_FLAG_F16X3_ATTENTION))
-        return fail(VS_ERR_INVALID, "VS_FLAG_BF16_ATTENTION and VS_FLAG_F16X3_ATTENTION are exclusive");
+    const int sig = (flags & VS_FLAG_SIGMOID) ? 1 : 0;
+    // which kernels run: decided once, in vs_forward_plan.h; everything below only reads `plan`
+    const VsForwardIn in{D.d_model, D.num_heads, D.num_layers, D.in_features, D.max_len, w->dn(), w->has_pe, w->has_b_embed,
+                         B, Tf, flags, cls != nullptr, pk != nullptr};
+    VsForwardPlan plan;
+    if (int rc = vs_forward_plan(in, vsk_options(), &plan, &g_err)) return rc;
+    T = plan.T;                         // sequence length the encoder sees
     const size_t need_core = vs_scorer_workspace_bytes(w, B, T);
     const size_t need = need_core + (cls ? align_up((size_t)B * T, 256) : 0);       // + the [B, T+1] key mask
     if (!workspace || workspace_bytes < need)
         return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
     if (((uintptr_t)workspace & 255) || ((uintptr_t)x & 15) || (hidden && ((uintptr_t)hidden & 15)) || (cls && ((uintptr_t)cls & 15)))
         return fail(VS_ERR_INVALID, "workspace must be 256-byte, x/hidden/cls_token 16-byte aligned");
+    // kernel-layout weight images this forward reads, (re)built only if the parameters changed since their last use
+    vsw_order(w, stream);       // parameters written on another stream (vs_weights_update): ordered on the device
+    if (plan.families) if (int rc = vsw_ensure(w, plan.families, stream)) return rc;
 
     hipStream_t st = (hipStream_t)stream;
-    const int d = D.d_model, H = D.num_heads, L = D.num_layers, M = B * T;
+    const int d = D.d_model, H = D.num_heads, L = D.num_layers, M = plan.M;
     const size_t md = align_up((size_t)M * d * sizeof(float), 256) / sizeof(float);
     float *ws = (float *)workspace;
     float *h0 = ws, *h1 = ws + md, *qkv = ws + 2 * md, *att = ws + 5 * md, *ffn = ws + 6 * md;
-    const int dn = w->dn();                             // LayerNorm width / the d_model of the attention scale (== d unless embedded)
-    const bool embedded = w->embedded();
-    const float scale = 1.0f / sqrtf((float)dn);       // reference simnet.py:126: d_model ** -0.5
-    const int sig = (flags & VS_FLAG_SIGMOID) ? 1 : 0;
-    // bf16 Linear kernels exist as LDS-tiled throughput kernels only: up to 8192 rows (measured crossover) the exact
-    // fp32 latency kernels are faster and are used whatever that flag says.  fp16x3 has its own latency kernels
-    // (same product order as its tiled kernels: a video's scores do not depend on the batch it is scored in).
-    // (measured crossover, T=1024: 8192 rows for the stand-alone bf16 GEMMs; where the fused layer kernels of
-    // vs_mlp_fused.hip apply - d_model 256 with bf16 attention - they win from a single T=320 video on (128-row tiles on
-    // 4-wave blocks below half a chip of 256-row tiles: 0.36 ms at 320 rows, 0.43 ms from 1k to 8k rows): 256 rows)
-    const VskOptions &opt = vsk_options();
-    const bool fused_ok = !embedded && vsk_mlp_bf16_supported(d) && (pk ? pk->prec == 1 : (flags & VS_FLAG_BF16_ATTENTION) != 0) &&
-                          !opt.lp_store32 && !opt.lp_mlp_unfused;
-    const int lp_min_rows = fused_ok && opt.lp_min_rows_fused < opt.lp_min_rows ? opt.lp_min_rows_fused
-                                                                               : opt.lp_min_rows;    // tests / tools pin the bf16 tiled kernels with 0
-    const int lbf = (flags & VS_FLAG_F16X3_LINEAR) ? 2 : ((flags & VS_FLAG_BF16_LINEAR) && M > lp_min_rows) ? 1 : 0;
-    // latency mode (VS_FLAG_SPLITK): exact kernels, latency-sized inputs, plain padded batches only
-    // (d_model 128 .. 512 - M-A and the reference's argparse default M-B: K slices that are multiples of 128, partials in the free regions)
-    const bool splitk = (flags & VS_FLAG_SPLITK) && (lbf == 0 || lbf == 2) && !pk && !cls && M <= vsk_skinny_max_rows() && (d == 128 || d == 256 || d == 512);
-    // the bf16 Linear + LayerNorm kernels stop at d_model 256 (validated above); fp16x3 has a wide variant too
-    const int lnbf = lbf;
-    {   // kernel-layout weight images this forward reads, (re)built only if the parameters changed since their last use
-        const int rows_min = cls ? B * Tf : M;
-        const bool wide16 = lbf == 1 && d > 256;       // the bf16-operand GEMM's weight copies (ring path below)
-        const unsigned fam = lbf == 1 ? (VSW_BF16 | (wide16 ? VSW_ROWS16 : 0u)) : rows_min > vsk_skinny_max_rows() ? 0u : lbf == 2 ? VSW_F16X3 : VSW_FRAGMENTS;
-        vsw_order(w, stream);       // parameters written on another stream (vs_weights_update): ordered on the device
-        if (fam) if (int rc = vsw_ensure(w, fam, stream)) return rc;
-    }
-    // bf16 mode: the tensors that are only ever read as bf16 matrix operands are WRITTEN as bf16 by their producers
-    // (q * scale * log2 e, k, v; the attention output; the MLP hidden tensor) - same bits, half the HBM bytes
-    const int aprec = pk ? pk->prec : (flags & VS_FLAG_F16X3_ATTENTION) ? 2 : (flags & VS_FLAG_BF16_ATTENTION) ? 1 : 0;
-    // (d_model > 256 - M-B and wider - has no bf16-storage consumers: its LayerNorm GEMMs are the plain bf16 GEMM + the
-    // row pass, which read fp32, and the head-dim-128 attention reads fp32 q / k / v: fp32 storage there)
-    const bool qkv16 = lbf == 1 && aprec == 1 && d <= 256 && !embedded && !vsk_options().lp_store32;
-    const bool ffn16 = lbf == 1 && d <= 256 && !embedded && !vsk_options().lp_store32;
-    const bool mlp16 = lbf == 1 && !embedded && vsk_mlp_bf16_supported(d) && !vsk_options().lp_mlp_unfused && !vsk_options().lp_store32;
-    // d_model > 256 in bf16 mode with a bf16 attention: the bf16-OPERAND GEMM (vs_gemm_ring.hip).  Every Linear after the
-    // embedding reads bf16 from HBM: q/k/v, the attention output and the MLP hidden tensor are written as bf16 by their
-    // producers, and the two LayerNorm passes write a bf16 copy of their rows beside the fp32 residual stream.
-    const bool ring = lbf == 1 && aprec == 1 && !pk && d > 256 && !opt.lp_store32 && vsk_gemm16_supported(M, d, d);
-    const size_t kv_stride = (qkv16 || ring) ? (size_t)M * d / 2 : (size_t)M * d;      // floats between the q, k and v planes
     void *h16 = ffn + 2 * md;               // [M, d] bf16 copy of the current LayerNorm output (the upper half of ffn: the
                                             // bf16 hidden tensor needs the lower half only)
-
-    // bf16 mode with bf16 q/k/v: every layer's tail kernel also projects its output rows to the NEXT layer's q/k/v, and
-    // the embedding kernel to the first layer's
-    const bool qkv_fused = mlp16 && qkv16 && !vsk_options().lp_qkv_unfused;
-    // exact fp32, d_model 256, throughput batches: out-projection + norm1 carries fc1, and fc2 + norm2 the NEXT layer's QKV, each
-    // fed from the registers that hold the rows it has just normalised (vs_kernels.hip: LnTail) - bit-identical to the four
-    // stand-alone kernels, which VS_EXACT_UNFUSED=1 brings back.  The first layer's QKV stays vsk_qkv.
-    const bool exact_fused = lbf == 0 && aprec == 0 && !embedded && !splitk && !opt.exact_unfused && vsk_layer_fused_supported(M, d) &&
-                             d % H == 0 && (d / H) % 32 == 0;
-    bool have_qkv = false;                  // q/k/v of the layer about to run were written by the kernel before it
+    const size_t kv = plan.kv_stride;       // floats between the q, k and v planes
+    const int dn = w->dn();                             // LayerNorm width / the d_model of the attention scale (== d unless embedded)
+    const float scale = 1.0f / sqrtf((float)dn);       // reference simnet.py:126: d_model ** -0.5
+    const float qs = vsk_attention_qscale(scale);
+    const bool f16x3 = plan.linear == VS_ARITH_F16X3;
+    auto frag = [&](size_t f, size_t h) { return w->p(f16x3 ? h : f); };      // a weight's fragment-major image in this arithmetic
     const float *pe_rows = pk ? pk->pe_rows : (w->has_pe ? w->p(w->pe) : nullptr);
-    // Embedding + positional table (simnet.py:211, 237-238)
-    if (cls) {
-        // frames through the embedding GEMM into a free region (h1), then token row + frames -> h0, mask -> mask'
+    {   // Embedding + positional table (simnet.py:211, 237-238)
         StageScope ps(VS_STAGE_EMBED, st);
-        VS_LAUNCH(vsk_linear(x, w->p(w->embed_w), w->p(lbf == 2 ? w->h_embed_w : w->f_embed_w), w->p(w->embed_b), h1, B * Tf, d,
-                             D.in_features, 0, pe_rows, Tf, lbf, st));
-        uint8_t *mask1 = key_pad_mask ? (uint8_t *)workspace + need_core : nullptr;
-        VS_LAUNCH(vsk_insert_cls(h1, cls, key_pad_mask, h0, mask1, B, Tf, d, st));
-        key_pad_mask = mask1;
-    } else if (lbf == 1 && w->has_b_embed && qkv_fused && L > 0 && !vsk_options().lp_embed_unfused) {
-        StageScope ps(VS_STAGE_EMBED, st);
-        const LayerOff &N = w->layers[0];
-        const VskNextQkv nq{w->p(N.b_qkv), w->p(N.bqkv), qkv, T, H, vsk_attention_qscale(scale)};
-        VS_LAUNCH(vsk_embed_bf16(x, w->p(w->b_embed), w->p(w->embed_b), pe_rows, T, h0, M, d, D.in_features, &nq, st));
-        have_qkv = true;
-    } else if (splitk && D.in_features % 1024 == 0) {
-        // K = in_features split 8 ways; the partials (8 x [M, d]: the q .. ffn regions, all free here) + bias + positional rows -> h0
-        StageScope ps(VS_STAGE_EMBED, st);
-        VS_LAUNCH(vsk_linear_parts(x, w->p(lbf == 2 ? w->h_embed_w : w->f_embed_w), qkv, M, d, D.in_features, 8, st, lbf == 2));
-        VS_LAUNCH(vsk_sum_parts_pe(qkv, 8, w->p(w->embed_b), pe_rows, T, h0, M, d, st));
-    } else {
-        StageScope ps(VS_STAGE_EMBED, st);
-        VS_LAUNCH(vsk_linear(x, w->p(w->embed_w), w->p(lbf == 2 ? w->h_embed_w : w->f_embed_w), w->p(w->embed_b), h0, M, d, D.in_features, 0,
-                             pe_rows, T, lbf, st));
+        switch (plan.embed) {
+        case VS_EMBED_CLS: {
+            // frames through the embedding GEMM into a free region (h1), then token row + frames -> h0, mask -> mask'
+            VS_LAUNCH(vsk_linear(x, w->p(w->embed_w), frag(w->f_embed_w, w->h_embed_w), w->p(w->embed_b), h1, B * Tf, d,
+                                 D.in_features, 0, pe_rows, Tf, plan.mode_linear, st));
+            uint8_t *mask1 = key_pad_mask ? (uint8_t *)workspace + need_core : nullptr;
+            VS_LAUNCH(vsk_insert_cls(h1, cls, key_pad_mask, h0, mask1, B, Tf, d, st));
+            key_pad_mask = mask1;
+        } break;
+        case VS_EMBED_BF16_QKV: {
+            const LayerOff &N = w->layers[0];
+            const VskNextQkv nq{w->p(N.b_qkv), w->p(N.bqkv), qkv, T, H, qs};
+            VS_LAUNCH(vsk_embed_bf16(x, w->p(w->b_embed), w->p(w->embed_b), pe_rows, T, h0, M, d, D.in_features, &nq, st));
+        } break;
+        case VS_EMBED_SPLITK:
+            // K = in_features split 8 ways; the partials (8 x [M, d]: the q .. ffn regions, all free here) + bias + positional rows -> h0
+            VS_LAUNCH(vsk_linear_parts(x, frag(w->f_embed_w, w->h_embed_w), qkv, M, d, D.in_features, 8, st, f16x3));
+            VS_LAUNCH(vsk_sum_parts_pe(qkv, 8, w->p(w->embed_b), pe_rows, T, h0, M, d, st));
+            break;
+        case VS_EMBED_GEMM:
+            VS_LAUNCH(vsk_linear(x, w->p(w->embed_w), frag(w->f_embed_w, w->h_embed_w), w->p(w->embed_b), h0, M, d, D.in_features, 0,
+                                 pe_rows, T, plan.mode_linear, st));
+            break;
+        }
     }
-    if (ring && L > 0) VS_LAUNCH(vsk_to_bf16(h0, h16, (size_t)M * d, st));
+    if (plan.layer == VS_LAYER_RING) VS_LAUNCH(vsk_to_bf16(h0, h16, (size_t)M * d, st));
     for (int l = 0; l < L; ++l) {
         const LayerOff &P = w->layers[l];
         const bool last = l == L - 1;
-        if (ring) {
-            const float qs = vsk_attention_qscale(scale);
-            {
-                StageScope ps(VS_STAGE_QKV, st);
-                VS_LAUNCH(vsk_gemm16(h16, w->p(P.r_wqkv), w->p(P.bqkv), qkv, M, 3 * d, d, 3, 1, T, H, d / H, qs, st));
+        float *dst = (last && hidden) ? hidden : h0;
+        // the score head rides on the last layer's closing kernel
+        const float *head_w = last ? w->p(w->final_w) : nullptr, *head_b = last ? w->p(w->final_b) : nullptr;
+        float *head_out = last ? scores : nullptr;
+        VskNextQkv nq{}, *next = nullptr;
+        if (plan.next_qkv && !last) {
+            const LayerOff &N = w->layers[l + 1];
+            nq = VskNextQkv{w->p(N.b_qkv), w->p(N.bqkv), qkv, T, H, qs};
+            next = &nq;
+        }
+        if (plan.layer == VS_LAYER_RING) {
+            StageScope ps(VS_STAGE_QKV, st);
+            VS_LAUNCH(vsk_gemm16(h16, w->p(P.r_wqkv), w->p(P.bqkv), qkv, M, 3 * d, d, 3, 1, T, H, d / H, qs, st));
+        } else if (l == 0 ? plan.embed != VS_EMBED_BF16_QKV : !plan.tail_writes_qkv()) {      // else: written by the kernel before this layer
+            StageScope ps(VS_STAGE_QKV, st);
+            VS_LAUNCH(vsk_qkv(h0, w->p(P.wqkv), frag(P.f_wqkv, P.h_wqkv), w->p(P.bqkv), qkv, B, T, d, H, plan.mode_qkv, st,
+                              plan.qkv16 ? qs : 1.0f));
+        }
+        if (ins) {
+            for (int i = 0; i < ins->n_layers; ++i) {
+                if (ins->layers[i] != l) continue;
+                const size_t rows = (size_t)B * H * T;
+                VS_LAUNCH(vsk_attention_probs(qkv, qkv + kv, key_pad_mask, ins->maps ? ins->maps + i * rows * T : nullptr,
+                                              ins->received ? ins->received + i * rows : nullptr,
+                                              ins->entropy ? ins->entropy + i * rows : nullptr, B, H, T, d / H, scale, ins->workspace, st));
             }
-            {
-                StageScope ps(VS_STAGE_ATTENTION, st);
-                VS_LAUNCH(vsk_attention_bf16(qkv, qkv + kv_stride, qkv + 2 * kv_stride, key_pad_mask, att, B, H, T, d / H, scale,
-                                             1 | VSK_STORE16, st));
+        }
+        {
+            StageScope ps(VS_STAGE_ATTENTION, st);
+            switch (plan.attention) {
+            case VS_ATT_PACKED:
+                VS_LAUNCH(vsk_attention_packed(qkv, qkv + kv, qkv + 2 * kv, att, H, M, d / H, scale, pk->cu, pk->work, pk->nwork, pk->nw,
+                                               plan.mode_attention, st));
+                break;
+            case VS_ATT_DH256:      // its log-sum-exp output lands in the MLP hidden region, which is free here
+                VS_LAUNCH(vst_attention_fwd(qkv, qkv + kv, qkv + 2 * kv, key_pad_mask, att, ffn, B, H, T, 256, scale, 0ull, 0u, 0.f, st, nullptr));
+                break;
+            case VS_ATT_SPLITKV:
+                VS_LAUNCH(vsk_attention_splitkv(qkv, qkv + kv, qkv + 2 * kv, key_pad_mask, att, B, H, T, d / H, scale, st));
+                break;
+            case VS_ATT_LOWPREC:
+                VS_LAUNCH(vsk_attention_bf16(qkv, qkv + kv, qkv + 2 * kv, key_pad_mask, att, B, H, T, d / H, scale, plan.mode_attention, st));
+                break;
+            case VS_ATT_EXACT:
+                VS_LAUNCH(vsk_attention(qkv, qkv + kv, qkv + 2 * kv, key_pad_mask, att, B, H, T, d / H, scale, st));
+                break;
             }
-            float *dst = (last && hidden) ? hidden : h0;
+        }
+        if (plan.ln1 != VS_LN_NONE) {       // out-projection + norm1 -> h1 as a stage of its own (the GEMM's output goes to the q
+                                            // region, free after the attention)
+            StageScope ps(VS_STAGE_OUTPROJ_LN, st);
+            switch (plan.ln1) {
+            case VS_LN_SPLITK_ROWS:     // K = d in two slices (q / k regions)
+                VS_LAUNCH(vsk_linear_parts(att, frag(P.f_wo, P.h_wo), qkv, M, d, d, 2, st, f16x3));
+                VS_LAUNCH(vsk_rows_res_ln(qkv, h0, w->p(P.ln1g), w->p(P.ln1b), h1, M, d, nullptr, nullptr, 0, 0, nullptr, st, nullptr, dn,
+                                          2, w->p(P.bo)));
+                break;
+            case VS_LN_GEMM_ROWS:
+                VS_LAUNCH(vsk_linear(att, w->p(P.wo), frag(P.f_wo, P.h_wo), w->p(P.bo), qkv, M, d, d, 0, nullptr, 1, plan.mode_linear, st));
+                VS_LAUNCH(vsk_rows_res_ln(qkv, h0, w->p(P.ln1g), w->p(P.ln1b), h1, M, d, nullptr, nullptr, 0, 0, nullptr, st, nullptr, dn));
+                break;
+            default:
+                VS_LAUNCH(vsk_linear_res_ln(att, w->p(P.wo), frag(P.f_wo, P.h_wo), w->p(P.bo), h0, w->p(P.ln1g), w->p(P.ln1b), h1, M, d, d,
+                                            nullptr, nullptr, 0, 0, nullptr, plan.mode_qkv, st));
+            }
+        }
+        switch (plan.layer) {
+        case VS_LAYER_RING: {
             {   // out-projection (bf16 attention output in, fp32 out into the q region, free by now) + norm1 -> h1 (+ bf16 copy)
                 StageScope ps(VS_STAGE_OUTPROJ_LN, st);
                 VS_LAUNCH(vsk_gemm16(att, w->p(P.r_wo), w->p(P.bo), qkv, M, d, d, 0, 0, 1, 0, 0, 1.0f, st));
@@ -536,66 +546,23 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
                 StageScope ps(VS_STAGE_FC1, st);
                 VS_LAUNCH(vsk_gemm16(h16, w->p(P.r_w1), w->p(P.b1), ffn, M, 4 * d, d, 1, 1, 1, 0, 0, 1.0f, st));
             }
-            {   // fc2 (fp32 out into the att region) + norm2 (+ score head) -> h0 / hidden (+ bf16 copy for the next layer)
-                StageScope ps(VS_STAGE_FC2_LN, st);
-                VS_LAUNCH(vsk_gemm16(ffn, w->p(P.r_w2), w->p(P.b2), att, M, d, 4 * d, 0, 0, 1, 0, 0, 1.0f, st));
-                VS_LAUNCH(vsk_rows_res_ln(att, h1, w->p(P.ln2g), w->p(P.ln2b), dst, M, d, last ? w->p(w->final_w) : nullptr,
-                                          last ? w->p(w->final_b) : nullptr, D.num_classes, sig, last ? scores : nullptr, st,
-                                          last ? nullptr : h16, dn));
-            }
-            continue;
-        }
-        VskNextQkv nq{}, *next = nullptr;
-        if (qkv_fused && !last) {
-            const LayerOff &N = w->layers[l + 1];
-            nq = VskNextQkv{w->p(N.b_qkv), w->p(N.bqkv), qkv, T, H, vsk_attention_qscale(scale)};
-            next = &nq;
-        }
-        if (!have_qkv) {
-            StageScope ps(VS_STAGE_QKV, st);
-            VS_LAUNCH(vsk_qkv(h0, w->p(P.wqkv), w->p(lbf == 2 ? P.h_wqkv : P.f_wqkv), w->p(P.bqkv), qkv, B, T, d, H,
-                              qkv16 ? (1 | VSK_STORE16) : lbf, st, qkv16 ? vsk_attention_qscale(scale) : 1.0f));
-        }
-        if (ins) {
-            for (int i = 0; i < ins->n_layers; ++i) {
-                if (ins->layers[i] != l) continue;
-                const size_t rows = (size_t)B * H * T;
-                VS_LAUNCH(vsk_attention_probs(qkv, qkv + (size_t)M * d, key_pad_mask, ins->maps ? ins->maps + i * rows * T : nullptr,
-                                              ins->received ? ins->received + i * rows : nullptr,
-                                              ins->entropy ? ins->entropy + i * rows : nullptr, B, H, T, d / H, scale, ins->workspace, st));
-            }
-        }
-        {
-            StageScope ps(VS_STAGE_ATTENTION, st);
-            if (pk)
-                VS_LAUNCH(vsk_attention_packed(qkv, qkv + kv_stride, qkv + 2 * kv_stride, att, H, M, d / H, scale,
-                                               pk->cu, pk->work, pk->nwork, pk->nw, qkv16 ? (1 | VSK_STORE16) : pk->prec, st));
-            else if (d / H == 256)      // head dim 256 (round 4, correctness first): the training path's exact forward kernel without
-                                        // dropout; its log-sum-exp output lands in the MLP hidden region, which is free here
-                VS_LAUNCH(vst_attention_fwd(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, key_pad_mask, att, ffn, B, H, T, 256, scale,
-                                            0ull, 0u, 0.f, st, nullptr));
-            else if (splitk && aprec != 1 && (d / H == 32 || d / H == 64 || d / H == 128))      // latency mode: the keys split over a block's waves
-                VS_LAUNCH(vsk_attention_splitkv(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, key_pad_mask, att, B, H, T, d / H, scale, st));
-            else if (aprec)
-                VS_LAUNCH(vsk_attention_bf16(qkv, qkv + kv_stride, qkv + 2 * kv_stride, key_pad_mask, att,
-                                             B, H, T, d / H, scale, qkv16 ? (1 | VSK_STORE16) : aprec, st));
-            else
-                VS_LAUNCH(vsk_attention(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, key_pad_mask, att, B, H,
-                                        T, d / H, scale, st));
-        }
-        float *dst = (last && hidden) ? hidden : h0;
-        // bf16 mode, d_model 256, bf16 attention output: out-projection + norm1 + the whole MLP block + norm2 (+ score
-        // head) as ONE kernel; h1 never exists in HBM
-        if (mlp16 && qkv16 && !vsk_options().lp_tail_unfused) {
+            // fc2 (fp32 out into the att region) + norm2 (+ score head) -> h0 / hidden (+ bf16 copy for the next layer)
+            StageScope ps(VS_STAGE_FC2_LN, st);
+            VS_LAUNCH(vsk_gemm16(ffn, w->p(P.r_w2), w->p(P.b2), att, M, d, 4 * d, 0, 0, 1, 0, 0, 1.0f, st));
+            VS_LAUNCH(vsk_rows_res_ln(att, h1, w->p(P.ln2g), w->p(P.ln2b), dst, M, d, head_w, head_b, D.num_classes, sig, head_out, st,
+                                      last ? nullptr : h16, dn));
+        } break;
+        case VS_LAYER_BF16_TAIL: {      // h1 never exists in HBM
             StageScope ps(VS_STAGE_FC2_LN, st);
             VS_LAUNCH(vsk_mlp_bf16(h0, att, w->p(P.bo), w->p(P.ln1g), w->p(P.ln1b), w->p(P.b_mlp), w->p(P.b1), w->p(P.b2),
-                                   w->p(P.ln2g), w->p(P.ln2b), dst, M, d, last ? w->p(w->final_w) : nullptr,
-                                   last ? w->p(w->final_b) : nullptr, D.num_classes, sig, last ? scores : nullptr, next, st));
-            have_qkv = next != nullptr;
-            continue;
-        }
-        have_qkv = false;
-        if (exact_fused) {
+                                   w->p(P.ln2g), w->p(P.ln2b), dst, M, d, head_w, head_b, D.num_classes, sig, head_out, next, st));
+        } break;
+        case VS_LAYER_BF16_MLP: {       // the whole MLP block as one kernel (hidden activations in registers)
+            StageScope ps(VS_STAGE_FC2_LN, st);
+            VS_LAUNCH(vsk_mlp_bf16(h1, nullptr, nullptr, nullptr, nullptr, w->p(P.b_mlp), w->p(P.b1), w->p(P.b2), w->p(P.ln2g), w->p(P.ln2b), dst, M, d,
+                                   head_w, head_b, D.num_classes, sig, head_out, next, st));
+        } break;
+        case VS_LAYER_EXACT_PAIR: {
             {   // recorded under fc1 / fc2: the stage table has no out-projection row then, and these two rows' FLOPs omit the
                 // out-projection and QKV shares (their TFLOP/s are understated, never overstated)
                 StageScope ps(VS_STAGE_FC1, st);
@@ -604,63 +571,34 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
             StageScope ps(VS_STAGE_FC2_LN, st);
             if (last) {
                 VS_LAUNCH(vsk_linear_res_ln(ffn, w->p(P.w2), w->p(P.f_w2), w->p(P.b2), h1, w->p(P.ln2g), w->p(P.ln2b), dst, M, d, 4 * d,
-                                            w->p(w->final_w), w->p(w->final_b), D.num_classes, sig, scores, 0, st));
+                                            head_w, head_b, D.num_classes, sig, head_out, 0, st));
             } else {
                 const LayerOff &N = w->layers[l + 1];
                 VS_LAUNCH(vsk_fc2_ln_qkv(ffn, w->p(P.w2), w->p(P.b2), h1, w->p(P.ln2g), w->p(P.ln2b), dst, w->p(N.wqkv), w->p(N.bqkv), qkv,
                                          B, T, d, H, st));
-                have_qkv = true;
             }
-            continue;
-        }
-        // d_model > 256: plain GEMM + the row LayerNorm pass (faster than the fused wide kernel at every M; the
-        // GEMM's output goes to a region of the workspace that is free at that point: q after the attention, att after fc1)
-        const bool split_ln = d > 256 || embedded;      // (an embedded model's LayerNorm width is not d: the row pass knows it)
-        {
-            StageScope ps(VS_STAGE_OUTPROJ_LN, st);
-            if (splitk && d >= 256) {     // K = d in two slices (q / k regions are free after the attention), LayerNorm as a row pass
-                const int so = 2;
-                VS_LAUNCH(vsk_linear_parts(att, w->p(lbf == 2 ? P.h_wo : P.f_wo), qkv, M, d, d, so, st, lbf == 2));
-                VS_LAUNCH(vsk_rows_res_ln(qkv, h0, w->p(P.ln1g), w->p(P.ln1b), h1, M, d, nullptr, nullptr, 0, 0, nullptr, st, nullptr, dn,
-                                          so, w->p(P.bo)));
-            } else if (split_ln) {
-                VS_LAUNCH(vsk_linear(att, w->p(P.wo), w->p(lnbf == 2 ? P.h_wo : P.f_wo), w->p(P.bo), qkv, M, d, d, 0, nullptr, 1, lnbf, st));
-                VS_LAUNCH(vsk_rows_res_ln(qkv, h0, w->p(P.ln1g), w->p(P.ln1b), h1, M, d, nullptr, nullptr, 0, 0, nullptr, st, nullptr, dn));
-            } else
-            VS_LAUNCH(vsk_linear_res_ln(att, w->p(P.wo), w->p(lnbf == 2 ? P.h_wo : P.f_wo), w->p(P.bo), h0, w->p(P.ln1g), w->p(P.ln1b), h1, M, d, d,
-                                        nullptr, nullptr, 0, 0, nullptr, qkv16 ? (1 | VSK_STORE16) : lnbf, st));
-        }
-        // bf16 mode, d_model 256, throughput batches: the whole MLP block as one kernel (hidden activations in registers)
-        if (mlp16) {
+        } break;
+        case VS_LAYER_STAGES: {
+            {
+                StageScope ps(VS_STAGE_FC1, st);
+                VS_LAUNCH(vsk_linear(h1, w->p(P.w1), frag(P.f_w1, P.h_w1), w->p(P.b1), ffn, M, 4 * d, d, 1, nullptr, 1, plan.mode_ffn, st));
+            }
             StageScope ps(VS_STAGE_FC2_LN, st);
-            VS_LAUNCH(vsk_mlp_bf16(h1, nullptr, nullptr, nullptr, nullptr, w->p(P.b_mlp), w->p(P.b1), w->p(P.b2), w->p(P.ln2g), w->p(P.ln2b), dst, M, d,
-                                   last ? w->p(w->final_w) : nullptr, last ? w->p(w->final_b) : nullptr,
-                                   D.num_classes, sig, last ? scores : nullptr, next, st));
-            have_qkv = next != nullptr;
-            continue;
-        }
-        {
-            StageScope ps(VS_STAGE_FC1, st);
-            VS_LAUNCH(vsk_linear(h1, w->p(P.w1), w->p(lbf == 2 ? P.h_w1 : P.f_w1), w->p(P.b1), ffn, M, 4 * d, d, 1, nullptr, 1,
-                                 ffn16 ? (1 | VSK_STORE16) : lbf, st));
-        }
-        if (splitk) {      // K = 4 d split four ways (partials in the q / k / v / att regions, free by now), LayerNorm (+ score head) as a row pass
-            StageScope ps(VS_STAGE_FC2_LN, st);
-            VS_LAUNCH(vsk_linear_parts(ffn, w->p(lbf == 2 ? P.h_w2 : P.f_w2), qkv, M, d, 4 * d, 4, st, lbf == 2));
-            VS_LAUNCH(vsk_rows_res_ln(qkv, h1, w->p(P.ln2g), w->p(P.ln2b), dst, M, d, last ? w->p(w->final_w) : nullptr,
-                                      last ? w->p(w->final_b) : nullptr, D.num_classes, sig, last ? scores : nullptr, st, nullptr, dn,
-                                      4, w->p(P.b2)));
-        } else if (split_ln) {
-            StageScope ps(VS_STAGE_FC2_LN, st);
-            VS_LAUNCH(vsk_linear(ffn, w->p(P.w2), w->p(lnbf == 2 ? P.h_w2 : P.f_w2), w->p(P.b2), att, M, d, 4 * d, 0, nullptr, 1, lnbf, st));
-            VS_LAUNCH(vsk_rows_res_ln(att, h1, w->p(P.ln2g), w->p(P.ln2b), dst, M, d, last ? w->p(w->final_w) : nullptr,
-                                      last ? w->p(w->final_b) : nullptr, D.num_classes, sig, last ? scores : nullptr, st, nullptr, dn));
-        } else {
-            StageScope ps(VS_STAGE_FC2_LN, st);
-            VS_LAUNCH(vsk_linear_res_ln(ffn, w->p(P.w2), w->p(lnbf == 2 ? P.h_w2 : P.f_w2), w->p(P.b2), h1, w->p(P.ln2g), w->p(P.ln2b), dst, M, d,
-                                        4 * d, last ? w->p(w->final_w) : nullptr,
-                                        last ? w->p(w->final_b) : nullptr, D.num_classes, sig,
-                                        last ? scores : nullptr, ffn16 ? (1 | VSK_STORE16) : lnbf, st));
+            switch (plan.ln2) {
+            case VS_LN_SPLITK_ROWS:     // K = 4 d split four ways (partials in the q / k / v / att regions, free by now), LayerNorm (+ score head) as a row pass
+                VS_LAUNCH(vsk_linear_parts(ffn, frag(P.f_w2, P.h_w2), qkv, M, d, 4 * d, 4, st, f16x3));
+                VS_LAUNCH(vsk_rows_res_ln(qkv, h1, w->p(P.ln2g), w->p(P.ln2b), dst, M, d, head_w, head_b, D.num_classes, sig, head_out, st, nullptr, dn,
+                                          4, w->p(P.b2)));
+                break;
+            case VS_LN_GEMM_ROWS:       // (the GEMM's output goes to the att region, free after fc1)
+                VS_LAUNCH(vsk_linear(ffn, w->p(P.w2), frag(P.f_w2, P.h_w2), w->p(P.b2), att, M, d, 4 * d, 0, nullptr, 1, plan.mode_linear, st));
+                VS_LAUNCH(vsk_rows_res_ln(att, h1, w->p(P.ln2g), w->p(P.ln2b), dst, M, d, head_w, head_b, D.num_classes, sig, head_out, st, nullptr, dn));
+                break;
+            default:
+                VS_LAUNCH(vsk_linear_res_ln(ffn, w->p(P.w2), frag(P.f_w2, P.h_w2), w->p(P.b2), h1, w->p(P.ln2g), w->p(P.ln2b), dst, M, d,
+                                            4 * d, head_w, head_b, D.num_classes, sig, head_out, plan.mode_ffn, st));
+            }
+        } break;
         }
     }
     return VS_OK;
@@ -741,7 +679,7 @@ int vs_attention_probs_f32(const float *q, const float *k, const uint8_t *key_pa
 
 // ---- packed ragged batches ----
 static int packed_plan(const vs_weights *w, const int32_t *lengths, int32_t B, std::vector<int> &cu,
-                       std::vector<int> &work, int &nw, bool narrow_only = false, bool wide_only = false) {
+                       std::vector<int> &work, int &nw, int aprec = 0) {
     if (!w || !lengths || B <= 0) return fail(VS_ERR_INVALID, "weights/lengths is NULL or B=%d", B);
     const vs_model_desc &D = w->desc;
     const int dh = D.d_model / D.num_heads;
@@ -758,8 +696,7 @@ static int packed_plan(const vs_weights *w, const int32_t *lengths, int32_t B, s
         r8 += (t + 255) / 256 * 256;
         r4 += (t + 127) / 128 * 128;
     }
-    nw = (!narrow_only && r8 * 100 <= r4 * 105) ? 8 : 4;     // 256-row query tiles unless the ragged tails waste too much
-    if (dh == 128) nw = wide_only ? 8 : 4;                   // head dim 128 (round 4): the exact kernel has 4-wave blocks, the bf16 one 8-wave blocks only
+    nw = vs_packed_waves(dh, aprec, r8, r4);
     const int qb = 32 * nw;
     work.clear();
     for (int b = 0; b < B; ++b)
@@ -791,13 +728,12 @@ int vs_scorer_forward_packed(const vs_weights *w, const float *x, const int32_t 
     if (!w) return fail(VS_ERR_INVALID, "weights is NULL");
     if ((flags & VS_FLAG_BF16_ATTENTION) && (flags & VS_FLAG_F16X3_ATTENTION))
         return fail(VS_ERR_INVALID, "VS_FLAG_BF16_ATTENTION and VS_FLAG_F16X3_ATTENTION are exclusive");
-    const int aprec = (flags & VS_FLAG_F16X3_ATTENTION) ? 2 : (flags & VS_FLAG_BF16_ATTENTION) ? 1 : 0;
+    const int aprec = vs_attention_prec(flags);
     std::vector<int> cu, work;
     int nw = 0;
-    // (the low-precision attention has no 8-wave form for head dim 32)
     if (aprec == 2 && w->desc.d_model / w->desc.num_heads == 128)
         return fail(VS_ERR_INVALID, "VS_FLAG_F16X3_ATTENTION needs head_dim 32 or 64 (got 128)");
-    if (int rc = packed_plan(w, lengths, B, cu, work, nw, aprec != 0 && w->desc.d_model / w->desc.num_heads == 32, aprec == 1)) return rc;
+    if (int rc = packed_plan(w, lengths, B, cu, work, nw, aprec)) return rc;
     const size_t need = vs_scorer_workspace_bytes_packed(w, lengths, B);
     if (!workspace || workspace_bytes < need)
         return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
@@ -812,14 +748,14 @@ int vs_scorer_forward_packed(const vs_weights *w, const float *x, const int32_t 
     const size_t cap = packed_plan_capacity(lengths, B);
     if (work.size() / 2 > cap) return fail(VS_ERR_INVALID, "internal: packed plan %zu > capacity %zu", work.size() / 2, cap);
     VS_LAUNCH(vsk_plan_packed(lengths_dev, B, 32 * nw, plan, plan + cu.size(), (int)cap, st));
-    PackedInfo pk{nullptr, plan, plan + cu.size(), (int)(work.size() / 2), nw, aprec};
+    PackedInfo pk{nullptr, plan, plan + cu.size(), (int)(work.size() / 2), nw};
     if (w->has_pe) {
         int tmax = 0;
         for (int b = 0; b < B; ++b) tmax = lengths[b] > tmax ? lengths[b] : tmax;
         VS_LAUNCH(vsk_gather_rows(w->p(w->pe), pk.cu, B, tmax, d, pe_rows, st));
         pk.pe_rows = pe_rows;
     }
-    return forward_core(w, x, nullptr, 1, M, flags & ~(VS_FLAG_F16X3_ATTENTION | VS_FLAG_BF16_ATTENTION), scores, hidden, workspace, 10 * md, stream, &pk);
+    return forward_core(w, x, nullptr, 1, M, flags, scores, hidden, workspace, 10 * md, stream, &pk);
 }
 
 int vs_profile_enable(int32_t on) {

@@ -5,6 +5,7 @@
 
 #include <vector>
 
+#include "vs_forward_plan.h"      // VSW_*: the image families
 #include "vs_scorer.h"
 
 struct LayerOff {
@@ -69,7 +70,6 @@ int vs_fail_msg(int code, const char *msg);     // vs_scorer.cpp: sets the threa
 
 // (re)builds the image families in `families` that are older than the handle's parameters, stream-ordered on `st`.
 // A handle's calls must be issued on ONE stream at a time (or be ordered by the caller): include/vs_scorer.h.
-enum { VSW_FRAGMENTS = 1, VSW_F16X3 = 2, VSW_BF16 = 4, VSW_ROWS16 = 8 };
 int vsw_ensure(const vs_weights *w, unsigned families, void *stream);
 // stream ordering helpers (vs_scorer.cpp): vsw_mark() after parameter writes / image rebuilds were enqueued on `stream`;
 // vsw_order() before a call on `stream` reads them (a no-op when it is the same stream)
