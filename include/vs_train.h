@@ -34,7 +34,7 @@ typedef struct vs_dropout_cfg {
     float p;
     uint64_t seed;
     uint32_t flags;      /* VS_TRAIN_FLAG_*; 0 = exact fp32 everywhere */
-    uint32_t reserved;   /* 0 */
+    uint32_t reserved;   /* 0; a backward may pass its forward's vs_train_last_format() (below) */
 } vs_dropout_cfg;
 
 /* Low-precision training, the counterpart of the reference's fp16 autocast (`with amp.autocast():` around the forward,
@@ -314,7 +314,9 @@ int vs_train_saved_field(const vs_weights *w, int32_t B, int32_t T, int32_t laye
  * (q/k/v; MLP hidden; written by the A-stationary GEMM), bit 5 the 16-bit type is fp16 (VS_TRAIN_FLAG_FP16).  Bits 0 and 1 both clear = the exact fp32 path ran, whatever
  * vs_dropout_cfg.flags asked for (low-precision training applies above VS_TRAIN_LP_MIN_ROWS frames per batch, default 1024).
  * Pass the value to vs_train_backward in vs_dropout_cfg.reserved: the backward then reads the record in the form it was
- * written in even if a library switch (vs_set_option) changed in between; reserved == 0 derives the form again. */
+ * written in even if a library switch (vs_set_option) changed in between; reserved == 0 derives the form again.  A word
+ * with bit 31 set that spells no form this model / batch can have is refused (VS_ERR_INVALID) before anything is launched
+ * (csrc/vs_train_plan.h). */
 uint32_t vs_train_last_format(void);
 
 /* module numbers (`site`) of the dropouts: embedding = 0; layer l: 1 + 4*l + {0 attention, 1 dropout1, 2 mlp, 3 dropout2} */

@@ -414,6 +414,54 @@ def test_backward_reads_the_record_in_the_form_the_forward_wrote(vsa, lp_train_e
         assert torch.isfinite(a).all() and torch.equal(a, b), n
 
 
+def test_backward_refuses_a_record_form_this_batch_cannot_have(vsa):
+    """vs_dropout_cfg.reserved is parsed by the plan (csrc/vs_train_plan.h) before any device work: a word that spells no
+    possible record form - q / k / v stored as 16-bit without the 16-bit Linears (0x80000004), a stray bit (0x80000040) - is
+    refused with VS_ERR_INVALID and the documented text, and nothing is launched (the gradient buffers keep their fill).  The
+    same backward with the forward's own vs_train_last_format() then runs, bit-identical to one that derives the form again."""
+    lib = vsa._lib.load()
+    m = vsa.SimNet(num_heads=4, d_model=256, num_layers=1, sparsity=0.0, dropout=0.0)
+    m.load_state_dict(vsa.synth.make_state_dict(256, 1, 3))
+    m = m.to(_dev()).train()
+    B, T = 1, 8
+    gen = torch.Generator().manual_seed(1)
+    x = torch.randn(B, T, 1024, generator=gen).to(_dev())
+    ds, dh = torch.randn(B, T, 1, generator=gen).to(_dev()), torch.randn(B, T, 256, generator=gen).to(_dev())
+    w = m._packed_weights(x.device).handle
+    scores, hidden = torch.empty(B, T, 1, device=_dev()), torch.empty(B, T, 256, device=_dev())
+    saved = torch.empty(lib.vs_train_saved_bytes(w, B, T), dtype=torch.uint8, device=_dev())
+    ws = torch.empty(lib.vs_train_workspace_bytes(w, B, T), dtype=torch.uint8, device=_dev())
+    vsa._lib.check(lib.vs_train_prepare(w, _stream()))
+    cfg = vsa._lib.DropoutCfg(0.0, 0.0, 0, 0, 0)
+    vsa._lib.check(lib.vs_train_forward(w, x.data_ptr(), None, B, T, C.byref(cfg), scores.data_ptr(), hidden.data_ptr(), saved.data_ptr(),
+                                        saved.numel(), ws.data_ptr(), ws.numel(), _stream()))
+    fmt = int(lib.vs_train_last_format())
+    assert fmt == 0x80000000       # exact fp32: bit 31 alone
+
+    def backward(reserved):
+        grads, G, _finish = vsa.simnet._grad_destinations(m, x.device)
+        dx = torch.full_like(x, 7.0)
+        for g in grads:
+            g.fill_(7.0)
+        cfg = vsa._lib.DropoutCfg(0.0, 0.0, 0, 0, reserved)
+        rc = lib.vs_train_backward(w, x.data_ptr(), None, B, T, C.byref(cfg), ds.data_ptr(), dh.data_ptr(), saved.data_ptr(), saved.numel(),
+                                   C.byref(G), dx.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        torch.cuda.synchronize()
+        return rc, [dx] + grads
+
+    for word in (0x80000004, 0x80000040):
+        rc, out = backward(word)
+        assert rc == vsa._lib.VS_ERR_INVALID
+        assert lib.vs_last_error().decode() == "vs_dropout_cfg.reserved = 0x%08x is not a record form this model / batch can have" % word
+        assert all(bool((g == 7.0).all()) for g in out), "a refused backward wrote a gradient"
+    rc, handed = backward(fmt)
+    assert rc == vsa._lib.VS_OK, lib.vs_last_error().decode()
+    rc, derived = backward(0)
+    assert rc == vsa._lib.VS_OK, lib.vs_last_error().decode()
+    for a, b in zip(handed, derived):
+        assert torch.isfinite(a).all() and not bool((a == 7.0).all()) and torch.equal(a, b)
+
+
 def test_low_precision_request_below_the_threshold_says_so(vsa):
     """below VS_TRAIN_LP_MIN_ROWS frames per batch the exact kernels run whatever set_train_dtype asked for -
     the model now records what ran (last_train_dtype) and warns once instead of doing so silently."""

@@ -1,7 +1,8 @@
 // vs_train.cpp — the C ABI of include/vs_train.h: the train-mode forward of the scorer with its activation record,
 // and the backward pass.  Launch sequences only; the kernels are in vs_kernels.hip (NT GEMMs, reused for every
 // forward Linear and — against transposed weights — for every dgrad), vs_train_kernels.hip and
-// vs_train_attention.hip.
+// vs_train_attention.hip.  Which form the record has and which mode word each launch gets is decided once per call, in
+// vs_train_plan.h; forward_impl / backward_impl only read that plan.
 #include "vs_train.h"
 
 #include <hip/hip_runtime.h>
@@ -10,6 +11,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <mutex>
+#include <string>
 
 #include "vs_train_device_sites.h"
 #include "vs_train_kernels.h"
@@ -40,18 +42,10 @@ int failf(int code, const char *fmt, ...) {
 
 size_t align_floats(size_t n) { return (n + 63) / 64 * 64; }      // 256-byte granules
 
-// The FORM of an activation record: which tensors of it are bf16 planes / which arithmetic wrote it.  The forward derives it
-// from the request (vs_dropout_cfg.flags), the batch size and the library's switches; the backward must read the record in
-// the form it was WRITTEN in.  The forward therefore publishes the form (vs_train_last_format(), per calling thread) and the
-// backward takes it back through vs_dropout_cfg.reserved - a switch flipped between the two calls (another model, a retained
-// graph, a test) can no longer make the backward read bf16 planes as fp32.  reserved == 0: derived again (older callers).
-struct RecordForm {
-    int lp; bool lpa, qkv16, h16, rows16, f16;      // f16: the 16-bit type of everything above is IEEE f16 (VS_TRAIN_FLAG_FP16)
-    uint32_t bits() const {
-        return 0x80000000u | (lp ? 1u : 0u) | (lpa ? 2u : 0u) | (qkv16 ? 4u : 0u) | (h16 ? 8u : 0u) | (rows16 ? 16u : 0u) | (f16 ? 32u : 0u);
-    }
-};
-thread_local uint32_t g_last_format = 0;
+thread_local uint32_t g_last_format = 0;      // VsTrainPlan::format of this thread's last forward (vs_train_last_format)
+
+// the weight images (re)built in this scope are ordered behind `s` when it ends (vs_weights_impl.h)
+struct Mark { const vs_weights *w; void *s; ~Mark() { vsw_mark(w, s); } };
 
 // A packed ragged batch (vs_train_forward_packed) as the host sees it: every row-wise kernel runs it as ONE "video" of Mtot
 // rows (B = 1, T = Mtot below); the positional rows, the attention, its keep words and the loss know the boundaries.
@@ -79,30 +73,8 @@ int packed_ctx(const vs_model_desc &D, const int32_t *lengths, int32_t B, Packed
     return VS_OK;
 }
 
-RecordForm derive_form(const vs_weights *w, const vs_dropout_cfg *drop, int B, int T, bool packed = false) {
-    RecordForm f{};
-    // low-precision training (VS_TRAIN_FLAG_BF16_LINEAR): every Linear / dgrad / wgrad GEMM on the bf16 matrix pipe, from the
-    // batch size up where that pays (VS_TRAIN_LP_MIN_ROWS, default 1024 frames: tools/sweep_lp_min_rows.py,
-    // profiles/r04_lp_min_rows_sweep.txt - break-even at ~1280 frames, never slower; rounds 2-3 used the scoring path's 8192)
-    f.lp = (drop && (drop->flags & VS_TRAIN_FLAG_BF16_LINEAR) && (long long)B * T > vsk_options().train_lp_min_rows) ? 1 : 0;
-    // ... and (VS_TRAIN_FLAG_BF16_ATTENTION) the attention products of the forward and the backward (head dim 32 / 64 / 128)
-    // (packed ragged batches: the attention stays exact fp32 unless VS_TRAIN_FLAG_PACKED_LP_ATTENTION opts in as well - the
-    // padded rule counted on the packed rows, B * T = Mtot here; padded calls do not read that bit)
-    f.lpa = drop && (drop->flags & VS_TRAIN_FLAG_BF16_ATTENTION) && (!packed || (drop->flags & VS_TRAIN_FLAG_PACKED_LP_ATTENTION)) &&
-            (long long)B * T > vsk_options().train_lp_min_rows && vst_attention_bf16_supported(w->desc.d_model / w->desc.num_heads);
-    // bf16 STORAGE of the tensors that are only ever bf16 matrix operands (VS_LP_STORE32 = 1 keeps them fp32: an A/B switch -
-    // the kernels round the fp32-stored values to the same bf16, so every result is bit-identical either way)
-    // (packed: the packed 16-bit attention kernels read fp32-stored planes and an fp32 dO only)
-    f.qkv16 = !packed && f.lp && f.lpa && !vsk_options().lp_store32;     // q / k / v of the record are bf16 planes
-    f.h16 = f.lp && !vsk_options().lp_store32;                // ... and so is the MLP hidden tensor (and, in the backward, its gradient)
-    // ... which the A-stationary GEMM writes where it applies (K = d_model = 256, batches that fill the chip; VS_LP_MLP_UNFUSED = 1: the
-    // tiled kernels, 2: the A-stationary kernel at every batch size - A/B and test switches)
-    f.f16 = (f.lp || f.lpa) && (drop->flags & VS_TRAIN_FLAG_FP16) != 0;
-    // (the A-stationary kernels and their pre-rounded weight copies exist in bf16 only: the fp16 mode runs the tiled GEMMs)
-    f.rows16 = f.h16 && !f.f16 && vsk_options().lp_mlp_unfused != 1 &&
-               vst_gemm_rows16_supported(B * T, 4 * w->desc.d_model, w->desc.d_model, vsk_options().lp_mlp_unfused == 2);
-    return f;
-}
+// ... of a call that has no model: any length fits
+int packed_lengths(const int32_t *lengths, int32_t B, PackedCtx &pc) { return packed_ctx(vs_model_desc{}, lengths, B, pc); }
 
 // ---- activation record (floats) ----
 struct LayerSaved { size_t qkv, att, lse, z1, st1, y1, ffn, z2, st2, y2, dbits; };
@@ -159,18 +131,51 @@ WorkLayout work_layout(const vs_model_desc &D, int B, int T, const PackedCtx *pc
     return W;
 }
 
-int check_common(const vs_weights *w, const float *x, int B, int T, const vs_dropout_cfg *drop, bool packed = false) {
+// Where field `field` of layer `layer` lies in the record (test / inspection hook); field 4, the log-sum-exp rows, is laid out
+// per head over the packed rows and exists for packed batches only
+int saved_field(const vs_weights *w, int B, int T, const PackedCtx *pc, int layer, int field, size_t *offset_bytes, size_t *count) {
+    const LayerSaved A = saved_layout(w->desc, B, T, pc).layers[layer];
+    const size_t M = (size_t)B * T, Md = M * w->desc.d_model;
+    size_t off, n;
+    switch (field) {
+        case 0: off = A.ffn; n = 4 * Md; break;
+        case 1: off = A.att; n = Md; break;
+        case 2: off = A.y1; n = Md; break;
+        case 3: off = A.y2; n = Md; break;
+        case 4: if (pc) { off = A.lse; n = M * w->desc.num_heads; break; }
+            [[fallthrough]];
+        default: return failf(VS_ERR_INVALID, "saved_field: unknown field %d", field);
+    }
+    *offset_bytes = off * sizeof(float);
+    *count = n;
+    return VS_OK;
+}
+
+// The checks of both directions that need no buffer, in their order: w / x, the plan's own (B, T, the positional table, the
+// dropout probabilities - and, in the backward, a handed-back record form), x's alignment, the device.  No device work yet.
+int plan_call(const vs_weights *w, const float *x, int B, int T, const vs_dropout_cfg *drop, bool packed, bool backward,
+              VsTrainPlan *plan) {
     if (!w || !x) return failf(VS_ERR_INVALID, "weights/x is NULL");
-    if (B <= 0 || T <= 0) return failf(VS_ERR_INVALID, "B=%d T=%d", B, T);
-    if ((long long)B * T > (1ll << 28)) return failf(VS_ERR_INVALID, "B*T too large");
-    if (!packed && w->has_pe && T > w->desc.max_len)
-        return failf(VS_ERR_INVALID, "T=%d exceeds the positional table (max_len=%d)", T, w->desc.max_len);
-    if (drop && (drop->p < 0.f || drop->p >= 1.f || drop->p_embed < 0.f || drop->p_embed >= 1.f))
-        return failf(VS_ERR_INVALID, "dropout probabilities must be in [0, 1): p=%g p_embed=%g", drop->p, drop->p_embed);
+    const VsTrainIn in{w->desc.d_model, w->desc.num_heads, w->desc.max_len, w->has_pe, B, T, packed, drop ? drop->flags : 0u,
+                       drop ? drop->p : 0.f, drop ? drop->p_embed : 0.f, drop ? drop->reserved : 0u, backward};
+    std::string err;
+    if (int rc = vs_train_plan(in, vsk_options(), plan, &err)) return vs_fail_msg(rc, err.c_str());
     if ((uintptr_t)x & 15) return failf(VS_ERR_INVALID, "x must be 16-byte aligned");
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != w->device)
         return failf(VS_ERR_INVALID, "called on device %d, the weights handle lives on device %d", dev, w->device);
+    return VS_OK;
+}
+
+// size and alignment of the record and the scratch; `hidden`: the forward's optional output
+int check_buffers(const SavedLayout &S, const WorkLayout &W, const void *saved, size_t saved_bytes, const void *workspace,
+                  size_t workspace_bytes, bool forward, const void *hidden) {
+    if (saved_bytes < S.total * sizeof(float))
+        return failf(VS_ERR_WORKSPACE, "saved %zu bytes < %zu needed", saved_bytes, S.total * sizeof(float));
+    if (workspace_bytes < W.total * sizeof(float))
+        return failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, W.total * sizeof(float));
+    if (((uintptr_t)saved & 255) || ((uintptr_t)workspace & 255) || (hidden && ((uintptr_t)hidden & 15)))
+        return vs_fail_msg(VS_ERR_INVALID, forward ? "saved/workspace must be 256-byte, hidden 16-byte aligned" : "saved/workspace must be 256-byte aligned");
     return VS_OK;
 }
 
@@ -205,7 +210,7 @@ int ensure_transposed(vs_weights *w, hipStream_t st, bool frags) {
     vsw_order(w, (void *)st);
     const bool do_t = w->t_version != w->version, do_f = frags && w->tf_version != w->version;
     if (!do_t && !do_f) return VS_OK;
-    struct Mark { const vs_weights *w; void *s; ~Mark() { vsw_mark(w, s); } } mark{w, (void *)st};
+    Mark mark{w, (void *)st};
     // one launch per family (was one per matrix: 17 transposes + 17 fragment packs + 4 conversions per optimizer step)
     VskMatJobs tj{}, fj{};
     auto add = [&](const float *W, size_t t_off, size_t tf_off, int N, int K) {
@@ -242,7 +247,7 @@ int ensure_t16(vs_weights *w, hipStream_t st) {
     std::lock_guard<std::mutex> lk(g_tmu);
     if (w->t16_version == w->version) return VS_OK;
     vsw_order(w, (void *)st);
-    struct Mark { const vs_weights *w; void *s; ~Mark() { vsw_mark(w, s); } } mark{w, (void *)st};
+    Mark mark{w, (void *)st};
     const size_t d = w->desc.d_model;
     for (int l = 0; l < w->desc.num_layers; ++l) {
         const LayerOffT &Q = w->tlayers[l];
@@ -278,17 +283,7 @@ int vs_train_saved_field(const vs_weights *w, int32_t B, int32_t T, int32_t laye
                          size_t *count) {
     if (!w || !offset_bytes || !count || B <= 0 || T <= 0 || layer < 0 || layer >= w->desc.num_layers)
         return failf(VS_ERR_INVALID, "saved_field: bad arguments");
-    const SavedLayout S = saved_layout(w->desc, B, T);
-    const LayerSaved &A = S.layers[layer];
-    const size_t Md = (size_t)B * T * w->desc.d_model;
-    switch (field) {
-        case 0: *offset_bytes = A.ffn * sizeof(float); *count = 4 * Md; break;
-        case 1: *offset_bytes = A.att * sizeof(float); *count = Md; break;
-        case 2: *offset_bytes = A.y1 * sizeof(float); *count = Md; break;
-        case 3: *offset_bytes = A.y2 * sizeof(float); *count = Md; break;
-        default: return failf(VS_ERR_INVALID, "saved_field: unknown field %d", field);
-    }
-    return VS_OK;
+    return saved_field(w, B, T, nullptr, layer, field, offset_bytes, count);
 }
 
 uint32_t vs_train_last_format(void) { return g_last_format; }
@@ -296,31 +291,62 @@ uint32_t vs_train_last_format(void) { return g_last_format; }
 uint32_t vs_train_dropout_site(int32_t layer, int32_t which) { return layer < 0 ? VS_SITE_EMBED : VS_SITE_LAYER(layer, which); }
 
 // pc != nullptr: a packed ragged batch, B = 1 and T = Mtot (no key mask)
+// One layer's attention, forward and backward, on the kernel the plan names.  q / k / v: planes `kv_stride` floats apart;
+// dbits: the layer's bit-packed keep words (p > 0) - the 16-bit kernels have no hash-per-element form, the exact ones take either
+static int attention_forward(const VsTrainPlan &plan, const float *qkv, const uint8_t *key_pad_mask, float *out, float *lse, int B,
+                             int H, int T, int dh, float scale, unsigned long long seed, unsigned site, float p,
+                             const unsigned *dbits, const VstPackedPlan &pk, hipStream_t st) {
+    const float *q = qkv, *k = qkv + plan.kv_stride, *v = qkv + 2 * plan.kv_stride;
+    switch (plan.attention) {
+        case VST_ATT_PACKED16: VST_LAUNCH(vst_attention_fwd_bf16_packed(q, k, v, out, lse, H, dh, scale, p, dbits, st, plan.form.f16, pk)); break;
+        case VST_ATT_PACKED_EXACT: VST_LAUNCH(vst_attention_fwd_packed(q, k, v, out, lse, H, dh, scale, seed, site, p, st, dbits, pk)); break;
+        case VST_ATT_PADDED16:
+            VST_LAUNCH(vst_attention_fwd_bf16(q, k, v, key_pad_mask, out, lse, B, H, T, dh, scale, p, dbits, st, plan.mode_attention));
+            break;
+        case VST_ATT_PADDED_EXACT: VST_LAUNCH(vst_attention_fwd(q, k, v, key_pad_mask, out, lse, B, H, T, dh, scale, seed, site, p, st, dbits)); break;   // :155-161
+    }
+    return VS_OK;
+}
+
+static int attention_backward(const VsTrainPlan &plan, const float *qkv, const uint8_t *key_pad_mask, const float *datt, const float *lse,
+                              const float *delta, float *dqkv, int B, int H, int T, int dh, float scale, unsigned long long seed,
+                              unsigned site, float p, const unsigned *dbits, const VstPackedPlan &pk, hipStream_t st) {
+    const float *q = qkv, *k = qkv + plan.kv_stride, *v = qkv + 2 * plan.kv_stride;
+    switch (plan.attention) {
+        case VST_ATT_PACKED16:
+            VST_LAUNCH(vst_attention_bwd_bf16_packed(q, k, v, datt, lse, delta, dqkv, H, dh, scale, p, dbits, st, plan.form.f16, pk));
+            break;
+        case VST_ATT_PACKED_EXACT:
+            VST_LAUNCH(vst_attention_bwd_packed(q, k, v, datt, lse, delta, dqkv, H, dh, scale, seed, site, p, st, dbits, pk));
+            break;
+        case VST_ATT_PADDED16:
+            VST_LAUNCH(vst_attention_bwd_bf16(q, k, v, key_pad_mask, datt, lse, delta, dqkv, B, H, T, dh, scale, p, dbits, st,
+                                              plan.mode_attention, plan.attention_out16));
+            break;
+        case VST_ATT_PADDED_EXACT:
+            VST_LAUNCH(vst_attention_bwd(q, k, v, key_pad_mask, datt, lse, delta, dqkv, B, H, T, dh, scale, seed, site, p, st, dbits));
+            break;
+    }
+    return VS_OK;
+}
+
+// pc != nullptr: a packed ragged batch, B = 1 and T = Mtot (no key mask)
 static int forward_impl(const vs_weights *w, const float *x, const uint8_t *key_pad_mask, int32_t B, int32_t T,
                         const vs_dropout_cfg *drop, float *scores, float *hidden, void *saved, size_t saved_bytes,
                         void *workspace, size_t workspace_bytes, void *stream, const PackedCtx *pc) {
-    if (int rc = check_common(w, x, B, T, drop, pc != nullptr)) return rc;
+    VsTrainPlan plan;
+    if (int rc = plan_call(w, x, B, T, drop, pc != nullptr, false, &plan)) return rc;
     if (!scores || !saved || !workspace) return failf(VS_ERR_INVALID, "scores/saved/workspace is NULL");
     const vs_model_desc &D = w->desc;
     const SavedLayout S = saved_layout(D, B, T, pc);
     const WorkLayout W = work_layout(D, B, T, pc);
-    if (saved_bytes < S.total * sizeof(float))
-        return failf(VS_ERR_WORKSPACE, "saved %zu bytes < %zu needed", saved_bytes, S.total * sizeof(float));
-    if (workspace_bytes < W.total * sizeof(float))
-        return failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, W.total * sizeof(float));
-    if (((uintptr_t)saved & 255) || ((uintptr_t)workspace & 255) || (hidden && ((uintptr_t)hidden & 15)))
-        return failf(VS_ERR_INVALID, "saved/workspace must be 256-byte, hidden 16-byte aligned");
+    if (int rc = check_buffers(S, W, saved, saved_bytes, workspace, workspace_bytes, true, hidden)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int d = D.d_model, H = D.num_heads, L = D.num_layers, M = B * T;
     const float p = drop ? drop->p : 0.f;
     // the embedding dropout lives INSIDE PositionalEncoding (simnet.py:224,237): a use_pos=False model has none
     const float p_embed = (drop && w->has_pe) ? drop->p_embed : 0.f;
-    const RecordForm form = derive_form(w, drop, B, T, pc != nullptr);
-    g_last_format = form.bits();
-    const int F = form.f16 ? VSK_F16 : 0;            // fp16 mode: rides on every 16-bit precision word below
-    const int lp = form.lp ? (1 | F) : 0;
-    const bool lpa = form.lpa, qkv16 = form.qkv16, h16 = form.h16, rows16 = form.rows16;
-    const size_t kvs = qkv16 ? (size_t)B * T * w->desc.d_model / 2 : (size_t)B * T * w->desc.d_model;     // floats between the planes
+    g_last_format = plan.format;
     const unsigned long long seed = drop ? drop->seed : 0ull;
     const int dn = w->dn();                                   // LayerNorm width / attention-scale d_model (== d unless embedded)
     const float scale = 1.0f / sqrtf((float)dn);             // simnet.py:126: d_model ** -0.5
@@ -328,8 +354,7 @@ static int forward_impl(const vs_weights *w, const float *x, const uint8_t *key_
     float *a = ws + W.a;
 
     vsw_order(w, stream);
-    if (M <= vsk_skinny_max_rows()) if (int rc = vsw_ensure(w, VSW_FRAGMENTS, stream)) return rc;
-    if (rows16) if (int rc = vsw_ensure(w, VSW_ROWS16, stream)) return rc;          // bf16 copy of W1 for the A-stationary fc1
+    if (plan.families) if (int rc = vsw_ensure(w, plan.families, stream)) return rc;
     // packed: the device builds cu / bo / the work list from the device lengths (no host memory is read after return), and
     // the positional rows are gathered per video - the embedding then adds row m of them to frame m
     VstPackedPlan pk{};
@@ -344,7 +369,7 @@ static int forward_impl(const vs_weights *w, const float *x, const uint8_t *key_
     // Embedding + positional table + dropout(sparsity)   simnet.py:211, 237-238
     float *h0 = sv + S.h0;
     VST_LAUNCH(vsk_linear(x, w->p(w->embed_w), w->p(w->f_embed_w), w->p(w->embed_b), h0, M, d, D.in_features, 0,
-                          pe, T, lp, st));
+                          pe, T, plan.mode_linear, st));
     if (p_embed > 0.f) VST_LAUNCH(vst_dropout_rows(h0, M, d, seed, VS_SITE_EMBED, p_embed, st));
     const float *h_in = h0;
     for (int l = 0; l < L; ++l) {
@@ -352,45 +377,31 @@ static int forward_impl(const vs_weights *w, const float *x, const uint8_t *key_
         const LayerSaved &A = S.layers[l];
         const bool last = l == L - 1;
         float *qkv = sv + A.qkv;
-        // bf16 GEMMs + bf16 attention: q (times scale * log2 e), k, v are WRITTEN as bf16 by the QKV GEMM's epilogue (the
-        // scoring path's form) - the attention kernels' only readers round them to bf16 anyway: same bits, half the
-        // saved bytes, nothing to convert per streamed tile
-        if (rows16 && qkv16)       // A-stationary form (bit-identical to the tiled one)
+        // (16-bit q / k / v: q arrives times scale * log2 e, the scoring path's form)
+        if (plan.qkv_rows16)       // A-stationary form (bit-identical to the tiled one)
             VST_LAUNCH(vst_gemm_rows16(h_in, w->p(P.r_wqkv), w->p(P.bqkv), qkv, nullptr, M, 3 * d, d, 3, vsk_attention_qscale(scale), 0ull, 0u,
                                        0.f, st, T, H, d / H));
         else
-        VST_LAUNCH(vsk_qkv(h_in, w->p(P.wqkv), w->p(P.f_wqkv), w->p(P.bqkv), qkv, B, T, d, H, qkv16 ? (1 | VSK_STORE16 | F) : lp, st,
-                           qkv16 ? vsk_attention_qscale(scale) : 1.0f));         // :148-153
+            VST_LAUNCH(vsk_qkv(h_in, w->p(P.wqkv), w->p(P.f_wqkv), w->p(P.bqkv), qkv, B, T, d, H, plan.mode_qkv, st,
+                               plan.form.qkv16 ? vsk_attention_qscale(scale) : 1.0f));         // :148-153
         unsigned *dbits = p > 0.f ? (unsigned *)(sv + A.dbits) : nullptr;
         if (dbits && pc) VST_LAUNCH(vst_attention_dropout_bits_packed(dbits, pc->B, H, pc->tmax, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st, pk));
         else if (dbits) VST_LAUNCH(vst_attention_dropout_bits(dbits, B, H, T, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st));
-        if (pc && lpa)      // (the bit-packed keep words above are built whenever p > 0: the 16-bit kernels have no hash-per-element form)
-            VST_LAUNCH(vst_attention_fwd_bf16_packed(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, sv + A.att, sv + A.lse, H, d / H,
-                                                     scale, p, dbits, st, form.f16, pk));
-        else if (pc)
-            VST_LAUNCH(vst_attention_fwd_packed(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, sv + A.att, sv + A.lse, H, d / H,
-                                                scale, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st, dbits, pk));
-        else if (lpa)
-            VST_LAUNCH(vst_attention_fwd_bf16(qkv, qkv + kvs, qkv + 2 * kvs, key_pad_mask, sv + A.att,
-                                              sv + A.lse, B, H, T, d / H, scale, p, dbits, st, (qkv16 ? 1 : 0) | F));
-        else
-        VST_LAUNCH(vst_attention_fwd(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, key_pad_mask, sv + A.att,
-                                     sv + A.lse, B, H, T, d / H, scale, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st, dbits));   // :155-161
-        VST_LAUNCH(vsk_linear(sv + A.att, w->p(P.wo), w->p(P.f_wo), w->p(P.bo), a, M, d, d, 0, nullptr, 1, lp, st));      // :163
+        if (int rc = attention_forward(plan, qkv, key_pad_mask, sv + A.att, sv + A.lse, B, H, T, d / H, scale, seed,
+                                       VS_SITE_LAYER(l, VS_SITE_ATTN), p, dbits, pk, st)) return rc;
+        VST_LAUNCH(vsk_linear(sv + A.att, w->p(P.wo), w->p(P.f_wo), w->p(P.bo), a, M, d, d, 0, nullptr, 1, plan.mode_linear, st));      // :163
         VST_LAUNCH(vst_rows_fwd(a, h_in, w->p(P.ln1g), w->p(P.ln1b), sv + A.z1, sv + A.y1, nullptr, sv + A.st1, M, d,
                                 seed, VS_SITE_LAYER(l, VS_SITE_DROP1), p, nullptr, nullptr, 0, nullptr, st, dn));              // :107
-        // bf16 GEMMs: the MLP hidden tensor (post ReLU, post dropout) is only ever a matrix operand or a sign - it is written
-        // and saved as bf16 (h16), and fc2, its weight gradient and the backward's gate read it as such
-        if (rows16)         // K = d_model = 256: the A-stationary form (vs_train_gemm_rows.hip), bit-identical to the tiled one
+        // fc1 (+ ReLU + mlp.dropout in the GEMM epilogue, :181) writes the MLP hidden tensor, fc2 reads it
+        if (plan.form.rows16)         // the A-stationary form (vs_train_gemm_rows.hip), bit-identical to the tiled one
             VST_LAUNCH(vst_gemm_rows16(sv + A.y1, w->p(P.r_w1), w->p(P.b1), sv + A.ffn, nullptr, M, 4 * d, d, p > 0.f ? 0 : 2, 0.f, seed,
                                        VS_SITE_LAYER(l, VS_SITE_MLP), p, st));
-        else if (p > 0.f)   // fc1 + ReLU + mlp.dropout in one GEMM epilogue (:181)
+        else if (p > 0.f)
             VST_LAUNCH(vsk_linear_relu_dropout(sv + A.y1, w->p(P.w1), w->p(P.f_w1), w->p(P.b1), sv + A.ffn, M, 4 * d, d, seed,
-                                               VS_SITE_LAYER(l, VS_SITE_MLP), p, st, h16 ? (1 | VSK_STORE16 | F) : lp));
+                                               VS_SITE_LAYER(l, VS_SITE_MLP), p, st, plan.mode_fc1));
         else
-            VST_LAUNCH(vsk_linear(sv + A.y1, w->p(P.w1), w->p(P.f_w1), w->p(P.b1), sv + A.ffn, M, 4 * d, d, 1, nullptr, 1,
-                                  h16 ? (1 | VSK_STORE16 | F) : lp, st));
-        VST_LAUNCH(vsk_linear(sv + A.ffn, w->p(P.w2), w->p(P.f_w2), w->p(P.b2), a, M, d, 4 * d, 0, nullptr, 1, h16 ? (1 | VSK_A16 | F) : lp, st));  // :182
+            VST_LAUNCH(vsk_linear(sv + A.y1, w->p(P.w1), w->p(P.f_w1), w->p(P.b1), sv + A.ffn, M, 4 * d, d, 1, nullptr, 1, plan.mode_fc1, st));
+        VST_LAUNCH(vsk_linear(sv + A.ffn, w->p(P.w2), w->p(P.f_w2), w->p(P.b2), a, M, d, 4 * d, 0, nullptr, 1, plan.mode_fc2, st));  // :182
         VST_LAUNCH(vst_rows_fwd(a, sv + A.y1, w->p(P.ln2g), w->p(P.ln2b), sv + A.z2, sv + A.y2, last ? hidden : nullptr,
                                 sv + A.st2, M, d, seed, VS_SITE_LAYER(l, VS_SITE_DROP2), p,
                                 last ? w->p(w->final_w) : nullptr, last ? w->p(w->final_b) : nullptr, D.num_classes,
@@ -404,42 +415,22 @@ static int backward_impl(vs_weights *w, const float *x, const uint8_t *key_pad_m
                          const vs_dropout_cfg *drop, const float *d_scores, const float *d_hidden, const void *saved,
                          size_t saved_bytes, const vs_model_grads *grads, float *dx, void *workspace,
                          size_t workspace_bytes, void *stream, const PackedCtx *pc) {
-    if (int rc = check_common(w, x, B, T, drop, pc != nullptr)) return rc;
+    VsTrainPlan plan;       // the form the record was written in: handed back in drop->reserved, else derived again
+    if (int rc = plan_call(w, x, B, T, drop, pc != nullptr, true, &plan)) return rc;
     if (!saved || !workspace || !grads || !grads->layers || !grads->embed_w || !grads->embed_b || !grads->final_w ||
         !grads->final_b)
         return failf(VS_ERR_INVALID, "saved/workspace/grads is NULL");
     const vs_model_desc &D = w->desc;
     const SavedLayout S = saved_layout(D, B, T, pc);
     const WorkLayout W = work_layout(D, B, T, pc);
-    if (saved_bytes < S.total * sizeof(float))
-        return failf(VS_ERR_WORKSPACE, "saved %zu bytes < %zu needed", saved_bytes, S.total * sizeof(float));
-    if (workspace_bytes < W.total * sizeof(float))
-        return failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, W.total * sizeof(float));
-    if (((uintptr_t)saved & 255) || ((uintptr_t)workspace & 255)) return failf(VS_ERR_INVALID, "saved/workspace must be 256-byte aligned");
+    if (int rc = check_buffers(S, W, saved, saved_bytes, workspace, workspace_bytes, false, nullptr)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = ensure_transposed(w, st, B * T <= vsk_skinny_max_rows())) return rc;
+    if (int rc = ensure_transposed(w, st, plan.transposed_fragments)) return rc;
+    if (plan.t16) if (int rc = ensure_t16(w, st)) return rc;
     const int d = D.d_model, H = D.num_heads, L = D.num_layers, M = B * T, nc = D.num_classes;
     const float p = drop ? drop->p : 0.f;
     // the embedding dropout lives INSIDE PositionalEncoding (simnet.py:224,237): a use_pos=False model has none
     const float p_embed = (drop && w->has_pe) ? drop->p_embed : 0.f;
-    // the form the record was written in: handed back by the caller (vs_dropout_cfg.reserved = vs_train_last_format() of the
-    // forward), else derived again from the same inputs
-    RecordForm form = derive_form(w, drop, B, T, pc != nullptr);
-    if (drop && (drop->reserved & 0x80000000u)) {
-        const uint32_t fb = drop->reserved;
-        form.lp = (fb & 1u) ? 1 : 0; form.lpa = (fb & 2u) != 0; form.qkv16 = (fb & 4u) != 0; form.h16 = (fb & 8u) != 0; form.rows16 = (fb & 16u) != 0;
-        form.f16 = (fb & 32u) != 0;
-        if ((form.qkv16 && !(form.lp && form.lpa)) || (form.h16 && !form.lp) || (form.rows16 && !form.h16) ||
-            (form.f16 && (form.rows16 || !(form.lp || form.lpa))) || (fb & 0x7fffffc0u) || (pc && form.qkv16) ||
-            (form.lpa && !vst_attention_bf16_supported(w->desc.d_model / w->desc.num_heads)) ||
-            (form.rows16 && !vst_gemm_rows16_supported(B * T, 4 * w->desc.d_model, w->desc.d_model, true)))
-            return failf(VS_ERR_INVALID, "vs_dropout_cfg.reserved = 0x%08x is not a record form this model / batch can have", fb);
-    }
-    const int F = form.f16 ? VSK_F16 : 0;            // fp16 mode: rides on every 16-bit precision word below
-    const int lp = form.lp ? (1 | F) : 0;
-    const bool lpa = form.lpa, qkv16 = form.qkv16, h16 = form.h16, rows16 = form.rows16;
-    if (rows16) if (int rc = ensure_t16(w, st)) return rc;
-    const size_t kvs = qkv16 ? (size_t)B * T * w->desc.d_model / 2 : (size_t)B * T * w->desc.d_model;     // floats between the planes
     const unsigned long long seed = drop ? drop->seed : 0ull;
     const int dn = w->dn();
     const float scale = 1.0f / sqrtf((float)dn);
@@ -482,63 +473,41 @@ static int backward_impl(vs_weights *w, const float *x, const uint8_t *key_pad_m
         VST_LAUNCH(vst_reduce_rows(part, nblk, 2, d, G.ln2_g, G.ln2_b, nullptr, 1, st));
         const float *dm = p > 0.f ? dbr : dz;
         // mlp.fc2: weight/bias gradient, then the gradient of its input
-        VST_LAUNCH(vst_wgrad(dm, d, sv + A.ffn, 4 * d, M, d, 4 * d, G.w2, nullptr, nullptr, G.b2, nullptr, nullptr, d, wg, st,
-                             h16 ? (1 | VST_WGRAD_X16 | F) : lp));
+        VST_LAUNCH(vst_wgrad(dm, d, sv + A.ffn, 4 * d, M, d, 4 * d, G.w2, nullptr, nullptr, G.b2, nullptr, nullptr, d, wg, st, plan.mode_wgrad_w2));
         // ... through mlp.dropout + ReLU in the GEMM's epilogue: the saved activation is > 0 exactly where both let
-        // the value through
-        // (h16: the gate tensor is the bf16-stored activation, and the gated gradient gf - again only ever a matrix operand -
-        // is written as bf16 too)
-        if (rows16)
-            VST_LAUNCH(vst_gemm_rows16(dm, w->tp(Q.t16_w2), zeros, gf, sv + A.ffn, M, 4 * d, d, 1, p > 0.f ? 1.0f / (1.0f - p) : 1.0f, 0ull, 0u,
-                                       0.f, st));
+        // the value through (the gated gradient gf is stored the way the activation is: plan.mode_gate)
+        const float gate_scale = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
+        if (plan.form.rows16)
+            VST_LAUNCH(vst_gemm_rows16(dm, w->tp(Q.t16_w2), zeros, gf, sv + A.ffn, M, 4 * d, d, 1, gate_scale, 0ull, 0u, 0.f, st));
         else
-        VST_LAUNCH(vsk_linear_gate(dm, w->tp(Q.t_w2), w->tp(Q.tf_w2), zeros, sv + A.ffn, p > 0.f ? 1.0f / (1.0f - p) : 1.0f, gf, M, 4 * d, d, st,
-                                   h16 ? (1 | VSK_STORE16 | F) : lp));
-        VST_LAUNCH(vst_wgrad(gf, 4 * d, sv + A.y1, d, M, 4 * d, d, G.w1, nullptr, nullptr, G.b1, nullptr, nullptr, 4 * d, wg, st,
-                             h16 ? (1 | VST_WGRAD_Y16 | F) : lp));
+            VST_LAUNCH(vsk_linear_gate(dm, w->tp(Q.t_w2), w->tp(Q.tf_w2), zeros, sv + A.ffn, gate_scale, gf, M, 4 * d, d, st, plan.mode_gate));
+        VST_LAUNCH(vst_wgrad(gf, 4 * d, sv + A.y1, d, M, 4 * d, d, G.w1, nullptr, nullptr, G.b1, nullptr, nullptr, 4 * d, wg, st, plan.mode_wgrad_w1));
         // d y1 = dz2 (residual) + d(fc1 input): the residual rides in the GEMM epilogue
-        VST_LAUNCH(vsk_linear(gf, w->tp(Q.t_w1), w->tp(Q.tf_w1), zeros, dy1, M, d, 4 * d, 0, dz, M, h16 ? (1 | VSK_A16 | F) : lp, st));
+        VST_LAUNCH(vsk_linear(gf, w->tp(Q.t_w1), w->tp(Q.tf_w1), zeros, dy1, M, d, 4 * d, 0, dz, M, plan.mode_dgrad_fc1, st));
         // norm1; d(feature_projection output) = dropout1 mask on dz1
         VST_LAUNCH(vst_ln_bwd(dy1, nullptr, nullptr, 0, sv + A.z1, sv + A.st1, w->p(P.ln1g), dz, p > 0.f ? dbr : nullptr, part,
                               M, d, seed, VS_SITE_LAYER(l, VS_SITE_DROP1), p, st, dn));
         VST_LAUNCH(vst_reduce_rows(part, nblk, 2, d, G.ln1_g, G.ln1_b, nullptr, 1, st));
         const float *da = p > 0.f ? dbr : dz;
-        VST_LAUNCH(vst_wgrad(da, d, sv + A.att, d, M, d, d, G.wo, nullptr, nullptr, G.bo, nullptr, nullptr, d, wg, st, lp));
-        // (qkv16: d(attention output) is written as bf16 - the attention backward multiplies bf16 operands, and delta is then the
-        // row dot of the SAME rounded dO with the saved fp32 output)
-        VST_LAUNCH(vsk_linear(da, w->tp(Q.t_wo), w->tp(Q.tf_wo), zeros, datt, M, d, d, 0, nullptr, 1, qkv16 ? (1 | VSK_STORE16 | F) : lp, st));
-        // attention
-        const float *qkv = sv + A.qkv;
-        VST_LAUNCH(vst_head_rowdot(datt, sv + A.att, delta, M, T, H, d / H, st, qkv16 ? (1 | F) : lpa ? (2 | F) : 0));
-        if (pc && lpa)
-            VST_LAUNCH(vst_attention_bwd_bf16_packed(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, datt, sv + A.lse, delta, dqkv, H,
-                                                     d / H, scale, p, p > 0.f ? (const unsigned *)(sv + A.dbits) : nullptr, st, form.f16, pk));
-        else if (pc)
-            VST_LAUNCH(vst_attention_bwd_packed(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, datt, sv + A.lse, delta, dqkv, H, d / H,
-                                                scale, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st,
-                                                p > 0.f ? (const unsigned *)(sv + A.dbits) : nullptr, pk));
-        else if (lpa)
-            VST_LAUNCH(vst_attention_bwd_bf16(qkv, qkv + kvs, qkv + 2 * kvs, key_pad_mask, datt, sv + A.lse,
-                                              delta, dqkv, B, H, T, d / H, scale, p,
-                                              p > 0.f ? (const unsigned *)(sv + A.dbits) : nullptr, st, (qkv16 ? 1 : 0) | F, qkv16));
-        else
-        VST_LAUNCH(vst_attention_bwd(qkv, qkv + (size_t)M * d, qkv + 2 * (size_t)M * d, key_pad_mask, datt, sv + A.lse, delta,
-                                     dqkv, B, H, T, d / H, scale, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st,
-                                     p > 0.f ? (const unsigned *)(sv + A.dbits) : nullptr));
+        VST_LAUNCH(vst_wgrad(da, d, sv + A.att, d, M, d, d, G.wo, nullptr, nullptr, G.bo, nullptr, nullptr, d, wg, st, plan.mode_linear));
+        // d(attention output), then delta = its row dot with the saved output, then the attention itself
+        VST_LAUNCH(vsk_linear(da, w->tp(Q.t_wo), w->tp(Q.tf_wo), zeros, datt, M, d, d, 0, nullptr, 1, plan.mode_datt, st));
+        VST_LAUNCH(vst_head_rowdot(datt, sv + A.att, delta, M, T, H, d / H, st, plan.mode_rowdot));
+        if (int rc = attention_backward(plan, sv + A.qkv, key_pad_mask, datt, sv + A.lse, delta, dqkv, B, H, T, d / H, scale, seed,
+                                        VS_SITE_LAYER(l, VS_SITE_ATTN), p, p > 0.f ? (const unsigned *)(sv + A.dbits) : nullptr, pk, st))
+            return rc;
         // q / k / v projections: one [3d, d] weight gradient dealt to the three parameters
-        // (qkv16: dq | dk | dv arrive as bf16 - only ever matrix operands of the two GEMMs below)
-        VST_LAUNCH(vst_wgrad(dqkv, 3 * d, h_in, d, M, 3 * d, d, G.wq, G.wk, G.wv, G.bq, G.bk, G.bv, d, wg, st,
-                             qkv16 ? (1 | VST_WGRAD_Y16 | F) : lp));
+        VST_LAUNCH(vst_wgrad(dqkv, 3 * d, h_in, d, M, 3 * d, d, G.wq, G.wk, G.wv, G.bq, G.bk, G.bv, d, wg, st, plan.mode_wgrad_qkv));
         // gradient of the layer input = dz1 (residual) + dqkv Wqkv
-        VST_LAUNCH(vsk_linear(dqkv, w->tp(Q.t_wqkv), w->tp(Q.tf_wqkv), zeros, g[cur ^ 1], M, d, 3 * d, 0, dz, M, qkv16 ? (1 | VSK_A16 | F) : lp, st));
+        VST_LAUNCH(vsk_linear(dqkv, w->tp(Q.t_wqkv), w->tp(Q.tf_wqkv), zeros, g[cur ^ 1], M, d, 3 * d, 0, dz, M, plan.mode_dgrad_qkv, st));
         cur ^= 1;
     }
     // Embedding (simnet.py:211, 237-238): dropout(sparsity) mask, then the Linear
     float *gh0 = g[cur];
     if (p_embed > 0.f) VST_LAUNCH(vst_dropout_rows(gh0, M, d, seed, VS_SITE_EMBED, p_embed, st));
     VST_LAUNCH(vst_wgrad(gh0, d, x, D.in_features, M, d, D.in_features, grads->embed_w, nullptr, nullptr, grads->embed_b,
-                         nullptr, nullptr, d, wg, st, lp));
-    if (dx) VST_LAUNCH(vsk_linear(gh0, w->tp(w->t_embed_w), w->tp(w->tf_embed_w), zeros, dx, M, D.in_features, d, 0, nullptr, 1, lp, st));
+                         nullptr, nullptr, d, wg, st, plan.mode_linear));
+    if (dx) VST_LAUNCH(vsk_linear(gh0, w->tp(w->t_embed_w), w->tp(w->tf_embed_w), zeros, dx, M, D.in_features, d, 0, nullptr, 1, plan.mode_linear, st));
     return VS_OK;
 }
 
@@ -587,18 +556,7 @@ int vs_train_saved_field_packed(const vs_weights *w, const int32_t *lengths, int
     if (!w || !offset_bytes || !count || layer < 0 || layer >= w->desc.num_layers)
         return failf(VS_ERR_INVALID, "saved_field: bad arguments");
     if (int rc = packed_ctx(w->desc, lengths, B, pc)) return rc;
-    const SavedLayout S = saved_layout(w->desc, 1, pc.Mtot, &pc);
-    const LayerSaved &A = S.layers[layer];
-    const size_t Md = (size_t)pc.Mtot * w->desc.d_model;
-    switch (field) {
-        case 0: *offset_bytes = A.ffn * sizeof(float); *count = 4 * Md; break;
-        case 1: *offset_bytes = A.att * sizeof(float); *count = Md; break;
-        case 2: *offset_bytes = A.y1 * sizeof(float); *count = Md; break;
-        case 3: *offset_bytes = A.y2 * sizeof(float); *count = Md; break;
-        case 4: *offset_bytes = A.lse * sizeof(float); *count = (size_t)pc.Mtot * w->desc.num_heads; break;
-        default: return failf(VS_ERR_INVALID, "saved_field: unknown field %d", field);
-    }
-    return VS_OK;
+    return saved_field(w, 1, pc.Mtot, &pc, layer, field, offset_bytes, count);
 }
 
 int vs_train_forward_packed(const vs_weights *w, const float *x, const int32_t *lengths, const int32_t *lengths_dev, int32_t B,
@@ -644,8 +602,7 @@ static size_t attention_packed_plan_floats(const PackedCtx &pc) { return align_f
 
 size_t vs_train_attention_packed_scratch_bytes(const int32_t *lengths, int32_t B, int32_t H) {
     PackedCtx pc;
-    vs_model_desc none{};
-    if (H <= 0 || packed_ctx(none, lengths, B, pc) != VS_OK) return 0;
+    if (H <= 0 || packed_lengths(lengths, B, pc) != VS_OK) return 0;
     return (attention_packed_plan_floats(pc) + align_floats((size_t)H * pc.Mtot)) * sizeof(float);
 }
 
@@ -655,9 +612,8 @@ int vs_train_attention_forward_packed(const float *q, const float *k, const floa
                                       void *stream) {
     if (!q || !k || !v || !out || !lse2 || !lengths_dev || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
     PackedCtx pc;
-    vs_model_desc none{};
     if (H <= 0) return failf(VS_ERR_INVALID, "H=%d", H);
-    if (int rc = packed_ctx(none, lengths, B, pc)) return rc;
+    if (int rc = packed_lengths(lengths, B, pc)) return rc;
     if (scratch_bytes < vs_train_attention_packed_scratch_bytes(lengths, B, H) || ((uintptr_t)scratch & 255))
         return failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, vs_train_attention_packed_scratch_bytes(lengths, B, H));
     hipStream_t st = (hipStream_t)stream;
@@ -673,9 +629,8 @@ int vs_train_attention_backward_packed(const float *q, const float *k, const flo
                                        void *scratch, size_t scratch_bytes, void *stream) {
     if (!q || !k || !v || !out || !d_out || !lse2 || !dqkv || !lengths_dev || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
     PackedCtx pc;
-    vs_model_desc none{};
     if (H <= 0) return failf(VS_ERR_INVALID, "H=%d", H);
-    if (int rc = packed_ctx(none, lengths, B, pc)) return rc;
+    if (int rc = packed_lengths(lengths, B, pc)) return rc;
     if (scratch_bytes < vs_train_attention_packed_scratch_bytes(lengths, B, H) || ((uintptr_t)scratch & 255))
         return failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, vs_train_attention_packed_scratch_bytes(lengths, B, H));
     hipStream_t st = (hipStream_t)stream;
@@ -700,11 +655,10 @@ PackedLpScratch packed_lp_scratch(const PackedCtx &pc, int H) {
 // the argument checks of the two entry points (before any device access); pc out
 int packed_lp_check(const int32_t *lengths, int32_t B, int32_t H, int32_t dh, float p, const void *scratch, size_t scratch_bytes,
                     PackedCtx &pc) {
-    vs_model_desc none{};
     if (H <= 0) return failf(VS_ERR_INVALID, "H=%d", H);
     if (!vst_attention_bf16_supported(dh)) return failf(VS_ERR_INVALID, "head dim %d: the 16-bit attention kernels take 32 / 64 / 128", dh);
     if (!(p >= 0.f && p < 1.f)) return failf(VS_ERR_INVALID, "dropout probability must be in [0, 1): p=%g", p);
-    if (int rc = packed_ctx(none, lengths, B, pc)) return rc;
+    if (int rc = packed_lengths(lengths, B, pc)) return rc;
     const size_t need = packed_lp_scratch(pc, H).total * sizeof(float);
     if (scratch_bytes < need || ((uintptr_t)scratch & 255))
         return failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, need);
@@ -714,8 +668,7 @@ int packed_lp_check(const int32_t *lengths, int32_t B, int32_t H, int32_t dh, fl
 
 size_t vs_train_attention_packed_lp_scratch_bytes(const int32_t *lengths, int32_t B, int32_t H) {
     PackedCtx pc;
-    vs_model_desc none{};
-    if (H <= 0 || packed_ctx(none, lengths, B, pc) != VS_OK) return 0;
+    if (H <= 0 || packed_lengths(lengths, B, pc) != VS_OK) return 0;
     return packed_lp_scratch(pc, H).total * sizeof(float);
 }
 
@@ -758,9 +711,8 @@ int vs_train_attention_backward_packed_lp(const float *q, const float *k, const 
 int vs_train_dropout_mask_attention_packed(uint8_t *keep, const int32_t *lengths, int32_t B, int32_t H, uint64_t seed,
                                            uint32_t site, float p, void *stream) {
     PackedCtx pc;
-    vs_model_desc none{};
     if (!keep || H <= 0) return failf(VS_ERR_INVALID, "bad arguments");
-    if (int rc = packed_ctx(none, lengths, B, pc)) return rc;
+    if (int rc = packed_lengths(lengths, B, pc)) return rc;
     size_t off = 0;
     int row0 = 0;
     for (int b = 0; b < B; ++b) {
@@ -804,6 +756,16 @@ HeadWork head_work(int B, int T, int d, int F) {
     W.total = off;
     return W;
 }
+// video_transform behind the head's own backward (d_feats in ws + W.dfeats), padded and packed: weight / bias gradient, then the
+// gradient of the hidden state (NT GEMM against W^T)
+int head_backward_tail(const float *hidden, const float *vt_w, int M, int d, int F, float *d_hidden, float *d_vt_w, float *d_vt_b,
+                       float *ws, const HeadWork &W, hipStream_t st) {
+    VST_LAUNCH(vst_wgrad(ws + W.dfeats, F, hidden, d, M, F, d, d_vt_w, nullptr, nullptr, d_vt_b, nullptr, nullptr, F, ws + W.wg, st));
+    VST_LAUNCH(vst_transpose(vt_w, ws + W.wt, F, d, st));                                     // [F,d] -> [d,F]
+    VST_HIP(hipMemsetAsync(ws + W.zeros, 0, (size_t)(d > F ? d : F) * sizeof(float), st));
+    VST_LAUNCH(vsk_linear(ws + W.dfeats, ws + W.wt, nullptr, ws + W.zeros, d_hidden, M, d, F, 0, nullptr, 1, 0, st));
+    return VS_OK;
+}
 }  // namespace
 
 size_t vs_pretrain_head_workspace_bytes(int32_t B, int32_t T, int32_t d, int32_t F) {
@@ -844,12 +806,7 @@ int vs_pretrain_head_backward(const float *hidden, const float *logits, const ui
     const int M = B * T;
     VST_LAUNCH(vsp_head_backward(feats, logits, key_pad_mask, vid, B, T, F, 1.0f / temp, entropy_penalty,
                                  (const float *)head_state, d_losses, ws + W.dfeats, d_logits, st));
-    // video_transform: weight / bias gradient, then the gradient of the hidden state (NT GEMM against W^T)
-    VST_LAUNCH(vst_wgrad(ws + W.dfeats, F, hidden, d, M, F, d, d_vt_w, nullptr, nullptr, d_vt_b, nullptr, nullptr, F, ws + W.wg, st));
-    VST_LAUNCH(vst_transpose(vt_w, ws + W.wt, F, d, st));                                     // [F,d] -> [d,F]
-    VST_HIP(hipMemsetAsync(ws + W.zeros, 0, (size_t)(d > F ? d : F) * sizeof(float), st));
-    VST_LAUNCH(vsk_linear(ws + W.dfeats, ws + W.wt, nullptr, ws + W.zeros, d_hidden, M, d, F, 0, nullptr, 1, 0, st));
-    return VS_OK;
+    return head_backward_tail(hidden, vt_w, M, d, F, d_hidden, d_vt_w, d_vt_b, ws, W, st);
 }
 
 // ---- the head on a packed ragged batch ----
@@ -859,8 +816,7 @@ bool head_width_ok(int F) { return F == 256 || F == 512 || F == 768 || F == 1024
 bool head_shape_ok(int d, int F) { return d > 0 && d % 32 == 0 && head_width_ok(F); }
 int head_packed_ctx(const int32_t *lengths, int32_t B, HeadPacked &hp) {
     PackedCtx pc;
-    vs_model_desc none{};
-    if (int rc = packed_ctx(none, lengths, B, pc)) return rc;
+    if (int rc = packed_lengths(lengths, B, pc)) return rc;
     hp.Mtot = pc.Mtot; hp.tmax = pc.tmax; hp.NC = 0;
     for (int b = 0; b < B; ++b) hp.NC += (lengths[b] + 63) / 64;
     return VS_OK;
@@ -921,12 +877,7 @@ int vs_pretrain_head_backward_packed(const float *hidden, const float *logits, c
     const int M = hp.Mtot;
     VST_LAUNCH(vsp_head_backward_packed(feats, logits, lengths_dev, B, M, hp.tmax, hp.NC, ref_len, F, 1.0f / temp, entropy_penalty,
                                         (float *)head_state, d_losses, ws + W.dfeats, d_logits, st));
-    // video_transform over the Mtot packed rows: weight / bias gradient, then the gradient of the hidden state
-    VST_LAUNCH(vst_wgrad(ws + W.dfeats, F, hidden, d, M, F, d, d_vt_w, nullptr, nullptr, d_vt_b, nullptr, nullptr, F, ws + W.wg, st));
-    VST_LAUNCH(vst_transpose(vt_w, ws + W.wt, F, d, st));
-    VST_HIP(hipMemsetAsync(ws + W.zeros, 0, (size_t)(d > F ? d : F) * sizeof(float), st));
-    VST_LAUNCH(vsk_linear(ws + W.dfeats, ws + W.wt, nullptr, ws + W.zeros, d_hidden, M, d, F, 0, nullptr, 1, 0, st));
-    return VS_OK;
+    return head_backward_tail(hidden, vt_w, M, d, F, d_hidden, d_vt_w, d_vt_b, ws, W, st);      // M = the Mtot packed rows
 }
 
 int vs_train_attention_forward(const float *q, const float *k, const float *v, const uint8_t *key_pad_mask, float *out,

@@ -806,8 +806,6 @@ static bool pick_form(int dh, bool drop, bool f16, F &&f) {
     });
 }
 
-bool vst_attention_bf16_supported(int dh) { return dh == 32 || dh == 64 || dh == 128; }
-
 // in16: q (already times scale * log2 e), k, v are bf16 [B, H, T, dh] planes (the QKV GEMM's bf16 epilogue) instead of fp32
 int vst_attention_fwd_bf16(const float *q, const float *k, const float *v, const uint8_t *mask, float *out, float *lse2,
                            int B, int H, int T, int dh, float scale, float p, const unsigned *dbits, hipStream_t st, int in16) {

@@ -171,13 +171,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rows16(
 
 }  // namespace
 
-// From 3/4 of a 256-row block per CU up (the grid is M / 256 blocks: at 16 384 rows it would fill a quarter of the chip and
-// measured 7 % slower per step than the tiled kernels' 256 tiles); MI355X: 256 CUs.
-// (any_rows: the kernel itself handles every M - tests pin it on small batches)
-bool vst_gemm_rows16_supported(int M, int N, int K, bool any_rows) {
-    return (K == 256 || K == 512) && N % 8 == 0 && N >= 64 && N <= 4096 && M > 0 && (any_rows || M >= 192 * 256);
-}
-
+// (which shapes, and from which batch size by itself: vst_gemm_rows16_supported, vs_train_plan.h)
 // epi 0: dropout(relu(.)) (seed, site, p); 1: gate (gate16, scale); 2: relu; 3: q / k / v planes (T, H, dh; scale = q's factor).
 // A fp32 [M, K]; W16 bf16 [N, K]; C16 bf16 [M, N] (epi 3: [3][M / T][H][T][dh]).
 int vst_gemm_rows16(const float *A, const void *W16, const float *bias, void *C16, const void *gate16, int M, int N, int K, int epi,

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "vs_kernels.h"
+#include "vs_train_plan.h"      // VST_WGRAD_*16, vst_attention_bf16_supported, vst_gemm_rows16_supported
 
 // z = dropout_{p,site}(a) + res; y = LayerNorm(z) * gamma + beta (y_copy: optional second copy); stats[row] = (mean, rstd);
 // optional score head scores[row, c] = y . score_w[c] + score_b[c]
@@ -26,7 +27,7 @@ int vst_head_rowdot(const float *dO, const float *O, float *delta, int M, int T,
 int vst_weighted_colsum(const float *w, int ws, const float *Y, float *part, int M, int d, hipStream_t st);
 // dW[N,K] = dY[M,N]^T X[M,K] (+ db = column sums of dY when db0 != NULL); rows of the result are dealt to up to three
 // destination tensors of rows_per_dest rows; work >= vst_wgrad_workspace_floats(M, N, K) floats
-enum { VST_WGRAD_Y16 = 2, VST_WGRAD_X16 = 4 };     // vst_wgrad prec = 1 | flag: dY / X is stored as bf16
+// (vst_wgrad prec = 1 | VST_WGRAD_Y16 / VST_WGRAD_X16: dY / X is stored as bf16 - vs_train_plan.h)
 int vst_wgrad_splits(int M, int N, int K);
 size_t vst_wgrad_workspace_floats(int M, int N, int K);
 int vst_wgrad(const float *dY, int ldy, const float *X, int ldx, int M, int N, int K, float *dW0, float *dW1, float *dW2,
@@ -60,7 +61,6 @@ int vst_attention_bwd(const float *q, const float *k, const float *v, const uint
                       unsigned long long seed, unsigned site, float p, hipStream_t st, const unsigned *dbits = nullptr);
 // the same two calls on the bf16 matrix pipe (vs_train_attention_bf16.hip; head dim 32 / 64): operands rounded to bf16, fp32
 // softmax / accumulation; p > 0 needs the bit-packed masks
-bool vst_attention_bf16_supported(int dh);
 int vst_attention_fwd_bf16(const float *q, const float *k, const float *v, const uint8_t *mask, float *out, float *lse2,
                            int B, int H, int T, int dh, float scale, float p, const unsigned *dbits, hipStream_t st, int in16 = 0);
 int vst_attention_bwd_bf16(const float *q, const float *k, const float *v, const uint8_t *mask, const float *dO,
@@ -119,6 +119,6 @@ int vsp_head_backward_packed(const float *feats, const float *scores, const int 
 
 // ---- vs_train_gemm_rows.hip: A-stationary bf16 GEMM for K = 256 with a bf16 C (fc1 forward, fc2 input gradient) ----
 // epi 0: dropout(relu(.)) (seed, site, p); 1: gate (gate16 = the bf16-stored activation, scale); 2: relu; 3: q / k / v planes
-bool vst_gemm_rows16_supported(int M, int N, int K, bool any_rows = false);
+// (which shapes: vst_gemm_rows16_supported, vs_train_plan.h)
 int vst_gemm_rows16(const float *A, const void *W16, const float *bias, void *C16, const void *gate16, int M, int N, int K, int epi,
                     float scale, unsigned long long seed, unsigned site, float p, hipStream_t st, int T = 0, int H = 0, int dh = 0);
