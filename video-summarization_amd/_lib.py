@@ -10,6 +10,7 @@ import ctypes as C
 import os
 import subprocess
 import threading
+from typing import NamedTuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -35,50 +36,6 @@ VS_TRAIN_FLAG_BF16_ATTENTION = 2
 VS_TRAIN_FLAG_FP16 = 4          # modifier: the 16-bit type is IEEE fp16 (the reference's own autocast type) instead of bf16
 VS_TRAIN_FLAG_PACKED_LP_ATTENTION = 8     # packed calls only: with BF16_ATTENTION, the packed attention on the 16-bit pipe too
 
-# every symbol include/vs_scorer.h declares
-EXPORTS = ("vs_abi_version", "vs_last_error", "vs_weights_pack", "vs_weights_free", "vs_weights_update", "vs_weights_set_norm_width", "vs_set_option",
-           "vs_scorer_workspace_bytes", "vs_scorer_forward", "vs_scorer_workspace_bytes_packed",
-           "vs_scorer_forward_packed", "vs_scorer_workspace_bytes_cls", "vs_scorer_forward_cls", "vs_linear_f32", "vs_qkv_proj_f32",
-           "vs_attention_f32", "vs_attention_bf16", "vs_attention_bf16_stored", "vs_attention_qscale", "vs_attention_f16x3", "vs_linear_residual_layernorm_f32",
-           "vs_linear_bf16", "vs_linear_residual_layernorm_bf16", "vs_linear_f16x3",
-           "vs_linear_residual_layernorm_f16x3", "vs_mlp_block_bf16",
-           "vs_linear_bf16_operands", "vs_qkv_proj_bf16_operands", "vs_to_bf16", "vs_linear_bf16_a16",
-           "vs_profile_enable", "vs_profile_collect", "vs_stage_name")
-# include/vs_eval.h
-EVAL_EXPORTS = ("vs_eval_upsample", "vs_eval_knapsack", "vs_eval_generate_summary", "vs_eval_fscore",
-                "vs_eval_rank_correlation", "vs_eval_corpus")
-# include/vs_eval_device.h (the same evaluation from device-resident scores; opt-in)
-EVAL_DEVICE_EXPORTS = ("vs_eval_set_create", "vs_eval_set_free", "vs_eval_set_workspace_bytes", "vs_eval_set_run")
-# include/vs_summary.h (scores on the device in, the summary and its selected frames on the device out)
-SUMMARY_EXPORTS = ("vs_summarize_workspace_bytes", "vs_summarize")
-# include/vs_batch.h (the batches of a training epoch cut from a device-resident set)
-BATCH_EXPORTS = ("vs_batch_gather_packed", "vs_batch_gather_padded", "vs_batch_gather_rows")
-# include/vs_train.h
-TRAIN_EXPORTS = ("vs_train_prepare", "vs_train_saved_bytes", "vs_train_workspace_bytes", "vs_train_forward", "vs_train_backward",
-                 "vs_mse_mask_loss_forward", "vs_mse_mask_loss_backward", "vs_train_attention_forward",
-                 "vs_train_attention_backward", "vs_train_attention_dropout_bits_bytes", "vs_train_attention_dropout_bits",
-                 "vs_train_attention_forward_bf16", "vs_train_attention_backward_bf16", "vs_train_wgrad_scratch_floats", "vs_train_wgrad", "vs_train_wgrad_bf16",
-                 "vs_train_dropout_mask_attention", "vs_train_dropout_mask_rows", "vs_train_dropout_site", "vs_train_saved_field", "vs_train_last_format",
-                 "vs_pretrain_head_state_bytes", "vs_pretrain_head_workspace_bytes", "vs_pretrain_head_forward",
-                 "vs_pretrain_head_backward",
-                 # packed ragged batches
-                 "vs_train_check_packed", "vs_train_saved_bytes_desc", "vs_train_saved_bytes_packed", "vs_train_workspace_bytes_packed",
-                 "vs_train_forward_packed", "vs_train_backward_packed", "vs_mse_packed_loss_forward", "vs_mse_packed_loss_backward",
-                 "vs_train_attention_packed_scratch_bytes", "vs_train_attention_forward_packed", "vs_train_attention_backward_packed",
-                 "vs_train_dropout_mask_attention_packed", "vs_train_saved_field_packed",
-                 "vs_train_attention_packed_lp_scratch_bytes", "vs_train_attention_forward_packed_lp", "vs_train_attention_backward_packed_lp",
-                 # the pretraining head on packed ragged batches
-                 "vs_pretrain_head_state_bytes_packed", "vs_pretrain_head_workspace_bytes_packed",
-                 "vs_pretrain_head_forward_packed", "vs_pretrain_head_backward_packed")
-# include/vs_segment.h (kernel temporal segmentation)
-SEGMENT_EXPORTS = ("vs_kts_workspace_bytes", "vs_kts_segment", "vs_kts_scatters",
-                   # cosine / Gaussian kernels, the one-launch ragged Gram, the score of given change points
-                   "vs_kts_gram_workspace_bytes", "vs_kts_gram", "vs_kts_workspace_bytes_k", "vs_kts_segment_k", "vs_kts_eval_score")
-# include/vs_optim.h (the Adam step)
-OPTIM_EXPORTS = ("vs_adam_step_tensors", "vs_adam_state_bytes", "vs_adam_state_init", "vs_adam_state_field", "vs_adam_step",
-                 "vs_grad_norm_workspace_bytes", "vs_grad_norm_tensors", "vs_grad_norm", "vs_grad_scale_tensors")
-# include/vs_inspect.h (attention maps on request)
-INSPECT_EXPORTS = ("vs_inspect_workspace_bytes", "vs_inspect_forward", "vs_attention_probs_workspace_bytes", "vs_attention_probs_f32")
 VS_ADAM_MAX_TENSORS = 64
 VS_GRAD_NORM_L2, VS_GRAD_NORM_MAX = 0, 1
 VS_KTS_FEATURES_F32, VS_KTS_KERNEL_F32, VS_KTS_KERNEL_F64 = 0, 1, 2
@@ -139,6 +96,162 @@ class KtsKernel(C.Structure):   # vs_kts_kernel (include/vs_segment.h)
 
 class GradTensor(C.Structure):  # vs_grad_tensor
     _fields_ = [("g", C.c_void_p), ("n", C.c_size_t)]
+
+
+# --------------------------------------------------------------------------------------------
+# the C ABI: {header: {symbol: (restype, argtypes)}}, every prototype of include/*.h once (tests/test_binding_host.py
+# compares names, argument counts and return kinds with the headers).  A wrong entry does not fail: it truncates.
+# --------------------------------------------------------------------------------------------
+_P, _I, _Z, _F, _D, _U32, _U64, _RC = C.c_void_p, C.c_int32, C.c_size_t, C.c_float, C.c_double, C.c_uint32, C.c_uint64, C.c_int
+_ref = C.POINTER
+_LINEAR = [_P] * 4 + [_I] * 4 + [_P, _I, _P]
+_LINEAR_OPERANDS = [_P] * 4 + [_I] * 5 + [_P]
+_LINEAR_LN = [_P] * 7 + [_I] * 3 + [_P] * 2 + [_I] * 2 + [_P] * 2
+_ATTENTION = [_P] * 5 + [_I] * 4 + [_F, _P]
+_BYTES_BT = (_Z, [_P, _I, _I])                     # (weights or lengths, B, T or width) -> bytes
+_DROPOUT_MASK = [_P, _I, _I, _I, _U64, _U32, _F, _P]
+_KTS_SIZES = [_P, _I, _I, _I, _P, _I]
+_BINDINGS = {
+    "vs_scorer.h": {
+        "vs_abi_version": (_RC, []),
+        "vs_last_error": (C.c_char_p, []),
+        "vs_weights_pack": (_RC, [_ref(ModelDesc), _ref(ModelParams), _P, _ref(_P)]),
+        "vs_weights_free": (None, [_P]),
+        "vs_weights_update": (_RC, [_P, _ref(ModelParams), _P]),
+        "vs_weights_set_norm_width": (_RC, [_P, _I]),
+        "vs_set_option": (_RC, [C.c_char_p, _I]),
+        "vs_scorer_workspace_bytes": _BYTES_BT,
+        "vs_scorer_forward": (_RC, [_P, _P, _P, _I, _I, _U32, _P, _P, _P, _Z, _P]),
+        "vs_scorer_workspace_bytes_packed": (_Z, [_P, _P, _I]),
+        "vs_scorer_forward_packed": (_RC, [_P, _P, _P, _P, _I, _U32, _P, _P, _P, _Z, _P]),
+        "vs_scorer_workspace_bytes_cls": _BYTES_BT,
+        "vs_scorer_forward_cls": (_RC, [_P, _P, _P, _P, _I, _I, _U32, _P, _P, _P, _Z, _P]),
+        "vs_linear_f32": (_RC, _LINEAR),
+        "vs_qkv_proj_f32": (_RC, [_P] * 4 + [_I] * 4 + [_P]),
+        "vs_attention_f32": (_RC, _ATTENTION),
+        "vs_attention_bf16": (_RC, _ATTENTION),
+        "vs_attention_bf16_stored": (_RC, [_P] * 5 + [_I] * 4 + [_P]),
+        "vs_attention_qscale": (_F, [_F]),
+        "vs_attention_f16x3": (_RC, _ATTENTION),
+        "vs_linear_residual_layernorm_f32": (_RC, _LINEAR_LN),
+        "vs_linear_bf16": (_RC, _LINEAR),
+        "vs_linear_residual_layernorm_bf16": (_RC, _LINEAR_LN),
+        "vs_linear_f16x3": (_RC, _LINEAR),
+        "vs_linear_residual_layernorm_f16x3": (_RC, _LINEAR_LN),
+        "vs_mlp_block_bf16": (_RC, [_P, _I, _P, _P, _I, _I, _I, _P, _P]),
+        "vs_linear_bf16_operands": (_RC, _LINEAR_OPERANDS),
+        "vs_qkv_proj_bf16_operands": (_RC, _LINEAR_OPERANDS),
+        "vs_to_bf16": (_RC, [_P, _P, _Z, _P]),
+        "vs_linear_bf16_a16": (_RC, [_P] * 4 + [_I] * 3 + [_P, _P]),
+        "vs_profile_enable": (_RC, [_I]),
+        "vs_profile_collect": (_RC, [_ref(_D), _ref(C.c_int64)]),
+        "vs_stage_name": (C.c_char_p, [_I]),
+    },
+    "vs_eval.h": {
+        "vs_eval_upsample": (_RC, [_P, _I, _P, _I, _I, _P]),
+        "vs_eval_knapsack": (_RC, [_I, _P, _P, _I, _P, _ref(_I)]),
+        "vs_eval_generate_summary": (_RC, [_P, _I, _P, _I, _I, _P, _I, _P, _I]),
+        "vs_eval_fscore": (_RC, [_P, _I, _P, _I, _I, _I, _ref(_D)]),
+        "vs_eval_rank_correlation": (_RC, [_P, _I, _P, _I, _ref(_D), _ref(_D)]),
+        "vs_eval_corpus": (_RC, [_ref(EvalVideo), _I, _I, _P, _P, _P]),
+    },
+    "vs_eval_device.h": {       # the same evaluation from device-resident scores; opt-in
+        "vs_eval_set_create": (_RC, [_ref(EvalVideo), _I, _P, _ref(_P)]),
+        "vs_eval_set_free": (None, [_P]),
+        "vs_eval_set_workspace_bytes": (_Z, [_P, _P, _I]),
+        "vs_eval_set_run": (_RC, [_P, _P, _P, _I] + [_P] * 5 + [_Z, _P]),
+    },
+    "vs_summary.h": {           # scores on the device in, the summary and its selected frames on the device out
+        "vs_summarize_workspace_bytes": (_Z, [_I] + [_P] * 4 + [_D]),
+        "vs_summarize": (_RC, [_I] + [_P] * 6 + [_D] + [_P] * 7 + [_Z, _P]),
+    },
+    "vs_batch.h": {             # the batches of a training epoch cut from a device-resident set
+        "vs_batch_gather_packed": (_RC, [_P] * 3 + [_I] + [_P] * 2 + [_I, C.c_int64, _I] + [_P] * 3),
+        "vs_batch_gather_padded": (_RC, [_P] * 3 + [_I] + [_P] * 2 + [_I] * 3 + [_F, _I] + [_P] * 4),
+        "vs_batch_gather_rows": (_RC, [_P, _I, _P, _I, _I, _P, _P]),
+    },
+    "vs_train.h": {
+        "vs_train_prepare": (_RC, [_P, _P]),
+        "vs_train_saved_bytes": _BYTES_BT,
+        "vs_train_workspace_bytes": _BYTES_BT,
+        "vs_train_forward": (_RC, [_P, _P, _P, _I, _I, _ref(DropoutCfg), _P, _P, _P, _Z, _P, _Z, _P]),
+        "vs_train_backward": (_RC, [_P, _P, _P, _I, _I, _ref(DropoutCfg), _P, _P, _P, _Z, _ref(ModelGrads), _P, _P, _Z, _P]),
+        "vs_mse_mask_loss_forward": (_RC, [_P, _P, _P, _I, _I, _P, _P, _P]),
+        "vs_mse_mask_loss_backward": (_RC, [_P, _P, _P, _P, _I, _I, _P, _P]),
+        "vs_train_attention_forward": (_RC, [_P] * 6 + [_I] * 4 + [_F, _U64, _U32, _F, _P]),
+        "vs_train_attention_backward": (_RC, [_P] * 9 + [_I] * 4 + [_F, _U64, _U32, _F, _P]),
+        "vs_train_attention_dropout_bits_bytes": (_Z, [_I] * 3),
+        "vs_train_attention_dropout_bits": (_RC, _DROPOUT_MASK),
+        "vs_train_attention_forward_bf16": (_RC, [_P] * 6 + [_I] * 4 + [_F, _F, _P, _I, _P]),
+        "vs_train_attention_backward_bf16": (_RC, [_P] * 9 + [_I] * 4 + [_F, _F, _P, _I, _P]),
+        "vs_train_wgrad_scratch_floats": (_Z, [_I] * 3),
+        "vs_train_wgrad": (_RC, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+        "vs_train_wgrad_bf16": (_RC, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+        "vs_train_dropout_mask_attention": (_RC, _DROPOUT_MASK),
+        "vs_train_dropout_mask_rows": (_RC, [_P, _I, _I, _U64, _U32, _F, _P]),
+        "vs_train_dropout_site": (_U32, [_I, _I]),
+        "vs_train_saved_field": (_RC, [_P, _I, _I, _I, _I, _ref(_Z), _ref(_Z)]),
+        "vs_train_last_format": (_U32, []),
+        "vs_pretrain_head_state_bytes": (_Z, [_I] * 3),
+        "vs_pretrain_head_workspace_bytes": (_Z, [_I] * 4),
+        "vs_pretrain_head_forward": (_RC, [_P] * 6 + [_I] * 4 + [_F, _I] + [_P] * 4),
+        "vs_pretrain_head_backward": (_RC, [_P] * 8 + [_I] * 4 + [_F, _I] + [_P] * 5 + [_Z, _P]),
+        # packed ragged batches (lengths: host int32 array, then the same values on the device)
+        "vs_train_check_packed": (_RC, [_ref(ModelDesc), _P, _I]),
+        "vs_train_saved_bytes_desc": (_Z, [_ref(ModelDesc), _P, _I, _I]),
+        "vs_train_saved_bytes_packed": (_Z, [_P, _P, _I]),
+        "vs_train_workspace_bytes_packed": (_Z, [_P, _P, _I]),
+        "vs_train_forward_packed": (_RC, [_P, _P, _P, _P, _I, _ref(DropoutCfg), _P, _P, _P, _Z, _P, _Z, _P]),
+        "vs_train_backward_packed": (_RC, [_P, _P, _P, _P, _I, _ref(DropoutCfg), _P, _P, _P, _Z, _ref(ModelGrads), _P, _P, _Z, _P]),
+        "vs_mse_packed_loss_forward": (_RC, [_P, _P, _I, _D, _P, _P, _P]),
+        "vs_mse_packed_loss_backward": (_RC, [_P, _P, _P, _I, _D, _P, _P]),
+        "vs_train_attention_packed_scratch_bytes": _BYTES_BT,
+        "vs_train_attention_forward_packed": (_RC, [_P] * 7 + [_I] * 3 + [_F, _U64, _U32, _F, _P, _Z, _P]),
+        "vs_train_attention_backward_packed": (_RC, [_P] * 9 + [_I] * 3 + [_F, _U64, _U32, _F, _P, _Z, _P]),
+        "vs_train_dropout_mask_attention_packed": (_RC, [_P, _P, _I, _I, _U64, _U32, _F, _P]),
+        "vs_train_saved_field_packed": (_RC, [_P, _P, _I, _I, _I, _ref(_Z), _ref(_Z)]),
+        # ... on the 16-bit pipe: (..., scale, seed, site, p, f16, scratch, scratch_bytes, stream)
+        "vs_train_attention_packed_lp_scratch_bytes": _BYTES_BT,
+        "vs_train_attention_forward_packed_lp": (_RC, [_P] * 7 + [_I] * 3 + [_F, _U64, _U32, _F, _I, _P, _Z, _P]),
+        "vs_train_attention_backward_packed_lp": (_RC, [_P] * 9 + [_I] * 3 + [_F, _U64, _U32, _F, _I, _P, _Z, _P]),
+        # ... and the pretraining head on them: (hidden, logits, lengths, lengths_dev, B, ref_len, vid, vt_w, ...)
+        "vs_pretrain_head_state_bytes_packed": _BYTES_BT,
+        "vs_pretrain_head_workspace_bytes_packed": (_Z, [_P, _I, _I, _I]),
+        "vs_pretrain_head_forward_packed": (_RC, [_P] * 4 + [_I] * 2 + [_P] * 3 + [_I] * 2 + [_F, _I] + [_P] * 4),
+        "vs_pretrain_head_backward_packed": (_RC, [_P] * 4 + [_I] * 2 + [_P] * 5 + [_I] * 2 + [_F, _I] + [_P] * 5 + [_Z, _P]),
+    },
+    "vs_segment.h": {           # kernel temporal segmentation
+        "vs_kts_workspace_bytes": (_Z, _KTS_SIZES),
+        "vs_kts_segment": (_RC, [_P, _I, _I, _P, _I] + [_P] * 5 + [_I] + [_P] * 4 + [_Z, _P]),
+        "vs_kts_scatters": (_RC, [_P, _I, _I, _I, _P, _P, _Z, _P]),
+        # cosine / Gaussian kernels, the one-launch ragged Gram, the score of given change points
+        "vs_kts_gram_workspace_bytes": _BYTES_BT,
+        "vs_kts_gram": (_RC, [_P, _I, _P, _I, _ref(KtsKernel), _P, _P, _Z, _P]),
+        "vs_kts_workspace_bytes_k": (_Z, _KTS_SIZES + [_ref(KtsKernel)]),
+        "vs_kts_segment_k": (_RC, [_P, _I, _I, _P, _I] + [_P] * 5 + [_I, _ref(KtsKernel)] + [_P] * 4 + [_Z, _P]),
+        "vs_kts_eval_score": (_RC, [_P, _I, _I, _ref(KtsKernel), _P, _I] + [_P] * 4 + [_Z, _P]),
+    },
+    "vs_optim.h": {             # the Adam step
+        "vs_adam_step_tensors": (_RC, [_ref(AdamTensor), _I, _ref(AdamCfg), _P, _P, _P, _P]),
+        "vs_adam_state_bytes": (_Z, [_P]),
+        "vs_adam_state_init": (_RC, [_P, _P, _P]),
+        "vs_adam_state_field": (_RC, [_P, _I, _I, _ref(_Z), _ref(_Z)]),
+        "vs_adam_step": (_RC, [_P, _ref(ModelParams), _ref(ModelGrads), _P, _ref(AdamCfg), _P, _P, _P]),
+        "vs_grad_norm_workspace_bytes": (_Z, [_ref(GradTensor), _I]),
+        "vs_grad_norm_tensors": (_RC, [_ref(GradTensor), _I, _I, _D, _P, _P, _P, _Z, _P]),
+        "vs_grad_norm": (_RC, [_P, _ref(ModelGrads), _I, _D, _P, _P, _P, _Z, _P]),
+        "vs_grad_scale_tensors": (_RC, [_ref(GradTensor), _I, _P, _P]),
+    },
+    "vs_inspect.h": {           # attention maps on request
+        "vs_inspect_workspace_bytes": (_Z, [_P, _I, _I, _I]),
+        "vs_inspect_forward": (_RC, [_P] * 4 + [_I] * 2 + [_ref(_I), _I] + [_P] * 6 + [_Z, _P]),
+        "vs_attention_probs_workspace_bytes": (_Z, [_I] * 3),
+        "vs_attention_probs_f32": (_RC, [_P] * 6 + [_I] * 4 + [_F, _P, _Z, _P]),
+    },
+}
+(EXPORTS, EVAL_EXPORTS, EVAL_DEVICE_EXPORTS, SUMMARY_EXPORTS, BATCH_EXPORTS, TRAIN_EXPORTS, SEGMENT_EXPORTS, OPTIM_EXPORTS,
+ INSPECT_EXPORTS) = (tuple(_BINDINGS["vs_%s.h" % h]) for h in ("scorer", "eval", "eval_device", "summary", "batch", "train", "segment",
+                                                                "optim", "inspect"))
 
 
 def hipcc_path() -> str:
@@ -203,6 +316,19 @@ def _build(out_path: str, extra, verbose: bool) -> str:
     return out_path
 
 
+def _bind(lib) -> None:
+    """Checks that ``lib`` has every symbol of ``_BINDINGS`` and the binding's ABI version, then sets the signatures."""
+    table = {name: sig for group in _BINDINGS.values() for name, sig in group.items()}
+    for name in table:
+        if not hasattr(lib, name):
+            raise RuntimeError("libvsscore.so lacks symbol %s (stale build?)" % name)
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    if lib.vs_abi_version() != ABI_VERSION:
+        raise RuntimeError("libvsscore.so ABI %d != binding ABI %d" % (lib.vs_abi_version(), ABI_VERSION))
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -223,297 +349,29 @@ def load() -> C.CDLL:
                 "Run `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). "
                 "There is no PyTorch/CPU fallback for the scoring path." % path)
         lib = C.CDLL(path)
-        for name in EXPORTS + EVAL_EXPORTS + EVAL_DEVICE_EXPORTS + SUMMARY_EXPORTS + BATCH_EXPORTS + TRAIN_EXPORTS + SEGMENT_EXPORTS + OPTIM_EXPORTS + INSPECT_EXPORTS:
-            if not hasattr(lib, name):
-                raise RuntimeError("libvsscore.so lacks symbol %s (stale build?)" % name)
-        lib.vs_abi_version.restype = C.c_int
-        if lib.vs_abi_version() != ABI_VERSION:
-            raise RuntimeError("libvsscore.so ABI %d != binding ABI %d" % (lib.vs_abi_version(), ABI_VERSION))
-        lib.vs_last_error.restype = C.c_char_p
-        lib.vs_weights_pack.restype = C.c_int
-        lib.vs_weights_pack.argtypes = [C.POINTER(ModelDesc), C.POINTER(ModelParams), C.c_void_p,
-                                        C.POINTER(C.c_void_p)]
-        lib.vs_weights_free.restype = None
-        lib.vs_weights_free.argtypes = [C.c_void_p]
-        lib.vs_weights_update.restype = C.c_int
-        lib.vs_weights_update.argtypes = [C.c_void_p, C.POINTER(ModelParams), C.c_void_p]
-        lib.vs_weights_set_norm_width.restype = C.c_int
-        lib.vs_weights_set_norm_width.argtypes = [C.c_void_p, C.c_int32]
-        lib.vs_set_option.restype = C.c_int
-        lib.vs_set_option.argtypes = [C.c_char_p, C.c_int32]
-        lib.vs_scorer_workspace_bytes.restype = C.c_size_t
-        lib.vs_scorer_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        lib.vs_scorer_forward.restype = C.c_int
-        lib.vs_scorer_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                          C.c_void_p]
-        lib.vs_scorer_workspace_bytes_cls.restype = C.c_size_t
-        lib.vs_scorer_workspace_bytes_cls.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        lib.vs_scorer_forward_cls.restype = C.c_int
-        lib.vs_scorer_forward_cls.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                              C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.vs_scorer_workspace_bytes_packed.restype = C.c_size_t
-        lib.vs_scorer_workspace_bytes_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-        lib.vs_scorer_forward_packed.restype = C.c_int
-        lib.vs_scorer_forward_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.vs_linear_f32.restype = C.c_int
-        lib.vs_linear_f32.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p]
-        lib.vs_qkv_proj_f32.restype = C.c_int
-        lib.vs_qkv_proj_f32.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]
-        lib.vs_attention_f32.restype = C.c_int
-        lib.vs_attention_f32.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_float, C.c_void_p]
-        lib.vs_attention_bf16_stored.restype = C.c_int
-        lib.vs_attention_bf16_stored.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p]
-        lib.vs_attention_qscale.restype = C.c_float
-        lib.vs_attention_qscale.argtypes = [C.c_float]
-        lib.vs_attention_bf16.restype = C.c_int
-        lib.vs_attention_bf16.argtypes = lib.vs_attention_f32.argtypes
-        lib.vs_attention_f16x3.restype = C.c_int
-        lib.vs_attention_f16x3.argtypes = lib.vs_attention_f32.argtypes
-        lib.vs_linear_residual_layernorm_f32.restype = C.c_int
-        lib.vs_linear_residual_layernorm_f32.argtypes = ([C.c_void_p] * 7 + [C.c_int32] * 3 + [C.c_void_p] * 2
-                                                         + [C.c_int32] * 2 + [C.c_void_p] * 2)
-        lib.vs_linear_bf16.restype = C.c_int
-        lib.vs_linear_bf16.argtypes = lib.vs_linear_f32.argtypes
-        lib.vs_linear_bf16_operands.restype = C.c_int
-        lib.vs_linear_bf16_operands.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]
-        lib.vs_qkv_proj_bf16_operands.restype = C.c_int
-        lib.vs_qkv_proj_bf16_operands.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]
-        lib.vs_linear_bf16_a16.restype = C.c_int
-        lib.vs_linear_bf16_a16.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p]
-        lib.vs_to_bf16.restype = C.c_int
-        lib.vs_to_bf16.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.vs_linear_residual_layernorm_bf16.restype = C.c_int
-        lib.vs_linear_residual_layernorm_bf16.argtypes = lib.vs_linear_residual_layernorm_f32.argtypes
-        lib.vs_linear_f16x3.restype = C.c_int
-        lib.vs_linear_f16x3.argtypes = lib.vs_linear_f32.argtypes
-        lib.vs_linear_residual_layernorm_f16x3.restype = C.c_int
-        lib.vs_linear_residual_layernorm_f16x3.argtypes = lib.vs_linear_residual_layernorm_f32.argtypes
-        lib.vs_mlp_block_bf16.restype = C.c_int
-        lib.vs_mlp_block_bf16.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                          C.c_void_p, C.c_void_p]
-        for name in EVAL_EXPORTS:
-            getattr(lib, name).restype = C.c_int
-        lib.vs_eval_upsample.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-        lib.vs_eval_knapsack.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]
-        lib.vs_eval_generate_summary.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                                 C.c_int32, C.c_void_p, C.c_int32]
-        lib.vs_eval_fscore.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                       C.POINTER(C.c_double)]
-        lib.vs_eval_rank_correlation.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_double),
-                                                 C.POINTER(C.c_double)]
-        lib.vs_train_last_format.restype = C.c_uint32
-        lib.vs_train_last_format.argtypes = []
-        lib.vs_eval_corpus.restype = C.c_int
-        lib.vs_eval_corpus.argtypes = [C.POINTER(EvalVideo), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        # include/vs_eval_device.h
-        lib.vs_eval_set_create.restype = C.c_int
-        lib.vs_eval_set_create.argtypes = [C.POINTER(EvalVideo), C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]
-        lib.vs_eval_set_free.restype = None
-        lib.vs_eval_set_free.argtypes = [C.c_void_p]
-        lib.vs_eval_set_workspace_bytes.restype = C.c_size_t
-        lib.vs_eval_set_workspace_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-        lib.vs_eval_set_run.restype = C.c_int
-        lib.vs_eval_set_run.argtypes = ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
-                                        + [C.c_size_t, C.c_void_p])
-        # include/vs_summary.h
-        lib.vs_summarize_workspace_bytes.restype = C.c_size_t
-        lib.vs_summarize_workspace_bytes.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_double]
-        lib.vs_summarize.restype = C.c_int
-        lib.vs_summarize.argtypes = ([C.c_int32] + [C.c_void_p] * 6 + [C.c_double] + [C.c_void_p] * 7
-                                     + [C.c_size_t, C.c_void_p])
-        # include/vs_batch.h
-        lib.vs_batch_gather_packed.restype = C.c_int
-        lib.vs_batch_gather_packed.argtypes = ([C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 2 + [C.c_int32, C.c_int64, C.c_int32]
-                                               + [C.c_void_p] * 3)
-        lib.vs_batch_gather_padded.restype = C.c_int
-        lib.vs_batch_gather_padded.argtypes = ([C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 2 + [C.c_int32] * 3
-                                               + [C.c_float, C.c_int32] + [C.c_void_p] * 4)
-        lib.vs_batch_gather_rows.restype = C.c_int
-        lib.vs_batch_gather_rows.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-        # include/vs_train.h
-        lib.vs_train_prepare.restype = C.c_int
-        lib.vs_train_prepare.argtypes = [C.c_void_p, C.c_void_p]
-        lib.vs_train_saved_bytes.restype = C.c_size_t
-        lib.vs_train_saved_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        lib.vs_train_workspace_bytes.restype = C.c_size_t
-        lib.vs_train_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        lib.vs_train_forward.restype = C.c_int
-        lib.vs_train_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DropoutCfg),
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.vs_train_backward.restype = C.c_int
-        lib.vs_train_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DropoutCfg),
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ModelGrads), C.c_void_p,
-                                          C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.vs_mse_mask_loss_forward.restype = C.c_int
-        lib.vs_mse_mask_loss_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p]
-        lib.vs_mse_mask_loss_backward.restype = C.c_int
-        lib.vs_mse_mask_loss_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                                  C.c_void_p, C.c_void_p]
-        lib.vs_train_attention_forward.restype = C.c_int
-        lib.vs_train_attention_forward.argtypes = ([C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_uint64, C.c_uint32,
-                                                                                       C.c_float, C.c_void_p])
-        lib.vs_train_attention_backward.restype = C.c_int
-        lib.vs_train_attention_backward.argtypes = ([C.c_void_p] * 9 + [C.c_int32] * 4 + [C.c_float, C.c_uint64, C.c_uint32,
-                                                                                        C.c_float, C.c_void_p])
-        lib.vs_train_attention_dropout_bits_bytes.restype = C.c_size_t
-        lib.vs_train_attention_dropout_bits_bytes.argtypes = [C.c_int32] * 3
-        lib.vs_train_attention_dropout_bits.restype = C.c_int
-        lib.vs_train_attention_dropout_bits.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32,
-                                                        C.c_float, C.c_void_p]
-        lib.vs_train_attention_forward_bf16.restype = C.c_int
-        lib.vs_train_attention_forward_bf16.argtypes = ([C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_float, C.c_void_p,
-                                                                                            C.c_int32, C.c_void_p])
-        lib.vs_train_attention_backward_bf16.restype = C.c_int
-        lib.vs_train_attention_backward_bf16.argtypes = ([C.c_void_p] * 9 + [C.c_int32] * 4 + [C.c_float, C.c_float, C.c_void_p,
-                                                                                             C.c_int32, C.c_void_p])
-        lib.vs_train_wgrad_scratch_floats.restype = C.c_size_t
-        lib.vs_train_wgrad_scratch_floats.argtypes = [C.c_int32] * 3
-        lib.vs_train_wgrad.restype = C.c_int
-        lib.vs_train_wgrad.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p]
-        lib.vs_train_wgrad_bf16.restype = C.c_int
-        lib.vs_train_wgrad_bf16.argtypes = lib.vs_train_wgrad.argtypes
-        lib.vs_train_dropout_mask_attention.restype = C.c_int
-        lib.vs_train_dropout_mask_attention.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32,
-                                                        C.c_float, C.c_void_p]
-        lib.vs_train_dropout_mask_rows.restype = C.c_int
-        lib.vs_train_dropout_mask_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_float,
-                                                   C.c_void_p]
-        lib.vs_pretrain_head_state_bytes.restype = C.c_size_t
-        lib.vs_pretrain_head_state_bytes.argtypes = [C.c_int32] * 3
-        lib.vs_pretrain_head_workspace_bytes.restype = C.c_size_t
-        lib.vs_pretrain_head_workspace_bytes.argtypes = [C.c_int32] * 4
-        lib.vs_pretrain_head_forward.restype = C.c_int
-        lib.vs_pretrain_head_forward.argtypes = ([C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_int32]
-                                                 + [C.c_void_p] * 4)
-        lib.vs_pretrain_head_backward.restype = C.c_int
-        lib.vs_pretrain_head_backward.argtypes = ([C.c_void_p] * 8 + [C.c_int32] * 4 + [C.c_float, C.c_int32]
-                                                  + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p])
-        lib.vs_train_saved_field.restype = C.c_int
-        lib.vs_train_saved_field.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t),
-                                             C.POINTER(C.c_size_t)]
-        lib.vs_train_dropout_site.restype = C.c_uint32
-        lib.vs_train_dropout_site.argtypes = [C.c_int32, C.c_int32]
-        # ... packed ragged batches (lengths: host int32 array, then the same values on the device)
-        lib.vs_train_check_packed.restype = C.c_int
-        lib.vs_train_check_packed.argtypes = [C.POINTER(ModelDesc), C.c_void_p, C.c_int32]
-        lib.vs_train_saved_bytes_desc.restype = C.c_size_t
-        lib.vs_train_saved_bytes_desc.argtypes = [C.POINTER(ModelDesc), C.c_void_p, C.c_int32, C.c_int32]
-        lib.vs_train_saved_bytes_packed.restype = C.c_size_t
-        lib.vs_train_saved_bytes_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-        lib.vs_train_workspace_bytes_packed.restype = C.c_size_t
-        lib.vs_train_workspace_bytes_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-        lib.vs_train_forward_packed.restype = C.c_int
-        lib.vs_train_forward_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(DropoutCfg),
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.vs_train_backward_packed.restype = C.c_int
-        lib.vs_train_backward_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(DropoutCfg),
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ModelGrads), C.c_void_p,
-                                                 C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.vs_mse_packed_loss_forward.restype = C.c_int
-        lib.vs_mse_packed_loss_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.vs_mse_packed_loss_backward.restype = C.c_int
-        lib.vs_mse_packed_loss_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]
-        lib.vs_train_attention_packed_scratch_bytes.restype = C.c_size_t
-        lib.vs_train_attention_packed_scratch_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        lib.vs_train_attention_forward_packed.restype = C.c_int
-        lib.vs_train_attention_forward_packed.argtypes = ([C.c_void_p] * 7 + [C.c_int32] * 3 + [C.c_float, C.c_uint64, C.c_uint32, C.c_float,
-                                                                                            C.c_void_p, C.c_size_t, C.c_void_p])
-        lib.vs_train_attention_backward_packed.restype = C.c_int
-        lib.vs_train_attention_backward_packed.argtypes = ([C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_float, C.c_uint64, C.c_uint32, C.c_float,
-                                                                                             C.c_void_p, C.c_size_t, C.c_void_p])
-        # ... on the 16-bit pipe: (..., scale, seed, site, p, f16, scratch, scratch_bytes, stream)
-        lib.vs_train_attention_packed_lp_scratch_bytes.restype = C.c_size_t
-        lib.vs_train_attention_packed_lp_scratch_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        lib.vs_train_attention_forward_packed_lp.restype = C.c_int
-        lib.vs_train_attention_forward_packed_lp.argtypes = ([C.c_void_p] * 7 + [C.c_int32] * 3 + [C.c_float, C.c_uint64, C.c_uint32, C.c_float,
-                                                                                               C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p])
-        lib.vs_train_attention_backward_packed_lp.restype = C.c_int
-        lib.vs_train_attention_backward_packed_lp.argtypes = ([C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_float, C.c_uint64, C.c_uint32, C.c_float,
-                                                                                                C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p])
-        lib.vs_train_dropout_mask_attention_packed.restype = C.c_int
-        lib.vs_train_dropout_mask_attention_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32,
-                                                               C.c_float, C.c_void_p]
-        lib.vs_train_saved_field_packed.restype = C.c_int
-        lib.vs_train_saved_field_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t),
-                                                    C.POINTER(C.c_size_t)]
-        # ... and the pretraining head on them: (hidden, logits, lengths, lengths_dev, B, ref_len, vid, vt_w, ...)
-        lib.vs_pretrain_head_state_bytes_packed.restype = C.c_size_t
-        lib.vs_pretrain_head_state_bytes_packed.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        lib.vs_pretrain_head_workspace_bytes_packed.restype = C.c_size_t
-        lib.vs_pretrain_head_workspace_bytes_packed.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
-        lib.vs_pretrain_head_forward_packed.restype = C.c_int
-        lib.vs_pretrain_head_forward_packed.argtypes = ([C.c_void_p] * 4 + [C.c_int32] * 2 + [C.c_void_p] * 3 + [C.c_int32] * 2
-                                                        + [C.c_float, C.c_int32] + [C.c_void_p] * 4)
-        lib.vs_pretrain_head_backward_packed.restype = C.c_int
-        lib.vs_pretrain_head_backward_packed.argtypes = ([C.c_void_p] * 4 + [C.c_int32] * 2 + [C.c_void_p] * 5 + [C.c_int32] * 2
-                                                         + [C.c_float, C.c_int32] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p])
-        # include/vs_segment.h
-        lib.vs_kts_workspace_bytes.restype = C.c_size_t
-        lib.vs_kts_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
-        lib.vs_kts_segment.restype = C.c_int
-        lib.vs_kts_segment.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
-                                       + [C.c_int32] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p])
-        lib.vs_kts_scatters.restype = C.c_int
-        lib.vs_kts_scatters.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
-                                        C.c_void_p]
-        lib.vs_kts_gram_workspace_bytes.restype = C.c_size_t
-        lib.vs_kts_gram_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        lib.vs_kts_gram.restype = C.c_int
-        lib.vs_kts_gram.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(KtsKernel), C.c_void_p, C.c_void_p,
-                                    C.c_size_t, C.c_void_p]
-        lib.vs_kts_workspace_bytes_k.restype = C.c_size_t
-        lib.vs_kts_workspace_bytes_k.argtypes = lib.vs_kts_workspace_bytes.argtypes + [C.POINTER(KtsKernel)]
-        lib.vs_kts_segment_k.restype = C.c_int
-        lib.vs_kts_segment_k.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
-                                         + [C.c_int32, C.POINTER(KtsKernel)] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p])
-        lib.vs_kts_eval_score.restype = C.c_int
-        lib.vs_kts_eval_score.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.POINTER(KtsKernel), C.c_void_p, C.c_int32]
-                                          + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p])
-        # include/vs_optim.h
-        lib.vs_adam_step_tensors.restype = C.c_int
-        lib.vs_adam_step_tensors.argtypes = [C.POINTER(AdamTensor), C.c_int32, C.POINTER(AdamCfg), C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p]
-        lib.vs_adam_state_bytes.restype = C.c_size_t
-        lib.vs_adam_state_bytes.argtypes = [C.c_void_p]
-        lib.vs_adam_state_init.restype = C.c_int
-        lib.vs_adam_state_init.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.vs_adam_state_field.restype = C.c_int
-        lib.vs_adam_state_field.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-        lib.vs_adam_step.restype = C.c_int
-        lib.vs_adam_step.argtypes = [C.c_void_p, C.POINTER(ModelParams), C.POINTER(ModelGrads), C.c_void_p, C.POINTER(AdamCfg),
-                                     C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.vs_grad_norm_workspace_bytes.restype = C.c_size_t
-        lib.vs_grad_norm_workspace_bytes.argtypes = [C.POINTER(GradTensor), C.c_int32]
-        lib.vs_grad_norm_tensors.restype = C.c_int
-        lib.vs_grad_norm_tensors.argtypes = [C.POINTER(GradTensor), C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.vs_grad_norm.restype = C.c_int
-        lib.vs_grad_norm.argtypes = [C.c_void_p, C.POINTER(ModelGrads), C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.vs_grad_scale_tensors.restype = C.c_int
-        lib.vs_grad_scale_tensors.argtypes = [C.POINTER(GradTensor), C.c_int32, C.c_void_p, C.c_void_p]
-        # include/vs_inspect.h
-        lib.vs_inspect_workspace_bytes.restype = C.c_size_t
-        lib.vs_inspect_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
-        lib.vs_inspect_forward.restype = C.c_int
-        lib.vs_inspect_forward.argtypes = ([C.c_void_p] * 4 + [C.c_int32] * 2 + [C.POINTER(C.c_int32), C.c_int32] + [C.c_void_p] * 6
-                                           + [C.c_size_t, C.c_void_p])
-        lib.vs_attention_probs_workspace_bytes.restype = C.c_size_t
-        lib.vs_attention_probs_workspace_bytes.argtypes = [C.c_int32] * 3
-        lib.vs_attention_probs_f32.restype = C.c_int
-        lib.vs_attention_probs_f32.argtypes = ([C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_float, C.c_void_p, C.c_size_t, C.c_void_p])
-        lib.vs_profile_enable.restype = C.c_int
-        lib.vs_profile_enable.argtypes = [C.c_int32]
-        lib.vs_profile_collect.restype = C.c_int
-        lib.vs_profile_collect.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-        lib.vs_stage_name.restype = C.c_char_p
-        lib.vs_stage_name.argtypes = [C.c_int32]
+        _bind(lib)
         _lib = lib
     return _lib
+
+
+class TrainForm(NamedTuple):
+    """The word of ``vs_train_last_format`` decoded (bits 0..5 of include/vs_train.h; ``VsTrainForm`` in csrc/vs_train_plan.h):
+    lp - 16-bit Linear / dgrad / wgrad products; lpa - 16-bit attention products; qkv16 / h16 - q / k / v, the MLP hidden
+    tensor stored as 16-bit planes; rows16 - written by the A-stationary GEMM; f16 - the 16-bit type is fp16, not bf16."""
+    lp: bool
+    lpa: bool
+    qkv16: bool
+    h16: bool
+    rows16: bool
+    f16: bool
+
+    def dtype(self, low_precision: bool) -> str:
+        """'fp32', or the 16-bit type's name where ``low_precision`` (one of the fields above, or several or-ed) holds"""
+        return ("fp16" if self.f16 else "bf16") if low_precision else "fp32"
+
+
+def train_form(word: int) -> TrainForm:
+    return TrainForm(*(bool(word >> bit & 1) for bit in range(6)))
 
 
 def set_option(name: str, value: int) -> None:

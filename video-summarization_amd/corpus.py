@@ -89,6 +89,14 @@ ScoreFn = Callable[[torch.Tensor, Optional[torch.Tensor]], torch.Tensor]   # (x,
 PackedScoreFn = Callable[[torch.Tensor, List[int]], torch.Tensor]           # (x [sum T, D], lengths) -> scores [sum T]
 
 
+def packed_scorer(model) -> Optional[PackedScoreFn]:
+    """``model.score_packed`` as the ``packed_fn`` of ``score_corpus``, or None: packed scoring exists for models that have
+    the method and whose head dim - the library's, for an embedded model - is 32, 64 or 128."""
+    if hasattr(model, "score_packed") and getattr(model, "_lib_dh", model.d_model // model.num_heads) in (32, 64, 128):
+        return lambda x, lens: model.score_packed(x, lens)
+    return None
+
+
 def score_corpus(score_fn: ScoreFn, videos: Sequence[torch.Tensor], rank: int = 0, world: int = 1,
                  group=None, device=None, max_frames: int = 65536,
                  packed_fn: Optional[PackedScoreFn] = None, force_collective: bool = False,

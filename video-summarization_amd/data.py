@@ -39,7 +39,8 @@ from torch.nn.utils.rnn import pad_sequence
 from torch.utils.data import Dataset
 
 from . import _lib
-from .corpus import bucket_batches
+from ._call import ptr, stream_of
+from .corpus import bucket_batches, packed_scorer
 from .synth import IN_FEATURES, PAD_VALUE
 
 # reference src/data/path.py:1-6
@@ -406,7 +407,7 @@ def val_step_from_dataset(model, dataset: TSDataset, device, max_frames: int = 6
     import torch.nn.functional as F
     from .evaluation import eval_metrics
     model.eval()
-    if getattr(model, "_lib_dh", model.d_model // model.num_heads) not in (32, 64, 128):
+    if packed_scorer(model) is None:
         raise RuntimeError("packed scoring needs head dim 32 or 64; use harness.val_step for this model")
     scores = score_dataset(model, dataset.data, device, max_frames)
     score_dict, user_dict, loss = {}, {}, 0.0
@@ -527,20 +528,19 @@ class _ResidentSet:
         ids_ptr = plan_dev.data_ptr() + 4 * off
         start_ptr = ids_ptr + 4 * B
         dev = self.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        side_ptr = side.data_ptr() if want_side else None
+        stream = stream_of(dev)
         if packed:
             x = torch.empty((rows, self.d), dtype=torch.float32, device=dev)
             y = torch.empty((rows,), dtype=torch.float32, device=dev) if want_side else None
-            _lib.check(lib.vs_batch_gather_packed(self.arena.data_ptr(), side.data_ptr() if want_side else None,
-                                                  self.video_start.data_ptr(), len(self), ids_ptr, start_ptr, B, rows, self.d,
-                                                  x.data_ptr(), y.data_ptr() if want_side else None, stream))
+            _lib.check(lib.vs_batch_gather_packed(self.arena.data_ptr(), side_ptr, self.video_start.data_ptr(), len(self), ids_ptr,
+                                                  start_ptr, B, rows, self.d, x.data_ptr(), ptr(y), stream))
             return x, y, None
         x = torch.empty((B, t_max, self.d), dtype=torch.float32, device=dev)
         y = torch.empty((B, t_max), dtype=torch.float32, device=dev) if want_side else None
         mask = torch.empty((B, t_max), dtype=torch.uint8, device=dev)
-        _lib.check(lib.vs_batch_gather_padded(self.arena.data_ptr(), side.data_ptr() if want_side else None,
-                                              self.video_start.data_ptr(), len(self), ids_ptr, start_ptr, B, t_max, t_max,
-                                              float(PAD_VALUE), self.d, x.data_ptr(), y.data_ptr() if want_side else None,
+        _lib.check(lib.vs_batch_gather_padded(self.arena.data_ptr(), side_ptr, self.video_start.data_ptr(), len(self), ids_ptr,
+                                              start_ptr, B, t_max, t_max, float(PAD_VALUE), self.d, x.data_ptr(), ptr(y),
                                               mask.data_ptr(), stream))
         return x, y, mask.view(torch.bool)
 
@@ -548,7 +548,7 @@ class _ResidentSet:
         lib = _lib.load()
         out = torch.empty((B, table.shape[1]), dtype=torch.float32, device=self.device)
         _lib.check(lib.vs_batch_gather_rows(table.data_ptr(), table.shape[0], plan_dev.data_ptr() + 4 * off, B, table.shape[1],
-                                            out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+                                            out.data_ptr(), stream_of(self.device)))
         return out
 
     def epoch(self, batch_size: int, shuffle: bool = True, drop_last: bool = False, generator=None, packed: bool = True):

@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._call import on_stream, scratch
 
 
 def _i32(a):
@@ -162,8 +163,7 @@ class EvalSet:
         self._handle = C.c_void_p()
         self._workspace = None
         self._need = (None, 0)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with on_stream(self.device) as stream:
             _lib.check(self._lib.vs_eval_set_create(recs, n, C.c_void_p(stream), C.byref(self._handle)))
 
     def close(self):
@@ -209,11 +209,10 @@ class EvalSet:
             self._need = (key, need)
         need = self._need[1]
         if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._workspace = scratch(need, self.device)
         f, kt, sp = (np.empty(ids.size, dtype=np.float64) for _ in range(3))
         sel = np.empty(sum(self.n_shots[j] for j in ids), dtype=np.int8) if return_selected else None
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with on_stream(self.device) as stream:
             _lib.check(lib.vs_eval_set_run(self._handle, C.c_void_p(scores.data_ptr()), _p(ids), ids.size, _p(f), _p(kt), _p(sp),
                                            _p(sel) if sel is not None else None, C.c_void_p(self._workspace.data_ptr()),
                                            self._workspace.numel(), C.c_void_p(stream)))

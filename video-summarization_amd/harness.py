@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .corpus import plan_shards, score_corpus
+from .corpus import packed_scorer, plan_shards, score_corpus
 from .evaluation import eval_metrics, eval_videos
 from .losses import mse_packed_loss, mse_with_mask_loss
 
@@ -192,9 +192,7 @@ def val_step_batched(model, features: Sequence[torch.Tensor], targets: Sequence[
     scored from the scores still on its device (no score all-gather, no score device-to-host copy), takes the MSE loss
     there too, and only the all-reduce of the four sums stays.  F-score, tau and rho are the default path's bit for bit."""
     model.eval()
-    # models with head dim 32 / 64 score PACKED batches (no sentinel padding, no mask; the same bits)
-    can_pack = hasattr(model, "score_packed") and getattr(model, "_lib_dh", model.d_model // model.num_heads) in (32, 64, 128)
-    packed_fn = (lambda x, lens: model.score_packed(x, lens)) if can_pack else None
+    packed_fn = packed_scorer(model)      # PACKED batches where the model has them (no sentinel padding, no mask; the same bits)
     if eval_set is not None:
         order, flat = score_corpus(lambda x, m: model.score(x, m), list(features), rank=rank, world=world, group=group,
                                    device=device, max_frames=max_frames, packed_fn=packed_fn, keep_on_device=True)

@@ -11,6 +11,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from ._call import mask_u8, on_stream, ptr
 
 
 class _MseMask(torch.autograd.Function):
@@ -21,17 +22,13 @@ class _MseMask(torch.autograd.Function):
         o, t = output.contiguous(), targets.contiguous().float()
         if o.numel() != t.numel():
             raise RuntimeError("output %s and targets %s differ in size" % (tuple(output.shape), tuple(targets.shape)))
-        m = None
-        if mask is not None:
-            m = mask.contiguous()
-            m = m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
-            if m.numel() != o.numel():
-                raise RuntimeError("mask %s does not match output %s" % (tuple(mask.shape), tuple(output.shape)))
+        m = mask_u8(mask)
+        if m is not None and m.numel() != o.numel():
+            raise RuntimeError("mask %s does not match output %s" % (tuple(mask.shape), tuple(output.shape)))
         loss = torch.empty((), dtype=torch.float32, device=o.device)
-        with torch.cuda.device(o.device):
+        with on_stream(o.device) as stream:
             scratch = torch.empty((256,), dtype=torch.float32, device=o.device)
-            stream = torch.cuda.current_stream(o.device).cuda_stream
-            _lib.check(lib.vs_mse_mask_loss_forward(o.data_ptr(), t.data_ptr(), None if m is None else m.data_ptr(),
+            _lib.check(lib.vs_mse_mask_loss_forward(o.data_ptr(), t.data_ptr(), ptr(m),
                                                     o.numel(), int(mean), scratch.data_ptr(), loss.data_ptr(), stream))
         ctx.save_for_backward(o, t, m)
         ctx.mean, ctx.shape = bool(mean), output.shape
@@ -44,9 +41,8 @@ class _MseMask(torch.autograd.Function):
         o, t, m = ctx.saved_tensors
         d_out = torch.empty_like(o)
         g = d_loss.contiguous().float()
-        with torch.cuda.device(o.device):
-            stream = torch.cuda.current_stream(o.device).cuda_stream
-            _lib.check(lib.vs_mse_mask_loss_backward(o.data_ptr(), t.data_ptr(), None if m is None else m.data_ptr(),
+        with on_stream(o.device) as stream:
+            _lib.check(lib.vs_mse_mask_loss_backward(o.data_ptr(), t.data_ptr(), ptr(m),
                                                      g.data_ptr(), o.numel(), int(ctx.mean), d_out.data_ptr(), stream))
         return d_out.view(ctx.shape), None, None, None
 
@@ -68,9 +64,8 @@ class _MsePacked(torch.autograd.Function):
         if o.numel() != t.numel():
             raise RuntimeError("output %s and targets %s differ in size" % (tuple(output.shape), tuple(targets.shape)))
         loss = torch.empty((), dtype=torch.float32, device=o.device)
-        with torch.cuda.device(o.device):
+        with on_stream(o.device) as stream:
             scratch = torch.empty((256,), dtype=torch.float32, device=o.device)
-            stream = torch.cuda.current_stream(o.device).cuda_stream
             _lib.check(lib.vs_mse_packed_loss_forward(o.data_ptr(), t.data_ptr(), o.numel(), float(denom), scratch.data_ptr(),
                                                       loss.data_ptr(), stream))
         ctx.save_for_backward(o, t)
@@ -84,8 +79,7 @@ class _MsePacked(torch.autograd.Function):
         o, t = ctx.saved_tensors
         d_out = torch.empty_like(o)
         g = d_loss.contiguous().float()
-        with torch.cuda.device(o.device):
-            stream = torch.cuda.current_stream(o.device).cuda_stream
+        with on_stream(o.device) as stream:
             _lib.check(lib.vs_mse_packed_loss_backward(o.data_ptr(), t.data_ptr(), g.data_ptr(), o.numel(), ctx.denom,
                                                        d_out.data_ptr(), stream))
         return d_out.view(ctx.shape), None, None

@@ -34,6 +34,7 @@ from torch import Tensor, nn
 from torch.optim import Optimizer
 
 from . import _lib
+from ._call import on_stream, ptr, scratch
 from .simnet import SimNet
 
 __all__ = ["Adam", "AdamW", "clip_grad_norm_", "grad_norm"]
@@ -87,8 +88,8 @@ class _ClipBuffers:
         if need == 0:
             raise RuntimeError("a gradient has 2^32 elements or more")
         if self.ws is None or self.ws.numel() < need:
-            self.ws = torch.empty((need,), dtype=torch.uint8, device=self.dev)
-        _lib.check(lib.vs_grad_norm_tensors(self.table, len(grads), kind, max_norm, None if grad_scale is None else grad_scale.data_ptr(),
+            self.ws = scratch(need, self.dev)
+        _lib.check(lib.vs_grad_norm_tensors(self.table, len(grads), kind, max_norm, ptr(grad_scale),
                                             self.out.data_ptr(), self.ws.data_ptr(), self.ws.numel(), stream))
         return self.out
 
@@ -126,8 +127,8 @@ def _measure(parameters, max_norm: float, norm_type, who: str):
         return None, None, None
     lib = _lib.load()
     buf = _ClipBuffers(dev)
-    with torch.cuda.device(dev):
-        out = buf.measure(lib, grads, kind, max_norm, None, torch.cuda.current_stream(dev).cuda_stream)
+    with on_stream(dev) as stream:
+        out = buf.measure(lib, grads, kind, max_norm, None, stream)
     return out, buf, len(grads)
 
 
@@ -152,8 +153,8 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     out, buf, n = _measure(parameters, max_norm, norm_type, "clip_grad_norm_")
     if out is None:
         return torch.zeros(())
-    with torch.cuda.device(buf.dev):
-        _lib.check(_lib.load().vs_grad_scale_tensors(buf.table, n, out.data_ptr() + 4, torch.cuda.current_stream(buf.dev).cuda_stream))
+    with on_stream(buf.dev) as stream:
+        _lib.check(_lib.load().vs_grad_scale_tensors(buf.table, n, out.data_ptr() + 4, stream))
     return out[0]
 
 
@@ -393,8 +394,8 @@ class Adam(Optimizer):
             raise RuntimeError("grad_scale / found_inf must be fp32 scalars on %s, got %s on %s" % (dev, grad_scale.dtype, grad_scale.device))
         if self._clip is None or self._clip.dev != dev:
             self._clip = _ClipBuffers(dev)
-        with torch.cuda.device(dev):
-            out = self._clip.measure(lib, grads, kind, max_norm, grad_scale, torch.cuda.current_stream(dev).cuda_stream)
+        with on_stream(dev) as stream:
+            out = self._clip.measure(lib, grads, kind, max_norm, grad_scale, stream)
         self.last_grad_norm = out[0]
         return out.data_ptr() + 8
 
@@ -424,7 +425,7 @@ class Adam(Optimizer):
             beta1, beta2 = group["betas"]
             cfg = _lib.AdamCfg(float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
                                1 if group.get("decoupled_weight_decay", False) else 0, 0)
-            gs, fi = (None if grad_scale is None else grad_scale.data_ptr()), (None if found_inf is None else found_inf.data_ptr())
+            gs, fi = ptr(grad_scale), ptr(found_inf)
             if divisor is not None:
                 gs = divisor        # grad_scale / clip_coef: the kernel's division unscales and clips at once
             state, views, live, hold, f32 = self.state, plan.views, plan.live, [], torch.float32
@@ -451,8 +452,7 @@ class Adam(Optimizer):
                 touched.append(p)
                 return g.data_ptr()
 
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
+            with on_stream(dev) as stream:
                 for part in plan.parts:
                     module = part.module
                     if module not in current:

@@ -22,14 +22,13 @@ them on their own tensors; ``forward`` does not go through them.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 from torch import Tensor
 
 from . import _lib
+from ._call import host_lengths, mask_u8, on_stream, ptr, scratch
 from .simnet import SimNet
 
 
@@ -44,17 +43,13 @@ class _PretrainHead(torch.autograd.Function):
         Fo = weight.shape[0]
         hidden, logits, vid = hidden.contiguous(), logits.contiguous(), vid.contiguous()
         w, bvec = weight.detach().contiguous(), bias.detach().contiguous()
-        m = None
-        if mask is not None:
-            m = mask.contiguous()
-            m = m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
+        m = mask_u8(mask)
         dev = hidden.device
         feats = torch.empty((B, T, Fo), dtype=torch.float32, device=dev)
         losses = torch.empty((3,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            state = torch.empty((lib.vs_pretrain_head_state_bytes(B, T, Fo),), dtype=torch.uint8, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.vs_pretrain_head_forward(hidden.data_ptr(), logits.data_ptr(), None if m is None else m.data_ptr(),
+        with on_stream(dev) as stream:
+            state = scratch(lib.vs_pretrain_head_state_bytes(B, T, Fo), dev)
+            _lib.check(lib.vs_pretrain_head_forward(hidden.data_ptr(), logits.data_ptr(), ptr(m),
                                                     vid.data_ptr(), w.data_ptr(), bvec.data_ptr(), B, T, d, Fo, float(temp),
                                                     int(entropy), feats.data_ptr(), state.data_ptr(), losses.data_ptr(), stream))
         ctx.save_for_backward(hidden, logits, vid, m, w, feats, state)
@@ -73,10 +68,9 @@ class _PretrainHead(torch.autograd.Function):
         g = d_losses.contiguous().float()
         d_hidden, d_logits = torch.empty_like(hidden), torch.empty((B, T), dtype=torch.float32, device=dev)
         d_w, d_b = torch.empty_like(w), torch.empty((Fo,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            ws = torch.empty((lib.vs_pretrain_head_workspace_bytes(B, T, d, Fo),), dtype=torch.uint8, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.vs_pretrain_head_backward(hidden.data_ptr(), logits.data_ptr(), None if m is None else m.data_ptr(),
+        with on_stream(dev) as stream:
+            ws = scratch(lib.vs_pretrain_head_workspace_bytes(B, T, d, Fo), dev)
+            _lib.check(lib.vs_pretrain_head_backward(hidden.data_ptr(), logits.data_ptr(), ptr(m),
                                                      vid.data_ptr(), w.data_ptr(), feats.data_ptr(), state.data_ptr(),
                                                      g.data_ptr(), B, T, d, Fo, temp, entropy, d_hidden.data_ptr(),
                                                      d_logits.data_ptr(), d_w.data_ptr(), d_b.data_ptr(), ws.data_ptr(),
@@ -100,7 +94,7 @@ class _PretrainHeadPacked(torch.autograd.Function):
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, hidden, logits, vid, lengths, ref_len, weight, bias, temp, entropy, lengths_dev=None):
         lib = _lib.load()
-        lengths = [int(t) for t in lengths]
+        lengths, host = host_lengths(lengths)
         Bv, (M, d) = len(lengths), hidden.shape
         Fo = weight.shape[0]
         if M != sum(lengths) or logits.numel() != M or tuple(vid.shape) != (Bv, Fo):
@@ -108,15 +102,13 @@ class _PretrainHeadPacked(torch.autograd.Function):
                                % (tuple(hidden.shape), tuple(logits.shape), tuple(vid.shape), sum(lengths), Bv, Fo))
         hidden, logits, vid = hidden.contiguous(), logits.contiguous(), vid.contiguous()
         w, bvec = weight.detach().contiguous(), bias.detach().contiguous()
-        host = (C.c_int32 * Bv)(*lengths)
         dev = hidden.device
         feats = torch.empty((M, Fo), dtype=torch.float32, device=dev)
         losses = torch.empty((3,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
+        with on_stream(dev) as stream:
             dev_len = _device_lengths(lengths, dev) if lengths_dev is None else lengths_dev
             # (invalid lengths / F give 0 bytes: the forward call below says why)
-            state = torch.empty((max(lib.vs_pretrain_head_state_bytes_packed(host, Bv, Fo), 256),), dtype=torch.uint8, device=dev)
+            state = scratch(lib.vs_pretrain_head_state_bytes_packed(host, Bv, Fo), dev, floor=256)
             _lib.check(lib.vs_pretrain_head_forward_packed(hidden.data_ptr(), logits.data_ptr(), host, dev_len.data_ptr(), Bv,
                                                            int(ref_len), vid.data_ptr(), w.data_ptr(), bvec.data_ptr(), d, Fo,
                                                            float(temp), int(entropy), feats.data_ptr(), state.data_ptr(),
@@ -134,13 +126,12 @@ class _PretrainHeadPacked(torch.autograd.Function):
         Bv, (M, d) = len(lengths), hidden.shape
         Fo = w.shape[0]
         dev = hidden.device
-        host = (C.c_int32 * Bv)(*lengths)
+        _, host = host_lengths(lengths)
         g = d_losses.contiguous().float()
         d_hidden, d_logits = torch.empty_like(hidden), torch.empty((M,), dtype=torch.float32, device=dev)
         d_w, d_b = torch.empty_like(w), torch.empty((Fo,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            ws = torch.empty((lib.vs_pretrain_head_workspace_bytes_packed(host, Bv, d, Fo),), dtype=torch.uint8, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
+        with on_stream(dev) as stream:
+            ws = scratch(lib.vs_pretrain_head_workspace_bytes_packed(host, Bv, d, Fo), dev)
             _lib.check(lib.vs_pretrain_head_backward_packed(hidden.data_ptr(), logits.data_ptr(), host, dev_len.data_ptr(), Bv,
                                                             ref_len, vid.data_ptr(), w.data_ptr(), feats.data_ptr(),
                                                             state.data_ptr(), g.data_ptr(), d, Fo, temp, entropy,

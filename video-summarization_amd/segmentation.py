@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._call import scratch, stream_of
 
 __all__ = ["cpd_nonlin", "kts_segmentation", "kts_seg", "kts_seg_batch", "uniform_seg", "get_segment_fn",
            "shots_from_change_points", "gram", "eval_score", "eval_cost", "estimate_vmax", "centering"]
@@ -110,11 +111,11 @@ def _segment(x, input_kind, lengths, ncp, mode, lmin=None, lmax=None, vmax=None,
         nbytes = lib.vs_kts_workspace_bytes_k(_p(cu), B, d, input_kind, _p(ncp), mode, C.byref(kern))
     if nbytes == 0:
         _lib.check(_lib.VS_ERR_INVALID)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ws = scratch(nbytes, x.device)
     cps = np.zeros(max(1, int(ncp.sum())), dtype=np.int64)
     n_cps = np.zeros(B, dtype=np.int32)
     scores = np.zeros(int(ncp.sum()) + B, dtype=np.float64)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
+    stream = stream_of(x.device)
     if kern is None:
         _lib.check(lib.vs_kts_segment(x.data_ptr(), input_kind, d, _p(cu), B, _p(ncp), _p(lmin), _p(lmax), _p(vm), _p(dr), mode,
                                       _p(cps), _p(n_cps), _p(scores), ws.data_ptr(), nbytes, stream))
@@ -138,10 +139,9 @@ def _scatters(x, input_kind, n):
     nbytes = lib.vs_kts_workspace_bytes(_p(cu), 1, d, input_kind, _p(zero), _lib.VS_KTS_SCORES)
     if nbytes == 0:
         _lib.check(_lib.VS_ERR_INVALID)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ws = scratch(nbytes, x.device)
     out = torch.empty((n, n), dtype=torch.float64, device=x.device)
-    _lib.check(lib.vs_kts_scatters(x.data_ptr(), input_kind, d, n, out.data_ptr(), ws.data_ptr(), nbytes,
-                                   torch.cuda.current_stream(x.device).cuda_stream))
+    _lib.check(lib.vs_kts_scatters(x.data_ptr(), input_kind, d, n, out.data_ptr(), ws.data_ptr(), nbytes, stream_of(x.device)))
     return out.cpu().numpy()
 
 
@@ -233,10 +233,10 @@ def gram(features_list, kernel: str = "dot", gamma=None):
     nbytes = lib.vs_kts_gram_workspace_bytes(_p(cu), B, int(x.shape[1]))
     if nbytes == 0:
         _lib.check(_lib.VS_ERR_INVALID)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ws = scratch(nbytes, x.device)
     out = torch.empty(sum(n * n for n in lengths), dtype=torch.float32, device=x.device)
     _lib.check(lib.vs_kts_gram(x.data_ptr(), int(x.shape[1]), _p(cu), B, C.byref(kern), out.data_ptr(), ws.data_ptr(), nbytes,
-                               torch.cuda.current_stream(x.device).cuda_stream))
+                               stream_of(x.device)))
     ws.record_stream(torch.cuda.current_stream(x.device))
     Ks, at = [], 0
     for n in lengths:
@@ -291,11 +291,11 @@ def eval_score(K, cps):
     nbytes = lib.vs_kts_workspace_bytes(_p(cu), 1, 0, kind, _p(ncp), _lib.VS_KTS_SCORES)
     if nbytes == 0:
         _lib.check(_lib.VS_ERR_INVALID)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
+    ws = scratch(nbytes, t.device)
     out = np.zeros(1, dtype=np.float64)
     cbuf = c if m else np.zeros(1, dtype=np.int64)
     _lib.check(lib.vs_kts_eval_score(t.data_ptr(), kind, 0, None, _p(cu), 1, _p(cbuf), _p(ncp), _p(out), ws.data_ptr(), nbytes,
-                                     torch.cuda.current_stream(t.device).cuda_stream))
+                                     stream_of(t.device)))
     return float(out[0])
 
 

@@ -15,12 +15,13 @@ or CPU fallback for either: a missing library or a non-HIP tensor raises.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
 
 from . import _lib
+from ._call import host_lengths, mask_u8, on_stream, ptr, scratch
 from .synth import IN_FEATURES, PE_MAX_LEN, positional_table
 
 # --------------------------------------------------------------------------------------------
@@ -44,10 +45,6 @@ class _Packed:
             pass
 
 
-def _ptr(t: Optional[Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
 @torch.library.custom_op("vs_amd::score_frames", mutates_args=(), device_types="cuda")
 def score_frames(x: Tensor, mask: Optional[Tensor], handle: int, d_model: int, num_classes: int,
                  flags: int, want_hidden: bool) -> Tuple[Tensor, Tensor]:
@@ -58,15 +55,10 @@ def score_frames(x: Tensor, mask: Optional[Tensor], handle: int, d_model: int, n
     x = x.contiguous()
     scores = torch.empty((B, T, num_classes), dtype=torch.float32, device=x.device)
     hidden = torch.empty((B, T, d_model) if want_hidden else (0,), dtype=torch.float32, device=x.device)
-    m = None
-    if mask is not None:
-        m = mask.contiguous()
-        m = m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
-    with torch.cuda.device(x.device):
-        need = lib.vs_scorer_workspace_bytes(handle, B, T)
-        ws = torch.empty((max(need, 256),), dtype=torch.uint8, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(lib.vs_scorer_forward(handle, x.data_ptr(), _ptr(m), B, T, flags, scores.data_ptr(),
+    m = mask_u8(mask)
+    with on_stream(x.device) as stream:
+        ws = scratch(lib.vs_scorer_workspace_bytes(handle, B, T), x.device, floor=256)
+        _lib.check(lib.vs_scorer_forward(handle, x.data_ptr(), ptr(m), B, T, flags, scores.data_ptr(),
                                          hidden.data_ptr() if want_hidden else None, ws.data_ptr(),
                                          ws.numel(), stream))
     return scores, hidden
@@ -84,22 +76,20 @@ def score_frames_packed(x: Tensor, lengths, handle: int, d_model: int, num_class
     """Packed ragged batch: x [sum(lengths), Din] fp32 (HIP device) = the frames of len(lengths) videos concatenated.
     Returns (scores [Mtot, num_classes], hidden [Mtot, d_model] or an empty tensor).  No padding, no mask."""
     lib = _lib.load()
-    lengths = [int(t) for t in lengths]
+    lengths, host = host_lengths(lengths)
     if x.dim() != 2 or x.size(0) != sum(lengths):
         raise RuntimeError("expected x of shape [sum(lengths)=%d, D], got %s" % (sum(lengths), tuple(x.shape)))
     x = x.contiguous()
     M, B = x.size(0), len(lengths)
-    host = (C.c_int32 * B)(*lengths)
     scores = torch.empty((M, num_classes), dtype=torch.float32, device=x.device)
     hidden = torch.empty((M, d_model) if want_hidden else (0,), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
+    with on_stream(x.device) as stream:
         dev_len = torch.tensor(lengths, dtype=torch.int32, device=x.device)
         need = lib.vs_scorer_workspace_bytes_packed(handle, host, B)
         if need == 0:
             _lib.check(lib.vs_scorer_forward_packed(handle, x.data_ptr(), host, dev_len.data_ptr(), B, flags,
                                                     scores.data_ptr(), None, None, 0, None))   # raises with the reason
-        ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
+        ws = scratch(need, x.device)
         _lib.check(lib.vs_scorer_forward_packed(handle, x.data_ptr(), host, dev_len.data_ptr(), B, flags,
                                                 scores.data_ptr(), hidden.data_ptr() if want_hidden else None,
                                                 ws.data_ptr(), ws.numel(), stream))
@@ -111,39 +101,72 @@ def score_frames_packed(x: Tensor, lengths, handle: int, d_model: int, num_class
 # --------------------------------------------------------------------------------------------
 
 
+class _TrainBatch(NamedTuple):
+    """How one training batch is described to include/vs_train.h, and the four entry points that take that description:
+    ``sizes`` follow the weights in the two size queries, ``where`` stands between ``x`` and the dropout config in the forward
+    and the backward.  Padded: (B, T) and (mask, B, T); packed: (lengths, n) and (lengths, lengths_dev, n)."""
+    sizes: tuple
+    where: tuple
+    frames: int
+    saved_bytes: object
+    workspace_bytes: object
+    forward: object
+    backward: object
+
+
+def _train_batch(lib, x: Tensor, keep: Optional[Tensor], lengths) -> _TrainBatch:
+    """``lengths`` None: x [B, T, in] with ``keep`` its uint8 mask (or None); else x [sum(lengths), in] with ``keep`` the
+    lengths on the device.  ``keep`` is what the Function saves beside ``x``: ``where`` holds its address."""
+    if lengths is None:
+        B, T, _ = x.shape
+        return _TrainBatch((B, T), (ptr(keep), B, T), B * T, lib.vs_train_saved_bytes, lib.vs_train_workspace_bytes,
+                           lib.vs_train_forward, lib.vs_train_backward)
+    lengths, host = host_lengths(lengths)
+    return _TrainBatch((host, len(lengths)), (host, keep.data_ptr(), len(lengths)), x.size(0), lib.vs_train_saved_bytes_packed,
+                       lib.vs_train_workspace_bytes_packed, lib.vs_train_forward_packed, lib.vs_train_backward_packed)
+
+
 class _TrainForward(torch.autograd.Function):
-    """``SimNet.forward`` under autograd (reference train.py:121 / pretrain.py:61): forward and backward are the HIP
-    kernels behind ``vs_train_forward`` / ``vs_train_backward``.  The parameters are passed as inputs so autograd
-    routes their gradients; the activation record is one uint8 tensor saved for the backward."""
+    """``SimNet.forward`` (reference train.py:121 / pretrain.py:61) and ``SimNet.forward_packed_train`` under autograd: forward
+    and backward are the HIP kernels behind ``vs_train_forward`` / ``vs_train_backward``, or behind their ``_packed`` forms on
+    the frames of several videos concatenated (``lengths`` given: no sentinel rows, no mask, nothing computed for padding).
+    The parameters are passed as inputs so autograd routes their gradients; the activation record is one uint8 tensor
+    saved for the backward."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)     # train.py:120 calls under amp.autocast()
-    def forward(ctx, module, x, mask, p, p_embed, seed, tflags, *params):
+    def forward(ctx, module, x, mask, lengths, p, p_embed, seed, tflags, *params):
         lib = _lib.load()
-        B, T, _ = x.shape
         x = x.contiguous()
-        m = None
-        if mask is not None:
-            m = mask.contiguous()
-            m = m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
         packed = module._packed_weights(x.device)
-        scores = torch.empty((B, T, module.num_classes), dtype=torch.float32, device=x.device)
-        hidden = torch.empty((B, T, module._lib_d), dtype=torch.float32, device=x.device)
+        scores = torch.empty(x.shape[:-1] + (module.num_classes,), dtype=torch.float32, device=x.device)
+        hidden = torch.empty(x.shape[:-1] + (module._lib_d,), dtype=torch.float32, device=x.device)
         cfg = _lib.DropoutCfg(float(p_embed), float(p), int(seed), int(tflags), 0)
-        with torch.cuda.device(x.device):
+        with on_stream(x.device) as stream:
             if not getattr(packed, "train_prepared", False):     # one-time allocation of the dgrad transposes, outside the backward
-                _lib.check(lib.vs_train_prepare(packed.handle, torch.cuda.current_stream(x.device).cuda_stream))
+                _lib.check(lib.vs_train_prepare(packed.handle, stream))
                 packed.train_prepared = True
-            saved = torch.empty((lib.vs_train_saved_bytes(packed.handle, B, T),), dtype=torch.uint8, device=x.device)
-            ws = torch.empty((lib.vs_train_workspace_bytes(packed.handle, B, T),), dtype=torch.uint8, device=x.device)
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            _lib.check(lib.vs_train_forward(packed.handle, x.data_ptr(), _ptr(m), B, T, C.byref(cfg), scores.data_ptr(),
-                                            hidden.data_ptr(), saved.data_ptr(), saved.numel(), ws.data_ptr(), ws.numel(),
-                                            stream))
+            keep = mask_u8(mask) if lengths is None else torch.tensor(lengths, dtype=torch.int32, device=x.device)
+            batch = _train_batch(lib, x, keep, lengths)
+            need = batch.saved_bytes(packed.handle, *batch.sizes)
+            # *batch.where below: (mask, B, T) of vs_train_forward, (lengths, lengths_dev, n) of vs_train_forward_packed
+            if need == 0 and lengths is not None:       # invalid lengths: the forward says why
+                _lib.check(batch.forward(packed.handle, x.data_ptr(), *batch.where, C.byref(cfg), scores.data_ptr(), None, None, 0,
+                                         None, 0, stream))
+            saved = scratch(need, x.device)
+            ws = scratch(batch.workspace_bytes(packed.handle, *batch.sizes), x.device)
+            _lib.check(batch.forward(packed.handle, x.data_ptr(), *batch.where, C.byref(cfg), scores.data_ptr(), hidden.data_ptr(),
+                                     saved.data_ptr(), saved.numel(), ws.data_ptr(), ws.numel(), stream))
             fmt = int(lib.vs_train_last_format())        # the form this record was written in: handed back to the backward
-        ctx.save_for_backward(x, m, saved)
+        ctx.save_for_backward(x, keep, saved)
         ctx.module, ctx.cfg, ctx.packed, ctx.packed_key = module, (float(p_embed), float(p), int(seed), int(tflags), fmt), packed, module._packed_key
-        module._note_train_arithmetic(int(tflags), fmt, B * T)
+        ctx.lengths = None if lengths is None else tuple(lengths)
+        if lengths is None:
+            module._note_train_arithmetic(int(tflags), fmt, batch.frames)
+        else:       # (last_train_dtype names the Linears' arithmetic; the packed attention has a word of its own)
+            module._note_train_arithmetic(int(tflags) & ~(_lib.VS_TRAIN_FLAG_BF16_ATTENTION | _lib.VS_TRAIN_FLAG_PACKED_LP_ATTENTION), fmt, batch.frames)
+            form = _lib.train_form(fmt)
+            module._last_packed_attention_dtype = form.dtype(form.lpa)
         ctx.set_materialize_grads(False)
         return scores, (hidden[..., :module.d_model] if module._plan else hidden)
 
@@ -151,11 +174,11 @@ class _TrainForward(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, d_scores, d_hidden):
         lib = _lib.load()
-        x, m, saved = ctx.saved_tensors
+        x, keep, saved = ctx.saved_tensors
         module, packed = ctx.module, ctx.packed
         if module._packed_key != ctx.packed_key or module._packed is not packed:
             raise RuntimeError("SimNet parameters were modified between forward and backward")
-        B, T, _ = x.shape
+        batch = _train_batch(lib, x, keep, ctx.lengths)
         grads, G, finish = _grad_destinations(module, x.device)
         dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
         ds = None if d_scores is None else d_scores.contiguous().float()
@@ -163,13 +186,29 @@ class _TrainForward(torch.autograd.Function):
         if dh is not None and module._plan:
             dh = module._pad(dh, ("res",)).contiguous()
         cfg = _lib.DropoutCfg(*ctx.cfg)
-        with torch.cuda.device(x.device):
-            ws = torch.empty((lib.vs_train_workspace_bytes(packed.handle, B, T),), dtype=torch.uint8, device=x.device)
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            _lib.check(lib.vs_train_backward(packed.handle, x.data_ptr(), _ptr(m), B, T, C.byref(cfg), _ptr(ds), _ptr(dh),
-                                             saved.data_ptr(), saved.numel(), C.byref(G), _ptr(dx), ws.data_ptr(),
-                                             ws.numel(), stream))
-        return (None, dx, None, None, None, None, None, *finish(grads))
+        with on_stream(x.device) as stream:
+            ws = scratch(batch.workspace_bytes(packed.handle, *batch.sizes), x.device)
+            # *batch.where: (mask, B, T) of vs_train_backward, (lengths, lengths_dev, n) of vs_train_backward_packed
+            _lib.check(batch.backward(packed.handle, x.data_ptr(), *batch.where, C.byref(cfg), ptr(ds), ptr(dh), saved.data_ptr(),
+                                      saved.numel(), C.byref(G), ptr(dx), ws.data_ptr(), ws.numel(), stream))
+        return (None, dx, None, None, None, None, None, None, *finish(grads))
+
+
+def _model_struct(cls, tensors, num_layers: int, use_pos: bool = False):
+    """A ``vs_model_params`` / ``vs_model_grads`` (``cls``) whose fields point at ``tensors``, given in the order of
+    ``SimNet._tensors()`` (``use_pos``: with the positional table, which only the parameters have)."""
+    it = iter(tensors)
+    S = cls()
+    S.embed_w, S.embed_b = next(it).data_ptr(), next(it).data_ptr()
+    if use_pos:
+        S.pos_embedding = next(it).data_ptr()
+    layers = (_lib.LayerParams * max(num_layers, 1))()
+    for l in range(num_layers):
+        for name in _lib._LAYER_FIELDS:
+            setattr(layers[l], name, next(it).data_ptr())
+    S.layers = layers
+    S.final_w, S.final_b = next(it).data_ptr(), next(it).data_ptr()
+    return S
 
 
 def _grad_destinations(module, device):
@@ -192,16 +231,7 @@ def _grad_destinations(module, device):
             offs.append(offs[-1] + (n_ + 63) // 64 * 64)          # 256-byte aligned views
         flat = torch.empty((offs[-1],), dtype=torch.float32, device=device)
         grads = [flat[o: o + n_].view(sh) for o, n_, sh in zip(offs, sizes, shapes)]
-    it = iter(grads)
-    G = _lib.ModelGrads()
-    G.embed_w, G.embed_b = next(it).data_ptr(), next(it).data_ptr()
-    layers = (_lib.LayerGrads * max(module.num_layers, 1))()
-    for l in range(module.num_layers):
-        for name in ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln1_g", "ln1_b",
-                     "w1", "b1", "w2", "b2", "ln2_g", "ln2_b"):
-            setattr(layers[l], name, next(it).data_ptr())
-    G.layers = layers
-    G.final_w, G.final_b = next(it).data_ptr(), next(it).data_ptr()
+    G = _model_struct(_lib.ModelGrads, grads, module.num_layers)
 
     def finish(gs):
         if module._plan:
@@ -210,76 +240,16 @@ def _grad_destinations(module, device):
     return grads, G, finish
 
 
-class _TrainForwardPacked(torch.autograd.Function):
-    """``SimNet.forward_packed_train`` under autograd: ``vs_train_forward_packed`` / ``vs_train_backward_packed`` on the frames
-    of several videos concatenated - no sentinel rows, no mask, nothing computed for padding.  Same structure as
-    ``_TrainForward``: parameters as inputs, the activation record one uint8 tensor saved for the backward."""
-
-    @staticmethod
-    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, module, x, lengths, p, p_embed, seed, tflags, *params):
-        lib = _lib.load()
-        x = x.contiguous()
-        M, Bv = x.size(0), len(lengths)
-        host = (C.c_int32 * Bv)(*lengths)
-        packed = module._packed_weights(x.device)
-        scores = torch.empty((M, module.num_classes), dtype=torch.float32, device=x.device)
-        hidden = torch.empty((M, module._lib_d), dtype=torch.float32, device=x.device)
-        cfg = _lib.DropoutCfg(float(p_embed), float(p), int(seed), int(tflags), 0)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            if not getattr(packed, "train_prepared", False):
-                _lib.check(lib.vs_train_prepare(packed.handle, stream))
-                packed.train_prepared = True
-            dev_len = torch.tensor(lengths, dtype=torch.int32, device=x.device)
-            need = lib.vs_train_saved_bytes_packed(packed.handle, host, Bv)
-            if need == 0:       # invalid lengths: the forward says why
-                _lib.check(lib.vs_train_forward_packed(packed.handle, x.data_ptr(), host, dev_len.data_ptr(), Bv, C.byref(cfg),
-                                                       scores.data_ptr(), None, None, 0, None, 0, stream))
-            saved = torch.empty((need,), dtype=torch.uint8, device=x.device)
-            ws = torch.empty((lib.vs_train_workspace_bytes_packed(packed.handle, host, Bv),), dtype=torch.uint8, device=x.device)
-            _lib.check(lib.vs_train_forward_packed(packed.handle, x.data_ptr(), host, dev_len.data_ptr(), Bv, C.byref(cfg),
-                                                   scores.data_ptr(), hidden.data_ptr(), saved.data_ptr(), saved.numel(),
-                                                   ws.data_ptr(), ws.numel(), stream))
-            fmt = int(lib.vs_train_last_format())
-        ctx.save_for_backward(x, dev_len, saved)
-        ctx.module, ctx.cfg, ctx.packed, ctx.packed_key = module, (float(p_embed), float(p), int(seed), int(tflags), fmt), packed, module._packed_key
-        ctx.lengths = tuple(lengths)
-        module._note_train_arithmetic(int(tflags) & ~(_lib.VS_TRAIN_FLAG_BF16_ATTENTION | _lib.VS_TRAIN_FLAG_PACKED_LP_ATTENTION), fmt, M)
-        module._last_packed_attention_dtype = ("fp16" if (fmt & 32) else "bf16") if (fmt & 2) else "fp32"
-        ctx.set_materialize_grads(False)
-        return scores, (hidden[..., :module.d_model] if module._plan else hidden)
-
-    @staticmethod
-    @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, d_scores, d_hidden):
-        lib = _lib.load()
-        x, dev_len, saved = ctx.saved_tensors
-        module, packed = ctx.module, ctx.packed
-        if module._packed_key != ctx.packed_key or module._packed is not packed:
-            raise RuntimeError("SimNet parameters were modified between forward and backward")
-        Bv = len(ctx.lengths)
-        host = (C.c_int32 * Bv)(*ctx.lengths)
-        grads, G, finish = _grad_destinations(module, x.device)
-        dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        ds = None if d_scores is None else d_scores.contiguous().float()
-        dh = None if d_hidden is None else d_hidden.contiguous().float()
-        if dh is not None and module._plan:
-            dh = module._pad(dh, ("res",)).contiguous()
-        cfg = _lib.DropoutCfg(*ctx.cfg)
-        with torch.cuda.device(x.device):
-            ws = torch.empty((lib.vs_train_workspace_bytes_packed(packed.handle, host, Bv),), dtype=torch.uint8, device=x.device)
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            _lib.check(lib.vs_train_backward_packed(packed.handle, x.data_ptr(), host, dev_len.data_ptr(), Bv, C.byref(cfg),
-                                                    _ptr(ds), _ptr(dh), saved.data_ptr(), saved.numel(), C.byref(G), _ptr(dx),
-                                                    ws.data_ptr(), ws.numel(), stream))
-        return (None, dx, None, None, None, None, None, *finish(grads))
-
-
 # --------------------------------------------------------------------------------------------
 # shapes outside the kernels' envelope: the model EMBEDDED in the next supported shape (include/vs_scorer.h,
 # vs_weights_set_norm_width)
 # --------------------------------------------------------------------------------------------
+
+
+# the head dims each low-precision attention arithmetic has kernels for (the library's, not the model's, when it is embedded):
+# 'bf16' / 'fp16x3' of scoring (set_compute_dtype), 'bf16' / 'fp16' of packed training (set_train_dtype(..., packed_attention=True));
+# the exact fp32 attention takes every head dim of embedding_plan
+_ATTENTION_HEAD_DIMS = {"bf16": (32, 64, 128), "fp16x3": (32, 64), "fp16": (32, 64, 128)}
 
 
 def embedding_plan(d_model: int, num_heads: int) -> Optional[Tuple[int, int]]:
@@ -501,28 +471,17 @@ class SimNet(nn.Module):
             ts.append(t if (t.dtype == torch.float32 and t.is_contiguous()) else t.detach().to(torch.float32).contiguous())
         if self._plan:        # embedded model: the library sees zero-padded parameters of its own shape
             ts = [self._pad(t.detach(), ax).contiguous() for t, ax in zip(ts, self._tensor_axes())]
-        it = iter(ts)
         reuse = self._packed is not None and self._packed_shape == shape_key
-        P = _lib.ModelParams()
-        P.embed_w, P.embed_b = next(it).data_ptr(), next(it).data_ptr()
-        P.pos_embedding = next(it).data_ptr() if self.use_pos else None
+        P = _model_struct(_lib.ModelParams, ts, self.num_layers, self.use_pos)
         if self.use_pos:
             pe = self.embedding_layer.positional_encoding.pos_embedding
             pe_key = (pe.data_ptr(), pe._version)
             if reuse and pe_key == self._packed_pe_key:
                 P.pos_embedding = None          # the table (a buffer) is unchanged: vs_weights_update keeps the packed copy
             self._packed_pe_key = pe_key
-        layers = (_lib.LayerParams * max(self.num_layers, 1))()
-        for l in range(self.num_layers):
-            for name in ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln1_g", "ln1_b",
-                         "w1", "b1", "w2", "b2", "ln2_g", "ln2_b"):
-                setattr(layers[l], name, next(it).data_ptr())
-        P.layers = layers
-        P.final_w, P.final_b = next(it).data_ptr(), next(it).data_ptr()
         desc = _lib.ModelDesc(self._lib_d, self.num_heads, self.num_layers, self.in_features,
                               self.pe_len if self.use_pos else 0, self.num_classes)
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device).cuda_stream
+        with on_stream(device) as stream:
             if reuse:
                 # parameters were written (optimizer step, load_state_dict): refill the existing device storage
                 _lib.check(lib.vs_weights_update(self._packed.handle, C.byref(P), stream))
@@ -542,29 +501,40 @@ class SimNet(nn.Module):
             return False
         return self.training or x.requires_grad or any(p.requires_grad for p in self.parameters())
 
-    def _forward_train(self, x: Tensor, mask: Optional[Tensor]):
-        """forward under autograd: dropout (train mode only, like nn.Dropout) with a fresh seed drawn from torch's
-        default CPU generator (so ``set_seed`` / ``torch.manual_seed``, reference utils.py:9-12, reproduces a run)."""
+    def _forward_train(self, x: Tensor, mask: Optional[Tensor], lengths=None):
+        """forward under autograd (``lengths``: of a packed batch): dropout (train mode only, like nn.Dropout) with a fresh seed
+        drawn from torch's default CPU generator (so ``set_seed`` / ``torch.manual_seed``, reference utils.py:9-12, reproduces
+        a run)."""
         p = self.drop_rate if self.training else 0.0
         p_embed = self.sparsity if (self.training and self.use_pos) else 0.0
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if (p > 0.0 or p_embed > 0.0) else 0
         params = [t for t in self._tensors() if isinstance(t, nn.Parameter)]
         x32 = x if x.dtype == torch.float32 else x.float()
-        return _TrainForward.apply(self, x32, mask, p, p_embed, seed, self._train_flags(), *params)
+        return _TrainForward.apply(self, x32, mask, lengths, p, p_embed, seed, self._train_flags(packed=lengths is not None), *params)
+
+    def _check_table(self, longest: int) -> None:
+        if self.use_pos and longest > self.pe_len:
+            raise RuntimeError("T=%d exceeds the positional table (%d rows)" % (longest, self.pe_len))
+
+    def _check_hip(self, x: Tensor) -> None:
+        if not x.is_cuda:
+            raise RuntimeError("SimNet runs on the MI355X HIP kernels only: move the module and its "
+                               "input to a HIP device (there is no CPU path for the scorer)")
+
+    def _check_padded(self, x: Tensor) -> None:
+        """what ``forward`` and the attention maps refuse, in this order: the shape, a video longer than the table, a CPU tensor"""
+        if x.dim() != 3 or x.size(2) != self.in_features:
+            raise RuntimeError("expected x of shape [B, T, %d], got %s" % (self.in_features, tuple(x.shape)))
+        self._check_table(x.size(1))
+        self._check_hip(x)
 
     def forward(self, x: Tensor, mask=None, vis_attention=None, model_score: bool = False):
         """Same contract as reference ``SimNet.forward`` (simnet.py:32-45): returns
         ``(final_out [B,T,num_classes] raw logits, hidden [B,T,d])``; a non-Tensor ``mask`` is ignored
         (:38); ``vis_attention`` is ignored (:41); ``model_score`` selects ``intermediate`` which is the
         same tensor because ``module_score`` is empty."""
-        if x.dim() != 3 or x.size(2) != self.in_features:
-            raise RuntimeError("expected x of shape [B, T, %d], got %s" % (self.in_features, tuple(x.shape)))
+        self._check_padded(x)
         mask = mask if isinstance(mask, Tensor) else None
-        if self.use_pos and x.size(1) > self.pe_len:
-            raise RuntimeError("T=%d exceeds the positional table (%d rows)" % (x.size(1), self.pe_len))
-        if not x.is_cuda:
-            raise RuntimeError("SimNet runs on the MI355X HIP kernels only: move the module and its "
-                               "input to a HIP device (there is no CPU path for the scorer)")
         if self.use_cls:
             return self._forward_cls(x, mask)
         if self._needs_autograd(x):
@@ -593,19 +563,15 @@ class SimNet(nn.Module):
         cls = self.embedding_layer.cls_token.detach()
         if cls.dtype != torch.float32 or not cls.is_contiguous():
             cls = cls.to(torch.float32).contiguous()
-        m = None
-        if mask is not None:
-            m = mask.contiguous()
-            m = m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
+        m = mask_u8(mask)
         flags = (_lib.VS_FLAG_SIGMOID if self.fused_sigmoid else 0) | self._attention_flag()
         scores = torch.empty((B, T + 1, self.num_classes), dtype=torch.float32, device=dev)
         hidden = torch.empty((B, T + 1, self._lib_d), dtype=torch.float32, device=dev)
         if self._plan:
             cls = self._pad(cls, ("res",)).contiguous()
-        with torch.cuda.device(dev):
-            ws = torch.empty((max(lib.vs_scorer_workspace_bytes_cls(packed.handle, B, T), 256),), dtype=torch.uint8, device=dev)
-            st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.vs_scorer_forward_cls(packed.handle, x32.data_ptr(), _ptr(m), cls.data_ptr(), B, T, flags,
+        with on_stream(dev) as st:
+            ws = scratch(lib.vs_scorer_workspace_bytes_cls(packed.handle, B, T), dev, floor=256)
+            _lib.check(lib.vs_scorer_forward_cls(packed.handle, x32.data_ptr(), ptr(m), cls.data_ptr(), B, T, flags,
                                                  scores.data_ptr(), hidden.data_ptr(), ws.data_ptr(), ws.numel(), st))
         return scores, (hidden[..., :self.d_model] if self._plan else hidden)
 
@@ -632,14 +598,8 @@ class SimNet(nn.Module):
     def _inspect(self, x: Tensor, mask, layers, want_maps: bool):
         """One ``vs_inspect_forward`` call: the exact fp32 eval forward plus the attention-map kernels on the q / k planes of
         the selected layers.  Returns (logits, maps or None, received or None, entropy or None), stacked over the layers."""
-        if x.dim() != 3 or x.size(2) != self.in_features:
-            raise RuntimeError("expected x of shape [B, T, %d], got %s" % (self.in_features, tuple(x.shape)))
+        self._check_padded(x)
         mask = mask if isinstance(mask, Tensor) else None
-        if self.use_pos and x.size(1) > self.pe_len:
-            raise RuntimeError("T=%d exceeds the positional table (%d rows)" % (x.size(1), self.pe_len))
-        if not x.is_cuda:
-            raise RuntimeError("SimNet runs on the MI355X HIP kernels only: move the module and its "
-                               "input to a HIP device (there is no CPU path for the scorer)")
         L = self.num_layers
         want = list(range(L)) if layers is None else [int(l) for l in layers]
         sel = [l + L if l < 0 else l for l in want]
@@ -657,21 +617,16 @@ class SimNet(nn.Module):
             cls = self.embedding_layer.cls_token.detach().to(torch.float32).contiguous()
             if self._plan:
                 cls = self._pad(cls, ("res",)).contiguous()
-        m = None
-        if mask is not None:
-            m = mask.contiguous()
-            m = m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
+        m = mask_u8(mask)
         scores = torch.empty((B, N, self.num_classes), dtype=torch.float32, device=dev)
         maps = torch.empty((len(asc), B, H, N, N), dtype=torch.float32, device=dev) if want_maps else None
         received = None if want_maps else torch.empty((len(asc), B, H, N), dtype=torch.float32, device=dev)
         entropy = None if want_maps else torch.empty((len(asc), B, H, N), dtype=torch.float32, device=dev)
         host_layers = (C.c_int32 * len(asc))(*asc)
-        with torch.cuda.device(dev):
-            need = lib.vs_inspect_workspace_bytes(packed.handle, B, T, 1 if self.use_cls else 0)
-            ws = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
-            st = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.vs_inspect_forward(packed.handle, x32.data_ptr(), _ptr(m), _ptr(cls), B, T, host_layers, len(asc),
-                                              scores.data_ptr(), None, _ptr(maps), _ptr(received), _ptr(entropy),
+        with on_stream(dev) as st:
+            ws = scratch(lib.vs_inspect_workspace_bytes(packed.handle, B, T, 1 if self.use_cls else 0), dev, floor=256)
+            _lib.check(lib.vs_inspect_forward(packed.handle, x32.data_ptr(), ptr(m), ptr(cls), B, T, host_layers, len(asc),
+                                              scores.data_ptr(), None, ptr(maps), ptr(received), ptr(entropy),
                                               ws.data_ptr(), ws.numel(), st))
         if sel != asc:      # the caller's order
             order = torch.tensor([asc.index(l) for l in sel], device=dev)
@@ -704,6 +659,11 @@ class SimNet(nn.Module):
         scores, _, received, entropy = self._inspect(x, mask, layers, False)
         return scores, received, entropy
 
+    def _check_head_dim(self, arithmetic: str) -> None:
+        ok = _ATTENTION_HEAD_DIMS[arithmetic]
+        if self._lib_dh not in ok:
+            raise ValueError("%s attention needs head_dim in %s, got %d" % (arithmetic, ok, self._lib_dh))
+
     @property
     def attention_dtype(self) -> str:
         return self._attention_dtype
@@ -712,9 +672,8 @@ class SimNet(nn.Module):
     def attention_dtype(self, value: str) -> None:
         if value not in ("fp32", "bf16", "fp16x3"):
             raise ValueError("attention_dtype must be 'fp32', 'bf16' or 'fp16x3', got %r" % (value,))
-        ok = (32, 64, 128) if value == "bf16" else (32, 64)
-        if value != "fp32" and self._lib_dh not in ok:
-            raise ValueError("%s attention needs head_dim in %s, got %d" % (value, ok, self._lib_dh))
+        if value != "fp32":
+            self._check_head_dim(value)
         self._attention_dtype = value
 
     @property
@@ -735,7 +694,7 @@ class SimNet(nn.Module):
         # models with head dim 128 (M-B) take what exists for them: fp16x3 -> every Linear emulated, attention exact;
         # bf16 -> every product on the bf16 pipe (head dim 128 has a bf16 attention; d_model > 256 runs the plain bf16
         # GEMMs + the row LayerNorm pass instead of the fused layer kernels)
-        head_ok = self._lib_dh in (32, 64)
+        head_ok = self._lib_dh in _ATTENTION_HEAD_DIMS["fp16x3"]
         if value not in ("fp32", "fp16x3", "bf16"):
             raise ValueError("compute dtype must be 'fp32', 'fp16x3' or 'bf16', got %r" % (value,))
         if value == "bf16":
@@ -748,8 +707,9 @@ class SimNet(nn.Module):
     def _note_train_arithmetic(self, tflags: int, fmt: int, frames: int) -> None:
         """Records which arithmetic the last training forward actually ran (``last_train_dtype``) and says so - once - when a
         low-precision request was not honoured (the library keeps batches below VS_TRAIN_LP_MIN_ROWS frames on the exact kernels)."""
-        self.last_train_dtype = ("fp16" if (fmt & 32) else "bf16") if (fmt & 3) else "fp32"
-        if tflags and not (fmt & 3) and not getattr(self, "_warned_train_dtype", False):
+        form = _lib.train_form(fmt)
+        self.last_train_dtype = form.dtype(form.lp or form.lpa)
+        if tflags and not (form.lp or form.lpa) and not getattr(self, "_warned_train_dtype", False):
             import warnings
             self._warned_train_dtype = True
             warnings.warn("set_train_dtype(%r) was requested but this batch (%d frames) ran on the exact fp32 kernels: the "
@@ -778,8 +738,8 @@ class SimNet(nn.Module):
         if value not in ("fp32", "bf16", "fp16"):
             raise ValueError("train dtype must be 'fp32', 'bf16' or 'fp16', got %r" % (value,))
         packed_attention = bool(packed_attention) and value != "fp32"
-        if packed_attention and self._lib_dh not in (32, 64, 128):
-            raise ValueError("%s attention needs head_dim in %s, got %d" % (value, (32, 64, 128), self._lib_dh))
+        if packed_attention:
+            self._check_head_dim(value)
         self._train_dtype = value
         self._packed_attention = packed_attention
         return self
@@ -811,22 +771,14 @@ class SimNet(nn.Module):
         work; no class token."""
         if self.use_cls:
             raise NotImplementedError("packed batches are not available with use_cls=True")
-        if not x.is_cuda:
-            raise RuntimeError("SimNet runs on the MI355X HIP kernels only: move the module and its "
-                               "input to a HIP device (there is no CPU path for the scorer)")
+        self._check_hip(x)
         lengths = [int(t) for t in lengths]
         if x.dim() != 2 or x.size(1) != self.in_features or x.size(0) != sum(lengths):
             raise RuntimeError("expected x of shape [sum(lengths)=%d, %d], got %s" % (sum(lengths), self.in_features, tuple(x.shape)))
         if not lengths or min(lengths) <= 0:
             raise RuntimeError("lengths must be positive, got %r" % (lengths,))
-        if self.use_pos and max(lengths) > self.pe_len:
-            raise RuntimeError("T=%d exceeds the positional table (%d rows)" % (max(lengths), self.pe_len))
-        p = self.drop_rate if self.training else 0.0
-        p_embed = self.sparsity if (self.training and self.use_pos) else 0.0
-        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if (p > 0.0 or p_embed > 0.0) else 0
-        params = [t for t in self._tensors() if isinstance(t, nn.Parameter)]
-        x32 = x if x.dtype == torch.float32 else x.float()
-        return _TrainForwardPacked.apply(self, x32, lengths, p, p_embed, seed, self._train_flags(packed=True), *params)
+        self._check_table(max(lengths))
+        return self._forward_train(x, None, lengths)
 
     @torch.no_grad()
     def forward_packed(self, x: Tensor, lengths, want_hidden: bool = True):
@@ -838,8 +790,8 @@ class SimNet(nn.Module):
             raise RuntimeError("SimNet scoring runs on the MI355X HIP kernels only (no CPU path for the scorer)")
         if self.use_cls:
             raise NotImplementedError("packed batches are not available with use_cls=True")
-        if self.use_pos and max(int(t) for t in lengths) > self.pe_len:
-            raise RuntimeError("T=%d exceeds the positional table (%d rows)" % (max(lengths), self.pe_len))
+        if self.use_pos:
+            self._check_table(max(int(t) for t in lengths))
         packed = self._packed_weights(x.device)
         x32 = x if x.dtype == torch.float32 else x.float()
         flags = (_lib.VS_FLAG_SIGMOID if self.fused_sigmoid else 0) | self._attention_flag()

@@ -15,6 +15,8 @@ import json
 import numpy as np
 
 from . import _lib
+from ._call import on_stream, scratch
+from .corpus import packed_scorer, score_corpus
 from . import evaluation
 
 
@@ -84,12 +86,11 @@ def summarize_scores(scores, change_points, n_frames, picks, proportion=0.15, n_
     out = torch.empty(total * 5, dtype=torch.uint8, device=dev)      # int32 frames first (aligned), then the int8 summary
     frames_all = out[: total * 4].view(torch.int32)
     summary_all = out[total * 4:].view(torch.int8)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = scratch(need, dev)
     n_sel = np.zeros(n, dtype=np.int32)
     sel = np.zeros(int(nsh.sum()), dtype=np.int8)
     means = np.zeros(int(nsh.sum()), dtype=np.float64)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    with on_stream(dev) as stream:
         rc = lib.vs_summarize(n, _p(nsc), _p(npos), _p(nf), _p(nsh), _p(pos_all), _p(cps_all), float(proportion),
                               C.c_void_p(scores.data_ptr()), C.c_void_p(summary_all.data_ptr()), C.c_void_p(frames_all.data_ptr()),
                               _p(n_sel), _p(sel), _p(means), C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream))
@@ -115,10 +116,7 @@ def _model_device(model):
 
 def _score_on_device(model, feats, dev, max_frames):
     """The videos' sigmoid scores concatenated in order, on the device (one batched pass, packed when the model allows)."""
-    from .corpus import score_corpus
-    can_pack = hasattr(model, "score_packed") and getattr(model, "_lib_dh", model.d_model // model.num_heads) in (32, 64, 128)
-    packed_fn = (lambda x, lens: model.score_packed(x, lens)) if can_pack else None
-    _, flat = score_corpus(lambda x, m: model.score(x, m), feats, device=dev, max_frames=max_frames, packed_fn=packed_fn,
+    _, flat = score_corpus(lambda x, m: model.score(x, m), feats, device=dev, max_frames=max_frames, packed_fn=packed_scorer(model),
                            keep_on_device=True)
     return flat
 
