@@ -853,15 +853,14 @@ def _library_masks(vsa, B, T, d, H, L, seed, p, p_embed):
 DROPOUT_STEPS = [(4, 256, 2, 2, 90, 0.3, 0.0, True), (8, 256, 1, 1, 130, 0.2, 0.5, False), (4, 512, 1, 2, 70, 0.3, 0.0, True)]
 
 
-@pytest.mark.parametrize("H,d,L,B,T,p,p_embed,masked", DROPOUT_STEPS)
-def test_training_step_with_dropout_matches_explicit_mask_model(vsa, H, d, L, B, T, p, p_embed, masked):
+def _dropout_step(vsa, H, d, L, B, T, p, p_embed, x, mask):
+    """One training step with dropout on features x and key mask `mask` (or None), against the float64 explicit-mask model fed
+    with the library's own keep masks."""
     synth = vsa.synth
     sd = synth.make_state_dict(d, L, 21)
     m = vsa.SimNet(num_heads=H, d_model=d, num_layers=L, sparsity=p_embed, dropout=p)
     m.load_state_dict(sd, strict=True)
     m = m.to(_dev()).train()
-    x = synth.make_features(B, T, 22, "randn", [T, T - 23][:B] if masked else None)
-    mask = synth.padding_mask(x) if masked else None
     target = torch.rand(B, T, generator=torch.Generator().manual_seed(1))
     torch.manual_seed(77)
     seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())        # what _forward_train will draw
@@ -894,6 +893,32 @@ def test_training_step_with_dropout_matches_explicit_mask_model(vsa, H, d, L, B,
     with torch.no_grad():
         e, _ = m.eval()(x.to(_dev()), md)
     assert (e - pred.detach())[valid.to(_dev())].abs().max().item() > 1e-3
+
+
+@pytest.mark.parametrize("H,d,L,B,T,p,p_embed,masked", DROPOUT_STEPS)
+def test_training_step_with_dropout_matches_explicit_mask_model(vsa, H, d, L, B, T, p, p_embed, masked):
+    x = vsa.synth.make_features(B, T, 22, "randn", [T, T - 23][:B] if masked else None)
+    mask = vsa.synth.padding_mask(x) if masked else None
+    _dropout_step(vsa, H, d, L, B, T, p, p_embed, x, mask)
+
+
+@pytest.mark.parametrize("family", ["skinny", "tiled"])
+def test_training_step_with_dropout_and_masked_leading_frames(vsa, family):
+    """The only route that takes the exact training attention through the bit-packed keep words (DROP == 2) with a dead first
+    key tile: video 0 starts at frame 33 (its first 32-key tile is wholly dead), video 1 at frame 64 and ends at frame 80.  Both
+    GEMM families, the checks of test_training_step_with_dropout_matches_explicit_mask_model."""
+    H, d, L, B, T, p = 4, 256, 2, 2, 90, 0.3
+    x = vsa.synth.make_features(B, T, 22, "randn")
+    mask = torch.zeros(B, T, dtype=torch.bool)
+    mask[0, :33] = True
+    mask[1, :64] = True
+    mask[1, 80:] = True
+    try:
+        if family == "tiled":
+            vsa._lib.set_option("VS_SKINNY_ROWS", 0)
+        _dropout_step(vsa, H, d, L, B, T, p, 0.0, x, mask)
+    finally:
+        vsa._lib.set_option("VS_SKINNY_ROWS", -1)
 
 
 @pytest.mark.parametrize("H,d,L,B,T,p,p_embed,masked", DROPOUT_STEPS)
