@@ -199,7 +199,8 @@ const char *vs_stage_name(int32_t stage);
  * environment variables of the same name, read ONCE when the library is first used - no forward calls getenv.
  * value < 0 restores the environment / built-in default.  Names: VS_SKINNY_ROWS, VS_LP_MIN_ROWS, VS_LP_MIN_ROWS_FUSED, VS_TRAIN_LP_MIN_ROWS, VS_ATTN_W64, VS_ATTN_W64_CHECKED,
  * VS_LP_STORE32, VS_LP_MLP_UNFUSED, VS_LP_TAIL_UNFUSED, VS_LP_QKV_UNFUSED, VS_LP_EMBED_UNFUSED, VS_LP_TILE256,
- * VS_EXACT_UNFUSED (exact fp32, d_model 256: the four stand-alone Linear kernels of a layer instead of the two fused ones; same bits)
+ * VS_EXACT_UNFUSED (exact fp32, d_model 256: the four stand-alone Linear kernels of a layer instead of the two fused ones; same bits),
+ * VS_LAYER_TAIL_MIN_ROWS (rows from which those two fused kernels run as one launch per layer; 0 forces it; same bits)
  * (+ VS_MLP_ABL, VS_ATTN_W64_ABL, which only the diagnostic build of the library acts on).  Process-wide; not meant to be flipped while forwards are in flight. */
 int vs_set_option(const char *name, int32_t value);
 

@@ -25,6 +25,8 @@ struct VskOptions {
     int lp_tile256;       // VS_LP_TILE256     the fused bf16 layer kernels always use 256-row tiles / 8-wave blocks (A/B)
     int lp_embed_unfused; // VS_LP_EMBED_UNFUSED bf16 mode runs the embedding as the generic GEMM + the first QKV kernel (A/B)
     int exact_unfused;    // VS_EXACT_UNFUSED  exact fp32, d_model 256: out-projection + norm1, fc1, fc2 + norm2 and QKV as four kernels (A/B, bit-identity tests)
+    int layer_tail_min_rows; // VS_LAYER_TAIL_MIN_ROWS (default 1024): rows from which the exact fused pair runs as ONE kernel per layer
+                          // (vsk_layer_tail; 0 forces it, a value above M keeps the pair; profiles/layer_tail_rows_sweep.txt)
     int mlp_abl;          // VS_MLP_ABL       (diagnostic builds only) timing ablation of the bf16 layer-tail kernel's MLP part (vs_mlp_fused.hip)
     int attn_w64_checked; // VS_ATTN_W64_CHECKED the one-wave-per-SIMD attention skips its optimistic pass (every tile checked; A/B and test pin)
     int attn_w64_abl;     // VS_ATTN_W64_ABL  (diagnostic builds only) timing ablation of the one-wave-per-SIMD attention

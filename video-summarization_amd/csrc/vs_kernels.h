@@ -56,6 +56,12 @@ int vsk_outproj_ln_fc1(const float *att, const float *Wo, const float *bo, const
                        float *h1, const float *W1, const float *b1, float *hidden, int M, int d, hipStream_t st);
 int vsk_fc2_ln_qkv(const float *hidden, const float *W2, const float *b2, const float *res, const float *gamma, const float *beta,
                    float *out, const float *Wqkv, const float *bqkv, float *qkv, int B, int T, int d, int H, hipStream_t st);
+// The two above as ONE launch, same bits: h1 is never stored (it stays in the accumulators), the hidden rows are read back by the
+// block that wrote them.  Wqkv != NULL: ends with the next layer's q / k / v; else with the score head (score_w != NULL).
+int vsk_layer_tail(const float *att, const float *Wo, const float *bo, const float *res, const float *g1, const float *be1,
+                   const float *W1, const float *b1, float *hidden, const float *W2, const float *b2, const float *g2, const float *be2,
+                   float *out, const float *Wqkv, const float *bqkv, float *qkv, const float *score_w, const float *score_b,
+                   int num_classes, int sigmoid, float *scores, int B, int T, int d, int H, hipStream_t st);
 // out = LayerNorm(a + res) * gamma + beta (+ score head): the row pass behind a plain GEMM for d_model > 256
 int vsk_rows_res_ln(const float *a, const float *res, const float *gamma, const float *beta, float *out, int M, int d,
                     const float *score_w, const float *score_b, int num_classes, int sigmoid, float *scores,

@@ -686,10 +686,18 @@ __global__ __launch_bounds__(256) void gemm_res_ln(
 //   TAIL 1: C2 = relu(rows * W2^T + b2), [M, 1024] row-major              (the MLP's fc1 behind out-projection + norm1)
 //   TAIL 2: q / k / v = rows * W2^T + b2, head-major planes [B, H, T, dh]   (the next layer's QKV behind fc2 + norm2)
 // Per output the accumulator starts at the bias x ones MFMA and takes its k in ascending order, as in gemm_nt_128: same bits.
+//   TAIL 3, 4: the WHOLE layer tail as two phases of one tile (round 9).  Phase 0 is TAIL 1 without the store of its rows: after
+//   the fc1 chunks acc[8] still holds h1 (tail_step only reads it), which is what phase 1 - fc2 over the hidden rows this block
+//   has just written, K = 1024 - wants as its starting accumulators.  Phase 1 ends as TAIL 2 (3) or with the score head (4).
 struct LnTail {
     const float *W2, *b2;       // [N2, 256], [N2]
     float *C2;
     int T, H, dhs;              // TAIL 2: frames per video, heads, log2 of the head dim (256 / H: a power of two)
+};
+struct LnPhase2 {               // TAIL 3, 4: phase 1's product (A = phase 0's C2, K = 4 * 256), norm, output rows and tail
+    const float *W, *bias, *gamma, *beta;
+    float *out;
+    LnTail tl;
 };
 
 template <int NT, int PREC, int A16, int DIAG, int TAIL>
@@ -698,17 +706,22 @@ __device__ __forceinline__ void ln_rows_tiles(
     const float *__restrict__ res, const float *__restrict__ gamma, const float *__restrict__ beta,
     float *__restrict__ out, int M, int K,
     const float *__restrict__ score_w, const float *__restrict__ score_b, int num_classes,
-    int sigmoid, float *__restrict__ scores, unsigned long long *__restrict__ diag, const LnTail tl) {
+    int sigmoid, float *__restrict__ scores, unsigned long long *__restrict__ diag, const LnTail tl, const LnPhase2 p2) {
     static_assert(TAIL == 0 || (NT == 8 && PREC == 0 && DIAG == 0), "the register-fed tail exists for exact fp32 at d_model 256");
     constexpr int BM = 128, N = 32 * NT, BK = 16, LD = BK + 4;
     constexpr int WL = (N * BK / 4 + 255) / 256;       // float4 of W per thread per k-tile (N=256: 4)
-    constexpr int TN2 = TAIL == 2 ? 3 * N : 4 * N;      // TAIL: output columns of the second product
-    __shared__ __attribute__((aligned(16))) float smem[2 * (BM + N) * LD + 4 * N + (TAIL != 0 ? TN2 : 0)];
+    constexpr bool TWO = TAIL >= 3;                     // two phases per tile
+    constexpr int NPH = TWO ? 2 : 1;
+    constexpr int TN2 = TAIL == 2 ? 3 * N : 4 * N;      // TAIL: output columns of the (first phase's) second product
+    // the small vectors of BOTH phases stay resident (75.8 KB per block with the staging area: two blocks per CU)
+    constexpr int SMALL2 = TAIL == 3 ? 3 * N + 3 * N : TAIL == 4 ? 3 * N : 0;
+    __shared__ __attribute__((aligned(16))) float smem[2 * (BM + N) * LD + 4 * N + (TAIL != 0 ? TN2 : 0) + SMALL2];
     float *gam_s = smem + 2 * (BM + N) * LD, *bet_s = gam_s + N, *sw_s = bet_s + N, *bias_s = sw_s + N;
     float *bias2_s = bias_s + N;                        // TAIL: the second product's bias
+    float *small2_s = bias2_s + TN2;                    // TWO: phase 1's gamma, beta, bias (and its tail's bias)
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
+    int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;       // (not const: a two-phase tile derives them again per phase)
+    int r = lane & 31, h = lane >> 5;
     const int ntiles = (M + BM - 1) / BM;
     const int nk = K / BK;
 
@@ -716,9 +729,14 @@ __device__ __forceinline__ void ln_rows_tiles(
     for (int i = tid; i < N; i += 256) { gam_s[i] = gamma[i]; bet_s[i] = beta[i]; bias_s[i] = bias[i] * SC; }
     if constexpr (TAIL != 0)
         for (int i = tid; i < TN2; i += 256) bias2_s[i] = tl.b2[i];
+    if constexpr (TWO) {
+        for (int i = tid; i < N; i += 256) { small2_s[i] = p2.gamma[i]; small2_s[N + i] = p2.beta[i]; small2_s[2 * N + i] = p2.bias[i]; }
+        if constexpr (TAIL == 3)
+            for (int i = tid; i < 3 * N; i += 256) small2_s[3 * N + i] = p2.tl.b2[i];
+    }
 
     // staging map: A 128 rows x 4 float4 (2 per thread), W N rows x 4 float4 (WL per thread)
-    const int lrow = tid >> 2, lc4 = (tid & 3) * 4;
+    int lrow = tid >> 2, lc4 = (tid & 3) * 4;
     f32x4 pa[2], pw[WL];
     u32x2 pa16[2];                                     // A16: 4 bf16 per thread and k-tile
     const float *aptr[2], *wptr[WL];
@@ -733,8 +751,8 @@ __device__ __forceinline__ void ln_rows_tiles(
     // map covers W exactly (N % 64 == 0: WL * 64 rows), so its LDS writes need no guard and the k-loop no branch.
     static_assert(PREC != 0 || N % 64 == 0, "the exact-fp32 staging map covers W without a guard");
     __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A), 0, 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(W), 0, N * K * 4, 0x00020000);
-    int aoff[2], woff[WL];
+    __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(W), 0, N * K * 4, 0x00020000);
+    int aoff[2], woff[WL];          // (TWO: wrs and woff are set again at the head of each phase)
 #pragma unroll
     for (int i = 0; i < WL; ++i) woff[i] = ((lrow + 64 * i) * K + lc4) * 4;
     auto gload = [&](int i, int kb) __attribute__((always_inline)) {       // piece i of the k-tile at byte offset kb: A 0..1, then W
@@ -788,11 +806,12 @@ __device__ __forceinline__ void ln_rows_tiles(
     // ---- TAIL: the weight tiles of the register-fed product.  Step (c, kt) consumes W2 rows 128c .. 128c + 127, k 32kt .. 32kt + 31
     // from LDS buffer kt & 1: [128][36] floats (conflict-free b128 fragment reads, as gemm_nt_128), 4 float4 per thread.  The two
     // buffers lie behind the four transposition corners of the epilogues, inside the k-loop's staging area. ----
-    constexpr int TCH = 128, TNC = TN2 / TCH, TWB = 4 * 32 * 36, TBUF = TCH * 36;
+    constexpr int TCH = 128, TWB = 4 * 32 * 36, TBUF = TCH * 36;
     static_assert(TAIL == 0 || TWB + 2 * TBUF <= 2 * (BM + N) * LD, "corners and weight tiles fit the staging area");
-    const int r2 = tid >> 3, c2 = (tid & 7) * 4;           // staging map of a weight tile: rows r2 + 32i
-    const __amdgpu_buffer_rsrc_t wrs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(tl.W2), 0, TN2 * N * 4, 0x00020000);
-    const int woff2 = (r2 * N + c2) * 4;
+    int r2 = tid >> 3, c2 = (tid & 7) * 4;           // staging map of a weight tile: rows r2 + 32i
+    __amdgpu_buffer_rsrc_t wrs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(tl.W2), 0, TN2 * N * 4, 0x00020000);
+    const float *tbias_s = bias2_s;                        // (TAIL 3: wrs2 and tbias_s are set again at the head of each phase)
+    int woff2 = (r2 * N + c2) * 4;
     f32x4 pw2[4];
     f32x16 U[4];
     auto tail_soff = [&](int c, int kt) __attribute__((always_inline)) { return (TCH * c * N + 32 * kt) * 4; };
@@ -807,7 +826,7 @@ __device__ __forceinline__ void ln_rows_tiles(
         const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
-            const float bv = bias2_s[TCH * c + 32 * jj + r];
+            const float bv = tbias_s[TCH * c + 32 * jj + r];
             U[jj] = MFMA32(h == 0 ? bv : 0.f, 1.0f, zero);
         }
     };
@@ -845,6 +864,30 @@ __device__ __forceinline__ void ln_rows_tiles(
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         if constexpr (DIAG != 0) tq = stamp();
         const int m0 = tile * BM;
+      static_for<NPH>([&](auto phc) __attribute__((always_inline)) {
+        constexpr int PH = decltype(phc)::value;
+        constexpr bool P1 = TWO && PH == 1;                 // the second phase of a two-phase tile
+        constexpr int PT = !TWO ? TAIL : PH == 0 ? 1 : TAIL == 3 ? 2 : 0;      // this phase's register-fed tail
+        constexpr int PTN2 = PT == 2 ? 3 * N : 4 * N, TNC = PTN2 / TCH;
+        const LnTail ptl = P1 ? p2.tl : tl;
+        const float *pA = P1 ? tl.C2 : A;
+        const int pK = P1 ? 4 * N : K, pnk = P1 ? 4 * N / BK : nk;
+        const float *pgam_s = P1 ? small2_s : gam_s, *pbet_s = P1 ? small2_s + N : bet_s, *pbias_s = P1 ? small2_s + 2 * N : bias_s;
+        float *pout = P1 ? p2.out : out;
+        if constexpr (TWO) {
+            // The thread's maps are derived again from an opaque copy of its index: otherwise the compiler keeps the loop-invariant
+            // offsets of BOTH phases alive across the tile loop, beside 192 accumulators, and spills them.
+            asm volatile("" : "+v"(tid));
+            lane = tid & 63; wave = tid >> 6; r = lane & 31; h = lane >> 5;
+            lrow = tid >> 2; lc4 = (tid & 3) * 4; r2 = tid >> 3; c2 = (tid & 7) * 4; woff2 = (r2 * N + c2) * 4;
+            wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(P1 ? p2.W : W), 0, N * pK * 4, 0x00020000);
+#pragma unroll
+            for (int i = 0; i < WL; ++i) woff[i] = ((lrow + 64 * i) * pK + lc4) * 4;
+            if constexpr (PT != 0) {
+                wrs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(ptl.W2), 0, PTN2 * N * 4, 0x00020000);
+                tbias_s = P1 ? small2_s + 3 * N : bias2_s;
+            }
+        }
         int row = m0 + 32 * wave + r;
         const bool row_ok = row < M;
         row = row_ok ? row : M - 1;
@@ -855,22 +898,41 @@ __device__ __forceinline__ void ln_rows_tiles(
                 aptr16[i] = (const unsigned short *)A + (size_t)ar * K + lc4;
                 pa16[i] = *(const u32x2 *)aptr16[i];
             } else if constexpr (PREC == 0) {
-                aoff[i] = ((ar - m0) * K + lc4) * 4;
+                aoff[i] = ((ar - m0) * pK + lc4) * 4;
             } else {
                 aptr[i] = A + (size_t)ar * K + lc4;
                 pa[i] = *(const f32x4 *)aptr[i];
             }
         }
         if constexpr (PREC == 0) {
-            ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(A + (size_t)m0 * K), 0, (M - m0 < BM ? M - m0 : BM) * K * 4, 0x00020000);
+            ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pA + (size_t)m0 * pK), 0, (M - m0 < BM ? M - m0 : BM) * pK * 4, 0x00020000);
+            if constexpr (P1) {
+                // The A staging map reads hidden rows that OTHER waves of this block stored in phase 0.  Every wave's stores are
+                // complete (gfx9 counts stores in vmcnt) and released before the barrier, and the loads are issued behind the
+                // acquire after it; never timing.  A block reads hidden rows only after it wrote them, and never reads a row of
+                // another tile: with more tiles than blocks each pass of this loop touches only its own tile's 128 rows (whole
+                // 4 KB rows, so no cache line is shared with a neighbour), and rows past M are clamped to row M - 1, which this
+                // tile wrote.  So no line of the hidden tensor can sit stale in this CU's vector cache from an earlier read.
+                // W2's first k-tile does not depend on any of that: it is in flight while the chunk stores drain.
 #pragma unroll
-            for (int i = 0; i < 2 + WL; ++i) gload(i, 0);
+                for (int i = 2; i < 2 + WL; ++i) gload(i, 0);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __syncthreads();            // also: every wave is done with the corners and the tail's weight tiles in LDS
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll
+                for (int i = 0; i < 2; ++i) gload(i, 0);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 2 + WL; ++i) gload(i, 0);
+            }
         } else {
 #pragma unroll
             for (int i = 0; i < WL; ++i) pw[i] = *(const f32x4 *)wptr[i];
         }
         // accumulators start at the residual (C-in of the first MFMA); bias joins in the epilogue from LDS
-        {
+        // (phase 1 of a two-phase tile: acc[] holds the residual already - the rows phase 0 normalised)
+        if constexpr (!P1) {
             const float *rp = res + (size_t)row * N + 4 * h;
 #pragma unroll
             for (int j = 0; j < NT; ++j)
@@ -882,13 +944,13 @@ __device__ __forceinline__ void ln_rows_tiles(
                     for (int e = 0; e < 4; ++e) acc[j][4 * q + e] = rv[e];
                 }
         }
-        __syncthreads();                 // previous tile's readers are done with both LDS buffers
+        if constexpr (!P1) __syncthreads();     // previous tile's readers are done with both LDS buffers (phase 1: its barrier above)
         stage(0);
         __syncthreads();
         if constexpr (DIAG != 0) { dsum[2] += stamp() - tq; ktiles += nk; }     // dsum[2]: tile prologue (loads of C-in and of k-tile 0)
 
-        for (int kt = 0; kt < nk; ++kt) {
-            const int kn = kt + 1 < nk ? kt + 1 : kt;         // last step reloads a duplicate: branch-free stream
+        for (int kt = 0; kt < pnk; ++kt) {
+            const int kn = kt + 1 < pnk ? kt + 1 : kt;         // last step reloads a duplicate: branch-free stream
             const float *As = smem + (kt & 1) * (BM + N) * LD, *Ws = As + BM * LD;
             if constexpr (PREC == 2) {
                 const float *arow = As + (32 * wave + r) * LD + 4 * h;
@@ -984,7 +1046,7 @@ __device__ __forceinline__ void ln_rows_tiles(
                 __syncthreads();
         }
         if constexpr (DIAG != 0) tq = stamp();
-        if constexpr (TAIL != 0) {          // the tail's first weight tile: in flight under the LayerNorm epilogue
+        if constexpr (PT != 0) {            // the tail's first weight tile: in flight under the LayerNorm epilogue
 #pragma unroll
             for (int i = 0; i < 4; ++i) tail_load(i, tail_soff(0, 0));
         }
@@ -997,7 +1059,7 @@ __device__ __forceinline__ void ln_rows_tiles(
             float pj = 0.f;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const f32x4 bv = *(const f32x4 *)&bias_s[32 * j + 8 * q + 4 * h];
+                const f32x4 bv = *(const f32x4 *)&pbias_s[32 * j + 8 * q + 4 * h];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { acc[j][4 * q + e] += bv[e]; pj += acc[j][4 * q + e]; }
             }
@@ -1023,20 +1085,26 @@ __device__ __forceinline__ void ln_rows_tiles(
         for (int j = 0; j < NT; ++j) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const f32x4 gv = *(const f32x4 *)&gam_s[32 * j + 8 * q + 4 * h];
-                const f32x4 bv = *(const f32x4 *)&bet_s[32 * j + 8 * q + 4 * h];
+                const f32x4 gv = *(const f32x4 *)&pgam_s[32 * j + 8 * q + 4 * h];
+                const f32x4 bv = *(const f32x4 *)&pbet_s[32 * j + 8 * q + 4 * h];
                 f32x4 y;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { y[e] = acc[j][4 * q + e] * rstd * gv[e] + bv[e]; acc[j][4 * q + e] = y[e]; }
-                *(f32x4 *)&tp[r * 36 + 8 * q + 4 * h] = y;
+                if constexpr (!TWO || P1) *(f32x4 *)&tp[r * 36 + 8 * q + 4 * h] = y;
             }
+            // phase 0 of a two-phase tile stores nothing, its rows stay in acc[]: without the corner's writes between them the
+            // scheduler would lift the gamma / beta reads of all eight blocks to the top, over the tail's weight tile in flight
+            if constexpr (TWO && !P1) __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!TWO || P1) {
 #pragma unroll
-            for (int pq = 0; pq < 4; ++pq) {
-                const f32x4 v = *(const f32x4 *)&tp[(trow + 8 * pq) * 36 + tc4];
-                const int orow = m0 + 32 * wave + trow + 8 * pq;
-                if (orow < M) *(f32x4 *)(out + (size_t)orow * N + 32 * j + tc4) = v;
+                for (int pq = 0; pq < 4; ++pq) {
+                    const f32x4 v = *(const f32x4 *)&tp[(trow + 8 * pq) * 36 + tc4];
+                    const int orow = m0 + 32 * wave + trow + 8 * pq;
+                    if (orow < M) *(f32x4 *)(pout + (size_t)orow * N + 32 * j + tc4) = v;
+                }
             }
         }
+        if constexpr (!TWO || (P1 && TAIL == 4))
         if (score_w != nullptr) {
             for (int c = 0; c < num_classes; ++c) {
                 __syncthreads();
@@ -1063,22 +1131,22 @@ __device__ __forceinline__ void ln_rows_tiles(
             }
         }
         if constexpr (DIAG != 0) dsum[1] += stamp() - tq;       // dsum[1]: epilogue
-        if constexpr (TAIL != 0) {
+        if constexpr (PT != 0) {
             // ---- the register-fed product: NC chunks of 128 output columns, 8 steps (k-tiles of 32 = one acc[kt]) each ----
             tail_stage(0);                      // step 0's weight tile: loaded ahead of the LayerNorm epilogue
             int rowoff[4];                      // this lane's four store rows (read-back map of the transposition corner)
             __amdgpu_buffer_rsrc_t crs;
-            if constexpr (TAIL == 1) {          // rows past M lie beyond the descriptor's end: their stores are dropped
-                crs = __builtin_amdgcn_make_buffer_rsrc(tl.C2 + (size_t)m0 * TN2, 0, (M - m0 < BM ? M - m0 : BM) * TN2 * 4, 0x00020000);
+            if constexpr (PT == 1) {            // rows past M lie beyond the descriptor's end: their stores are dropped
+                crs = __builtin_amdgcn_make_buffer_rsrc(ptl.C2 + (size_t)m0 * PTN2, 0, (M - m0 < BM ? M - m0 : BM) * PTN2 * 4, 0x00020000);
 #pragma unroll
-                for (int p = 0; p < 4; ++p) rowoff[p] = ((32 * wave + trow + 8 * p) * TN2 + tc4) * 4;
+                for (int p = 0; p < 4; ++p) rowoff[p] = ((32 * wave + trow + 8 * p) * PTN2 + tc4) * 4;
             } else {
-                crs = __builtin_amdgcn_make_buffer_rsrc(tl.C2, 0, 0, 0x00020000);
+                crs = __builtin_amdgcn_make_buffer_rsrc(ptl.C2, 0, 0, 0x00020000);
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
                     const int orow = m0 + 32 * wave + trow + 8 * p;
-                    const int bb = orow / tl.T, tt = orow - bb * tl.T;
-                    rowoff[p] = orow < M ? (((bb * tl.H * tl.T + tt) << tl.dhs) + tc4) * 4 : (int)0x80000000;
+                    const int bb = orow / ptl.T, tt = orow - bb * ptl.T;
+                    rowoff[p] = orow < M ? (((bb * ptl.H * ptl.T + tt) << ptl.dhs) + tc4) * 4 : (int)0x80000000;
                 }
             }
             bias_mfma(0);
@@ -1089,9 +1157,9 @@ __device__ __forceinline__ void ln_rows_tiles(
                     constexpr int kt = decltype(ktc)::value;
                     tail_step(ktc, kt < 7 ? tail_soff(c, kt + 1) : tail_soff(cn, 0));
                 });
-                if constexpr (TAIL == 2) {
+                if constexpr (PT == 2) {
                     const int which = c >> 1;                           // 128-column chunks never straddle q / k / v (d_model 256)
-                    crs = __builtin_amdgcn_make_buffer_rsrc(tl.C2 + (size_t)which * M * N, 0, M * N * 4, 0x00020000);
+                    crs = __builtin_amdgcn_make_buffer_rsrc(ptl.C2 + (size_t)which * M * N, 0, M * N * 4, 0x00020000);
                 }
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
@@ -1103,14 +1171,14 @@ __device__ __forceinline__ void ln_rows_tiles(
                     for (int q = 0; q < 4; ++q) {
                         f32x4 v;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = TAIL == 1 ? relu1(U[jj][4 * q + e]) : U[jj][4 * q + e];
+                        for (int e = 0; e < 4; ++e) v[e] = PT == 1 ? relu1(U[jj][4 * q + e]) : U[jj][4 * q + e];
                         *(f32x4 *)&tp[r * 36 + 8 * q + 4 * h] = v;
                     }
                     int soff;
-                    if constexpr (TAIL == 1) soff = (TCH * c + 32 * jj) * 4;
+                    if constexpr (PT == 1) soff = (TCH * c + 32 * jj) * 4;
                     else {                                              // a 32-column block never straddles a head
-                        const int cc = (TCH * c + 32 * jj) & (N - 1), head = cc >> tl.dhs, e0 = cc - (head << tl.dhs);
-                        soff = (((head * tl.T) << tl.dhs) + e0) * 4;
+                        const int cc = (TCH * c + 32 * jj) & (N - 1), head = cc >> ptl.dhs, e0 = cc - (head << ptl.dhs);
+                        soff = (((head * ptl.T) << ptl.dhs) + e0) * 4;
                     }
 #pragma unroll
                     for (int p = 0; p < 4; ++p) {
@@ -1122,6 +1190,7 @@ __device__ __forceinline__ void ln_rows_tiles(
                 bias_mfma(cn);
             }
         }
+      });
     }
     if constexpr (DIAG != 0) {
         if (diag != nullptr && lane == 0) {
@@ -1140,7 +1209,7 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_rows(
     const float *__restrict__ score_w, const float *__restrict__ score_b, int num_classes,
     int sigmoid, float *__restrict__ scores, unsigned long long *__restrict__ diag = nullptr) {
     ln_rows_tiles<NT, PREC, A16, DIAG, 0>(A, W, bias, res, gamma, beta, out, M, K, score_w, score_b, num_classes, sigmoid, scores, diag,
-                                          LnTail{nullptr, nullptr, nullptr, 0, 0, 0});
+                                          LnTail{nullptr, nullptr, nullptr, 0, 0, 0}, LnPhase2{});
 }
 
 // The exact-fp32 layer kernels of d_model 256: a gemm_ln_rows<8, 0> tile each, then the tail.
@@ -1151,7 +1220,7 @@ __global__ __launch_bounds__(256, 2) void layer_outproj_ln_fc1(
     const float *__restrict__ res, const float *__restrict__ gamma, const float *__restrict__ beta,
     float *__restrict__ out, int M, int K, const float *__restrict__ W1, const float *__restrict__ b1, float *__restrict__ hidden) {
     ln_rows_tiles<8, 0, 0, 0, 1>(A, W, bias, res, gamma, beta, out, M, K, nullptr, nullptr, 0, 0, nullptr, nullptr,
-                                 LnTail{W1, b1, hidden, 0, 0, 0});
+                                 LnTail{W1, b1, hidden, 0, 0, 0}, LnPhase2{});
 }
 __global__ __launch_bounds__(256, 2) void layer_fc2_ln_qkv(
     const float *__restrict__ A, const float *__restrict__ W, const float *__restrict__ bias,
@@ -1159,7 +1228,30 @@ __global__ __launch_bounds__(256, 2) void layer_fc2_ln_qkv(
     float *__restrict__ out, int M, int K, const float *__restrict__ Wqkv, const float *__restrict__ bqkv, float *__restrict__ qkv,
     int T, int H, int dhs) {
     ln_rows_tiles<8, 0, 0, 0, 2>(A, W, bias, res, gamma, beta, out, M, K, nullptr, nullptr, 0, 0, nullptr, nullptr,
-                                 LnTail{Wqkv, bqkv, qkv, T, H, dhs});
+                                 LnTail{Wqkv, bqkv, qkv, T, H, dhs}, LnPhase2{});
+}
+// The two as ONE kernel (round 9): h1 stays in the accumulators between them, the hidden rows are read back by the block that
+// wrote them.  gemm_ln_rows_tail_qkv ends with the next layer's q / k / v, gemm_ln_rows_tail_score (the last layer) with the
+// score head.  (Named as members of the gemm_ln_rows family, which they are: the launch is recorded as the fc2 + norm2 stage, and
+// bench.py finds the kernel behind that stage in the measured-traffic file by this prefix.)
+struct LayerTailArgs {
+    const float *att, *Wo, *bo, *res, *g1, *be1;        // out-projection + norm1 over the residual
+    const float *W1, *b1;                               // fc1
+    float *hidden;
+    const float *W2, *b2, *g2, *be2;                    // fc2 + norm2
+    float *out;
+    int M;
+};
+__global__ __launch_bounds__(256, 2) void gemm_ln_rows_tail_qkv(const LayerTailArgs a, const float *__restrict__ Wqkv,
+                                                         const float *__restrict__ bqkv, float *__restrict__ qkv, int T, int H, int dhs) {
+    ln_rows_tiles<8, 0, 0, 0, 3>(a.att, a.Wo, a.bo, a.res, a.g1, a.be1, nullptr, a.M, 256, nullptr, nullptr, 0, 0, nullptr, nullptr,
+                                 LnTail{a.W1, a.b1, a.hidden, 0, 0, 0}, LnPhase2{a.W2, a.b2, a.g2, a.be2, a.out, LnTail{Wqkv, bqkv, qkv, T, H, dhs}});
+}
+__global__ __launch_bounds__(256, 2) void gemm_ln_rows_tail_score(const LayerTailArgs a, const float *__restrict__ score_w,
+                                                           const float *__restrict__ score_b, int num_classes, int sigmoid,
+                                                           float *__restrict__ scores) {
+    ln_rows_tiles<8, 0, 0, 0, 4>(a.att, a.Wo, a.bo, a.res, a.g1, a.be1, nullptr, a.M, 256, score_w, score_b, num_classes, sigmoid, scores, nullptr,
+                                 LnTail{a.W1, a.b1, a.hidden, 0, 0, 0}, LnPhase2{a.W2, a.b2, a.g2, a.be2, a.out, LnTail{nullptr, nullptr, nullptr, 0, 0, 0}});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2305,6 +2397,29 @@ int vsk_fc2_ln_qkv(const float *hidden, const float *W2, const float *b2, const 
     if (blocks < 0) return (int)hipErrorInvalidDevice;
     if (blocks > (M + 127) / 128) blocks = (M + 127) / 128;
     hipLaunchKernelGGL(layer_fc2_ln_qkv, dim3(blocks), dim3(256), 0, st, hidden, W2, b2, res, gamma, beta, out, M, 4 * d, Wqkv, bqkv, qkv, T, H, dhs);
+    VSK_CHECK_LAUNCH();
+    return 0;
+}
+
+int vsk_layer_tail(const float *att, const float *Wo, const float *bo, const float *res, const float *g1, const float *be1,
+                   const float *W1, const float *b1, float *hidden, const float *W2, const float *b2, const float *g2, const float *be2,
+                   float *out, const float *Wqkv, const float *bqkv, float *qkv, const float *score_w, const float *score_b,
+                   int num_classes, int sigmoid, float *scores, int B, int T, int d, int H, hipStream_t st) {
+    const int M = B * T;
+    if (!vsk_layer_fused_supported(M, d, skinny_max_rows())) return -1;
+    int blocks = persistent_blocks((M + 127) / 128);
+    if (blocks < 0) return (int)hipErrorInvalidDevice;
+    if (blocks > (M + 127) / 128) blocks = (M + 127) / 128;
+    const LayerTailArgs a{att, Wo, bo, res, g1, be1, W1, b1, hidden, W2, b2, g2, be2, out, M};
+    if (Wqkv != nullptr) {
+        if (H <= 0 || d % H || (d / H) % 32) return -1;     // a 32-column block within one head
+        int dhs = 5;                                        // head dim 32, 64, 128 or 256
+        while ((1 << dhs) < d / H) ++dhs;
+        hipLaunchKernelGGL(gemm_ln_rows_tail_qkv, dim3(blocks), dim3(256), 0, st, a, Wqkv, bqkv, qkv, T, H, dhs);
+    } else {
+        if (score_w == nullptr) return -1;
+        hipLaunchKernelGGL(gemm_ln_rows_tail_score, dim3(blocks), dim3(256), 0, st, a, score_w, score_b, num_classes, sigmoid, scores);
+    }
     VSK_CHECK_LAUNCH();
     return 0;
 }

@@ -120,6 +120,7 @@ const OptionName kOptions[] = {
     {"VS_LP_MIN_ROWS_FUSED", &VskOptions::lp_min_rows_fused, 256}, {"VS_LP_TILE256", &VskOptions::lp_tile256, 0},
     {"VS_ATTN_W64_CHECKED", &VskOptions::attn_w64_checked, 0}, {"VS_TRAIN_LP_MIN_ROWS", &VskOptions::train_lp_min_rows, 1024},
     {"VS_ATTN_W64", &VskOptions::attn_w64, 1},           {"VS_ATTN_W64_ABL", &VskOptions::attn_w64_abl, 0},
+    {"VS_LAYER_TAIL_MIN_ROWS", &VskOptions::layer_tail_min_rows, 1024},
 };
 int option_from_env(const OptionName &o) {
     const char *e = getenv(o.name);
@@ -563,6 +564,17 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
                                    head_w, head_b, D.num_classes, sig, head_out, next, st));
         } break;
         case VS_LAYER_EXACT_PAIR: {
+            if (M >= vsk_options().layer_tail_min_rows) {
+                // one launch instead of the pair (a launcher fact, like cu and work: the plan says EXACT_PAIR either way); h1 stays
+                // in registers.  Recorded under fc2 alone: bench.py folds the out-projection, fc1 and QKV shares into that row
+                // when fc1 has no launches, as for the bf16 tail.
+                StageScope ps(VS_STAGE_FC2_LN, st);
+                const LayerOff *N = last ? nullptr : &w->layers[l + 1];
+                VS_LAUNCH(vsk_layer_tail(att, w->p(P.wo), w->p(P.bo), h0, w->p(P.ln1g), w->p(P.ln1b), w->p(P.w1), w->p(P.b1), ffn, w->p(P.w2),
+                                         w->p(P.b2), w->p(P.ln2g), w->p(P.ln2b), dst, N ? w->p(N->wqkv) : nullptr, N ? w->p(N->bqkv) : nullptr,
+                                         qkv, head_w, head_b, D.num_classes, sig, head_out, B, T, d, H, st));
+                break;
+            }
             {   // recorded under fc1 / fc2: the stage table has no out-projection row then, and these two rows' FLOPs omit the
                 // out-projection and QKV shares (their TFLOP/s are understated, never overstated)
                 StageScope ps(VS_STAGE_FC1, st);
