@@ -13,6 +13,13 @@ GPU (the reference's arithmetic, every layer's softmax kept).  The long shape ru
   * (attention_maps - attention_summary) against the bytes of the maps over 6.29 TB/s, the achievable HBM rate of
     MI355X_MICROARCH.md (the stores overlap the products of the same kernel: this difference is what the maps ADD, not a
     bandwidth measurement).
+
+    python tools/bench_attention_maps.py --packed [--seed 7] [--out profiles/attention_maps_packed_bench.txt]
+
+The packed leg: a ragged batch - 64 videos of `synth.corpus_lengths(64, seed)` (100 to 650 frames) and the reference's B = 4 -
+through `attention_summary_packed` / `attention_maps_packed` against `attention_summary` / `attention_maps` on the same videos
+right-padded to the longest with the 1000.0 sentinel and the key mask; `forward_packed` and `forward` beside them, because the
+forward inside the call does not shrink by the side kernels' factor.  All legs alternate inside this one process.
 """
 import argparse
 import importlib
@@ -89,14 +96,93 @@ def attention_stage_ms(model, x, reps):
     return ms / reps, n // reps
 
 
+def time_legs_spread(legs, reps):
+    """{name: (median, min, max) ms}: time_legs' loop, keeping the spread"""
+    for fn in legs.values():
+        fn()
+        fn()
+    torch.cuda.synchronize()
+    ts = {n: [] for n in legs}
+    for _ in range(reps):
+        for n, fn in legs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts[n].append(a.elapsed_time(b))
+    return {n: (float(np.median(v)), float(np.min(v)), float(np.max(v))) for n, v in ts.items()}
+
+
+def packed_legs(args, dev):
+    """packed against padded on the same ragged videos; returns the lines of the report"""
+    sd = vsa.synth.make_state_dict(D, L, 3)
+    model = vsa.SimNet(num_heads=H, d_model=D, num_layers=L, sparsity=0.0, dropout=0.3)
+    model.load_state_dict(sd, strict=True)
+    model = model.to(dev).eval()
+    lines = []
+    for B in (64, 4):
+        lengths = vsa.synth.corpus_lengths(B, args.seed)
+        tmax, M = max(lengths), sum(lengths)
+        x = vsa.synth.make_features(B, tmax, 4, "randn", lengths).to(dev)          # right-padded with the sentinel
+        mask = vsa.synth.padding_mask(x)
+        xp = torch.cat([x[b, :t] for b, t in enumerate(lengths)], dim=0).contiguous()
+
+        def fwd():
+            with torch.no_grad():
+                return model(x, mask)
+
+        legs = {"forward padded": fwd, "forward packed": lambda: model.forward_packed(xp, lengths, want_hidden=False),
+                "summary padded": lambda: model.attention_summary(x, mask),
+                "summary packed": lambda: model.attention_summary_packed(xp, lengths),
+                "maps padded": lambda: model.attention_maps(x, mask), "maps packed": lambda: model.attention_maps_packed(xp, lengths)}
+        t = time_legs_spread(legs, args.reps)
+        sq = sum(u * u for u in lengths)
+        lines.append("B=%-3d lengths %d..%d (seed %d)   rows %d packed / %d padded   fill %.3f   sum T^2 / (B Tmax^2) %.3f"
+                     % (B, min(lengths), tmax, args.seed, M, B * tmax, M / (B * tmax), sq / (B * tmax * tmax)))
+        for what in ("forward", "summary", "maps"):
+            (pm, plo, phi), (km, klo, khi) = t[what + " padded"], t[what + " packed"]
+            lines.append("  %-8s padded %7.3f ms (%.3f..%.3f)   packed %7.3f ms (%.3f..%.3f)   packed / padded %.3f"
+                         % (what, pm, plo, phi, km, klo, khi, km / pm))
+        side_pad = t["summary padded"][0] - t["forward padded"][0]
+        side_pk = t["summary packed"][0] - t["forward packed"][0]
+        lines.append("  summary - forward (the side kernels, %d layers): padded %.3f ms, packed %.3f ms (%.3f)"
+                     % (L, side_pad, side_pk, side_pk / side_pad if side_pad > 0 else float("nan")))
+        lines.append("  map memory, all %d layers: padded %.1f MiB, packed %.1f MiB (%.3f)"
+                     % (L, L * B * H * tmax * tmax * 4 / 2 ** 20, L * H * sq * 4 / 2 ** 20, sq / (B * tmax * tmax)))
+        lines.append("")
+        print("\n".join(lines[-7:]), flush=True)
+        del x, xp, mask
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--packed", action="store_true", help="run the packed-against-padded legs only")
+    ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attention_maps_packed_bench.txt"))
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "attention_maps_bench.json"))
     ap.add_argument("--skip-long", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark needs the MI355X"
     dev = torch.device("cuda", 0)
+    if args.packed:
+        head = ["Attention maps and summaries on packed ragged batches against the padded calls - measured on one MI355X",
+                "=" * 103, "",
+                "tools/bench_attention_maps.py --packed --reps %d --seed %d; model M-A (H%d / d%d / L%d), every layer selected, exact fp32."
+                % (args.reps, args.seed, H, D, L),
+                "Device events around each call after two warm-up calls per leg; the six legs alternate inside one process, %d rounds:" % args.reps,
+                "median (min..max).  Lengths: synth.corpus_lengths(B, seed), uniform 100..650 frames; the padded legs take the same videos",
+                "right-padded to the longest with the 1000.0 sentinel and the key mask.  sum T^2 / (B Tmax^2) is the ratio of the side",
+                "kernels' work and of the map memory; the forward inside each call does not shrink by that factor.", ""]
+        lines = head + packed_legs(args, dev)
+        if args.out:
+            os.makedirs(os.path.dirname(args.out), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines))
+        return
     shapes = [dict(name="b1_t320", B=1, T=320, fin=1024, pe=2000, maps=True),
               dict(name="b64_t1024", B=64, T=1024, fin=1024, pe=2000, maps=True)]
     if not args.skip_long:

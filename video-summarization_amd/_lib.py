@@ -253,6 +253,18 @@ _BINDINGS = {
  INSPECT_EXPORTS) = (tuple(_BINDINGS["vs_%s.h" % h]) for h in ("scorer", "eval", "eval_device", "summary", "batch", "train", "segment",
                                                                 "optim", "inspect"))
 
+# The attention maps on packed ragged batches: include/packed/vs_inspect_packed.h, an addition BESIDE the table above (which
+# is every prototype of include/*.h, pinned by tests/test_binding_host.py) with the same form and the same check of its own
+# (tests/test_attention_maps_packed_host.py).  lengths: host int32 array, then the same values on the device.
+PACKED_INSPECT_HEADER = os.path.join("packed", "vs_inspect_packed.h")
+_PACKED_INSPECT_BINDINGS = {
+    "vs_inspect_workspace_bytes_packed": (_Z, [_P, _P, _I]),
+    "vs_inspect_forward_packed": (_RC, [_P] * 4 + [_I, _ref(_I), _I] + [_P] * 6 + [_Z, _P]),
+    "vs_attention_probs_packed_workspace_bytes": (_Z, [_P, _I, _I]),
+    "vs_attention_probs_packed_f32": (_RC, [_P] * 4 + [_I] * 3 + [_F] + [_P] * 4 + [_Z, _P]),
+}
+PACKED_INSPECT_EXPORTS = tuple(_PACKED_INSPECT_BINDINGS)
+
 
 def hipcc_path() -> str:
     for p in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc"):
@@ -266,6 +278,7 @@ def needs_build() -> bool:
         return True
     t = os.path.getmtime(LIB_PATH)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE)]
+    deps.append(os.path.join(INCLUDE, PACKED_INSPECT_HEADER))
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -329,6 +342,16 @@ def _bind(lib) -> None:
         raise RuntimeError("libvsscore.so ABI %d != binding ABI %d" % (lib.vs_abi_version(), ABI_VERSION))
 
 
+def _bind_packed_inspect(lib) -> None:
+    """``_bind`` for the table of include/packed/vs_inspect_packed.h: every symbol present, then the signatures."""
+    for name in _PACKED_INSPECT_BINDINGS:
+        if not hasattr(lib, name):
+            raise RuntimeError("libvsscore.so lacks symbol %s (stale build?)" % name)
+    for name, (restype, argtypes) in _PACKED_INSPECT_BINDINGS.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -350,6 +373,7 @@ def load() -> C.CDLL:
                 "There is no PyTorch/CPU fallback for the scoring path." % path)
         lib = C.CDLL(path)
         _bind(lib)
+        _bind_packed_inspect(lib)
         _lib = lib
     return _lib
 

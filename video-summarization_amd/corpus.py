@@ -175,6 +175,24 @@ def score_corpus(score_fn: ScoreFn, videos: Sequence[torch.Tensor], rank: int = 
     return out
 
 
+def attention_summary_corpus(model, videos: Sequence[torch.Tensor], layers=None, max_frames: int = 65536, device=None) -> list:
+    """``SimNet.attention_summary_packed`` over a corpus of videos of any lengths - the counterpart of the reference's
+    ``save_attention_weights`` loop over a loader (train.py:155-165), without ever storing a ``[T, T]`` map.  Returns, in input
+    order, one ``(received [n_layers, H, T_i], entropy [n_layers, H, T_i])`` pair per video; the tensors stay on the device.
+    The videos are grouped with ``bucket_batches`` (at most ``max_frames`` packed frames per group) and every group is ONE packed
+    call; a video's result is bit-identical to a packed call on that video alone.  ``device``: where the frames are moved to
+    (default: where each video already is)."""
+    lengths = [int(v.shape[0]) for v in videos]
+    out: list = [None] * len(videos)
+    for batch in bucket_batches(range(len(videos)), lengths, max_frames, packed=True):
+        x = torch.cat([videos[i].to(device=device, dtype=torch.float32) for i in batch], dim=0)
+        lens = [lengths[i] for i in batch]
+        _, received, entropy = model.attention_summary_packed(x, lens, layers=layers)
+        for i, r, e in zip(batch, received.split(lens, dim=-1), entropy.split(lens, dim=-1)):
+            out[i] = (r, e)
+    return out
+
+
 def score_host_batches(score_fn: ScoreFn, batches, device) -> List[torch.Tensor]:
     """Scores a sequence of HOST batches - padded (x [B,T,D] pinned or pageable, mask or None) or packed
     (x [sum T, D], list of lengths; `score_fn` is then `SimNet.score_packed`) - with the host-to-device

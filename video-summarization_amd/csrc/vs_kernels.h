@@ -44,6 +44,14 @@ int vsk_attention_bf16_w64_packed(const void *q, const void *k, const void *v, v
 size_t vsk_attention_probs_workspace_bytes(int B, int H, int T);
 int vsk_attention_probs(const float *q, const float *k, const uint8_t *mask, float *maps, float *received, float *entropy,
                         int B, int H, int T, int dh, float scale, void *workspace, hipStream_t st);
+// ... on a packed ragged batch: q, k head-major [H, M, dh] (M = sum of the lengths, video b = rows cu[b] .. cu[b+1]-1 of every
+// plane), head dim 32 / 64 / 128; received / entropy [H, M], maps = the videos' [H, T_b, T_b] blocks one after the other.
+// tiles = sum ceil(T_b / 32) by the HOST lengths sizes the grid and the plan.  _plan builds cu, the 64-bit map offsets and the
+// (video, tile) list inside `workspace` from the device lengths, once per batch; cu == nullptr: the plan's own copy.
+size_t vsk_attention_probs_packed_workspace_bytes(int B, int H, int M, int tiles);
+int vsk_attention_probs_packed_plan(const int *lengths_dev, int B, int H, int M, int tiles, void *workspace, hipStream_t st);
+int vsk_attention_probs_packed(const float *q, const float *k, const int *cu, float *maps, float *received, float *entropy, int B,
+                               int H, int M, int tiles, int dh, float scale, void *workspace, hipStream_t st);
 int vsk_linear_res_ln(const float *A, const float *W, const float *Wf, const float *bias, const float *res,
                       const float *gamma, const float *beta, float *out, int M, int N, int K,
                       const float *score_w, const float *score_b, int num_classes, int sigmoid,

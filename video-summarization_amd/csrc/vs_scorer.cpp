@@ -395,6 +395,10 @@ struct InspectHook {
     int n_layers;
     float *maps, *received, *entropy;      // [n_layers, B, H, N, N] / [n_layers, B, H, N] / [n_layers, B, H, N], any nullptr
     void *workspace;         // vsk_attention_probs_workspace_bytes(B, H, N)
+    // packed (pk != nullptr): received / entropy [n_layers, H, M], maps [n_layers] x the videos' [H, T_b, T_b] blocks;
+    // workspace: vsk_attention_probs_packed_workspace_bytes, its plan already built (vsk_attention_probs_packed_plan)
+    int videos = 0, tiles = 0;             // B and sum ceil(T_b / 32) of the packed batch
+    size_t map_stride = 0;                 // H * sum T_b^2: floats of one layer's maps
 };
 
 // cls != nullptr (use_cls=True, reference simnet.py:205-206, 214-216, 47-51): x has T frames per video, a class token
@@ -492,6 +496,13 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
             for (int i = 0; i < ins->n_layers; ++i) {
                 if (ins->layers[i] != l) continue;
                 const size_t rows = (size_t)B * H * T;
+                if (pk) {       // B = 1, T = M: at flags 0 the q / k planes are the head-major [H, M, dh] planes of the packed kernels
+                    VS_LAUNCH(vsk_attention_probs_packed(qkv, qkv + kv, pk->cu, ins->maps ? ins->maps + i * ins->map_stride : nullptr,
+                                                         ins->received ? ins->received + i * rows : nullptr,
+                                                         ins->entropy ? ins->entropy + i * rows : nullptr, ins->videos, H, M, ins->tiles,
+                                                         d / H, scale, ins->workspace, st));
+                    continue;
+                }
                 VS_LAUNCH(vsk_attention_probs(qkv, qkv + kv, key_pad_mask, ins->maps ? ins->maps + i * rows * T : nullptr,
                                               ins->received ? ins->received + i * rows : nullptr,
                                               ins->entropy ? ins->entropy + i * rows : nullptr, B, H, T, d / H, scale, ins->workspace, st));
@@ -733,9 +744,10 @@ size_t vs_scorer_workspace_bytes_packed(const vs_weights *w, const int32_t *leng
     return 11 * md + align_up((cu.size() + 2 * packed_plan_capacity(lengths, B)) * sizeof(int), 256);
 }
 
-int vs_scorer_forward_packed(const vs_weights *w, const float *x, const int32_t *lengths, const int32_t *lengths_dev,
-                             int32_t B, uint32_t flags, float *scores, float *hidden, void *workspace,
-                             size_t workspace_bytes, void *stream) {
+// vs_scorer_forward_packed, and vs_inspect_forward_packed (ins != nullptr: its hook, workspace_bytes = the forward's share)
+static int forward_packed(const vs_weights *w, const float *x, const int32_t *lengths, const int32_t *lengths_dev,
+                          int32_t B, uint32_t flags, float *scores, float *hidden, void *workspace,
+                          size_t workspace_bytes, void *stream, const InspectHook *ins) {
     if (!lengths_dev) return fail(VS_ERR_INVALID, "lengths_dev is NULL");
     if (!w) return fail(VS_ERR_INVALID, "weights is NULL");
     if ((flags & VS_FLAG_BF16_ATTENTION) && (flags & VS_FLAG_F16X3_ATTENTION))
@@ -767,7 +779,102 @@ int vs_scorer_forward_packed(const vs_weights *w, const float *x, const int32_t 
         VS_LAUNCH(vsk_gather_rows(w->p(w->pe), pk.cu, B, tmax, d, pe_rows, st));
         pk.pe_rows = pe_rows;
     }
-    return forward_core(w, x, nullptr, 1, M, flags, scores, hidden, workspace, 10 * md, stream, &pk);
+    return forward_core(w, x, nullptr, 1, M, flags, scores, hidden, workspace, 10 * md, stream, &pk, nullptr, ins);
+}
+
+int vs_scorer_forward_packed(const vs_weights *w, const float *x, const int32_t *lengths, const int32_t *lengths_dev,
+                             int32_t B, uint32_t flags, float *scores, float *hidden, void *workspace,
+                             size_t workspace_bytes, void *stream) {
+    return forward_packed(w, x, lengths, lengths_dev, B, flags, scores, hidden, workspace, workspace_bytes, stream, nullptr);
+}
+
+// ---- attention maps on packed ragged batches (include/vs_inspect.h) ----
+// M = sum of the lengths, tiles = sum ceil(T_b / 32) (the capacity rule of the size function AND of the launch), sumsq = sum T_b^2
+static int probs_packed_sizes(const int32_t *lengths, int32_t B, int &M, int &tiles, size_t &sumsq) {
+    if (!lengths || B <= 0) return fail(VS_ERR_INVALID, "lengths is NULL or B=%d", B);
+    long long m = 0, n = 0;
+    sumsq = 0;
+    for (int b = 0; b < B; ++b) {
+        const int t = lengths[b];
+        if (t <= 0) return fail(VS_ERR_INVALID, "lengths[%d]=%d", b, t);
+        m += t;
+        n += (t + 31) / 32;
+        sumsq += (size_t)t * (size_t)t;
+        if (m > (1ll << 30)) return fail(VS_ERR_INVALID, "too many frames");
+    }
+    M = (int)m;
+    tiles = (int)n;
+    return VS_OK;
+}
+
+size_t vs_attention_probs_packed_workspace_bytes(const int32_t *lengths, int32_t B, int32_t H) {
+    int M = 0, tiles = 0;
+    size_t sumsq = 0;
+    if (H <= 0 || probs_packed_sizes(lengths, B, M, tiles, sumsq) != VS_OK) return 0;
+    return vsk_attention_probs_packed_workspace_bytes(B, H, M, tiles);
+}
+
+int vs_attention_probs_packed_f32(const float *q, const float *k, const int32_t *lengths, const int32_t *lengths_dev, int32_t B,
+                                  int32_t H, int32_t dh, float scale, float *maps, float *received, float *entropy,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+    if (!q || !k) return fail(VS_ERR_INVALID, "q / k is NULL");
+    if (!lengths_dev) return fail(VS_ERR_INVALID, "lengths_dev is NULL");
+    if (!maps && !received && !entropy) return fail(VS_ERR_INVALID, "maps, received and entropy are all NULL");
+    if (H <= 0) return fail(VS_ERR_INVALID, "H=%d", H);
+    int M = 0, tiles = 0;
+    size_t sumsq = 0;
+    if (int rc = probs_packed_sizes(lengths, B, M, tiles, sumsq)) return rc;
+    if (dh != 32 && dh != 64 && dh != 128) return fail(VS_ERR_INVALID, "head_dim=%d unsupported on packed batches (32, 64 or 128)", dh);
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)maps | (uintptr_t)received | (uintptr_t)entropy) & 15)
+        return fail(VS_ERR_INVALID, "q / k / maps / received / entropy must be 16-byte aligned");
+    const size_t need = vsk_attention_probs_packed_workspace_bytes(B, H, M, tiles);
+    if (!workspace || workspace_bytes < need)
+        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 255) return fail(VS_ERR_INVALID, "workspace must be 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    VS_LAUNCH(vsk_attention_probs_packed_plan(lengths_dev, B, H, M, tiles, workspace, st));
+    VS_LAUNCH(vsk_attention_probs_packed(q, k, nullptr, maps, received, entropy, B, H, M, tiles, dh, scale, workspace, st));
+    return VS_OK;
+}
+
+size_t vs_inspect_workspace_bytes_packed(const vs_weights *w, const int32_t *lengths, int32_t B) {
+    const size_t core = vs_scorer_workspace_bytes_packed(w, lengths, B);      // 0: invalid (checks w, lengths, the head dim)
+    if (core == 0) return 0;
+    return align_up(core, 256) + vs_attention_probs_packed_workspace_bytes(lengths, B, w->desc.num_heads);
+}
+
+int vs_inspect_forward_packed(const vs_weights *w, const float *x, const int32_t *lengths, const int32_t *lengths_dev, int32_t B,
+                              const int32_t *layers, int32_t n_layers, float *scores, float *hidden, float *maps, float *received,
+                              float *entropy, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!w) return fail(VS_ERR_INVALID, "weights is NULL");
+    if (!lengths_dev) return fail(VS_ERR_INVALID, "lengths_dev is NULL");
+    if (!layers || n_layers <= 0) return fail(VS_ERR_INVALID, "layers is NULL or n_layers=%d", n_layers);
+    for (int i = 0; i < n_layers; ++i) {
+        if (layers[i] < 0 || layers[i] >= w->desc.num_layers)
+            return fail(VS_ERR_INVALID, "layers[%d]=%d out of range (num_layers=%d)", i, layers[i], w->desc.num_layers);
+        if (i && layers[i] <= layers[i - 1]) return fail(VS_ERR_INVALID, "layers must be strictly ascending (layers[%d]=%d after %d)", i, layers[i], layers[i - 1]);
+    }
+    if (!x || !scores) return fail(VS_ERR_INVALID, "weights/x/scores is NULL");
+    if (!maps && !received && !entropy) return fail(VS_ERR_INVALID, "maps, received and entropy are all NULL");
+    if (((uintptr_t)maps | (uintptr_t)received | (uintptr_t)entropy | (uintptr_t)x | (uintptr_t)hidden) & 15)
+        return fail(VS_ERR_INVALID, "x / hidden / maps / received / entropy must be 16-byte aligned");
+    std::vector<int> cu, work;
+    int nw = 0;
+    if (int rc = packed_plan(w, lengths, B, cu, work, nw)) return rc;      // B, the lengths, the positional table, the head dim
+    int M = 0, tiles = 0;
+    size_t sumsq = 0;
+    if (int rc = probs_packed_sizes(lengths, B, M, tiles, sumsq)) return rc;
+    const size_t core = align_up(vs_scorer_workspace_bytes_packed(w, lengths, B), 256);
+    const size_t need = core + vsk_attention_probs_packed_workspace_bytes(B, w->desc.num_heads, M, tiles);
+    if (!workspace || workspace_bytes < need)
+        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 255) return fail(VS_ERR_INVALID, "workspace must be 256-byte aligned");
+    InspectHook ins{layers, n_layers, maps, received, entropy, (char *)workspace + core};
+    ins.videos = B;
+    ins.tiles = tiles;
+    ins.map_stride = (size_t)w->desc.num_heads * sumsq;
+    VS_LAUNCH(vsk_attention_probs_packed_plan(lengths_dev, B, w->desc.num_heads, M, tiles, ins.workspace, (hipStream_t)stream));
+    return forward_packed(w, x, lengths, lengths_dev, B, 0u, scores, hidden, workspace, core, stream, &ins);
 }
 
 int vs_profile_enable(int32_t on) {

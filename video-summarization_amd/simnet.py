@@ -595,17 +595,21 @@ class SimNet(nn.Module):
         return scores.squeeze(-1)
 
     # ---- attention maps on request (include/vs_inspect.h) ----------------------------------
-    def _inspect(self, x: Tensor, mask, layers, want_maps: bool):
-        """One ``vs_inspect_forward`` call: the exact fp32 eval forward plus the attention-map kernels on the q / k planes of
-        the selected layers.  Returns (logits, maps or None, received or None, entropy or None), stacked over the layers."""
-        self._check_padded(x)
-        mask = mask if isinstance(mask, Tensor) else None
+    def _select_layers(self, layers):
+        """(the selected layers in the caller's order, the same ascending - the order the C entries take)"""
         L = self.num_layers
         want = list(range(L)) if layers is None else [int(l) for l in layers]
         sel = [l + L if l < 0 else l for l in want]
         if not sel or any(l < 0 or l >= L for l in sel) or len(set(sel)) != len(sel):
             raise IndexError("layers must be distinct indices of the %d encoder layers, got %r" % (L, want))
-        asc = sorted(sel)
+        return sel, sorted(sel)
+
+    def _inspect(self, x: Tensor, mask, layers, want_maps: bool):
+        """One ``vs_inspect_forward`` call: the exact fp32 eval forward plus the attention-map kernels on the q / k planes of
+        the selected layers.  Returns (logits, maps or None, received or None, entropy or None), stacked over the layers."""
+        self._check_padded(x)
+        mask = mask if isinstance(mask, Tensor) else None
+        sel, asc = self._select_layers(layers)
         lib = _lib.load()
         B, T, _ = x.shape
         dev = x.device
@@ -645,7 +649,7 @@ class SimNet(nn.Module):
         The maps describe the EXACT fp32 path: whatever ``set_compute_dtype`` / ``set_latency_mode`` / ``fused_sigmoid``
         / ``model.training`` say, this call runs the default exact kernels in eval semantics (it changes none of those
         settings), and ``logits`` are the raw logits of ``forward`` in the default mode, bit for bit.  Unlike the
-        reference the tensors stay on the device.  No autograd, no packed batches, no CPU path."""
+        reference the tensors stay on the device.  No autograd, no CPU path; ragged batches: ``attention_maps_packed``."""
         scores, maps, _, _ = self._inspect(x, mask, layers, True)
         return scores, list(maps.unbind(0))
 
@@ -657,6 +661,69 @@ class SimNet(nn.Module):
         ``entropy[l, b, h, i]`` is the entropy of frame ``i``'s weights in nats (0: it attends to one frame; ``log n``:
         uniform over the ``n`` valid frames).  Same arithmetic, modes and limits as ``attention_maps``."""
         scores, _, received, entropy = self._inspect(x, mask, layers, False)
+        return scores, received, entropy
+
+    def _inspect_packed(self, x: Tensor, lengths, layers, want_maps: bool):
+        """One ``vs_inspect_forward_packed`` call.  Returns (logits [M, C], lengths, maps [n_layers, H * sum T^2] or None,
+        received [n_layers, H, M] or None, entropy or None), the layers in the caller's order.  Refuses, in this order and all
+        before any launch: a class token, head dim 256, the shape, a video longer than the table, the layers, a CPU tensor."""
+        if self.use_cls:
+            raise NotImplementedError("packed batches are not available with use_cls=True")
+        if self._lib_dh not in (32, 64, 128):
+            raise RuntimeError("packed batches need head_dim 32, 64 or 128 (got %d)" % self._lib_dh)
+        lengths, host = host_lengths(lengths)
+        if x.dim() != 2 or x.size(1) != self.in_features or x.size(0) != sum(lengths):
+            raise RuntimeError("expected x of shape [sum(lengths)=%d, %d], got %s" % (sum(lengths), self.in_features, tuple(x.shape)))
+        if not lengths or min(lengths) <= 0:
+            raise RuntimeError("lengths must be positive, got %r" % (lengths,))
+        self._check_table(max(lengths))
+        sel, asc = self._select_layers(layers)
+        self._check_hip(x)
+        lib = _lib.load()
+        dev, M, B, H = x.device, x.size(0), len(lengths), self.num_heads
+        x32 = (x if x.dtype == torch.float32 else x.float()).contiguous()
+        packed = self._packed_weights(dev)
+        scores = torch.empty((M, self.num_classes), dtype=torch.float32, device=dev)
+        maps = torch.empty((len(asc), H * sum(t * t for t in lengths)), dtype=torch.float32, device=dev) if want_maps else None
+        received = None if want_maps else torch.empty((len(asc), H, M), dtype=torch.float32, device=dev)
+        entropy = None if want_maps else torch.empty((len(asc), H, M), dtype=torch.float32, device=dev)
+        host_layers = (C.c_int32 * len(asc))(*asc)
+        with on_stream(dev) as st:
+            dev_len = torch.tensor(lengths, dtype=torch.int32, device=dev)
+            ws = scratch(lib.vs_inspect_workspace_bytes_packed(packed.handle, host, B), dev, floor=256)
+            _lib.check(lib.vs_inspect_forward_packed(packed.handle, x32.data_ptr(), host, dev_len.data_ptr(), B, host_layers, len(asc),
+                                                     scores.data_ptr(), None, ptr(maps), ptr(received), ptr(entropy),
+                                                     ws.data_ptr(), ws.numel(), st))
+        if sel != asc:      # the caller's order
+            order = torch.tensor([asc.index(l) for l in sel], device=dev)
+            maps, received, entropy = (t if t is None else t.index_select(0, order) for t in (maps, received, entropy))
+        return scores, lengths, maps, received, entropy
+
+    @torch.no_grad()
+    def attention_maps_packed(self, x: Tensor, lengths, layers=None):
+        """``attention_maps`` on a RAGGED batch without padding: x [sum(lengths), in_features] = the videos' frames concatenated
+        (``forward_packed``).  Returns ``(logits [M, num_classes], maps)``: ``maps[l][b]`` is the ``[H, T_b, T_b]`` fp32 weights
+        of video ``b`` in the ``l``-th selected layer, a view into ONE allocation per call of ``n_layers * H * sum(T_b^2)``
+        floats - where the padded call allocates ``n_layers * B * H * Tmax^2``.  No padded row or masked column exists.  Same
+        semantics as ``attention_maps``: exact fp32 eval arithmetic whatever the modes say (none is changed), ``logits`` are the
+        bits of ``forward_packed`` in the default mode, ``layers`` as there.  A video's maps are bit-identical whatever it is
+        packed with.  Head dim 32 / 64 / 128, no class token (as ``forward_packed``)."""
+        scores, lengths, maps, _, _ = self._inspect_packed(x, lengths, layers, True)
+        H, out = self.num_heads, []
+        for layer in maps.unbind(0):
+            views, off = [], 0
+            for t in lengths:
+                views.append(layer[off:off + H * t * t].view(H, t, t))
+                off += H * t * t
+            out.append(views)
+        return scores, out
+
+    @torch.no_grad()
+    def attention_summary_packed(self, x: Tensor, lengths, layers=None):
+        """``attention_summary`` on a packed ragged batch (see ``attention_maps_packed``): returns ``(logits [M, num_classes],
+        received [n_layers, H, M], entropy [n_layers, H, M])``, packed like the frames: video ``b`` = columns
+        ``sum(lengths[:b]) ...``.  ``received`` sums to 1 over each video's own frames.  Never stores ``[T, T]``."""
+        scores, _, _, received, entropy = self._inspect_packed(x, lengths, layers, False)
         return scores, received, entropy
 
     def _check_head_dim(self, arithmetic: str) -> None:
