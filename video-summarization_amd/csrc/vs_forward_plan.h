@@ -32,10 +32,9 @@ struct VskOptions {
     int attn_w64_abl;     // VS_ATTN_W64_ABL  (diagnostic builds only) timing ablation of the one-wave-per-SIMD attention
 };
 
-// kernel mode words (the `bf16` / `prec` argument of the launchers in vs_kernels.h): 0 exact, 1 bf16 operands, 2 fp16x3, and
-// 1 | VSK_STORE16: additionally the tensors that are ONLY ever consumed as bf16 matrix operands live in HBM as bf16
-enum { VSK_STORE16 = 16, VSK_A16 = 32, VSK_F16 = 64 };      // VSK_A16 (training path): A of vsk_linear is stored as bf16;
-// VSK_F16 (training path's fp16 mode): the 16-bit type of this call - operands, stored C, stored A - is IEEE f16, not bf16
+// kernel mode words (the `mode` / `prec` argument of the launchers in vs_kernels.h): 0 exact, 1 bf16 operands, 2 fp16x3, and on 1
+// the bits below; what they mean and which words are valid: vsk_linear_mode (vs_linear_pick.h)
+enum { VSK_STORE16 = 16, VSK_A16 = 32, VSK_F16 = 64 };
 
 // kernel-layout weight image families (vsw_ensure, vs_weights_impl.h)
 enum { VSW_FRAGMENTS = 1, VSW_F16X3 = 2, VSW_BF16 = 4, VSW_ROWS16 = 8 };

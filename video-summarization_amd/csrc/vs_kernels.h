@@ -6,24 +6,21 @@
 
 #include "vs_forward_plan.h"      // VskOptions, the mode words, vsk_*_supported
 
-// bf16 != 0: operands rounded to bf16 for the matrix pipe (opt-in; fp32 storage, bias, accumulation, LayerNorm)
-// bf16 == (1 | VSK_STORE16): additionally the tensors that are ONLY ever consumed as bf16 matrix operands live in HBM
-// as bf16: C of vsk_qkv and of vsk_linear(relu), A of vsk_linear_res_ln, q/k/v/out of the bf16 attention.  The
-// rounding happens in the producer instead of the consumer: same bits, half the bytes.
-// (VSK_STORE16, VSK_A16, VSK_F16: vs_forward_plan.h)
+// mode: the mode word of the Linear launchers (vs_linear_pick.h: vsk_linear_mode decodes it, vsk_gemm_pick / vsk_ln_pick say
+// which kernel a shape runs)
 // Wf: the weight in fragment-major order (vsk_pack_fragments) or nullptr; enables the packed latency kernels
 int vsk_linear(const float *A, const float *W, const float *Wf, const float *bias, float *C, int M, int N, int K,
-               int relu, const float *pe, int T, int bf16, hipStream_t st);
-// training-path epilogues on the same GEMM kernels (exact fp32): ReLU/dropout gate of a dgrad; fc1 + ReLU + dropout
+               int relu, const float *pe, int T, int mode, hipStream_t st);
+// training-path epilogues on the same GEMM kernels: ReLU/dropout gate of a dgrad; fc1 + ReLU + dropout
 int vsk_linear_gate(const float *A, const float *W, const float *Wf, const float *bias, const float *gate, float scale,
-                    float *C, int M, int N, int K, hipStream_t st, int bf16 = 0);
+                    float *C, int M, int N, int K, hipStream_t st, int mode = 0);
 int vsk_linear_relu_dropout(const float *A, const float *W, const float *Wf, const float *bias, float *C, int M, int N,
-                            int K, unsigned long long seed, unsigned site, float p, hipStream_t st, int bf16 = 0);
+                            int K, unsigned long long seed, unsigned site, float p, hipStream_t st, int mode = 0);
 int vsk_pack_fragments(const float *W, float *Wf, int N, int K, hipStream_t st);
-// the fp16x3 counterpart (hi|lo f16 halves of 2^10 * W, same size): pass it as `Wf` together with bf16 == 2
+// the fp16x3 counterpart (hi|lo f16 halves of 2^10 * W, same size): pass it as `Wf` together with mode == 2
 int vsk_pack_fragments_f16x3(const float *W, float *Wh, int N, int K, hipStream_t st);
 int vsk_qkv(const float *h, const float *Wqkv, const float *Wf, const float *bqkv, float *qkv, int B, int T, int d,
-            int H, int bf16, hipStream_t st, float qscale = 1.0f);
+            int H, int mode, hipStream_t st, float qscale = 1.0f);
 int vsk_attention(const float *q, const float *k, const float *v, const uint8_t *mask, float *out,
                   int B, int H, int T, int dh, float scale, hipStream_t st);
 int vsk_attention_packed(const float *q, const float *k, const float *v, float *out, int H, int Mtot, int dh,
@@ -55,7 +52,7 @@ int vsk_attention_probs_packed(const float *q, const float *k, const int *cu, fl
 int vsk_linear_res_ln(const float *A, const float *W, const float *Wf, const float *bias, const float *res,
                       const float *gamma, const float *beta, float *out, int M, int N, int K,
                       const float *score_w, const float *score_b, int num_classes, int sigmoid,
-                      float *scores, int bf16, hipStream_t st);
+                      float *scores, int mode, hipStream_t st);
 // Exact fp32, d_model 256, M above the skinny threshold: vsk_linear_res_ln followed, in the same kernel and from registers, by
 // the next Linear - bit-identical to the two stand-alone kernels (-1: shape outside these kernels).
 //   vsk_outproj_ln_fc1: h1 = LN(att * Wo^T + bo + res), hidden [M, 4d] = relu(h1 * W1^T + b1)
