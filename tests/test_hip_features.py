@@ -1,0 +1,299 @@
+"""GPU: the GoogLeNet pool5 front end (features.GoogLeNetFeatures, include/features/vs_features.h) against tests/googlenet_ref.py, our
+float64 restatement of torchvision's network in torch functions.
+
+Tolerance: the project's parity bar, 1e-4 of the float64 tensor's largest entry (README, smoke()).  torch's own fp32 CPU forward of
+the restatement sits at 1.5e-7 .. 1.2e-6 of it, so the bar leaves about 80x over what fp32 arithmetic itself needs; every test that
+uses the bar also asserts that this fp32 forward is inside it, so a failure cannot be blamed on the bar.  Pools, batch independence,
+chunking and the two key forms are bit-equal: no tolerance.  Each case prints its distance ("features_parity ..." lines, collected
+in profiles/features_parity.txt)."""
+import ctypes as C
+import importlib
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import googlenet_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+BAR = 1e-4
+CANARY = -777.25
+GUARD = 256         # floats of canary on either side of a raw kernel's output
+
+
+def _dev():
+    assert torch.cuda.is_available(), "these tests need a HIP device"
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def vsa():
+    return importlib.import_module("video-summarization_amd")
+
+
+def _report(case, got, want64, fp32_cpu=None):
+    """asserts the parity bar on ``got`` (and on torch's own fp32 forward, where given), prints the distances"""
+    top = want64.abs().max().item()
+    d = (got.double().cpu() - want64).abs().max().item() / top
+    line = "features_parity %-44s ours %.3e" % (case, d)
+    d32 = None
+    if fp32_cpu is not None:
+        d32 = (fp32_cpu.double() - want64).abs().max().item() / top
+        line += "  torch fp32 cpu %.3e" % d32
+    print(line + "  (of max |float64| = %.4g; bar %.0e)" % (top, BAR))
+    assert top > 0 and torch.isfinite(got).all()
+    if d32 is not None:
+        assert d32 < BAR, (case, d32)
+    assert d < BAR, (case, d)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# single convs: conv + folded BatchNorm + ReLU through vs_cnn_pack_conv / vs_cnn_conv
+# ------------------------------------------------------------------------------------------------------------------------
+def _conv_case(vsa, seed, n, h, w, cin, cout, k, stride, pad, kind, c0=0, ldc=None):
+    L = vsa._lib
+    lib = L.load()
+    dev = _dev()
+    ldc = cout if ldc is None else ldc
+    g = torch.Generator().manual_seed(seed)
+    wt = torch.randn(cout, cin, k, k, generator=g) * (2.0 / (cin * k * k)) ** 0.5
+    gamma, var = 0.5 + torch.rand(cout, generator=g), 0.5 + torch.rand(cout, generator=g)
+    beta, mean = 0.3 * torch.randn(cout, generator=g), 0.3 * torch.randn(cout, generator=g)
+    if kind == L.VS_CNN_INPUT_U8_NHWC:
+        frames = torch.randint(0, 256, (n, h, w, 3), generator=g, dtype=torch.uint8)
+        x64, x32 = ref.normalise(frames, torch.float64), ref.normalise(frames, torch.float32)      # signed: mean / std
+        given = frames
+    else:
+        x32 = torch.randn(n, cin, h, w, generator=g)                                               # signed
+        x64 = x32.double()
+        given = x32 if kind == L.VS_CNN_INPUT_F32_NCHW else x32.permute(0, 2, 3, 1).contiguous()
+
+    def restated(x, dt):
+        y = F.conv2d(x, wt.to(dt), None, stride, pad)
+        y = F.batch_norm(y, mean.to(dt), var.to(dt), gamma.to(dt), beta.to(dt), training=False, eps=0.001)
+        return F.relu(y).permute(0, 2, 3, 1).contiguous()                                          # NHWC
+
+    want, cpu32 = restated(x64, torch.float64), restated(x32, torch.float32)
+    assert (want == 0).any() and (want > 0).any()                                                  # the ReLU cuts something
+    ho, wo = want.shape[1], want.shape[2]
+    m = n * ho * wo
+    P = L.CnnConvParams()
+    keep = [t.to(dev).contiguous() for t in (wt, gamma, beta, mean, var)]
+    for f, t in zip(("weight", "gamma", "beta", "running_mean", "running_var"), keep):
+        setattr(P, f, t.data_ptr())
+    packed = torch.empty(lib.vs_cnn_packed_floats(cout, cin, k), dtype=torch.float32, device=dev)
+    assert packed.numel() > 0
+    given = given.to(dev)
+    out = torch.full((GUARD + m * ldc + GUARD,), CANARY, dtype=torch.float32, device=dev)
+    L.check(lib.vs_cnn_pack_conv(C.byref(P), cout, cin, k, packed.data_ptr(), None))
+    L.check(lib.vs_cnn_conv(given.data_ptr(), kind, n, h, w, cin, packed.data_ptr(), cout, k, stride, pad,
+                            out[GUARD:].data_ptr(), c0, ldc, None))
+    torch.cuda.synchronize()
+    out = out.cpu()
+    assert (out[:GUARD] == CANARY).all() and (out[GUARD + m * ldc:] == CANARY).all()
+    body = out[GUARD:GUARD + m * ldc].view(n, ho, wo, ldc)
+    assert (body[..., :c0] == CANARY).all() and (body[..., c0 + cout:] == CANARY).all()            # the other channels: untouched
+    return body[..., c0:c0 + cout], want, cpu32
+
+
+CONVS = {   # name: (n, h, w, cin, cout, k, stride, pad, kind, c0, ldc)
+    "7x7s2p3 3->64 2x37x45 f32 nchw": (2, 37, 45, 3, 64, 7, 2, 3, 0, 0, None),
+    "7x7s2p3 3->64 2x37x45 uint8": (2, 37, 45, 3, 64, 7, 2, 3, 1, 0, None),
+    "3x3p1 64->192 3x9x7": (3, 9, 7, 64, 192, 3, 1, 1, 2, 0, None),
+    "1x1 480->16 2x5x7": (2, 5, 7, 480, 16, 1, 1, 0, 2, 0, None),
+    "1x1 512->24 1x9x8": (1, 9, 8, 512, 24, 1, 1, 0, 2, 0, None),
+    "1x1 832->384 5x7x7": (5, 7, 7, 832, 384, 1, 1, 0, 2, 0, None),
+    "3x3p1 24->64 1x2x3": (1, 2, 3, 24, 64, 3, 1, 1, 2, 0, None),
+    "3x3p1 96->208 2x6x5 at c0=192 of 512": (2, 6, 5, 96, 208, 3, 1, 1, 2, 192, 512),
+    "1x1 512->144 2x3x11 at c0=112 of 300": (2, 3, 11, 512, 144, 1, 1, 0, 2, 112, 300),
+}
+
+
+@pytest.mark.parametrize("name", list(CONVS))
+def test_single_conv_against_float64(vsa, name):
+    n, h, w, cin, cout, k, stride, pad, kind, c0, ldc = CONVS[name]
+    got, want, cpu32 = _conv_case(vsa, 100 + list(CONVS).index(name), n, h, w, cin, cout, k, stride, pad, kind, c0, ldc)
+    assert got.shape == want.shape
+    _report("conv " + name, got, want, cpu32)
+
+
+def test_conv_padding_tap_of_uint8_frames_is_zero_after_normalisation(vsa):
+    """all-zero frames: a padding tap that read (0 - mean) / std would be right at the border by accident, a padding tap that
+    reads 0 is what the reference's zero padding of the normalised tensor gives; 255-valued frames tell the two apart too"""
+    L = vsa._lib
+    for value in (0, 255):
+        lib, dev = L.load(), _dev()
+        frames = torch.full((1, 9, 10, 3), value, dtype=torch.uint8)
+        g = torch.Generator().manual_seed(7)
+        wt = torch.randn(64, 3, 7, 7, generator=g) * 0.1
+        one, zero = torch.ones(64), torch.zeros(64)
+        want = F.relu(F.batch_norm(F.conv2d(ref.normalise(frames, torch.float64), wt.double(), None, 2, 3), zero.double(), one.double(),
+                                   one.double(), zero.double(), training=False, eps=0.001)).permute(0, 2, 3, 1)
+        P = L.CnnConvParams()
+        keep = [t.to(dev) for t in (wt, one, zero, zero, one)]
+        for f, t in zip(("weight", "gamma", "beta", "running_mean", "running_var"), keep):
+            setattr(P, f, t.data_ptr())
+        packed = torch.empty(lib.vs_cnn_packed_floats(64, 3, 7), dtype=torch.float32, device=dev)
+        out = torch.empty(want.shape, dtype=torch.float32, device=dev)
+        fr = frames.to(dev)
+        L.check(lib.vs_cnn_pack_conv(C.byref(P), 64, 3, 7, packed.data_ptr(), None))
+        L.check(lib.vs_cnn_conv(fr.data_ptr(), L.VS_CNN_INPUT_U8_NHWC, 1, 9, 10, 3, packed.data_ptr(), 64, 7, 2, 3, out.data_ptr(), 0, 64, None))
+        torch.cuda.synchronize()
+        _report("conv1 uint8 frames all %d, border taps" % value, out, want)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# pools: bit-equal to torch
+# ------------------------------------------------------------------------------------------------------------------------
+POOLS = {   # name: (n, h, w, c, k, stride, pad)
+    "k3s2 ceil 7x7 C=528": (2, 7, 7, 528, 3, 2, 0),
+    "k3s2 ceil 8x9": (2, 8, 9, 64, 3, 2, 0),
+    "k3s1p1 5x4": (3, 5, 4, 24, 3, 1, 1),
+    "k2s2 ceil 7x5": (2, 7, 5, 832, 2, 2, 0),
+    "k3s2 ceil 2x3 (window larger than the input)": (1, 2, 3, 4, 3, 2, 0),
+}
+
+
+@pytest.mark.parametrize("name", list(POOLS))
+def test_maxpool_is_bit_equal_to_torch(vsa, name):
+    n, h, w, c, k, stride, pad = POOLS[name]
+    L = vsa._lib
+    lib, dev = L.load(), _dev()
+    g = torch.Generator().manual_seed(200 + list(POOLS).index(name))
+    x = torch.randn(n, c, h, w, generator=g) - 2.0                  # mostly negative: zero padding instead of -inf would win
+    if h * w > 6:                                                   # (the one-window case keeps a negative maximum)
+        x[:, :, 0, 0] = -0.0
+    want = F.max_pool2d(x, k, stride, pad, ceil_mode=True).permute(0, 2, 3, 1).contiguous()
+    assert (want < 0).any()
+    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
+    out = torch.full((GUARD + want.numel() + GUARD,), CANARY, dtype=torch.float32, device=dev)
+    L.check(lib.vs_cnn_maxpool(xd.data_ptr(), n, h, w, c, k, stride, pad, 1, out[GUARD:].data_ptr(), None))
+    torch.cuda.synchronize()
+    out = out.cpu()
+    assert (out[:GUARD] == CANARY).all() and (out[GUARD + want.numel():] == CANARY).all()
+    got = out[GUARD:GUARD + want.numel()].view(want.shape)
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    print("features_parity %-44s bit-equal to F.max_pool2d" % ("maxpool " + name))
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the whole network
+# ------------------------------------------------------------------------------------------------------------------------
+WSEED = 11
+SHAPES = ((1, 224, 224), (1, 224, 398), (3, 64, 80), (2, 33, 47), (2, 17, 15))
+
+
+@pytest.fixture(scope="module")
+def sd(vsa):
+    return vsa.features.make_state_dict(WSEED)
+
+
+@pytest.fixture(scope="module")
+def model(vsa, sd):
+    m = vsa.GoogLeNetFeatures()
+    m.load_state_dict(sd, strict=True)
+    return m.to(_dev())
+
+
+def _frames(shape, seed):
+    return torch.randint(0, 256, shape + (3,), generator=torch.Generator().manual_seed(seed), dtype=torch.uint8)
+
+
+_REFS = {}
+
+
+def _reference(sd, shape):
+    """(frames, float64 features, torch's fp32 CPU features) of a shape: computed once, shared, never written"""
+    if shape not in _REFS:
+        frames = _frames(shape, 300 + SHAPES.index(shape))
+        want = ref.forward(ref.cast(sd, torch.float64), ref.normalise(frames, torch.float64))
+        cpu32 = ref.forward(ref.cast(sd, torch.float32), ref.normalise(frames, torch.float32))
+        _REFS[shape] = (frames, want, cpu32)
+    return _REFS[shape]
+
+
+@pytest.mark.parametrize("kind", ("uint8 frames", "float32 nchw"))
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%dx%d" % s)
+def test_whole_network_against_float64(model, sd, shape, kind):
+    frames, want, cpu32 = _reference(sd, shape)
+    if kind == "uint8 frames":
+        got = model.extract(frames.to(_dev()))
+    else:
+        got = model(ref.normalise(frames, torch.float32).to(_dev()))
+    assert got.shape == (shape[0], 1024) and got.dtype == torch.float32 and got.is_cuda
+    _report("network %dx%dx%d %s" % (shape + (kind,)), got, want, cpu32)
+
+
+def test_a_frame_does_not_depend_on_its_batch(model):
+    dev = _dev()
+    frames = _frames((5, 33, 47), 400).to(dev)
+    x = ref.normalise(frames.cpu(), torch.float32).to(dev)
+    for run, data in ((model.extract, frames), (model.forward, x)):
+        five = run(data)
+        for i in range(5):
+            alone = run(data[i:i + 1])
+            assert torch.equal(alone[0].view(torch.int32), five[i].view(torch.int32)), i
+            others = [j for j in range(5) if j != i][:2]
+            three = run(data[others + [i]])
+            assert torch.equal(three[2].view(torch.int32), five[i].view(torch.int32)), i
+    assert (five[0] != five[1]).any()
+
+
+def test_extract_in_chunks_is_bit_equal_to_one_call(vsa, model, sd):
+    dev = _dev()
+    frames = _frames((7, 33, 47), 401).to(dev)
+    whole = model.extract(frames)
+    chunked = vsa.GoogLeNetFeatures(max_batch=3)
+    chunked.load_state_dict(sd, strict=True)
+    chunked = chunked.to(dev)
+    part = chunked.extract(frames)
+    assert part.shape == (7, 1024) and torch.equal(part.view(torch.int32), whole.view(torch.int32))
+    x = ref.normalise(frames.cpu(), torch.float32).to(dev)
+    assert torch.equal(chunked(x).view(torch.int32), model(x).view(torch.int32))
+
+
+def test_reference_sequential_names_give_the_same_bits(vsa, model, sd):
+    dev = _dev()
+    other = vsa.GoogLeNetFeatures()
+    other.load_state_dict(vsa.features.to_sequential_names(sd), strict=True)
+    other = other.to(dev)
+    frames = _frames((2, 17, 15), 402).to(dev)
+    assert torch.equal(other.extract(frames).view(torch.int32), model.extract(frames).view(torch.int32))
+
+
+def test_repack_after_the_weights_change(vsa, sd):
+    """the packed model follows (data_ptr, _version): new values through load_state_dict give new features, the old values the old"""
+    dev = _dev()
+    m = vsa.GoogLeNetFeatures()
+    m.load_state_dict(sd, strict=True)
+    m = m.to(dev)
+    frames = _frames((1, 17, 15), 403).to(dev)
+    a = m.extract(frames)
+    packed = m._packed
+    assert m.extract(frames) is not None and m._packed is packed                 # cached
+    m.load_state_dict(vsa.features.make_state_dict(WSEED + 1), strict=True)
+    b = m.extract(frames)
+    assert m._packed is not packed and (a != b).any()
+    m.load_state_dict(sd, strict=True)
+    assert torch.equal(m.extract(frames).view(torch.int32), a.view(torch.int32))
+    assert torch.equal(m.train().extract(frames).view(torch.int32), a.view(torch.int32))       # train(): still the running statistics
+
+
+def test_a_frame_below_the_smallest_side_is_refused_with_the_reason(model):
+    with pytest.raises(RuntimeError, match="smallest h, w: 15"):
+        model.extract(torch.zeros(1, 14, 20, 3, dtype=torch.uint8, device=_dev()))
+    assert model.extract(torch.zeros(1, 15, 17, 3, dtype=torch.uint8, device=_dev())).shape == (1, 1024)     # torch accepts it too
+
+
+def test_frames_to_scores_without_leaving_the_device(vsa, model):
+    dev = _dev()
+    frames = _frames((6, 33, 47), 404).to(dev)
+    feats = model.extract(frames)
+    assert feats.is_cuda and feats.shape == (6, 1024)
+    scorer = vsa.SimNet(num_heads=4, d_model=256, num_layers=2, sparsity=0.0, dropout=0.0)
+    scorer.load_state_dict(vsa.synth.make_state_dict(256, 2, seed=5), strict=True)
+    scorer = scorer.to(dev).eval()
+    scores = scorer.score(feats.unsqueeze(0))
+    assert scores.is_cuda and scores.shape == (1, 6) and torch.isfinite(scores).all()
+    assert ((scores > 0) & (scores < 1)).all()

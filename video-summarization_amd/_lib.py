@@ -21,7 +21,7 @@ DIAG_LIB_PATH = os.path.join(HERE, "libvsscore_diag.so")
 SOURCES = ("vs_kernels.hip", "vs_attention.hip", "vs_attention_w64.hip", "vs_mlp_fused.hip", "vs_gemm_ring.hip", "vs_scorer.cpp", "vs_eval.cpp",
            "vs_train_kernels.hip", "vs_train_attention.hip", "vs_train_attention_bf16.hip", "vs_train_gemm_rows.hip", "vs_pretrain_kernels.hip",
            "vs_train.cpp", "vs_segment.hip", "vs_segment_gram.hip", "vs_segment.cpp", "vs_optim.hip", "vs_attention_maps.hip",
-           "vs_eval_device.hip", "vs_eval_device.cpp", "vs_summary.hip", "vs_summary.cpp", "vs_batch.hip")
+           "vs_eval_device.hip", "vs_eval_device.cpp", "vs_summary.hip", "vs_summary.cpp", "vs_batch.hip", "vs_cnn.hip", "vs_cnn.cpp")
 ABI_VERSION = 3
 
 VS_OK, VS_ERR_INVALID, VS_ERR_WORKSPACE, VS_ERR_HIP = 0, 1, 2, 3
@@ -41,6 +41,8 @@ VS_GRAD_NORM_L2, VS_GRAD_NORM_MAX = 0, 1
 VS_KTS_FEATURES_F32, VS_KTS_KERNEL_F32, VS_KTS_KERNEL_F64 = 0, 1, 2
 VS_KTS_SCORES, VS_KTS_BACKTRACK, VS_KTS_AUTO = 0, 1, 2
 VS_KTS_GRAM_DOT, VS_KTS_GRAM_COSINE, VS_KTS_GRAM_RBF = 0, 1, 2
+VS_CNN_INPUT_F32_NCHW, VS_CNN_INPUT_U8_NHWC, VS_CNN_INPUT_F32_NHWC = 0, 1, 2
+VS_CNN_NUM_CONVS, VS_CNN_FEATURES = 57, 1024
 NUM_STAGES = 6
 
 
@@ -96,6 +98,14 @@ class KtsKernel(C.Structure):   # vs_kts_kernel (include/vs_segment.h)
 
 class GradTensor(C.Structure):  # vs_grad_tensor
     _fields_ = [("g", C.c_void_p), ("n", C.c_size_t)]
+
+
+class CnnConvParams(C.Structure):   # vs_cnn_conv_params (include/features/vs_features.h)
+    _fields_ = [(n, C.c_void_p) for n in ("weight", "gamma", "beta", "running_mean", "running_var")]
+
+
+class CnnParams(C.Structure):       # vs_cnn_params
+    _fields_ = [("conv", CnnConvParams * VS_CNN_NUM_CONVS)]
 
 
 # --------------------------------------------------------------------------------------------
@@ -265,6 +275,22 @@ _PACKED_INSPECT_BINDINGS = {
 }
 PACKED_INSPECT_EXPORTS = tuple(_PACKED_INSPECT_BINDINGS)
 
+# The GoogLeNet pool5 frame features: include/features/vs_features.h, a table of its own beside the two above, with the same
+# form and the same check (tests/test_features_host.py).
+FEATURES_HEADER = os.path.join("features", "vs_features.h")
+_FEATURES_BINDINGS = {
+    "vs_cnn_pack": (_RC, [_ref(CnnParams), _P, _ref(_P)]),
+    "vs_cnn_free": (None, [_P]),
+    "vs_cnn_min_side": (_I, []),
+    "vs_cnn_workspace_bytes": (_Z, [_I] * 3),
+    "vs_cnn_forward": (_RC, [_P, _P] + [_I] * 4 + [_P, _P, _Z, _P]),
+    "vs_cnn_packed_floats": (_Z, [_I] * 3),
+    "vs_cnn_pack_conv": (_RC, [_ref(CnnConvParams)] + [_I] * 3 + [_P, _P]),
+    "vs_cnn_conv": (_RC, [_P] + [_I] * 5 + [_P] + [_I] * 4 + [_P, _I, _I, _P]),
+    "vs_cnn_maxpool": (_RC, [_P] + [_I] * 8 + [_P, _P]),
+}
+FEATURES_EXPORTS = tuple(_FEATURES_BINDINGS)
+
 
 def hipcc_path() -> str:
     for p in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc"):
@@ -279,6 +305,7 @@ def needs_build() -> bool:
     t = os.path.getmtime(LIB_PATH)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE)]
     deps.append(os.path.join(INCLUDE, PACKED_INSPECT_HEADER))
+    deps.append(os.path.join(INCLUDE, FEATURES_HEADER))
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -342,14 +369,23 @@ def _bind(lib) -> None:
         raise RuntimeError("libvsscore.so ABI %d != binding ABI %d" % (lib.vs_abi_version(), ABI_VERSION))
 
 
-def _bind_packed_inspect(lib) -> None:
-    """``_bind`` for the table of include/packed/vs_inspect_packed.h: every symbol present, then the signatures."""
-    for name in _PACKED_INSPECT_BINDINGS:
+def _bind_table(lib, table) -> None:
+    for name in table:
         if not hasattr(lib, name):
             raise RuntimeError("libvsscore.so lacks symbol %s (stale build?)" % name)
-    for name, (restype, argtypes) in _PACKED_INSPECT_BINDINGS.items():
+    for name, (restype, argtypes) in table.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
+
+
+def _bind_packed_inspect(lib) -> None:
+    """``_bind`` for the table of include/packed/vs_inspect_packed.h: every symbol present, then the signatures."""
+    _bind_table(lib, _PACKED_INSPECT_BINDINGS)
+
+
+def _bind_features(lib) -> None:
+    """``_bind`` for the table of include/features/vs_features.h."""
+    _bind_table(lib, _FEATURES_BINDINGS)
 
 
 _lib = None
@@ -374,6 +410,7 @@ def load() -> C.CDLL:
         lib = C.CDLL(path)
         _bind(lib)
         _bind_packed_inspect(lib)
+        _bind_features(lib)
         _lib = lib
     return _lib
 
