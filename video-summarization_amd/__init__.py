@@ -17,9 +17,9 @@ from .segmentation import get_segment_fn, kts_seg, kts_seg_batch  # noqa: F401
 from . import summary  # noqa: F401
 from .summary import summarize, summarize_scores  # noqa: F401
 from . import features  # noqa: F401
-from .features import GoogLeNetFeatures, get_google_net_features  # noqa: F401
+from .features import GoogLeNetFeatures, get_google_net_features, resize_frames_device, resize_output_size  # noqa: F401
 
 __all__ = ["SimNet", "PretrainModel", "score_frames", "synth", "mse_with_mask_loss", "mse_packed_loss", "segmentation", "get_segment_fn", "kts_seg",
            "kts_seg_batch", "optim", "Adam", "AdamW", "clip_grad_norm_", "grad_norm", "collate_fn_pretrain_packed", "pretrain_step_packed", "summary", "summarize",
            "summarize_scores", "TrainSet", "PretrainSet", "epoch_plan", "train_epoch_resident", "pretrain_epoch_resident", "features",
-           "GoogLeNetFeatures", "get_google_net_features"]
+           "GoogLeNetFeatures", "get_google_net_features", "resize_frames_device", "resize_output_size"]

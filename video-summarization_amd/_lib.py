@@ -21,7 +21,10 @@ DIAG_LIB_PATH = os.path.join(HERE, "libvsscore_diag.so")
 SOURCES = ("vs_kernels.hip", "vs_attention.hip", "vs_attention_w64.hip", "vs_mlp_fused.hip", "vs_gemm_ring.hip", "vs_scorer.cpp", "vs_eval.cpp",
            "vs_train_kernels.hip", "vs_train_attention.hip", "vs_train_attention_bf16.hip", "vs_train_gemm_rows.hip", "vs_pretrain_kernels.hip",
            "vs_train.cpp", "vs_segment.hip", "vs_segment_gram.hip", "vs_segment.cpp", "vs_optim.hip", "vs_attention_maps.hip",
-           "vs_eval_device.hip", "vs_eval_device.cpp", "vs_summary.hip", "vs_summary.cpp", "vs_batch.hip", "vs_cnn.hip", "vs_cnn.cpp")
+           "vs_eval_device.hip", "vs_eval_device.cpp", "vs_summary.hip", "vs_summary.cpp", "vs_batch.hip", "vs_cnn.hip", "vs_cnn.cpp",
+           "vs_resize.hip", "vs_resize.cpp")
+# vs_resize.cpp computes PIL's coefficient tables in double: no multiply-add of it may be contracted, whatever the host
+EXTRA_FLAGS = {"vs_resize.cpp": ("-ffp-contract=off",)}
 ABI_VERSION = 3
 
 VS_OK, VS_ERR_INVALID, VS_ERR_WORKSPACE, VS_ERR_HIP = 0, 1, 2, 3
@@ -43,6 +46,8 @@ VS_KTS_SCORES, VS_KTS_BACKTRACK, VS_KTS_AUTO = 0, 1, 2
 VS_KTS_GRAM_DOT, VS_KTS_GRAM_COSINE, VS_KTS_GRAM_RBF = 0, 1, 2
 VS_CNN_INPUT_F32_NCHW, VS_CNN_INPUT_U8_NHWC, VS_CNN_INPUT_F32_NHWC = 0, 1, 2
 VS_CNN_NUM_CONVS, VS_CNN_FEATURES = 57, 1024
+VS_RESIZE_SWAP_RB = 1
+VS_RESIZE_PATH_FUSED, VS_RESIZE_PATH_SMALL_TILE = 0, 1
 NUM_STAGES = 6
 
 
@@ -291,6 +296,18 @@ _FEATURES_BINDINGS = {
 }
 FEATURES_EXPORTS = tuple(_FEATURES_BINDINGS)
 
+# The frame resize in front of them: include/features/vs_resize.h, again a table of its own (tests/test_resize_host.py).
+RESIZE_HEADER = os.path.join("features", "vs_resize.h")
+_RESIZE_BINDINGS = {
+    "vs_resize_output_size": (_RC, [_I] * 3 + [_ref(_I)] * 2),
+    "vs_resize_plan_create": (_RC, [_I] * 4 + [_P, _ref(_P)]),
+    "vs_resize_plan_free": (None, [_P]),
+    "vs_resize_plan_describe": (_RC, [_P] + [_ref(_I)] * 3),
+    "vs_resize_workspace_bytes": (_Z, [_P, _I]),
+    "vs_resize_run": (_RC, [_P, _P, _I, _U32, _P, _P, _Z, _P]),
+}
+RESIZE_EXPORTS = tuple(_RESIZE_BINDINGS)
+
 
 def hipcc_path() -> str:
     for p in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc"):
@@ -306,6 +323,7 @@ def needs_build() -> bool:
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE)]
     deps.append(os.path.join(INCLUDE, PACKED_INSPECT_HEADER))
     deps.append(os.path.join(INCLUDE, FEATURES_HEADER))
+    deps.append(os.path.join(INCLUDE, RESIZE_HEADER))
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -331,7 +349,7 @@ def _build(out_path: str, extra, verbose: bool) -> str:
 
     def compile_one(pair):
         src, obj = pair
-        cmd = [hipcc_path()] + flags + ["-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [hipcc_path()] + flags + list(EXTRA_FLAGS.get(src, ())) + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd))
         return subprocess.run(cmd, capture_output=True, text=True)
@@ -388,6 +406,11 @@ def _bind_features(lib) -> None:
     _bind_table(lib, _FEATURES_BINDINGS)
 
 
+def _bind_resize(lib) -> None:
+    """``_bind`` for the table of include/features/vs_resize.h."""
+    _bind_table(lib, _RESIZE_BINDINGS)
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -411,6 +434,7 @@ def load() -> C.CDLL:
         _bind(lib)
         _bind_packed_inspect(lib)
         _bind_features(lib)
+        _bind_resize(lib)
         _lib = lib
     return _lib
 

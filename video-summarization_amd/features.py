@@ -10,6 +10,9 @@ own statistics - a frame's features would depend on the frames it is batched wit
 module always uses the running statistics, which is what every published ``google_pool5`` feature set uses.  ``train()`` does not
 change that.
 
+The reference's ``transforms.Resize`` in front of the network: ``resize_frames`` on the host through PIL (the default), or
+``resize_frames_device`` / ``extract(frames, size=...)`` on the device, bit-equal to it (C ABI: ``include/features/vs_resize.h``).
+
 There is no CPU path: a CPU tensor raises.
 """
 from __future__ import annotations
@@ -222,15 +225,46 @@ class GoogLeNetFeatures(nn.Module):
         return self._run(x, _lib.VS_CNN_INPUT_F32_NCHW, x.size(0), x.size(2), x.size(3))
 
     @torch.no_grad()
-    def extract(self, frames: Tensor) -> Tensor:
-        """``frames``: ``[N, H, W, 3]`` uint8 RGB on the device -> ``[N, 1024]``; x / 255, - mean, / std happen in conv1"""
+    def extract(self, frames: Tensor, size=None, bgr: bool = False) -> Tensor:
+        """``frames``: ``[N, H, W, 3]`` uint8 RGB on the device -> ``[N, 1024]``; x / 255, - mean, / std happen in conv1.
+        ``size`` (an int for the shorter side, or (h, w)) resizes on the device first, bit-equal to the reference's
+        ``transforms.Resize(size)`` on PIL images: each chunk of ``max_batch`` frames is resized into scratch and fed to conv1,
+        so the resized video is never held whole.  ``bgr=True`` takes decoded OpenCV frames (B, G, R)."""
         self._check_hip(frames)
         if frames.dim() != 4 or frames.size(3) != 3 or frames.dtype != torch.uint8:
             raise ValueError("expected a uint8 [N, H, W, 3] tensor, got %s %s" % (frames.dtype, tuple(frames.shape)))
         if frames.size(0) == 0:
             return torch.empty((0, _lib.VS_CNN_FEATURES), dtype=torch.float32, device=frames.device)
         frames = frames.contiguous()
-        return self._run(frames, _lib.VS_CNN_INPUT_U8_NHWC, frames.size(0), frames.size(1), frames.size(2))
+        if size is None and not bgr:
+            return self._run(frames, _lib.VS_CNN_INPUT_U8_NHWC, frames.size(0), frames.size(1), frames.size(2))
+        return self._run_resized(frames, size, bgr)
+
+    def _run_resized(self, frames: Tensor, size, bgr: bool) -> Tensor:
+        """``_run`` with the device resize (and / or the R/B swap) in front of conv1, chunk by chunk"""
+        lib = _lib.load()
+        dev = frames.device
+        n, h, w = frames.size(0), frames.size(1), frames.size(2)
+        oh, ow = (h, w) if size is None else resize_output_size(h, w, size)
+        plan = _resize_plan(dev, h, w, oh, ow)
+        packed = self._packed_weights(dev)
+        out = torch.empty((n, _lib.VS_CNN_FEATURES), dtype=torch.float32, device=dev)
+        step = min(n, self.max_batch)
+        need = lib.vs_cnn_workspace_bytes(step, oh, ow)
+        flags = _lib.VS_RESIZE_SWAP_RB if bgr else 0
+        with on_stream(dev) as stream:
+            if need == 0:
+                _lib.check(_lib.VS_ERR_INVALID)
+            ws = scratch(need, dev, floor=256)
+            small = torch.empty((step, oh, ow, 3), dtype=torch.uint8, device=dev)
+            rws = scratch(lib.vs_resize_workspace_bytes(plan.handle, step), dev)
+            for at in range(0, n, step):
+                chunk = frames.narrow(0, at, min(step, n - at))
+                _lib.check(lib.vs_resize_run(plan.handle, chunk.data_ptr(), chunk.size(0), flags, small.data_ptr(),
+                                             rws.data_ptr() if rws.numel() else None, rws.numel(), stream))
+                _lib.check(lib.vs_cnn_forward(packed.handle, small.data_ptr(), _lib.VS_CNN_INPUT_U8_NHWC, chunk.size(0), oh, ow,
+                                              out[at:].data_ptr(), ws.data_ptr(), ws.numel(), stream))
+        return out
 
 
 def resize_frames(video, size):
@@ -253,12 +287,94 @@ def resize_frames(video, size):
     return out
 
 
-def get_google_net_features(video, size=224, *, model: GoogLeNetFeatures = None, weights=None, device="cuda"):
-    """Drop-in for the reference's function: ``video`` numpy uint8 ``[T, H, W, 3]`` -> numpy float32 ``[T, 1024]``.  The resize
-    runs on the host exactly as in the reference (``size=None`` skips it); everything after it on the device.  Pretrained weights
+def resize_output_size(h: int, w: int, size):
+    """(oh, ow) of ``transforms.Resize(size)`` for an ``h x w`` image: an int scales the shorter side to ``size`` and the longer
+    to ``int(size * long / short)`` (``w <= h`` counts as "w is shorter"), a pair is (h, w).  The rule inside ``resize_frames``,
+    computed by the library (``vs_resize_output_size``)."""
+    if isinstance(size, int):
+        oh, ow = C.c_int32(), C.c_int32()
+        _lib.check(_lib.load().vs_resize_output_size(int(h), int(w), size, C.byref(oh), C.byref(ow)))
+        return oh.value, ow.value
+    oh, ow = size
+    return int(oh), int(ow)
+
+
+class _ResizePlan:
+    """vs_resize_plan* of one (device, geometry): the coefficient tables on the device and the tile the host chose"""
+
+    def __init__(self, device, h, w, oh, ow):
+        self.handle = C.c_void_p()
+        with on_stream(device) as stream:
+            _lib.check(_lib.load().vs_resize_plan_create(h, w, oh, ow, stream, C.byref(self.handle)))
+        path, th, tw = C.c_int32(), C.c_int32(), C.c_int32()
+        _lib.check(_lib.load().vs_resize_plan_describe(self.handle, C.byref(path), C.byref(th), C.byref(tw)))
+        self.path, self.tile = path.value, (th.value, tw.value)
+
+    def __del__(self):
+        try:
+            if self.handle:
+                _lib.load().vs_resize_plan_free(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+_RESIZE_PLANS = {}
+
+
+def _resize_plan(device, h, w, oh, ow) -> _ResizePlan:
+    key = (torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device(), h, w, oh, ow)
+    plan = _RESIZE_PLANS.get(key)
+    if plan is None:
+        plan = _RESIZE_PLANS[key] = _ResizePlan(device, h, w, oh, ow)
+    return plan
+
+
+def resize_plan_path(device, h: int, w: int, oh: int, ow: int):
+    """(path, (tile_oh, tile_ow)) the cached plan of this geometry chose: ``_lib.VS_RESIZE_PATH_FUSED`` for the default tile,
+    ``_lib.VS_RESIZE_PATH_SMALL_TILE`` where its input rows or columns would not fit the LDS staging"""
+    plan = _resize_plan(device, h, w, oh, ow)
+    return plan.path, plan.tile
+
+
+@torch.no_grad()
+def resize_frames_device(frames: Tensor, size, *, bgr: bool = False) -> Tensor:
+    """``resize_frames`` on the device: uint8 ``[N, H, W, 3]`` on a HIP device -> uint8 ``[N, oh, ow, 3]``, bit-equal to
+    ``PIL.Image.resize((ow, oh), Image.BILINEAR)`` frame by frame (C ABI: ``include/features/vs_resize.h``).  ``bgr=True`` swaps
+    R and B on the way (decoded OpenCV frames).  With equal sizes and ``bgr=False`` the input itself is returned.  Plans (the
+    coefficient tables) are cached per (device, geometry).  There is no CPU path: a CPU tensor raises."""
+    if not frames.is_cuda:
+        raise RuntimeError("resize_frames_device runs on the MI355X HIP kernel only: move the frames to a HIP device "
+                           "(there is no CPU path; resize_frames is the host form)")
+    if frames.dim() != 4 or frames.size(3) != 3 or frames.dtype != torch.uint8:
+        raise ValueError("expected a uint8 [N, H, W, 3] tensor, got %s %s" % (frames.dtype, tuple(frames.shape)))
+    n, h, w = frames.size(0), frames.size(1), frames.size(2)
+    oh, ow = resize_output_size(h, w, size)
+    if (oh, ow) == (h, w) and not bgr:
+        return frames
+    out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=frames.device)
+    if n == 0:
+        return out
+    frames = frames.contiguous()
+    lib = _lib.load()
+    plan = _resize_plan(frames.device, h, w, oh, ow)
+    with on_stream(frames.device) as stream:
+        ws = scratch(lib.vs_resize_workspace_bytes(plan.handle, n), frames.device)
+        _lib.check(lib.vs_resize_run(plan.handle, frames.data_ptr(), n, _lib.VS_RESIZE_SWAP_RB if bgr else 0, out.data_ptr(),
+                                     ws.data_ptr() if ws.numel() else None, ws.numel(), stream))
+    return out
+
+
+def get_google_net_features(video, size=224, *, model: GoogLeNetFeatures = None, weights=None, device="cuda", resize="host"):
+    """Drop-in for the reference's function: ``video`` numpy uint8 ``[T, H, W, 3]`` -> numpy float32 ``[T, 1024]``.  With
+    ``resize="host"`` (the default) the resize runs on the host exactly as in the reference (``size=None`` skips it) and
+    everything after it on the device; ``resize="device"`` uploads the raw frames in chunks of ``model.max_batch`` and resizes
+    them there, to the same bytes.  Pretrained weights
     are never fetched: pass ``model=`` (a ``GoogLeNetFeatures`` on a HIP device) or ``weights=`` (a path for ``torch.load`` or a
     state dict, a torchvision ``googlenet`` checkpoint or the reference's ``model.<i>`` form)."""
     import numpy as np
+    if resize not in ("host", "device"):
+        raise ValueError("resize must be 'host' or 'device', got %r" % (resize,))
     if model is None:
         if weights is None:
             raise ValueError("get_google_net_features needs model= or weights= (a torchvision googlenet checkpoint): "
@@ -270,8 +386,14 @@ def get_google_net_features(video, size=224, *, model: GoogLeNetFeatures = None,
     video = np.asarray(video)
     if video.ndim != 4 or video.shape[3] != 3 or video.dtype != np.uint8:
         raise ValueError("expected a uint8 [T, H, W, 3] array, got %s %s" % (video.dtype, video.shape))
+    dev = next(model.parameters()).device
+    if resize == "device" and size is not None:
+        out = np.empty((video.shape[0], _lib.VS_CNN_FEATURES), dtype=np.float32)
+        for at in range(0, video.shape[0], model.max_batch):
+            raw = torch.from_numpy(np.ascontiguousarray(video[at:at + model.max_batch])).to(dev)
+            out[at:at + raw.size(0)] = model.extract(raw, size=size).cpu().numpy()
+        return out
     if size is not None:
         video = resize_frames(video, size)
-    dev = next(model.parameters()).device
     frames = torch.from_numpy(np.ascontiguousarray(video)).to(dev)
     return model.extract(frames).cpu().numpy()
