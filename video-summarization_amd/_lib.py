@@ -22,7 +22,7 @@ SOURCES = ("vs_kernels.hip", "vs_attention.hip", "vs_attention_w64.hip", "vs_mlp
            "vs_train_kernels.hip", "vs_train_attention.hip", "vs_train_attention_bf16.hip", "vs_train_gemm_rows.hip", "vs_pretrain_kernels.hip",
            "vs_train.cpp", "vs_segment.hip", "vs_segment_gram.hip", "vs_segment.cpp", "vs_optim.hip", "vs_attention_maps.hip",
            "vs_eval_device.hip", "vs_eval_device.cpp", "vs_summary.hip", "vs_summary.cpp", "vs_batch.hip", "vs_cnn.hip", "vs_cnn.cpp",
-           "vs_resize.hip", "vs_resize.cpp")
+           "vs_resize.hip", "vs_resize.cpp", "vs_weights.cpp", "vs_error.cpp")
 # vs_resize.cpp computes PIL's coefficient tables in double: no multiply-add of it may be contracted, whatever the host
 EXTRA_FLAGS = {"vs_resize.cpp": ("-ffp-contract=off",)}
 ABI_VERSION = 3

@@ -13,14 +13,12 @@
 // Whatever the device arrays hold, stores stay inside the output the HOST integers describe and loads inside the arena:
 // the search returns a slot in [0, B), ids are clamped to [0, V) and source rows to [0, video_start[V]).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "vs_batch.h"
+#include "vs_error.h"
 #include "vs_scorer.h"
-
-int vs_fail_msg(int code, const char *msg);     // vs_scorer.cpp: sets the thread-local error text
 
 namespace {
 
@@ -136,26 +134,17 @@ __global__ __launch_bounds__(NT) void gather_table_rows(const float *table_, int
     }
 }
 
-int failf(int code, const char *fmt, ...) {
-    char buf[384];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return vs_fail_msg(code, buf);
-}
-
 bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
 int check_common(const char *fn, const float *arena, const float *side, const int64_t *video_start, int32_t n_videos,
                  const int32_t *ids, const int32_t *out_start, int32_t B, int32_t d, const float *out, const float *side_out) {
     if (!arena || !video_start || !ids || !out_start || !out)
-        return failf(VS_ERR_INVALID, "%s: arena / video_start / ids / out_start / out is NULL", fn);
+        return vs_failf(VS_ERR_INVALID, "%s: arena / video_start / ids / out_start / out is NULL", fn);
     if ((side == nullptr) != (side_out == nullptr))
-        return failf(VS_ERR_INVALID, "%s: side and side_out go together, one of them is NULL", fn);
-    if (n_videos < 1) return failf(VS_ERR_INVALID, "%s: n_videos=%d (>= 1)", fn, n_videos);
-    if (B < 1) return failf(VS_ERR_INVALID, "%s: B=%d (>= 1)", fn, B);
-    if (d < 1) return failf(VS_ERR_INVALID, "%s: d=%d (>= 1)", fn, d);
+        return vs_failf(VS_ERR_INVALID, "%s: side and side_out go together, one of them is NULL", fn);
+    if (n_videos < 1) return vs_failf(VS_ERR_INVALID, "%s: n_videos=%d (>= 1)", fn, n_videos);
+    if (B < 1) return vs_failf(VS_ERR_INVALID, "%s: B=%d (>= 1)", fn, B);
+    if (d < 1) return vs_failf(VS_ERR_INVALID, "%s: d=%d (>= 1)", fn, d);
     return VS_OK;
 }
 
@@ -170,7 +159,7 @@ int launch_gather(GatherArgs a, int32_t d, void *stream) {
     if (vec) hipLaunchKernelGGL((gather_rows_of_videos<vec4, PADDED>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((gather_rows_of_videos<float, PADDED>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, a);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return failf(VS_ERR_HIP, "batch gather launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return vs_failf(VS_ERR_HIP, "batch gather launch failed: %s", hipGetErrorString(e));
     return VS_OK;
 }
 
@@ -185,7 +174,7 @@ int vs_batch_gather_packed(const float *arena, const float *side_or_null, const 
                               side_out_or_null))
         return rc;
     if (total_rows < B || total_rows >= ((int64_t)1 << 31))
-        return failf(VS_ERR_INVALID, "vs_batch_gather_packed: total_rows=%lld for B=%d videos (every video has a row; < 2^31)",
+        return vs_failf(VS_ERR_INVALID, "vs_batch_gather_packed: total_rows=%lld for B=%d videos (every video has a row; < 2^31)",
                      (long long)total_rows, B);
     GatherArgs a{};
     a.arena = arena; a.side = side_or_null; a.video_start = video_start; a.ids = ids; a.out_start = out_start;
@@ -201,9 +190,9 @@ int vs_batch_gather_padded(const float *arena, const float *side_or_null, const 
     if (int rc = check_common("vs_batch_gather_padded", arena, side_or_null, video_start, n_videos, ids, out_start, B, d, out,
                               side_out_or_null))
         return rc;
-    if (longest < 1) return failf(VS_ERR_INVALID, "vs_batch_gather_padded: longest=%d (>= 1)", longest);
+    if (longest < 1) return vs_failf(VS_ERR_INVALID, "vs_batch_gather_padded: longest=%d (>= 1)", longest);
     if (t_max < longest)
-        return failf(VS_ERR_INVALID, "vs_batch_gather_padded: t_max=%d is below the longest video of the batch (%d frames)", t_max,
+        return vs_failf(VS_ERR_INVALID, "vs_batch_gather_padded: t_max=%d is below the longest video of the batch (%d frames)", t_max,
                      longest);
     GatherArgs a{};
     a.arena = arena; a.side = side_or_null; a.video_start = video_start; a.ids = ids; a.out_start = out_start;
@@ -214,10 +203,10 @@ int vs_batch_gather_padded(const float *arena, const float *side_or_null, const 
 
 int vs_batch_gather_rows(const float *table, int32_t n_rows, const int32_t *ids, int32_t B, int32_t w, float *out,
                          void *stream) {
-    if (!table || !ids || !out) return failf(VS_ERR_INVALID, "vs_batch_gather_rows: table / ids / out is NULL");
-    if (n_rows < 1) return failf(VS_ERR_INVALID, "vs_batch_gather_rows: n_rows=%d (>= 1)", n_rows);
-    if (B < 1) return failf(VS_ERR_INVALID, "vs_batch_gather_rows: B=%d (>= 1)", B);
-    if (w < 1) return failf(VS_ERR_INVALID, "vs_batch_gather_rows: w=%d (>= 1)", w);
+    if (!table || !ids || !out) return vs_failf(VS_ERR_INVALID, "vs_batch_gather_rows: table / ids / out is NULL");
+    if (n_rows < 1) return vs_failf(VS_ERR_INVALID, "vs_batch_gather_rows: n_rows=%d (>= 1)", n_rows);
+    if (B < 1) return vs_failf(VS_ERR_INVALID, "vs_batch_gather_rows: B=%d (>= 1)", B);
+    if (w < 1) return vs_failf(VS_ERR_INVALID, "vs_batch_gather_rows: w=%d (>= 1)", w);
     const bool vec = w % 4 == 0 && aligned16(table) && aligned16(out);
     const int32_t wv = vec ? w / 4 : w;
     const int64_t total = (int64_t)B * wv;
@@ -226,7 +215,7 @@ int vs_batch_gather_rows(const float *table, int32_t n_rows, const int32_t *ids,
     if (vec) hipLaunchKernelGGL(gather_table_rows<vec4>, dim3(grid), dim3(NT), 0, (hipStream_t)stream, table, n_rows, ids, total, wv, out);
     else hipLaunchKernelGGL(gather_table_rows<float>, dim3(grid), dim3(NT), 0, (hipStream_t)stream, table, n_rows, ids, total, wv, out);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return failf(VS_ERR_HIP, "vs_batch_gather_rows launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return vs_failf(VS_ERR_HIP, "vs_batch_gather_rows launch failed: %s", hipGetErrorString(e));
     return VS_OK;
 }
 

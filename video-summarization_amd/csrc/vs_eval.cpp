@@ -14,10 +14,9 @@
 #include <thread>
 #include <vector>
 
+#include "vs_error.h"
 #include "vs_eval_runs.h"
 #include "vs_scorer.h"
-
-int vs_fail_msg(int code, const char *msg);     // vs_scorer.cpp: sets the thread-local error text
 
 namespace {
 

@@ -6,45 +6,22 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <numeric>
 #include <vector>
 
+#include "vs_error.h"
 #include "vs_eval_device.h"
 #include "vs_eval_device_kernels.h"
 #include "vs_eval_runs.h"
 #include "vs_scorer.h"
-
-int vs_fail_msg(int code, const char *msg);     // vs_scorer.cpp: sets the thread-local error text
 
 namespace {
 
 using vs_eval_detail::Ranked;
 using vs_eval_detail::Scratch;
 using vs_eval_detail::rank_runs;
-
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return vs_fail_msg(code, buf);
-}
-
-#define EV_HIP(call)                                                                               \
-    do {                                                                                           \
-        const hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return fail(VS_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));     \
-    } while (0)
-
-#define EV_LAUNCH(call)                                                                            \
-    do {                                                                                           \
-        const int e_ = (call);                                                                     \
-        if (e_ != 0) return fail(VS_ERR_HIP, "%s: %s", #call, hipGetErrorString((hipError_t)e_));  \
-    } while (0)
 
 // 4 * saa, 4 * sbb and 4 * sab are at most n^3 / 3 (the untied case): exact in int64 and, divided by 4, in double
 constexpr int32_t kMaxFrames = 1 << 18;
@@ -88,13 +65,13 @@ namespace {
 
 int check_record(const vs_eval_video &V, int v) {
     if (!V.positions || !V.change_points || !V.user_summary)
-        return fail(VS_ERR_INVALID, "eval_set: video %d has a NULL positions / change_points / user_summary", v);
+        return vs_failf(VS_ERR_INVALID, "eval_set: video %d has a NULL positions / change_points / user_summary", v);
     if (V.n_shots < 1 || V.n_users < 1 || V.n_positions < 1 || V.n_frames < 0 || V.n_scores < 0 || V.user_len < 0)
-        return fail(VS_ERR_INVALID, "eval_set: video %d has an empty or negative field (n_shots=%d n_users=%d n_positions=%d n_frames=%d n_scores=%d)",
+        return vs_failf(VS_ERR_INVALID, "eval_set: video %d has an empty or negative field (n_shots=%d n_users=%d n_positions=%d n_frames=%d n_scores=%d)",
                     v, V.n_shots, V.n_users, V.n_positions, V.n_frames, V.n_scores);
     if (V.user_scores && (V.n_score_users < 1 || V.n_frames < 2))
-        return fail(VS_ERR_INVALID, "eval_set: video %d: user_scores needs n_score_users >= 1 and n_frames >= 2", v);
-    if (V.n_frames > kMaxFrames) return fail(VS_ERR_INVALID, "eval_set: video %d: n_frames=%d above %d", v, V.n_frames, kMaxFrames);
+        return vs_failf(VS_ERR_INVALID, "eval_set: video %d: user_scores needs n_score_users >= 1 and n_frames >= 2", v);
+    if (V.n_frames > kMaxFrames) return vs_failf(VS_ERR_INVALID, "eval_set: video %d: n_frames=%d above %d", v, V.n_frames, kMaxFrames);
     return VS_OK;
 }
 
@@ -117,7 +94,7 @@ int build_video(const vs_eval_video &V, int v, Flat &F, vs_eval_set &set, Ranked
     auto pos = [&](int i) { return i < V.n_positions ? V.positions[i] : nf; };
     for (int i = 0; i + 1 < np_; ++i) {
         const int lo = std::max(0, std::min(pos(i), nf)), hi = std::max(0, std::min(pos(i + 1), nf));
-        if (i > V.n_scores) return fail(VS_ERR_INVALID, "eval_set: video %d: more pick segments than scores + 1", v);
+        if (i > V.n_scores) return vs_failf(VS_ERR_INVALID, "eval_set: video %d: more pick segments than scores + 1", v);
         for (int f = lo; f < hi; ++f) src[f] = i == V.n_scores ? -1 : i;
     }
     std::vector<int> xstart;                      // run r of the prediction covers frames [xstart[r], xstart[r + 1])
@@ -129,20 +106,20 @@ int build_video(const vs_eval_video &V, int v, Flat &F, vs_eval_set &set, Ranked
 
     // shots: generate_summary.py:41-46 and the summary's frames
     const int last_end = V.change_points[2 * (V.n_shots - 1) + 1];
-    if (last_end < 0) return fail(VS_ERR_INVALID, "eval_set: video %d: the last shot ends before frame 0", v);
+    if (last_end < 0) return vs_failf(VS_ERR_INVALID, "eval_set: video %d: the last shot ends before frame 0", v);
     const int summary_len = last_end + 1;
     E.W = (int)((double)(last_end + 1) * 0.15);
     std::vector<int> ca(V.n_shots), cb(V.n_shots);
     int prev_end = -1;
     for (int s = 0; s < V.n_shots; ++s) {
         const int a = V.change_points[2 * s], b = V.change_points[2 * s + 1];
-        if (b - a + 1 < 0) return fail(VS_ERR_INVALID, "eval_set: video %d: shot %d has a negative length", v, s);
+        if (b - a + 1 < 0) return vs_failf(VS_ERR_INVALID, "eval_set: video %d: shot %d has a negative length", v, s);
         const int lo = std::max(0, std::min(a, nf)), hi = std::max(lo, std::min(b + 1, nf));
         F.shot_lo.push_back(lo); F.shot_hi.push_back(hi); F.shot_wt.push_back(b - a + 1);
         ca[s] = std::max(0, a); cb[s] = std::min(summary_len - 1, b);
         const int clip = std::max(0, cb[s] - ca[s] + 1);
         if (clip > 0) {
-            if (ca[s] <= prev_end) return fail(VS_ERR_INVALID, "eval_set: video %d: shot %d overlaps or precedes an earlier shot", v, s);
+            if (ca[s] <= prev_end) return vs_failf(VS_ERR_INVALID, "eval_set: video %d: shot %d overlaps or precedes an earlier shot", v, s);
             prev_end = cb[s];
         }
         F.shot_clip.push_back(clip);
@@ -213,15 +190,15 @@ int upload(vs_eval_set &set, hipStream_t st) {
                   o_lo = place(off, F.shot_lo), o_hi = place(off, F.shot_hi), o_wt = place(off, F.shot_wt),
                   o_clip = place(off, F.shot_clip), o_cnt = place(off, F.cnt), o_xs = place(off, F.xrun_src),
                   o_xw = place(off, F.xrun_w), o_jw = place(off, F.jw), o_jx = place(off, F.jx), o_jy = place(off, F.jy);
-    EV_HIP(hipMalloc(&set.dev, (size_t)std::max<int64_t>(off, 256)));
+    VS_HIP(hipMalloc(&set.dev, (size_t)std::max<int64_t>(off, 256)));
     char *d = (char *)set.dev;
 #define EV_PUT(o, v) \
-    if (!(v).empty()) EV_HIP(hipMemcpyAsync(d + (o), (v).data(), (v).size() * sizeof((v)[0]), hipMemcpyHostToDevice, st))
+    if (!(v).empty()) VS_HIP(hipMemcpyAsync(d + (o), (v).data(), (v).size() * sizeof((v)[0]), hipMemcpyHostToDevice, st))
     EV_PUT(o_vid, F.vid); EV_PUT(o_pairs, F.pairs); EV_PUT(o_src, F.frame_src); EV_PUT(o_lo, F.shot_lo); EV_PUT(o_hi, F.shot_hi);
     EV_PUT(o_wt, F.shot_wt); EV_PUT(o_clip, F.shot_clip); EV_PUT(o_cnt, F.cnt); EV_PUT(o_xs, F.xrun_src); EV_PUT(o_xw, F.xrun_w);
     EV_PUT(o_jw, F.jw); EV_PUT(o_jx, F.jx); EV_PUT(o_jy, F.jy);
 #undef EV_PUT
-    EV_HIP(hipStreamSynchronize(st));
+    VS_HIP(hipStreamSynchronize(st));
     EvStatic &S = set.S;
     S.vid = (const EvVideo *)(d + o_vid); S.pairs = (const EvPair *)(d + o_pairs); S.frame_src = (const int32_t *)(d + o_src);
     S.shot_lo = (const int32_t *)(d + o_lo); S.shot_hi = (const int32_t *)(d + o_hi); S.shot_wt = (const int32_t *)(d + o_wt);
@@ -236,11 +213,11 @@ int upload(vs_eval_set &set, hipStream_t st) {
 // Checks the ids (no GPU) and lays out the run: slots in video_ids order, (slot, user) tasks with the most joint runs first
 // (the long pairs should not start last), the workspace.  The last plan is kept: same ids, nothing to do.
 int make_plan(const vs_eval_set *set, const int32_t *ids, int32_t n_ids, Plan &P) {
-    if (!set) return fail(VS_ERR_INVALID, "eval_set: set is NULL");
-    if (!ids || n_ids < 1) return fail(VS_ERR_INVALID, "eval_set: video_ids is NULL or empty");
+    if (!set) return vs_failf(VS_ERR_INVALID, "eval_set: set is NULL");
+    if (!ids || n_ids < 1) return vs_failf(VS_ERR_INVALID, "eval_set: video_ids is NULL or empty");
     const int32_t nv = (int32_t)set->vid.size();
     for (int32_t i = 0; i < n_ids; ++i)
-        if (ids[i] < 0 || ids[i] >= nv) return fail(VS_ERR_INVALID, "eval_set: video_ids[%d]=%d outside [0, %d)", i, ids[i], nv);
+        if (ids[i] < 0 || ids[i] >= nv) return vs_failf(VS_ERR_INVALID, "eval_set: video_ids[%d]=%d outside [0, %d)", i, ids[i], nv);
     if ((int32_t)P.ids.size() == n_ids && std::equal(ids, ids + n_ids, P.ids.begin())) return VS_OK;
     P = Plan{};
     P.ids.assign(ids, ids + n_ids);
@@ -262,7 +239,7 @@ int make_plan(const vs_eval_set *set, const int32_t *ids, int32_t n_ids, Plan &P
         else s.rows_off = -1;
         for (int32_t u = 0; u < V.n_score_users; ++u) { tasks.push_back(EvTask{i, u}); weight.push_back(set->pairs[V.pair_off + u].m); }
         if (scores > INT32_MAX || P.n_shots > INT32_MAX || P.n_users > INT32_MAX || P.n_xruns > INT32_MAX)
-            return fail(VS_ERR_INVALID, "eval_set: the listed videos exceed 2^31 scores, shots, users or runs");
+            return vs_failf(VS_ERR_INVALID, "eval_set: the listed videos exceed 2^31 scores, shots, users or runs");
     }
     std::vector<int32_t> order(tasks.size());
     std::iota(order.begin(), order.end(), 0);
@@ -292,9 +269,9 @@ int make_plan(const vs_eval_set *set, const int32_t *ids, int32_t n_ids, Plan &P
 extern "C" {
 
 int vs_eval_set_create(const vs_eval_video *videos, int32_t n_videos, void *stream, vs_eval_set **out) {
-    if (!out) return fail(VS_ERR_INVALID, "eval_set: out is NULL");
+    if (!out) return vs_failf(VS_ERR_INVALID, "eval_set: out is NULL");
     *out = nullptr;
-    if (!videos || n_videos < 1) return fail(VS_ERR_INVALID, "eval_set: videos is NULL or n_videos < 1");
+    if (!videos || n_videos < 1) return vs_failf(VS_ERR_INVALID, "eval_set: videos is NULL or n_videos < 1");
     for (int32_t v = 0; v < n_videos; ++v)
         if (int rc = check_record(videos[v], v)) return rc;
     vs_eval_set *set = new vs_eval_set;
@@ -329,28 +306,28 @@ size_t vs_eval_set_workspace_bytes(const vs_eval_set *set, const int32_t *video_
 int vs_eval_set_run(vs_eval_set *set, const float *scores_dev, const int32_t *video_ids, int32_t n_ids, double *f_score,
                     double *kendall, double *spearman, int8_t *selected_or_null, void *workspace, size_t workspace_bytes,
                     void *stream) {
-    if (!set) return fail(VS_ERR_INVALID, "eval_set: set is NULL");
+    if (!set) return vs_failf(VS_ERR_INVALID, "eval_set: set is NULL");
     Plan &P = set->plan;
     if (int rc = make_plan(set, video_ids, n_ids, P)) { P = Plan{}; return rc; }
-    if (!scores_dev || !f_score || !kendall || !spearman) return fail(VS_ERR_INVALID, "eval_set: scores_dev / f_score / kendall / spearman is NULL");
+    if (!scores_dev || !f_score || !kendall || !spearman) return vs_failf(VS_ERR_INVALID, "eval_set: scores_dev / f_score / kendall / spearman is NULL");
     if (!workspace || workspace_bytes < (size_t)P.total)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
-    if (((uintptr_t)workspace & 255) != 0) return fail(VS_ERR_INVALID, "eval_set: workspace is not 256-byte aligned");
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+    if (((uintptr_t)workspace & 255) != 0) return vs_failf(VS_ERR_INVALID, "eval_set: workspace is not 256-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
     if (int rc = upload(*set, st)) return rc;
-    EV_HIP(hipMemcpyAsync(ws, P.up.data(), P.up.size(), hipMemcpyHostToDevice, st));
+    VS_HIP(hipMemcpyAsync(ws, P.up.data(), P.up.size(), hipMemcpyHostToDevice, st));
     EvRun R{};
     R.slots = (const EvSlot *)ws; R.tasks = (const EvTask *)(ws + P.tasks_off); R.scores = scores_dev;
     R.vidout = (int64_t *)(ws + P.vidout_off); R.pairout = (int64_t *)(ws + P.pairout_off); R.ov = (int32_t *)(ws + P.ov_off);
     R.sel = (int8_t *)(ws + P.sel_off); R.val = (double *)(ws + P.val_off); R.rank2x = (int32_t *)(ws + P.rank_off);
     R.bits = (unsigned long long *)(ws + P.bits_off); R.rows = (double *)(ws + P.rows_off);
-    EV_LAUNCH(vsk_eval_summary(set->S, R, n_ids, st));
-    EV_LAUNCH(vsk_eval_xrank(set->S, R, n_ids, st));
-    EV_LAUNCH(vsk_eval_pairs(set->S, R, P.n_tasks, st));
+    VS_LAUNCH_HIP(vsk_eval_summary(set->S, R, n_ids, st));
+    VS_LAUNCH_HIP(vsk_eval_xrank(set->S, R, n_ids, st));
+    VS_LAUNCH_HIP(vsk_eval_pairs(set->S, R, P.n_tasks, st));
     set->down.resize((size_t)(P.down_end - P.vidout_off));
-    EV_HIP(hipMemcpyAsync(set->down.data(), ws + P.vidout_off, set->down.size(), hipMemcpyDeviceToHost, st));
-    EV_HIP(hipStreamSynchronize(st));
+    VS_HIP(hipMemcpyAsync(set->down.data(), ws + P.vidout_off, set->down.size(), hipMemcpyDeviceToHost, st));
+    VS_HIP(hipStreamSynchronize(st));
 
     const char *dn = set->down.data();
     const int64_t *vidout = (const int64_t *)dn, *pairout = (const int64_t *)(dn + (P.pairout_off - P.vidout_off));
@@ -359,7 +336,7 @@ int vs_eval_set_run(vs_eval_set *set, const float *scores_dev, const int32_t *vi
     const EvSlot *slots = (const EvSlot *)P.up.data();
     for (int32_t i = 0; i < n_ids; ++i)
         if (vidout[4 * (size_t)i + 1] != 0)
-            return fail(VS_ERR_INVALID, "eval_set: video_ids[%d]=%d: capacity index out of range in the knapsack back-track (IndexError in the reference)",
+            return vs_failf(VS_ERR_INVALID, "eval_set: video_ids[%d]=%d: capacity index out of range in the knapsack back-track (IndexError in the reference)",
                         i, video_ids[i]);
     if (selected_or_null) std::memcpy(selected_or_null, sel, (size_t)P.n_shots);
     auto pairs = [](long long c) { return c * (c - 1) / 2; };

@@ -36,8 +36,12 @@ struct VskOptions {
 // the bits below; what they mean and which words are valid: vsk_linear_mode (vs_linear_pick.h)
 enum { VSK_STORE16 = 16, VSK_A16 = 32, VSK_F16 = 64 };
 
-// kernel-layout weight image families (vsw_ensure, vs_weights_impl.h)
-enum { VSW_FRAGMENTS = 1, VSW_F16X3 = 2, VSW_BF16 = 4, VSW_ROWS16 = 8 };
+// kernel-layout weight image families (vsw_ensure, vs_weights_impl.h; the table of DESIGN.md section 42)
+enum { VSW_FRAGMENTS = 1, VSW_F16X3 = 2, VSW_BF16 = 4, VSW_ROWS16 = 8,
+       // the training backward's: W^T of every matrix row-major (the dgrad GEMMs), the same in fragment-major order (latency
+       // kernels), and the bf16 copy of every W2^T (the A-stationary gate GEMM of the bf16 training mode)
+       VSW_TRANSPOSED = 16, VSW_TRANSPOSED_FRAGMENTS = 32, VSW_TRANSPOSED_W2_16 = 64,
+       VSW_NUM_FAMILIES = 7 };
 
 // ---- which shapes a kernel group takes ----
 // the fused bf16 layer kernels of vs_mlp_fused.hip (and their weight images)

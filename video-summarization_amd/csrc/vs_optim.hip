@@ -17,10 +17,10 @@
 // update kernel itself is unchanged; grad_scale_multi_tensor scales gradients in place for a loop with another optimizer.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 
+#include "vs_error.h"
 #include "vs_optim.h"
 #include "vs_weights_impl.h"
 
@@ -303,24 +303,15 @@ __global__ __launch_bounds__(NT) void grad_scale_multi_tensor(const GradTable ta
     }
 }
 
-int failf(int code, const char *fmt, ...) {
-    char buf[384];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return vs_fail_msg(code, buf);
-}
-
 int check_cfg(const vs_adam_cfg *cfg) {
-    if (!cfg) return failf(VS_ERR_INVALID, "vs_adam_cfg is NULL");
-    if (!(cfg->lr >= 0.0) || !isfinite(cfg->lr)) return failf(VS_ERR_INVALID, "adam: lr=%g invalid (>= 0)", cfg->lr);
-    if (!(cfg->beta1 >= 0.0 && cfg->beta1 < 1.0)) return failf(VS_ERR_INVALID, "adam: beta1=%g invalid ([0, 1))", cfg->beta1);
-    if (!(cfg->beta2 >= 0.0 && cfg->beta2 < 1.0)) return failf(VS_ERR_INVALID, "adam: beta2=%g invalid ([0, 1))", cfg->beta2);
-    if (!(cfg->eps >= 0.0) || !isfinite(cfg->eps)) return failf(VS_ERR_INVALID, "adam: eps=%g invalid (>= 0)", cfg->eps);
+    if (!cfg) return vs_failf(VS_ERR_INVALID, "vs_adam_cfg is NULL");
+    if (!(cfg->lr >= 0.0) || !isfinite(cfg->lr)) return vs_failf(VS_ERR_INVALID, "adam: lr=%g invalid (>= 0)", cfg->lr);
+    if (!(cfg->beta1 >= 0.0 && cfg->beta1 < 1.0)) return vs_failf(VS_ERR_INVALID, "adam: beta1=%g invalid ([0, 1))", cfg->beta1);
+    if (!(cfg->beta2 >= 0.0 && cfg->beta2 < 1.0)) return vs_failf(VS_ERR_INVALID, "adam: beta2=%g invalid ([0, 1))", cfg->beta2);
+    if (!(cfg->eps >= 0.0) || !isfinite(cfg->eps)) return vs_failf(VS_ERR_INVALID, "adam: eps=%g invalid (>= 0)", cfg->eps);
     if (!(cfg->weight_decay >= 0.0) || !isfinite(cfg->weight_decay))
-        return failf(VS_ERR_INVALID, "adam: weight_decay=%g invalid (>= 0)", cfg->weight_decay);
-    if (cfg->decoupled != 0 && cfg->decoupled != 1) return failf(VS_ERR_INVALID, "adam: decoupled=%d invalid (0 or 1)", cfg->decoupled);
+        return vs_failf(VS_ERR_INVALID, "adam: weight_decay=%g invalid (>= 0)", cfg->weight_decay);
+    if (cfg->decoupled != 0 && cfg->decoupled != 1) return vs_failf(VS_ERR_INVALID, "adam: decoupled=%d invalid (0 or 1)", cfg->decoupled);
     return VS_OK;
 }
 
@@ -413,24 +404,24 @@ size_t grad_table_chunks(const vs_grad_tensor *table, int32_t n_tensors, const c
         const vs_grad_tensor &t = table[i];
         if (!t.g || t.n == 0) continue;
         if (t.n >= ((size_t)1 << 32)) {
-            if (report) failf(VS_ERR_INVALID, "%s: tensor %d has %zu elements (< 2^32)", who, i, t.n);
+            if (report) vs_failf(VS_ERR_INVALID, "%s: tensor %d has %zu elements (< 2^32)", who, i, t.n);
             return (size_t)-1;
         }
         chunks += (t.n + CHUNK - 1) / CHUNK;
     }
     if (chunks >= GRAD_MAX_CHUNKS) {
-        if (report) failf(VS_ERR_INVALID, "%s: %zu chunks of %u elements (< 2^31)", who, chunks, CHUNK);
+        if (report) vs_failf(VS_ERR_INVALID, "%s: %zu chunks of %u elements (< 2^31)", who, chunks, CHUNK);
         return (size_t)-1;
     }
     return chunks;
 }
 
 int check_norm_args(const char *who, int32_t kind, double max_norm, const float *out, const void *workspace) {
-    if (!out) return failf(VS_ERR_INVALID, "%s: out is NULL", who);
-    if (!workspace) return failf(VS_ERR_INVALID, "%s: workspace is NULL", who);
-    if ((uintptr_t)workspace & 7u) return failf(VS_ERR_INVALID, "%s: workspace must be 8-byte aligned", who);
-    if (kind != VS_GRAD_NORM_L2 && kind != VS_GRAD_NORM_MAX) return failf(VS_ERR_INVALID, "%s: kind=%d (0 L2, 1 max)", who, kind);
-    if (!(max_norm > 0.0)) return failf(VS_ERR_INVALID, "%s: max_norm=%g invalid (> 0; +inf measures only)", who, max_norm);
+    if (!out) return vs_failf(VS_ERR_INVALID, "%s: out is NULL", who);
+    if (!workspace) return vs_failf(VS_ERR_INVALID, "%s: workspace is NULL", who);
+    if ((uintptr_t)workspace & 7u) return vs_failf(VS_ERR_INVALID, "%s: workspace must be 8-byte aligned", who);
+    if (kind != VS_GRAD_NORM_L2 && kind != VS_GRAD_NORM_MAX) return vs_failf(VS_ERR_INVALID, "%s: kind=%d (0 L2, 1 max)", who, kind);
+    if (!(max_norm > 0.0)) return vs_failf(VS_ERR_INVALID, "%s: max_norm=%g invalid (> 0; +inf measures only)", who, max_norm);
     return VS_OK;
 }
 
@@ -443,45 +434,16 @@ int norm_finish(GradLauncher &ln, int32_t kind, double max_norm, const float *gr
             hipLaunchKernelGGL(grad_norm_finalize<VS_GRAD_NORM_MAX>, dim3(1), dim3(NT), 0, ln.st, ln.partials, ln.chunks(), max_norm, grad_scale, out);
         ln.err = hipGetLastError();
     }
-    if (ln.err != hipSuccess) return failf(VS_ERR_HIP, "grad norm launch failed: %s", hipGetErrorString(ln.err));
+    if (ln.err != hipSuccess) return vs_failf(VS_ERR_HIP, "grad norm launch failed: %s", hipGetErrorString(ln.err));
     return VS_OK;
 }
 
 // ---- state of a handle: [sync word | 256 B] [step counts] [m of every tensor] [v of every tensor], 256-byte granules ----
-struct HandleTensor { size_t blob_off, n; };
-
 size_t pad64(size_t n) { return (n + 63) / 64 * 64; }
 
-int handle_tensor_count(const vs_weights *w) { return 4 + 16 * w->desc.num_layers; }
-
-// tensor `i` in vs_model_params order (include/vs_optim.h: vs_adam_state_field)
-HandleTensor handle_tensor(const vs_weights *w, int i) {
-    const size_t d = w->desc.d_model, din = w->desc.in_features, nc = w->desc.num_classes;
-    const int L = w->desc.num_layers;
-    if (i == 0) return {w->embed_w, d * din};
-    if (i == 1) return {w->embed_b, d};
-    if (i == 2 + 16 * L) return {w->final_w, nc * d};
-    if (i == 3 + 16 * L) return {w->final_b, nc};
-    const LayerOff &o = w->layers[(i - 2) / 16];
-    switch ((i - 2) % 16) {
-        case 0: return {o.wqkv, d * d};
-        case 1: return {o.bqkv, d};
-        case 2: return {o.wqkv + d * d, d * d};
-        case 3: return {o.bqkv + d, d};
-        case 4: return {o.wqkv + 2 * d * d, d * d};
-        case 5: return {o.bqkv + 2 * d, d};
-        case 6: return {o.wo, d * d};
-        case 7: return {o.bo, d};
-        case 8: return {o.ln1g, d};
-        case 9: return {o.ln1b, d};
-        case 10: return {o.w1, 4 * d * d};
-        case 11: return {o.b1, 4 * d};
-        case 12: return {o.w2, 4 * d * d};
-        case 13: return {o.b2, d};
-        case 14: return {o.ln2g, d};
-        default: return {o.ln2b, d};
-    }
-}
+// the handle's tensors in vs_model_params order (include/vs_optim.h: vs_adam_state_field): the layout's tensor table
+int handle_tensor_count(const vs_weights *w) { return (int)w->tensors.size(); }
+const VsTensorAt &handle_tensor(const vs_weights *w, int i) { return w->tensors[i]; }
 
 constexpr size_t STATE_HEADER_FLOATS = 64;
 
@@ -504,16 +466,16 @@ extern "C" {
 
 int vs_adam_step_tensors(const vs_adam_tensor *table, int32_t n_tensors, const vs_adam_cfg *cfg, const float *grad_scale,
                          const float *found_inf, void *sync_word, void *stream) {
-    if (n_tensors < 0) return failf(VS_ERR_INVALID, "vs_adam_step_tensors: n_tensors=%d", n_tensors);
-    if (n_tensors > 0 && !table) return failf(VS_ERR_INVALID, "vs_adam_step_tensors: table is NULL");
-    if (!sync_word) return failf(VS_ERR_INVALID, "vs_adam_step_tensors: sync_word is NULL");
+    if (n_tensors < 0) return vs_failf(VS_ERR_INVALID, "vs_adam_step_tensors: n_tensors=%d", n_tensors);
+    if (n_tensors > 0 && !table) return vs_failf(VS_ERR_INVALID, "vs_adam_step_tensors: table is NULL");
+    if (!sync_word) return vs_failf(VS_ERR_INVALID, "vs_adam_step_tensors: sync_word is NULL");
     if (int rc = check_cfg(cfg)) return rc;
     for (int i = 0; i < n_tensors; ++i) {
         const vs_adam_tensor &t = table[i];
         if (t.n == 0) continue;
         if (!t.p || !t.g || !t.m || !t.v || !t.step)
-            return failf(VS_ERR_INVALID, "vs_adam_step_tensors: tensor %d has a NULL p / g / m / v / step pointer", i);
-        if (t.n >= ((size_t)1 << 32)) return failf(VS_ERR_INVALID, "vs_adam_step_tensors: tensor %d has %zu elements (< 2^32)", i, t.n);
+            return vs_failf(VS_ERR_INVALID, "vs_adam_step_tensors: tensor %d has a NULL p / g / m / v / step pointer", i);
+        if (t.n >= ((size_t)1 << 32)) return vs_failf(VS_ERR_INVALID, "vs_adam_step_tensors: tensor %d has %zu elements (< 2^32)", i, t.n);
     }
     Launcher ln(*cfg, grad_scale, found_inf, sync_word, stream);
     for (int i = 0; i < n_tensors; ++i) {
@@ -521,7 +483,7 @@ int vs_adam_step_tensors(const vs_adam_tensor *table, int32_t n_tensors, const v
         ln.add(t.p, t.g, t.m, t.v, t.mirror, t.step, t.n);
     }
     ln.flush();
-    if (ln.err != hipSuccess) return failf(VS_ERR_HIP, "adam launch failed: %s", hipGetErrorString(ln.err));
+    if (ln.err != hipSuccess) return vs_failf(VS_ERR_HIP, "adam launch failed: %s", hipGetErrorString(ln.err));
     return VS_OK;
 }
 
@@ -531,18 +493,18 @@ size_t vs_adam_state_bytes(const vs_weights *w) {
 }
 
 int vs_adam_state_init(const vs_weights *w, void *state, void *stream) {
-    if (!w || !state) return failf(VS_ERR_INVALID, "vs_adam_state_init: weights/state is NULL");
-    if ((uintptr_t)state & 255u) return failf(VS_ERR_INVALID, "vs_adam_state_init: state must be 256-byte aligned");
+    if (!w || !state) return vs_failf(VS_ERR_INVALID, "vs_adam_state_init: weights/state is NULL");
+    if ((uintptr_t)state & 255u) return vs_failf(VS_ERR_INVALID, "vs_adam_state_init: state must be 256-byte aligned");
     const hipError_t e = hipMemsetAsync(state, 0, vs_adam_state_bytes(w), (hipStream_t)stream);
-    if (e != hipSuccess) return failf(VS_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return vs_failf(VS_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     return VS_OK;
 }
 
 int vs_adam_state_field(const vs_weights *w, int32_t tensor, int32_t which, size_t *offset_bytes, size_t *count) {
-    if (!w || !offset_bytes || !count) return failf(VS_ERR_INVALID, "vs_adam_state_field: NULL argument");
+    if (!w || !offset_bytes || !count) return vs_failf(VS_ERR_INVALID, "vs_adam_state_field: NULL argument");
     const int nt = handle_tensor_count(w);
-    if (tensor < 0 || tensor >= nt) return failf(VS_ERR_INVALID, "vs_adam_state_field: tensor=%d outside [0, %d)", tensor, nt);
-    if (which < 0 || which > 2) return failf(VS_ERR_INVALID, "vs_adam_state_field: which=%d (0 m, 1 v, 2 step)", which);
+    if (tensor < 0 || tensor >= nt) return vs_failf(VS_ERR_INVALID, "vs_adam_state_field: tensor=%d outside [0, %d)", tensor, nt);
+    if (which < 0 || which > 2) return vs_failf(VS_ERR_INVALID, "vs_adam_state_field: which=%d (0 m, 1 v, 2 step)", which);
     if (which == 2) {
         *offset_bytes = (STATE_HEADER_FLOATS + (size_t)tensor) * sizeof(float);
         *count = 1;
@@ -557,17 +519,17 @@ int vs_adam_state_field(const vs_weights *w, int32_t tensor, int32_t which, size
 
 int vs_adam_step(vs_weights *w, const vs_model_params *params, const vs_model_grads *grads, void *state,
                  const vs_adam_cfg *cfg, const float *grad_scale, const float *found_inf, void *stream) {
-    if (!w || !grads || !state) return failf(VS_ERR_INVALID, "vs_adam_step: weights/grads/state is NULL");
-    if ((uintptr_t)state & 255u) return failf(VS_ERR_INVALID, "vs_adam_step: state must be 256-byte aligned");
+    if (!w || !grads || !state) return vs_failf(VS_ERR_INVALID, "vs_adam_step: weights/grads/state is NULL");
+    if ((uintptr_t)state & 255u) return vs_failf(VS_ERR_INVALID, "vs_adam_step: state must be 256-byte aligned");
     if (int rc = check_cfg(cfg)) return rc;
     if (w->embedded())
-        return failf(VS_ERR_INVALID, "vs_adam_step: the handle embeds a d_model=%d model in d_model=%d; use vs_adam_step_tensors on the "
+        return vs_failf(VS_ERR_INVALID, "vs_adam_step: the handle embeds a d_model=%d model in d_model=%d; use vs_adam_step_tensors on the "
                                      "caller's tensors and vs_weights_update", w->dn(), w->desc.d_model);
     const int L = w->desc.num_layers, nt = handle_tensor_count(w);
-    if (L > 0 && (!grads->layers || (params && !params->layers))) return failf(VS_ERR_INVALID, "vs_adam_step: layers is NULL");
+    if (L > 0 && (!grads->layers || (params && !params->layers))) return vs_failf(VS_ERR_INVALID, "vs_adam_step: layers is NULL");
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != w->device)
-        return failf(VS_ERR_INVALID, "vs_adam_step on device %d, handle was packed on device %d", dev, w->device);
+        return vs_failf(VS_ERR_INVALID, "vs_adam_step on device %d, handle was packed on device %d", dev, w->device);
     auto grad_of = [&](int i) -> const float * {
         if (i == 0) return grads->embed_w;
         if (i == 1) return grads->embed_b;
@@ -584,7 +546,7 @@ int vs_adam_step(vs_weights *w, const vs_model_params *params, const vs_model_gr
     };
     if (params)
         for (int i = 0; i < nt; ++i)
-            if (grad_of(i) && !param_of(i)) return failf(VS_ERR_INVALID, "vs_adam_step: tensor %d has a gradient but a NULL parameter pointer", i);
+            if (grad_of(i) && !param_of(i)) return vs_failf(VS_ERR_INVALID, "vs_adam_step: tensor %d has a gradient but a NULL parameter pointer", i);
     float *sf = (float *)state;
     float *steps = sf + STATE_HEADER_FLOATS;
     float *m = steps + pad64((size_t)nt);
@@ -592,9 +554,9 @@ int vs_adam_step(vs_weights *w, const vs_model_params *params, const vs_model_gr
     vsw_order(w, stream);       // images still being read / built on another stream
     Launcher ln(*cfg, grad_scale, found_inf, state, stream);
     for (int i = 0; i < nt; ++i) {
-        const HandleTensor t = handle_tensor(w, i);
+        const VsTensorAt &t = handle_tensor(w, i);
         if (const float *g = grad_of(i)) {
-            float *slot = w->blob + t.blob_off;
+            float *slot = w->blob + t.off;
             if (params) ln.add(const_cast<float *>(param_of(i)), g, m, v, slot, steps + i, t.n);
             else ln.add(slot, g, m, v, nullptr, steps + i, t.n);
         }
@@ -604,7 +566,7 @@ int vs_adam_step(vs_weights *w, const vs_model_params *params, const vs_model_gr
     ln.flush();
     ++w->version;        // as vs_weights_update: every image family and the transposes are rebuilt on their next use
     vsw_mark(w, stream);
-    if (ln.err != hipSuccess) return failf(VS_ERR_HIP, "adam launch failed: %s", hipGetErrorString(ln.err));
+    if (ln.err != hipSuccess) return vs_failf(VS_ERR_HIP, "adam launch failed: %s", hipGetErrorString(ln.err));
     return VS_OK;
 }
 
@@ -616,13 +578,13 @@ size_t vs_grad_norm_workspace_bytes(const vs_grad_tensor *table, int32_t n_tenso
 
 int vs_grad_norm_tensors(const vs_grad_tensor *table, int32_t n_tensors, int32_t kind, double max_norm,
                          const float *grad_scale, float *out, void *workspace, size_t workspace_bytes, void *stream) {
-    if (n_tensors < 0) return failf(VS_ERR_INVALID, "vs_grad_norm_tensors: n_tensors=%d", n_tensors);
-    if (!table) return failf(VS_ERR_INVALID, "vs_grad_norm_tensors: table is NULL");
+    if (n_tensors < 0) return vs_failf(VS_ERR_INVALID, "vs_grad_norm_tensors: n_tensors=%d", n_tensors);
+    if (!table) return vs_failf(VS_ERR_INVALID, "vs_grad_norm_tensors: table is NULL");
     if (int rc = check_norm_args("vs_grad_norm_tensors", kind, max_norm, out, workspace)) return rc;
     const size_t chunks = grad_table_chunks(table, n_tensors, "vs_grad_norm_tensors", true);
     if (chunks == (size_t)-1) return VS_ERR_INVALID;
     if (workspace_bytes < grad_ws_bytes(chunks))
-        return failf(VS_ERR_WORKSPACE, "vs_grad_norm_tensors: workspace %zu bytes < %zu needed", workspace_bytes, grad_ws_bytes(chunks));
+        return vs_failf(VS_ERR_WORKSPACE, "vs_grad_norm_tensors: workspace %zu bytes < %zu needed", workspace_bytes, grad_ws_bytes(chunks));
     GradLauncher ln(kind, (double *)workspace, nullptr, stream);
     for (int i = 0; i < n_tensors; ++i) ln.add(table[i].g, table[i].n);
     return norm_finish(ln, kind, max_norm, grad_scale, out);
@@ -630,13 +592,13 @@ int vs_grad_norm_tensors(const vs_grad_tensor *table, int32_t n_tensors, int32_t
 
 int vs_grad_norm(const vs_weights *w, const vs_model_grads *grads, int32_t kind, double max_norm, const float *grad_scale,
                  float *out, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!w || !grads) return failf(VS_ERR_INVALID, "vs_grad_norm: weights/grads is NULL");
+    if (!w || !grads) return vs_failf(VS_ERR_INVALID, "vs_grad_norm: weights/grads is NULL");
     if (int rc = check_norm_args("vs_grad_norm", kind, max_norm, out, workspace)) return rc;
     if (w->embedded())
-        return failf(VS_ERR_INVALID, "vs_grad_norm: the handle embeds a d_model=%d model in d_model=%d; use vs_grad_norm_tensors on the "
+        return vs_failf(VS_ERR_INVALID, "vs_grad_norm: the handle embeds a d_model=%d model in d_model=%d; use vs_grad_norm_tensors on the "
                                      "caller's tensors", w->dn(), w->desc.d_model);
     const int L = w->desc.num_layers, nt = handle_tensor_count(w);
-    if (L > 0 && !grads->layers) return failf(VS_ERR_INVALID, "vs_grad_norm: layers is NULL");
+    if (L > 0 && !grads->layers) return vs_failf(VS_ERR_INVALID, "vs_grad_norm: layers is NULL");
     auto grad_of = [&](int i) -> float * {
         if (i == 0) return grads->embed_w;
         if (i == 1) return grads->embed_b;
@@ -648,21 +610,21 @@ int vs_grad_norm(const vs_weights *w, const vs_model_grads *grads, int32_t kind,
     for (int i = 0; i < nt; ++i)
         if (grad_of(i)) chunks += (handle_tensor(w, i).n + CHUNK - 1) / CHUNK;
     if (workspace_bytes < grad_ws_bytes(chunks))
-        return failf(VS_ERR_WORKSPACE, "vs_grad_norm: workspace %zu bytes < %zu needed", workspace_bytes, grad_ws_bytes(chunks));
+        return vs_failf(VS_ERR_WORKSPACE, "vs_grad_norm: workspace %zu bytes < %zu needed", workspace_bytes, grad_ws_bytes(chunks));
     GradLauncher ln(kind, (double *)workspace, nullptr, stream);
     for (int i = 0; i < nt; ++i) ln.add(grad_of(i), handle_tensor(w, i).n);
     return norm_finish(ln, kind, max_norm, grad_scale, out);
 }
 
 int vs_grad_scale_tensors(const vs_grad_tensor *table, int32_t n_tensors, const float *coef, void *stream) {
-    if (n_tensors < 0) return failf(VS_ERR_INVALID, "vs_grad_scale_tensors: n_tensors=%d", n_tensors);
-    if (!table) return failf(VS_ERR_INVALID, "vs_grad_scale_tensors: table is NULL");
-    if (!coef) return failf(VS_ERR_INVALID, "vs_grad_scale_tensors: coef is NULL");
+    if (n_tensors < 0) return vs_failf(VS_ERR_INVALID, "vs_grad_scale_tensors: n_tensors=%d", n_tensors);
+    if (!table) return vs_failf(VS_ERR_INVALID, "vs_grad_scale_tensors: table is NULL");
+    if (!coef) return vs_failf(VS_ERR_INVALID, "vs_grad_scale_tensors: coef is NULL");
     if (grad_table_chunks(table, n_tensors, "vs_grad_scale_tensors", true) == (size_t)-1) return VS_ERR_INVALID;
     GradLauncher ln(VS_GRAD_NORM_L2, nullptr, coef, stream);
     for (int i = 0; i < n_tensors; ++i) ln.add(table[i].g, table[i].n);
     ln.flush();
-    if (ln.err != hipSuccess) return failf(VS_ERR_HIP, "grad scale launch failed: %s", hipGetErrorString(ln.err));
+    if (ln.err != hipSuccess) return vs_failf(VS_ERR_HIP, "grad scale launch failed: %s", hipGetErrorString(ln.err));
     return VS_OK;
 }
 

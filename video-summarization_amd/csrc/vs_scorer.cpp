@@ -1,5 +1,5 @@
-// vs_scorer.cpp — the C ABI of include/vs_scorer.h: argument checks, weight packing, workspace
-// carving and the per-layer launch sequence of the scorer's eval forward.
+// vs_scorer.cpp — the C ABI of include/vs_scorer.h: argument checks, workspace carving and the per-layer launch
+// sequence of the scorer's eval forward.  The weights handle it reads is vs_weights.cpp's, the error text vs_error.cpp's.
 #include "vs_scorer.h"
 #include "vs_inspect.h"
 
@@ -7,7 +7,6 @@
 
 #include <atomic>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,43 +14,12 @@
 #include <string>
 #include <vector>
 
+#include "vs_error.h"
 #include "vs_kernels.h"
 #include "vs_train_kernels.h"      // vst_attention_fwd: the head-dim-256 attention of the scoring path
 #include "vs_weights_impl.h"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-}  // namespace
-
-// shared with vs_eval.cpp
-int vs_fail_msg(int code, const char *msg) { g_err = msg; return code; }
-
-namespace {
-
-#define VS_HIP(call)                                                                       \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) return fail(VS_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
-
-#define VS_LAUNCH(call)                                                                     \
-    do {                                                                                    \
-        int e_ = (call);                                                                    \
-        if (e_ > 0) return fail(VS_ERR_HIP, "%s: %s", #call, hipGetErrorString((hipError_t)e_)); \
-        if (e_ < 0) return fail(VS_ERR_INVALID, "%s: unsupported shape", #call);            \
-    } while (0)
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -88,23 +56,6 @@ struct StageScope {
         g_prof.push_back({stage, a, b});
     }
 };
-
-int check_desc(const vs_model_desc *d) {
-    if (!d) return fail(VS_ERR_INVALID, "desc is NULL");
-    if (d->d_model <= 0 || d->d_model % 64 || d->d_model > 1024)
-        return fail(VS_ERR_INVALID, "d_model=%d unsupported (multiple of 64, <= 1024)", d->d_model);
-    if (d->num_heads <= 0 || d->d_model % d->num_heads)
-        return fail(VS_ERR_INVALID, "d_model=%d not divisible by num_heads=%d", d->d_model, d->num_heads);
-    const int dh = d->d_model / d->num_heads;
-    if (dh != 32 && dh != 64 && dh != 128 && dh != 256)
-        return fail(VS_ERR_INVALID, "head_dim=%d unsupported (32, 64, 128 or 256)", dh);
-    if (d->num_layers < 1) return fail(VS_ERR_INVALID, "num_layers=%d unsupported (>= 1)", d->num_layers);
-    if (d->in_features <= 0 || d->in_features % 32)
-        return fail(VS_ERR_INVALID, "in_features=%d unsupported (multiple of 32)", d->in_features);
-    if (d->num_classes <= 0) return fail(VS_ERR_INVALID, "num_classes=%d", d->num_classes);
-    if (d->max_len < 0) return fail(VS_ERR_INVALID, "max_len=%d", d->max_len);
-    return VS_OK;
-}
 
 }  // namespace
 
@@ -153,223 +104,6 @@ extern "C" {
 
 int vs_abi_version(void) { return VS_ABI_VERSION; }
 
-const char *vs_last_error(void) { return g_err.c_str(); }
-
-// copies the parameters into w->blob (stream-ordered on `st`): one batched copy kernel for the embedding / head and
-// one per encoder layer instead of 16 hipMemcpyAsync per layer (an optimizer step re-packs on every iteration).
-// params->pos_embedding == NULL on an UPDATE keeps the table already packed (it is a buffer: an optimizer never writes it).
-static int fill_weights(vs_weights *w, const vs_model_params *params, hipStream_t st, bool update) {
-    const vs_model_desc *desc = &w->desc;
-    const size_t d = desc->d_model, din = desc->in_features, nc = desc->num_classes;
-    if (!params->embed_w || !params->embed_b || !params->final_w || !params->final_b ||
-        (desc->num_layers > 0 && !params->layers))
-        return fail(VS_ERR_INVALID, "a required parameter pointer is NULL");
-    if ((params->pos_embedding != nullptr) != (desc->max_len > 0) && !(update && !params->pos_embedding))
-        return fail(VS_ERR_INVALID, "pos_embedding / max_len mismatch");
-    VskCopySegs segs{};
-    bool ok = true;
-    auto add = [&](size_t dst, const float *src, size_t n) {
-        if (!src || segs.count >= VSK_COPY_MAX_SEGS) { ok = false; return; }
-        segs.src[segs.count] = src; segs.dst[segs.count] = w->blob + dst; segs.n[segs.count] = (unsigned)n; ++segs.count;
-    };
-    auto flush = [&]() { if (ok && segs.count) ok = vsk_copy_segments(segs, st) == 0; segs.count = 0; };
-    add(w->embed_w, params->embed_w, d * din);
-    add(w->embed_b, params->embed_b, d);
-    add(w->final_w, params->final_w, nc * d);
-    add(w->final_b, params->final_b, nc);
-    flush();
-    if (w->has_pe && params->pos_embedding)
-        ok &= hipMemcpyAsync(w->blob + w->pe, params->pos_embedding, (size_t)desc->max_len * d * sizeof(float),
-                             hipMemcpyDeviceToDevice, st) == hipSuccess;
-    for (int l = 0; l < desc->num_layers && ok; ++l) {
-        const vs_layer_params &P = params->layers[l];
-        const LayerOff &L = w->layers[l];
-        add(L.wqkv, P.wq, d * d); add(L.wqkv + d * d, P.wk, d * d); add(L.wqkv + 2 * d * d, P.wv, d * d);
-        add(L.bqkv, P.bq, d);     add(L.bqkv + d, P.bk, d);         add(L.bqkv + 2 * d, P.bv, d);
-        add(L.wo, P.wo, d * d);   add(L.bo, P.bo, d);
-        add(L.ln1g, P.ln1_g, d);  add(L.ln1b, P.ln1_b, d);
-        add(L.w1, P.w1, 4 * d * d); add(L.b1, P.b1, 4 * d);
-        add(L.w2, P.w2, 4 * d * d); add(L.b2, P.b2, d);
-        add(L.ln2g, P.ln2_g, d);  add(L.ln2b, P.ln2_b, d);
-        flush();
-    }
-    if (!ok)
-        return fail(VS_ERR_HIP, "parameter copy failed (NULL pointer or launch error: %s)",
-                    hipGetErrorString(hipGetLastError()));
-    return VS_OK;
-}
-
-}  // extern "C"
-
-namespace { std::mutex g_wmu; }
-
-// kernel-layout images, built on first use after each pack / update (see vs_weights_impl.h)
-void vsw_mark(const vs_weights *w, void *stream) {
-    if (!w->order_event) {
-        hipEvent_t ev = nullptr;
-        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return; }
-        w->order_event = (void *)ev;
-    }
-    if (hipEventRecord((hipEvent_t)w->order_event, (hipStream_t)stream) == hipSuccess) {
-        w->order_stream = stream;
-        w->order_recorded = true;
-    } else {
-        (void)hipGetLastError();
-    }
-}
-
-void vsw_order(const vs_weights *w, void *stream) {
-    if (w->order_recorded && w->order_stream != stream)
-        if (hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)w->order_event, 0) != hipSuccess) (void)hipGetLastError();
-}
-
-int vsw_ensure(const vs_weights *w, unsigned families, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(g_wmu);
-    vsw_order(w, stream);       // parameters written / images built on another stream: wait for them on the device
-    const bool rebuilt = ((families & VSW_FRAGMENTS) && w->f_version != w->version) || ((families & VSW_F16X3) && w->h_version != w->version) ||
-                         ((families & VSW_BF16) && w->b_version != w->version) || ((families & VSW_ROWS16) && w->r_version != w->version);
-    struct Mark { const vs_weights *w; void *s; bool on; ~Mark() { if (on) vsw_mark(w, s); } } mark{w, stream, rebuilt};
-    const size_t d = w->desc.d_model, din = w->desc.in_features;
-    float *blob = w->blob;
-    bool pk = true;
-    if ((families & VSW_FRAGMENTS) && w->f_version != w->version) {
-        // one launch for all matrices (a reference-sized training step rebuilds this family after every optimizer step)
-        VskMatJobs fj{};
-        auto add = [&](size_t src, size_t dst, int N, int K) {
-            if (fj.n == VskMatJobs::MAX) { pk &= vsk_pack_fragments_batch(fj, st) == 0; fj.n = 0; }
-            fj.in[fj.n] = blob + src; fj.out[fj.n] = blob + dst; fj.rows[fj.n] = N; fj.cols[fj.n] = K; ++fj.n;
-        };
-        add(w->embed_w, w->f_embed_w, (int)d, (int)din);
-        for (const auto &L : w->layers) {
-            add(L.wqkv, L.f_wqkv, (int)(3 * d), (int)d);
-            add(L.wo, L.f_wo, (int)d, (int)d);
-            add(L.w1, L.f_w1, (int)(4 * d), (int)d);
-            add(L.w2, L.f_w2, (int)d, (int)(4 * d));
-        }
-        pk &= vsk_pack_fragments_batch(fj, st) == 0;
-        if (pk) w->f_version = w->version;
-    }
-    if ((families & VSW_F16X3) && w->h_version != w->version) {
-        pk &= vsk_pack_fragments_f16x3(blob + w->embed_w, blob + w->h_embed_w, (int)d, (int)din, st) == 0;
-        for (const auto &L : w->layers) {
-            pk &= vsk_pack_fragments_f16x3(blob + L.wqkv, blob + L.h_wqkv, (int)(3 * d), (int)d, st) == 0;
-            pk &= vsk_pack_fragments_f16x3(blob + L.wo, blob + L.h_wo, (int)d, (int)d, st) == 0;
-            pk &= vsk_pack_fragments_f16x3(blob + L.w1, blob + L.h_w1, (int)(4 * d), (int)d, st) == 0;
-            pk &= vsk_pack_fragments_f16x3(blob + L.w2, blob + L.h_w2, (int)d, (int)(4 * d), st) == 0;
-        }
-        if (pk) w->h_version = w->version;
-    }
-    if ((families & VSW_BF16) && w->b_version != w->version) {
-        if (w->has_b_embed) pk &= vsk_pack_embed_bf16(blob + w->embed_w, blob + w->b_embed, (int)d, (int)din, st) == 0;
-        if (vsk_mlp_bf16_supported((int)d))
-            for (const auto &L : w->layers) {
-                pk &= vsk_pack_mlp_bf16(blob + L.wo, blob + L.w1, blob + L.w2, blob + L.b_mlp, (int)d, st) == 0;
-                pk &= vsk_pack_qkv_bf16(blob + L.wqkv, blob + L.b_qkv, (int)d, st) == 0;
-            }
-        if (pk) w->b_version = w->version;
-    }
-    if ((families & VSW_ROWS16) && w->r_version != w->version) {
-        for (const auto &L : w->layers) {
-            pk &= vsk_to_bf16(blob + L.wqkv, blob + L.r_wqkv, 3 * d * d, st) == 0;
-            pk &= vsk_to_bf16(blob + L.wo, blob + L.r_wo, d * d, st) == 0;
-            pk &= vsk_to_bf16(blob + L.w1, blob + L.r_w1, 4 * d * d, st) == 0;
-            pk &= vsk_to_bf16(blob + L.w2, blob + L.r_w2, 4 * d * d, st) == 0;
-        }
-        if (pk) w->r_version = w->version;
-    }
-    if (!pk) return fail(VS_ERR_HIP, "weight image packing failed: %s", hipGetErrorString(hipGetLastError()));
-    return VS_OK;
-}
-
-extern "C" {
-
-int vs_weights_pack(const vs_model_desc *desc, const vs_model_params *params, void *stream,
-                    vs_weights **out) {
-    if (int rc = check_desc(desc)) return rc;
-    if (!params || !out) return fail(VS_ERR_INVALID, "params/out is NULL");
-    const size_t d = desc->d_model, din = desc->in_features, nc = desc->num_classes;
-
-    vs_weights *w = new vs_weights();
-    w->desc = *desc;
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += align_up(n, 64); return o; };   // 256-B aligned
-    w->embed_w = take(d * din);
-    w->embed_b = take(d);
-    w->has_pe = params->pos_embedding != nullptr;
-    if (w->has_pe) w->pe = take((size_t)desc->max_len * d);
-    w->layers.resize(desc->num_layers);
-    for (auto &L : w->layers) {
-        L.wqkv = take(3 * d * d); L.bqkv = take(3 * d);
-        L.wo = take(d * d);       L.bo = take(d);
-        L.ln1g = take(d);         L.ln1b = take(d);
-        L.w1 = take(4 * d * d);   L.b1 = take(4 * d);
-        L.w2 = take(4 * d * d);   L.b2 = take(d);
-        L.ln2g = take(d);         L.ln2b = take(d);
-    }
-    w->final_w = take(nc * d);
-    w->final_b = take(nc);
-    w->f_embed_w = take(d * din);
-    for (auto &L : w->layers) {
-        L.f_wqkv = take(3 * d * d); L.f_wo = take(d * d); L.f_w1 = take(4 * d * d); L.f_w2 = take(4 * d * d);
-    }
-    w->h_embed_w = take(d * din);
-    for (auto &L : w->layers) {
-        L.h_wqkv = take(3 * d * d); L.h_wo = take(d * d); L.h_w1 = take(4 * d * d); L.h_w2 = take(4 * d * d);
-    }
-    if (vsk_mlp_bf16_supported((int)d))
-        for (auto &L : w->layers) {
-            L.b_mlp = take(vsk_mlp_bf16_image_bytes((int)d) / sizeof(float));
-            L.b_qkv = take(vsk_qkv_bf16_image_bytes((int)d) / sizeof(float));
-        }
-    for (auto &L : w->layers) {
-        L.r_wqkv = take(3 * d * d / 2); L.r_wo = take(d * d / 2); L.r_w1 = take(4 * d * d / 2); L.r_w2 = take(4 * d * d / 2);
-    }
-    w->has_b_embed = vsk_embed_bf16_image_bytes((int)d, (int)din) != 0;
-    if (w->has_b_embed) w->b_embed = take(vsk_embed_bf16_image_bytes((int)d, (int)din) / sizeof(float));
-    w->blob_floats = off;
-    if (hipGetDevice(&w->device) != hipSuccess) { delete w; return fail(VS_ERR_HIP, "hipGetDevice failed"); }
-    hipError_t e = hipMalloc((void **)&w->blob, off * sizeof(float));
-    if (e != hipSuccess) { delete w; return fail(VS_ERR_HIP, "hipMalloc(%zu): %s", off * sizeof(float), hipGetErrorString(e)); }
-    if (int rc = fill_weights(w, params, (hipStream_t)stream, false)) {
-        (void)hipFree(w->blob);
-        delete w;
-        return rc;
-    }
-    w->version = 1;
-    vsw_mark(w, stream);
-    *out = w;
-    return VS_OK;
-}
-
-int vs_weights_update(vs_weights *w, const vs_model_params *params, void *stream) {
-    if (!w || !params) return fail(VS_ERR_INVALID, "weights/params is NULL");
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != w->device)
-        return fail(VS_ERR_INVALID, "vs_weights_update on device %d, handle was packed on device %d", dev, w->device);
-    ++w->version;        // every image family (and the training side's transposes) is rebuilt on its next use
-    vsw_order(w, stream);   // (images still being read / built on another stream)
-    const int rc = fill_weights(w, params, (hipStream_t)stream, true);
-    vsw_mark(w, stream);
-    return rc;
-}
-
-int vs_weights_set_norm_width(vs_weights *w, int32_t norm_width) {
-    if (!w) return fail(VS_ERR_INVALID, "weights is NULL");
-    if (norm_width <= 0 || norm_width % 4 || norm_width > w->desc.d_model)
-        return fail(VS_ERR_INVALID, "norm_width=%d unsupported (multiple of 4, 0 < norm_width <= d_model = %d)", norm_width, w->desc.d_model);
-    w->norm_width = norm_width;
-    return VS_OK;
-}
-
-void vs_weights_free(vs_weights *w) {
-    if (!w) return;
-    if (w->blob) (void)hipFree(w->blob);
-    if (w->tblob) (void)hipFree(w->tblob);
-    if (w->order_event) (void)hipEventDestroy((hipEvent_t)w->order_event);
-    delete w;
-}
-
 size_t vs_scorer_workspace_bytes(const vs_weights *w, int32_t B, int32_t T) {
     if (!w || B <= 0 || T <= 0) return 0;
     const size_t md = align_up((size_t)B * T * w->desc.d_model * sizeof(float), 256);
@@ -408,8 +142,8 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
                  int32_t T, uint32_t flags, float *scores, float *hidden, void *workspace,
                  size_t workspace_bytes, void *stream, const PackedInfo *pk, const float *cls = nullptr,
                  const InspectHook *ins = nullptr) {
-    if (!w || !x || !scores) return fail(VS_ERR_INVALID, "weights/x/scores is NULL");
-    if (B <= 0 || T <= 0) return fail(VS_ERR_INVALID, "B=%d T=%d", B, T);
+    if (!w || !x || !scores) return vs_failf(VS_ERR_INVALID, "weights/x/scores is NULL");
+    if (B <= 0 || T <= 0) return vs_failf(VS_ERR_INVALID, "B=%d T=%d", B, T);
     const vs_model_desc &D = w->desc;
     const int Tf = T;                   // frames per video (rows of x, positional rows)
     const int sig = (flags & VS_FLAG_SIGMOID) ? 1 : 0;
@@ -417,14 +151,15 @@ int forward_core(const vs_weights *w, const float *x, const uint8_t *key_pad_mas
     const VsForwardIn in{D.d_model, D.num_heads, D.num_layers, D.in_features, D.max_len, w->dn(), w->has_pe, w->has_b_embed,
                          B, Tf, flags, cls != nullptr, pk != nullptr};
     VsForwardPlan plan;
-    if (int rc = vs_forward_plan(in, vsk_options(), &plan, &g_err)) return rc;
+    std::string err;
+    if (int rc = vs_forward_plan(in, vsk_options(), &plan, &err)) return vs_fail_msg(rc, err.c_str());
     T = plan.T;                         // sequence length the encoder sees
     const size_t need_core = vs_scorer_workspace_bytes(w, B, T);
     const size_t need = need_core + (cls ? align_up((size_t)B * T, 256) : 0);       // + the [B, T+1] key mask
     if (!workspace || workspace_bytes < need)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
     if (((uintptr_t)workspace & 255) || ((uintptr_t)x & 15) || (hidden && ((uintptr_t)hidden & 15)) || (cls && ((uintptr_t)cls & 15)))
-        return fail(VS_ERR_INVALID, "workspace must be 256-byte, x/hidden/cls_token 16-byte aligned");
+        return vs_failf(VS_ERR_INVALID, "workspace must be 256-byte, x/hidden/cls_token 16-byte aligned");
     // kernel-layout weight images this forward reads, (re)built only if the parameters changed since their last use
     vsw_order(w, stream);       // parameters written on another stream (vs_weights_update): ordered on the device
     if (plan.families) if (int rc = vsw_ensure(w, plan.families, stream)) return rc;
@@ -644,7 +379,7 @@ size_t vs_scorer_workspace_bytes_cls(const vs_weights *w, int32_t B, int32_t T) 
 int vs_scorer_forward_cls(const vs_weights *w, const float *x, const uint8_t *key_pad_mask, const float *cls_token,
                           int32_t B, int32_t T, uint32_t flags, float *scores, float *hidden, void *workspace,
                           size_t workspace_bytes, void *stream) {
-    if (!cls_token) return fail(VS_ERR_INVALID, "cls_token is NULL");
+    if (!cls_token) return vs_failf(VS_ERR_INVALID, "cls_token is NULL");
     return forward_core(w, x, key_pad_mask, B, T, flags, scores, hidden, workspace, workspace_bytes, stream, nullptr, cls_token);
 }
 
@@ -659,21 +394,21 @@ int vs_inspect_forward(const vs_weights *w, const float *x, const uint8_t *key_p
                        int32_t B, int32_t T, const int32_t *layers, int32_t n_layers,
                        float *scores, float *hidden, float *maps, float *received, float *entropy,
                        void *workspace, size_t workspace_bytes, void *stream) {
-    if (!w) return fail(VS_ERR_INVALID, "weights is NULL");
-    if (!layers || n_layers <= 0) return fail(VS_ERR_INVALID, "layers is NULL or n_layers=%d", n_layers);
+    if (!w) return vs_failf(VS_ERR_INVALID, "weights is NULL");
+    if (!layers || n_layers <= 0) return vs_failf(VS_ERR_INVALID, "layers is NULL or n_layers=%d", n_layers);
     for (int i = 0; i < n_layers; ++i) {
         if (layers[i] < 0 || layers[i] >= w->desc.num_layers)
-            return fail(VS_ERR_INVALID, "layers[%d]=%d out of range (num_layers=%d)", i, layers[i], w->desc.num_layers);
-        if (i && layers[i] <= layers[i - 1]) return fail(VS_ERR_INVALID, "layers must be strictly ascending (layers[%d]=%d after %d)", i, layers[i], layers[i - 1]);
+            return vs_failf(VS_ERR_INVALID, "layers[%d]=%d out of range (num_layers=%d)", i, layers[i], w->desc.num_layers);
+        if (i && layers[i] <= layers[i - 1]) return vs_failf(VS_ERR_INVALID, "layers must be strictly ascending (layers[%d]=%d after %d)", i, layers[i], layers[i - 1]);
     }
-    if (!maps && !received && !entropy) return fail(VS_ERR_INVALID, "maps, received and entropy are all NULL");
+    if (!maps && !received && !entropy) return vs_failf(VS_ERR_INVALID, "maps, received and entropy are all NULL");
     if (((uintptr_t)maps | (uintptr_t)received | (uintptr_t)entropy) & 15)
-        return fail(VS_ERR_INVALID, "maps / received / entropy must be 16-byte aligned");
-    if (B <= 0 || T <= 0) return fail(VS_ERR_INVALID, "B=%d T=%d", B, T);
+        return vs_failf(VS_ERR_INVALID, "maps / received / entropy must be 16-byte aligned");
+    if (B <= 0 || T <= 0) return vs_failf(VS_ERR_INVALID, "B=%d T=%d", B, T);
     const size_t core = align_up(cls_token ? vs_scorer_workspace_bytes_cls(w, B, T) : vs_scorer_workspace_bytes(w, B, T), 256);
     const size_t need = vs_inspect_workspace_bytes(w, B, T, cls_token != nullptr);
     if (!workspace || workspace_bytes < need)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
     const InspectHook ins{layers, n_layers, maps, received, entropy, (char *)workspace + core};
     return forward_core(w, x, key_pad_mask, B, T, 0u, scores, hidden, workspace, core, stream, nullptr, cls_token, &ins);
 }
@@ -686,16 +421,16 @@ size_t vs_attention_probs_workspace_bytes(int32_t B, int32_t H, int32_t T) {
 int vs_attention_probs_f32(const float *q, const float *k, const uint8_t *key_pad_mask, float *maps, float *received,
                            float *entropy, int32_t B, int32_t H, int32_t T, int32_t dh, float scale, void *workspace,
                            size_t workspace_bytes, void *stream) {
-    if (!q || !k) return fail(VS_ERR_INVALID, "q / k is NULL");
-    if (!maps && !received && !entropy) return fail(VS_ERR_INVALID, "maps, received and entropy are all NULL");
-    if (B <= 0 || H <= 0 || T <= 0) return fail(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
-    if (dh != 32 && dh != 64 && dh != 128 && dh != 256) return fail(VS_ERR_INVALID, "head_dim=%d unsupported (32, 64, 128 or 256)", dh);
+    if (!q || !k) return vs_failf(VS_ERR_INVALID, "q / k is NULL");
+    if (!maps && !received && !entropy) return vs_failf(VS_ERR_INVALID, "maps, received and entropy are all NULL");
+    if (B <= 0 || H <= 0 || T <= 0) return vs_failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
+    if (dh != 32 && dh != 64 && dh != 128 && dh != 256) return vs_failf(VS_ERR_INVALID, "head_dim=%d unsupported (32, 64, 128 or 256)", dh);
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)maps | (uintptr_t)received | (uintptr_t)entropy) & 15)
-        return fail(VS_ERR_INVALID, "q / k / maps / received / entropy must be 16-byte aligned");
+        return vs_failf(VS_ERR_INVALID, "q / k / maps / received / entropy must be 16-byte aligned");
     const size_t need = vsk_attention_probs_workspace_bytes(B, H, T);
     if (!workspace || workspace_bytes < need)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
-    if ((uintptr_t)workspace & 255) return fail(VS_ERR_INVALID, "workspace must be 256-byte aligned");
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 255) return vs_failf(VS_ERR_INVALID, "workspace must be 256-byte aligned");
     VS_LAUNCH(vsk_attention_probs(q, k, key_pad_mask, maps, received, entropy, B, H, T, dh, scale, workspace, (hipStream_t)stream));
     return VS_OK;
 }
@@ -703,18 +438,18 @@ int vs_attention_probs_f32(const float *q, const float *k, const uint8_t *key_pa
 // ---- packed ragged batches ----
 static int packed_plan(const vs_weights *w, const int32_t *lengths, int32_t B, std::vector<int> &cu,
                        std::vector<int> &work, int &nw, int aprec = 0) {
-    if (!w || !lengths || B <= 0) return fail(VS_ERR_INVALID, "weights/lengths is NULL or B=%d", B);
+    if (!w || !lengths || B <= 0) return vs_failf(VS_ERR_INVALID, "weights/lengths is NULL or B=%d", B);
     const vs_model_desc &D = w->desc;
     const int dh = D.d_model / D.num_heads;
-    if (dh != 32 && dh != 64 && dh != 128) return fail(VS_ERR_INVALID, "packed batches need head_dim 32, 64 or 128 (got %d)", dh);
+    if (dh != 32 && dh != 64 && dh != 128) return vs_failf(VS_ERR_INVALID, "packed batches need head_dim 32, 64 or 128 (got %d)", dh);
     cu.assign(B + 1, 0);
     long long r8 = 0, r4 = 0;
     for (int b = 0; b < B; ++b) {
         const int t = lengths[b];
-        if (t <= 0) return fail(VS_ERR_INVALID, "lengths[%d]=%d", b, t);
+        if (t <= 0) return vs_failf(VS_ERR_INVALID, "lengths[%d]=%d", b, t);
         if (w->has_pe && t > D.max_len)
-            return fail(VS_ERR_INVALID, "T=%d exceeds the positional table (max_len=%d)", t, D.max_len);
-        if ((long long)cu[b] + t > (1ll << 30)) return fail(VS_ERR_INVALID, "too many frames");
+            return vs_failf(VS_ERR_INVALID, "T=%d exceeds the positional table (max_len=%d)", t, D.max_len);
+        if ((long long)cu[b] + t > (1ll << 30)) return vs_failf(VS_ERR_INVALID, "too many frames");
         cu[b + 1] = cu[b] + t;
         r8 += (t + 255) / 256 * 256;
         r4 += (t + 127) / 128 * 128;
@@ -748,20 +483,20 @@ size_t vs_scorer_workspace_bytes_packed(const vs_weights *w, const int32_t *leng
 static int forward_packed(const vs_weights *w, const float *x, const int32_t *lengths, const int32_t *lengths_dev,
                           int32_t B, uint32_t flags, float *scores, float *hidden, void *workspace,
                           size_t workspace_bytes, void *stream, const InspectHook *ins) {
-    if (!lengths_dev) return fail(VS_ERR_INVALID, "lengths_dev is NULL");
-    if (!w) return fail(VS_ERR_INVALID, "weights is NULL");
+    if (!lengths_dev) return vs_failf(VS_ERR_INVALID, "lengths_dev is NULL");
+    if (!w) return vs_failf(VS_ERR_INVALID, "weights is NULL");
     if ((flags & VS_FLAG_BF16_ATTENTION) && (flags & VS_FLAG_F16X3_ATTENTION))
-        return fail(VS_ERR_INVALID, "VS_FLAG_BF16_ATTENTION and VS_FLAG_F16X3_ATTENTION are exclusive");
+        return vs_failf(VS_ERR_INVALID, "VS_FLAG_BF16_ATTENTION and VS_FLAG_F16X3_ATTENTION are exclusive");
     const int aprec = vs_attention_prec(flags);
     std::vector<int> cu, work;
     int nw = 0;
     if (aprec == 2 && w->desc.d_model / w->desc.num_heads == 128)
-        return fail(VS_ERR_INVALID, "VS_FLAG_F16X3_ATTENTION needs head_dim 32 or 64 (got 128)");
+        return vs_failf(VS_ERR_INVALID, "VS_FLAG_F16X3_ATTENTION needs head_dim 32 or 64 (got 128)");
     if (int rc = packed_plan(w, lengths, B, cu, work, nw, aprec)) return rc;
     const size_t need = vs_scorer_workspace_bytes_packed(w, lengths, B);
     if (!workspace || workspace_bytes < need)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
-    if ((uintptr_t)workspace & 255) return fail(VS_ERR_INVALID, "workspace must be 256-byte aligned");
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 255) return vs_failf(VS_ERR_INVALID, "workspace must be 256-byte aligned");
     const int M = cu[B], d = w->desc.d_model;
     const size_t md = align_up((size_t)M * d * sizeof(float), 256);
     hipStream_t st = (hipStream_t)stream;
@@ -770,7 +505,7 @@ static int forward_packed(const vs_weights *w, const float *x, const int32_t *le
     // the device builds its own copy of the plan from the device lengths (no host memory is read after return,
     // no synchronisation); the host copy above only sized the launch
     const size_t cap = packed_plan_capacity(lengths, B);
-    if (work.size() / 2 > cap) return fail(VS_ERR_INVALID, "internal: packed plan %zu > capacity %zu", work.size() / 2, cap);
+    if (work.size() / 2 > cap) return vs_failf(VS_ERR_INVALID, "internal: packed plan %zu > capacity %zu", work.size() / 2, cap);
     VS_LAUNCH(vsk_plan_packed(lengths_dev, B, 32 * nw, plan, plan + cu.size(), (int)cap, st));
     PackedInfo pk{nullptr, plan, plan + cu.size(), (int)(work.size() / 2), nw};
     if (w->has_pe) {
@@ -791,16 +526,16 @@ int vs_scorer_forward_packed(const vs_weights *w, const float *x, const int32_t 
 // ---- attention maps on packed ragged batches (include/vs_inspect.h) ----
 // M = sum of the lengths, tiles = sum ceil(T_b / 32) (the capacity rule of the size function AND of the launch), sumsq = sum T_b^2
 static int probs_packed_sizes(const int32_t *lengths, int32_t B, int &M, int &tiles, size_t &sumsq) {
-    if (!lengths || B <= 0) return fail(VS_ERR_INVALID, "lengths is NULL or B=%d", B);
+    if (!lengths || B <= 0) return vs_failf(VS_ERR_INVALID, "lengths is NULL or B=%d", B);
     long long m = 0, n = 0;
     sumsq = 0;
     for (int b = 0; b < B; ++b) {
         const int t = lengths[b];
-        if (t <= 0) return fail(VS_ERR_INVALID, "lengths[%d]=%d", b, t);
+        if (t <= 0) return vs_failf(VS_ERR_INVALID, "lengths[%d]=%d", b, t);
         m += t;
         n += (t + 31) / 32;
         sumsq += (size_t)t * (size_t)t;
-        if (m > (1ll << 30)) return fail(VS_ERR_INVALID, "too many frames");
+        if (m > (1ll << 30)) return vs_failf(VS_ERR_INVALID, "too many frames");
     }
     M = (int)m;
     tiles = (int)n;
@@ -817,20 +552,20 @@ size_t vs_attention_probs_packed_workspace_bytes(const int32_t *lengths, int32_t
 int vs_attention_probs_packed_f32(const float *q, const float *k, const int32_t *lengths, const int32_t *lengths_dev, int32_t B,
                                   int32_t H, int32_t dh, float scale, float *maps, float *received, float *entropy,
                                   void *workspace, size_t workspace_bytes, void *stream) {
-    if (!q || !k) return fail(VS_ERR_INVALID, "q / k is NULL");
-    if (!lengths_dev) return fail(VS_ERR_INVALID, "lengths_dev is NULL");
-    if (!maps && !received && !entropy) return fail(VS_ERR_INVALID, "maps, received and entropy are all NULL");
-    if (H <= 0) return fail(VS_ERR_INVALID, "H=%d", H);
+    if (!q || !k) return vs_failf(VS_ERR_INVALID, "q / k is NULL");
+    if (!lengths_dev) return vs_failf(VS_ERR_INVALID, "lengths_dev is NULL");
+    if (!maps && !received && !entropy) return vs_failf(VS_ERR_INVALID, "maps, received and entropy are all NULL");
+    if (H <= 0) return vs_failf(VS_ERR_INVALID, "H=%d", H);
     int M = 0, tiles = 0;
     size_t sumsq = 0;
     if (int rc = probs_packed_sizes(lengths, B, M, tiles, sumsq)) return rc;
-    if (dh != 32 && dh != 64 && dh != 128) return fail(VS_ERR_INVALID, "head_dim=%d unsupported on packed batches (32, 64 or 128)", dh);
+    if (dh != 32 && dh != 64 && dh != 128) return vs_failf(VS_ERR_INVALID, "head_dim=%d unsupported on packed batches (32, 64 or 128)", dh);
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)maps | (uintptr_t)received | (uintptr_t)entropy) & 15)
-        return fail(VS_ERR_INVALID, "q / k / maps / received / entropy must be 16-byte aligned");
+        return vs_failf(VS_ERR_INVALID, "q / k / maps / received / entropy must be 16-byte aligned");
     const size_t need = vsk_attention_probs_packed_workspace_bytes(B, H, M, tiles);
     if (!workspace || workspace_bytes < need)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
-    if ((uintptr_t)workspace & 255) return fail(VS_ERR_INVALID, "workspace must be 256-byte aligned");
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 255) return vs_failf(VS_ERR_INVALID, "workspace must be 256-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     VS_LAUNCH(vsk_attention_probs_packed_plan(lengths_dev, B, H, M, tiles, workspace, st));
     VS_LAUNCH(vsk_attention_probs_packed(q, k, nullptr, maps, received, entropy, B, H, M, tiles, dh, scale, workspace, st));
@@ -846,18 +581,18 @@ size_t vs_inspect_workspace_bytes_packed(const vs_weights *w, const int32_t *len
 int vs_inspect_forward_packed(const vs_weights *w, const float *x, const int32_t *lengths, const int32_t *lengths_dev, int32_t B,
                               const int32_t *layers, int32_t n_layers, float *scores, float *hidden, float *maps, float *received,
                               float *entropy, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!w) return fail(VS_ERR_INVALID, "weights is NULL");
-    if (!lengths_dev) return fail(VS_ERR_INVALID, "lengths_dev is NULL");
-    if (!layers || n_layers <= 0) return fail(VS_ERR_INVALID, "layers is NULL or n_layers=%d", n_layers);
+    if (!w) return vs_failf(VS_ERR_INVALID, "weights is NULL");
+    if (!lengths_dev) return vs_failf(VS_ERR_INVALID, "lengths_dev is NULL");
+    if (!layers || n_layers <= 0) return vs_failf(VS_ERR_INVALID, "layers is NULL or n_layers=%d", n_layers);
     for (int i = 0; i < n_layers; ++i) {
         if (layers[i] < 0 || layers[i] >= w->desc.num_layers)
-            return fail(VS_ERR_INVALID, "layers[%d]=%d out of range (num_layers=%d)", i, layers[i], w->desc.num_layers);
-        if (i && layers[i] <= layers[i - 1]) return fail(VS_ERR_INVALID, "layers must be strictly ascending (layers[%d]=%d after %d)", i, layers[i], layers[i - 1]);
+            return vs_failf(VS_ERR_INVALID, "layers[%d]=%d out of range (num_layers=%d)", i, layers[i], w->desc.num_layers);
+        if (i && layers[i] <= layers[i - 1]) return vs_failf(VS_ERR_INVALID, "layers must be strictly ascending (layers[%d]=%d after %d)", i, layers[i], layers[i - 1]);
     }
-    if (!x || !scores) return fail(VS_ERR_INVALID, "weights/x/scores is NULL");
-    if (!maps && !received && !entropy) return fail(VS_ERR_INVALID, "maps, received and entropy are all NULL");
+    if (!x || !scores) return vs_failf(VS_ERR_INVALID, "weights/x/scores is NULL");
+    if (!maps && !received && !entropy) return vs_failf(VS_ERR_INVALID, "maps, received and entropy are all NULL");
     if (((uintptr_t)maps | (uintptr_t)received | (uintptr_t)entropy | (uintptr_t)x | (uintptr_t)hidden) & 15)
-        return fail(VS_ERR_INVALID, "x / hidden / maps / received / entropy must be 16-byte aligned");
+        return vs_failf(VS_ERR_INVALID, "x / hidden / maps / received / entropy must be 16-byte aligned");
     std::vector<int> cu, work;
     int nw = 0;
     if (int rc = packed_plan(w, lengths, B, cu, work, nw)) return rc;      // B, the lengths, the positional table, the head dim
@@ -867,8 +602,8 @@ int vs_inspect_forward_packed(const vs_weights *w, const float *x, const int32_t
     const size_t core = align_up(vs_scorer_workspace_bytes_packed(w, lengths, B), 256);
     const size_t need = core + vsk_attention_probs_packed_workspace_bytes(B, w->desc.num_heads, M, tiles);
     if (!workspace || workspace_bytes < need)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
-    if ((uintptr_t)workspace & 255) return fail(VS_ERR_INVALID, "workspace must be 256-byte aligned");
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace & 255) return vs_failf(VS_ERR_INVALID, "workspace must be 256-byte aligned");
     InspectHook ins{layers, n_layers, maps, received, entropy, (char *)workspace + core};
     ins.videos = B;
     ins.tiles = tiles;
@@ -890,17 +625,17 @@ int vs_profile_enable(int32_t on) {
 }
 
 int vs_set_option(const char *name, int32_t value) {
-    if (!name) return fail(VS_ERR_INVALID, "option name is NULL");
+    if (!name) return vs_failf(VS_ERR_INVALID, "option name is NULL");
     for (const auto &k : kOptions)
         if (strcmp(k.name, name) == 0) {
             vsk_options().*(k.field) = value < 0 ? option_from_env(k) : value;
             return VS_OK;
         }
-    return fail(VS_ERR_INVALID, "unknown option %s", name);
+    return vs_failf(VS_ERR_INVALID, "unknown option %s", name);
 }
 
 int vs_profile_collect(double *ms_sum, int64_t *launches) {
-    if (!ms_sum || !launches) return fail(VS_ERR_INVALID, "NULL pointer");
+    if (!ms_sum || !launches) return vs_failf(VS_ERR_INVALID, "NULL pointer");
     std::lock_guard<std::mutex> lk(g_prof_mu);
     for (int i = 0; i < VS_NUM_STAGES; ++i) { ms_sum[i] = 0.0; launches[i] = 0; }
     for (auto &r : g_prof) {
@@ -943,44 +678,44 @@ int vs_diag_attention_lp(const float *q, const float *k, const float *v, float *
 
 static int linear_entry(const float *A, const float *W, const float *bias, float *C, int32_t M, int32_t N,
                         int32_t K, int32_t relu, const float *pe, int32_t T, int bf16, void *stream) {
-    if (!A || !W || !bias || !C) return fail(VS_ERR_INVALID, "NULL pointer");
+    if (!A || !W || !bias || !C) return vs_failf(VS_ERR_INVALID, "NULL pointer");
     if (M <= 0 || N <= 0 || N % 32 || K <= 0 || K % 32)
-        return fail(VS_ERR_INVALID, "M=%d N=%d K=%d unsupported (N, K multiples of 32)", M, N, K);
-    if (pe && (T <= 0 || relu)) return fail(VS_ERR_INVALID, "pe needs T > 0 and relu == 0");
+        return vs_failf(VS_ERR_INVALID, "M=%d N=%d K=%d unsupported (N, K multiples of 32)", M, N, K);
+    if (pe && (T <= 0 || relu)) return vs_failf(VS_ERR_INVALID, "pe needs T > 0 and relu == 0");
     VS_LAUNCH(vsk_linear(A, W, nullptr, bias, C, M, N, K, relu, pe, T > 0 ? T : 1, bf16, (hipStream_t)stream));
     return VS_OK;
 }
 
 int vs_linear_bf16_operands(const void *A16, const void *W16, const float *bias, void *C, int32_t M, int32_t N, int32_t K,
                             int32_t relu, int32_t c16, void *stream) {
-    if (!A16 || !W16 || !bias || !C) return fail(VS_ERR_INVALID, "NULL pointer");
-    if (!vsk_gemm16_supported(M, N, K)) return fail(VS_ERR_INVALID, "M=%d N=%d K=%d unsupported (N, K multiples of 32)", M, N, K);
-    if (((uintptr_t)A16 | (uintptr_t)W16 | (uintptr_t)C | (uintptr_t)bias) & 15) return fail(VS_ERR_INVALID, "operands must be 16-byte aligned");
+    if (!A16 || !W16 || !bias || !C) return vs_failf(VS_ERR_INVALID, "NULL pointer");
+    if (!vsk_gemm16_supported(M, N, K)) return vs_failf(VS_ERR_INVALID, "M=%d N=%d K=%d unsupported (N, K multiples of 32)", M, N, K);
+    if (((uintptr_t)A16 | (uintptr_t)W16 | (uintptr_t)C | (uintptr_t)bias) & 15) return vs_failf(VS_ERR_INVALID, "operands must be 16-byte aligned");
     VS_LAUNCH(vsk_gemm16(A16, W16, bias, C, M, N, K, relu ? 1 : 0, c16 ? 1 : 0, 1, 0, 0, 1.0f, (hipStream_t)stream));
     return VS_OK;
 }
 
 int vs_qkv_proj_bf16_operands(const void *h16, const void *Wqkv16, const float *bqkv, void *qkv, int32_t B, int32_t T,
                               int32_t d, int32_t H, int32_t c16, void *stream) {
-    if (!h16 || !Wqkv16 || !bqkv || !qkv) return fail(VS_ERR_INVALID, "NULL pointer");
+    if (!h16 || !Wqkv16 || !bqkv || !qkv) return vs_failf(VS_ERR_INVALID, "NULL pointer");
     if (B <= 0 || T <= 0 || d <= 0 || d % 32 || H <= 0 || d % H || (d / H) % 32)
-        return fail(VS_ERR_INVALID, "B=%d T=%d d=%d H=%d unsupported", B, T, d, H);
+        return vs_failf(VS_ERR_INVALID, "B=%d T=%d d=%d H=%d unsupported", B, T, d, H);
     VS_LAUNCH(vsk_gemm16(h16, Wqkv16, bqkv, qkv, B * T, 3 * d, d, 3, c16 ? 1 : 0, T, H, d / H,
                          vsk_attention_qscale(1.0f / sqrtf((float)d)), (hipStream_t)stream));
     return VS_OK;
 }
 
 int vs_to_bf16(const float *src, void *dst16, size_t n, void *stream) {
-    if (!src || !dst16 || n % 8 || (((uintptr_t)src | (uintptr_t)dst16) & 15)) return fail(VS_ERR_INVALID, "vs_to_bf16: n %% 8 == 0, 16-byte aligned pointers");
+    if (!src || !dst16 || n % 8 || (((uintptr_t)src | (uintptr_t)dst16) & 15)) return vs_failf(VS_ERR_INVALID, "vs_to_bf16: n %% 8 == 0, 16-byte aligned pointers");
     VS_LAUNCH(vsk_to_bf16(src, dst16, n, (hipStream_t)stream));
     return VS_OK;
 }
 
 int vs_linear_bf16_a16(const void *A16, const float *W, const float *bias, float *C, int32_t M, int32_t N, int32_t K,
                        const float *pe, void *stream) {
-    if (!A16 || !W || !bias || !C) return fail(VS_ERR_INVALID, "NULL pointer");
+    if (!A16 || !W || !bias || !C) return vs_failf(VS_ERR_INVALID, "NULL pointer");
     if (M <= 0 || N <= 0 || N % 32 || K <= 0 || K % 32)
-        return fail(VS_ERR_INVALID, "M=%d N=%d K=%d unsupported (N, K multiples of 32)", M, N, K);
+        return vs_failf(VS_ERR_INVALID, "M=%d N=%d K=%d unsupported (N, K multiples of 32)", M, N, K);
     VS_LAUNCH(vsk_linear((const float *)A16, W, nullptr, bias, C, M, N, K, 0, pe, M, 1 | VSK_A16, (hipStream_t)stream));
     return VS_OK;
 }
@@ -997,12 +732,12 @@ int vs_linear_bf16(const float *A, const float *W, const float *bias, float *C, 
 
 int vs_mlp_block_bf16(const vs_weights *w, int32_t layer, const float *h, float *out, int32_t M, int32_t with_head,
                       int32_t sigmoid, float *scores, void *stream) {
-    if (!w || !h || !out) return fail(VS_ERR_INVALID, "NULL pointer");
-    if (layer < 0 || layer >= w->desc.num_layers || M <= 0) return fail(VS_ERR_INVALID, "layer=%d M=%d", layer, M);
+    if (!w || !h || !out) return vs_failf(VS_ERR_INVALID, "NULL pointer");
+    if (layer < 0 || layer >= w->desc.num_layers || M <= 0) return vs_failf(VS_ERR_INVALID, "layer=%d M=%d", layer, M);
     if (!vsk_mlp_bf16_supported(w->desc.d_model))
-        return fail(VS_ERR_INVALID, "the fused bf16 MLP kernel needs d_model == 256 (got %d)", w->desc.d_model);
-    if (with_head && !scores) return fail(VS_ERR_INVALID, "scores is NULL");
-    if (((uintptr_t)h & 15) || ((uintptr_t)out & 15)) return fail(VS_ERR_INVALID, "h/out must be 16-byte aligned");
+        return vs_failf(VS_ERR_INVALID, "the fused bf16 MLP kernel needs d_model == 256 (got %d)", w->desc.d_model);
+    if (with_head && !scores) return vs_failf(VS_ERR_INVALID, "scores is NULL");
+    if (((uintptr_t)h & 15) || ((uintptr_t)out & 15)) return vs_failf(VS_ERR_INVALID, "h/out must be 16-byte aligned");
     const LayerOff &P = w->layers[layer];
     if (int rc = vsw_ensure(w, VSW_BF16, stream)) return rc;
     VS_LAUNCH(vsk_mlp_bf16(h, nullptr, nullptr, nullptr, nullptr, w->p(P.b_mlp), w->p(P.b1), w->p(P.b2), w->p(P.ln2g), w->p(P.ln2b), out, M,
@@ -1018,28 +753,28 @@ int vs_linear_f16x3(const float *A, const float *W, const float *bias, float *C,
 
 int vs_qkv_proj_f32(const float *h, const float *Wqkv, const float *bqkv, float *qkv, int32_t B,
                     int32_t T, int32_t d, int32_t H, void *stream) {
-    if (!h || !Wqkv || !bqkv || !qkv) return fail(VS_ERR_INVALID, "NULL pointer");
+    if (!h || !Wqkv || !bqkv || !qkv) return vs_failf(VS_ERR_INVALID, "NULL pointer");
     if (B <= 0 || T <= 0 || d <= 0 || d % 32 || H <= 0 || d % H || (d / H) % 32)
-        return fail(VS_ERR_INVALID, "B=%d T=%d d=%d H=%d unsupported", B, T, d, H);
+        return vs_failf(VS_ERR_INVALID, "B=%d T=%d d=%d H=%d unsupported", B, T, d, H);
     VS_LAUNCH(vsk_qkv(h, Wqkv, nullptr, bqkv, qkv, B, T, d, H, 0, (hipStream_t)stream));
     return VS_OK;
 }
 
 int vs_attention_f32(const float *q, const float *k, const float *v, const uint8_t *key_pad_mask,
                      float *out, int32_t B, int32_t H, int32_t T, int32_t dh, float scale, void *stream) {
-    if (!q || !k || !v || !out) return fail(VS_ERR_INVALID, "NULL pointer");
-    if (B <= 0 || H <= 0 || T <= 0) return fail(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
-    if (dh != 32 && dh != 64 && dh != 128) return fail(VS_ERR_INVALID, "head_dim=%d unsupported", dh);
+    if (!q || !k || !v || !out) return vs_failf(VS_ERR_INVALID, "NULL pointer");
+    if (B <= 0 || H <= 0 || T <= 0) return vs_failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
+    if (dh != 32 && dh != 64 && dh != 128) return vs_failf(VS_ERR_INVALID, "head_dim=%d unsupported", dh);
     VS_LAUNCH(vsk_attention(q, k, v, key_pad_mask, out, B, H, T, dh, scale, (hipStream_t)stream));
     return VS_OK;
 }
 
 static int attention_lp_entry(const float *q, const float *k, const float *v, const uint8_t *key_pad_mask,
                               float *out, int32_t B, int32_t H, int32_t T, int32_t dh, float scale, int prec, void *stream) {
-    if (!q || !k || !v || !out) return fail(VS_ERR_INVALID, "NULL pointer");
-    if (B <= 0 || H <= 0 || T <= 0) return fail(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
+    if (!q || !k || !v || !out) return vs_failf(VS_ERR_INVALID, "NULL pointer");
+    if (B <= 0 || H <= 0 || T <= 0) return vs_failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
     if (dh != 32 && dh != 64 && !(dh == 128 && prec == 1))
-        return fail(VS_ERR_INVALID, "head_dim=%d unsupported on the %s path", dh, prec == 1 ? "bf16" : "f16x3");
+        return vs_failf(VS_ERR_INVALID, "head_dim=%d unsupported on the %s path", dh, prec == 1 ? "bf16" : "f16x3");
     VS_LAUNCH(vsk_attention_bf16(q, k, v, key_pad_mask, out, B, H, T, dh, scale, prec, (hipStream_t)stream));
     return VS_OK;
 }
@@ -1051,11 +786,11 @@ int vs_attention_bf16(const float *q, const float *k, const float *v, const uint
 
 int vs_attention_bf16_stored(const void *q16, const void *k16, const void *v16, const uint8_t *key_pad_mask,
                              void *out16, int32_t B, int32_t H, int32_t T, int32_t dh, void *stream) {
-    if (!q16 || !k16 || !v16 || !out16) return fail(VS_ERR_INVALID, "NULL pointer");
-    if (B <= 0 || H <= 0 || T <= 0) return fail(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
-    if (dh != 32 && dh != 64 && dh != 128) return fail(VS_ERR_INVALID, "head_dim=%d unsupported on the bf16 path", dh);
+    if (!q16 || !k16 || !v16 || !out16) return vs_failf(VS_ERR_INVALID, "NULL pointer");
+    if (B <= 0 || H <= 0 || T <= 0) return vs_failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
+    if (dh != 32 && dh != 64 && dh != 128) return vs_failf(VS_ERR_INVALID, "head_dim=%d unsupported on the bf16 path", dh);
     if ((((uintptr_t)q16 | (uintptr_t)k16 | (uintptr_t)v16 | (uintptr_t)out16) & 15) != 0)
-        return fail(VS_ERR_INVALID, "q16 / k16 / v16 / out16 must be 16-byte aligned");
+        return vs_failf(VS_ERR_INVALID, "q16 / k16 / v16 / out16 must be 16-byte aligned");
     VS_LAUNCH(vsk_attention_bf16((const float *)q16, (const float *)k16, (const float *)v16, key_pad_mask, (float *)out16, B, H, T, dh,
                                  1.0f, 1 | VSK_STORE16, (hipStream_t)stream));
     return VS_OK;
@@ -1073,12 +808,12 @@ static int linear_ln_entry(const float *A, const float *W, const float *bias,
                            float *out, int32_t M, int32_t N, int32_t K, const float *score_w,
                            const float *score_b, int32_t num_classes, int32_t sigmoid,
                            float *scores, int bf16, void *stream) {
-    if (!A || !W || !bias || !residual || !gamma || !beta || !out) return fail(VS_ERR_INVALID, "NULL pointer");
+    if (!A || !W || !bias || !residual || !gamma || !beta || !out) return vs_failf(VS_ERR_INVALID, "NULL pointer");
     if (M <= 0 || N <= 0 || N % 64 || N > 512 || K <= 0 || K % 16)
-        return fail(VS_ERR_INVALID, "M=%d N=%d K=%d unsupported (N multiple of 64 <= 512, K multiple of 16)", M, N, K);
+        return vs_failf(VS_ERR_INVALID, "M=%d N=%d K=%d unsupported (N multiple of 64 <= 512, K multiple of 16)", M, N, K);
     if (score_w && (!score_b || !scores || num_classes <= 0))
-        return fail(VS_ERR_INVALID, "score head needs score_b, scores and num_classes > 0");
-    if (bf16 && N > 256) return fail(VS_ERR_INVALID, "N=%d unsupported on the bf16 path (N <= 256)", N);
+        return vs_failf(VS_ERR_INVALID, "score head needs score_b, scores and num_classes > 0");
+    if (bf16 && N > 256) return vs_failf(VS_ERR_INVALID, "N=%d unsupported on the bf16 path (N <= 256)", N);
     VS_LAUNCH(vsk_linear_res_ln(A, W, nullptr, bias, residual, gamma, beta, out, M, N, K, score_w, score_b, num_classes,
                                 sigmoid, scores, bf16, (hipStream_t)stream));
     return VS_OK;

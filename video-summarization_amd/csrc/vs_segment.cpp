@@ -4,41 +4,17 @@
 
 #include <climits>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
+#include "vs_error.h"
 #include "vs_kernels.h"
 #include "vs_scorer.h"
 #include "vs_segment.h"
 #include "vs_segment_kernels.h"
 
-int vs_fail_msg(int code, const char *msg);     // vs_scorer.cpp: sets the thread-local error text
-
 namespace {
-
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return vs_fail_msg(code, buf);
-}
-
-#define KTS_HIP(call)                                                                              \
-    do {                                                                                           \
-        const hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return fail(VS_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));     \
-    } while (0)
-
-#define KTS_LAUNCH(call)                                                                           \
-    do {                                                                                           \
-        const int e_ = (call);                                                                     \
-        if (e_ > 0) return fail(VS_ERR_HIP, "%s: %s", #call, hipGetErrorString((hipError_t)e_));   \
-        if (e_ < 0) return fail(VS_ERR_INVALID, "%s: unsupported shape", #call);                   \
-    } while (0)
 
 constexpr int32_t kMaxFrames = 1 << 16;          // (n + 1)^2 doubles of W stay addressable with 32-bit row indices
 constexpr int32_t kDefaultLmax = 100000;         // the reference's cpd_nonlin default
@@ -59,15 +35,15 @@ struct Plan {
 // Checks everything that needs no GPU and lays out the workspace.  Returns VS_OK or VS_ERR_INVALID (message set).
 int make_plan(const int32_t *cu, int32_t batch, int32_t d, int32_t input, const int32_t *ncp, const int32_t *lmin,
               const int32_t *lmax, int32_t mode, Plan &P) {
-    if (!cu || !ncp) return fail(VS_ERR_INVALID, "cu / ncp is NULL");
-    if (batch <= 0) return fail(VS_ERR_INVALID, "batch=%d must be positive", batch);
+    if (!cu || !ncp) return vs_failf(VS_ERR_INVALID, "cu / ncp is NULL");
+    if (batch <= 0) return vs_failf(VS_ERR_INVALID, "batch=%d must be positive", batch);
     if (input != VS_KTS_FEATURES_F32 && input != VS_KTS_KERNEL_F32 && input != VS_KTS_KERNEL_F64)
-        return fail(VS_ERR_INVALID, "input=%d is not a VS_KTS_* input kind", input);
+        return vs_failf(VS_ERR_INVALID, "input=%d is not a VS_KTS_* input kind", input);
     if (mode != VS_KTS_SCORES && mode != VS_KTS_BACKTRACK && mode != VS_KTS_AUTO)
-        return fail(VS_ERR_INVALID, "mode=%d is not a VS_KTS_* mode", mode);
+        return vs_failf(VS_ERR_INVALID, "mode=%d is not a VS_KTS_* mode", mode);
     const bool feats = input == VS_KTS_FEATURES_F32;
-    if (feats && d <= 0) return fail(VS_ERR_INVALID, "d=%d must be positive for features", d);
-    if (cu[0] != 0) return fail(VS_ERR_INVALID, "cu[0]=%d must be 0", cu[0]);
+    if (feats && d <= 0) return vs_failf(VS_ERR_INVALID, "d=%d must be positive for features", d);
+    if (cu[0] != 0) return vs_failf(VS_ERR_INVALID, "cu[0]=%d must be 0", cu[0]);
     P.vids.assign(batch, KtsVideo{});
     P.d_pad = feats ? round32(d) : 0;
     int64_t off = align256((int64_t)batch * (int64_t)sizeof(KtsVideo));
@@ -77,13 +53,13 @@ int make_plan(const int32_t *cu, int32_t batch, int32_t d, int32_t input, const 
         const int32_t n = cu[b + 1] - cu[b];
         const int32_t m = ncp[b];
         const int32_t lo = lmin ? lmin[b] : 1, hi = lmax ? lmax[b] : kDefaultLmax;
-        if (n <= 0 || n > kMaxFrames) return fail(VS_ERR_INVALID, "video %d: n=%d frames outside [1, %d]", b, n, kMaxFrames);
-        if (m < 0) return fail(VS_ERR_INVALID, "video %d: ncp=%d must be >= 0", b, m);
-        if (!(hi >= lo && lo >= 1)) return fail(VS_ERR_INVALID, "video %d: needs lmax >= lmin >= 1 (lmin=%d lmax=%d)", b, lo, hi);
+        if (n <= 0 || n > kMaxFrames) return vs_failf(VS_ERR_INVALID, "video %d: n=%d frames outside [1, %d]", b, n, kMaxFrames);
+        if (m < 0) return vs_failf(VS_ERR_INVALID, "video %d: ncp=%d must be >= 0", b, m);
+        if (!(hi >= lo && lo >= 1)) return vs_failf(VS_ERR_INVALID, "video %d: needs lmax >= lmin >= 1 (lmin=%d lmax=%d)", b, lo, hi);
         if ((int64_t)n < (int64_t)(m + 1) * lo)
-            return fail(VS_ERR_INVALID, "video %d: needs n >= (ncp + 1) * lmin (n=%d ncp=%d lmin=%d)", b, n, m, lo);
+            return vs_failf(VS_ERR_INVALID, "video %d: needs n >= (ncp + 1) * lmin (n=%d ncp=%d lmin=%d)", b, n, m, lo);
         if ((int64_t)n > (int64_t)(m + 1) * hi)
-            return fail(VS_ERR_INVALID, "video %d: needs n <= (ncp + 1) * lmax (n=%d ncp=%d lmax=%d)", b, n, m, hi);
+            return vs_failf(VS_ERR_INVALID, "video %d: needs n <= (ncp + 1) * lmax (n=%d ncp=%d lmax=%d)", b, n, m, hi);
         KtsVideo &V = P.vids[b];
         V.n = n; V.m = m; V.lmin = lo; V.lmax = hi; V.mbest = m;
         const int64_t ld = n + 1;
@@ -129,21 +105,21 @@ int make_plan(const int32_t *cu, int32_t batch, int32_t d, int32_t input, const 
 // buffer (zero rows / columns add nothing), C = Xpad[:n] Xpad^T with a zero bias, row stride round32(n)
 int gram(const float *x, int32_t d, const int32_t *cu, const Plan &P, char *ws, hipStream_t st) {
     float *bias = (float *)(ws + P.bias_off), *xpad = (float *)(ws + P.xpad_off);
-    KTS_HIP(hipMemsetAsync(bias, 0, (size_t)round32(P.n_max) * 4, st));
+    VS_HIP(hipMemsetAsync(bias, 0, (size_t)round32(P.n_max) * 4, st));
     for (size_t b = 0; b < P.vids.size(); ++b) {
         const KtsVideo &V = P.vids[b];
         const int32_t npad = V.ldk;
-        if (d != P.d_pad) KTS_HIP(hipMemsetAsync(xpad, 0, (size_t)npad * P.d_pad * 4, st));
-        else if (npad > V.n) KTS_HIP(hipMemsetAsync(xpad + (size_t)V.n * P.d_pad, 0, (size_t)(npad - V.n) * P.d_pad * 4, st));
-        KTS_HIP(hipMemcpy2DAsync(xpad, (size_t)P.d_pad * 4, x + (size_t)cu[b] * d, (size_t)d * 4, (size_t)d * 4, V.n,
+        if (d != P.d_pad) VS_HIP(hipMemsetAsync(xpad, 0, (size_t)npad * P.d_pad * 4, st));
+        else if (npad > V.n) VS_HIP(hipMemsetAsync(xpad + (size_t)V.n * P.d_pad, 0, (size_t)(npad - V.n) * P.d_pad * 4, st));
+        VS_HIP(hipMemcpy2DAsync(xpad, (size_t)P.d_pad * 4, x + (size_t)cu[b] * d, (size_t)d * 4, (size_t)d * 4, V.n,
                                  hipMemcpyDeviceToDevice, st));
-        KTS_LAUNCH(vsk_linear(xpad, xpad, nullptr, bias, (float *)(ws + V.k_off), V.n, npad, P.d_pad, 0, nullptr, 1, 0, st));
+        VS_LAUNCH(vsk_linear(xpad, xpad, nullptr, bias, (float *)(ws + V.k_off), V.n, npad, P.d_pad, 0, nullptr, 1, 0, st));
     }
     return VS_OK;
 }
 
 int upload(const Plan &P, char *ws, hipStream_t st) {
-    KTS_HIP(hipMemcpyAsync(ws, P.vids.data(), P.vids.size() * sizeof(KtsVideo), hipMemcpyHostToDevice, st));
+    VS_HIP(hipMemcpyAsync(ws, P.vids.data(), P.vids.size() * sizeof(KtsVideo), hipMemcpyHostToDevice, st));
     return VS_OK;
 }
 
@@ -154,21 +130,21 @@ int table(const void *x, int32_t input, int32_t d, const int32_t *cu, const Plan
     const KtsVideo *dv = (const KtsVideo *)ws;
     if (input == VS_KTS_FEATURES_F32) {
         if (int rc = gram((const float *)x, d, cu, P, ws, st)) return rc;
-        KTS_LAUNCH(vsk_kts_scatter_table(dv, B, P.n_max, ws, ws, 0, st));
+        VS_LAUNCH(vsk_kts_scatter_table(dv, B, P.n_max, ws, ws, 0, st));
     } else {
-        KTS_LAUNCH(vsk_kts_scatter_table(dv, B, P.n_max, ws, x, input == VS_KTS_KERNEL_F64, st));
+        VS_LAUNCH(vsk_kts_scatter_table(dv, B, P.n_max, ws, x, input == VS_KTS_KERNEL_F64, st));
     }
     return VS_OK;
 }
 
 
 int check_kernel(const vs_kts_kernel *kern) {
-    if (!kern) return fail(VS_ERR_INVALID, "kern is NULL");
+    if (!kern) return vs_failf(VS_ERR_INVALID, "kern is NULL");
     if (kern->kind != VS_KTS_GRAM_DOT && kern->kind != VS_KTS_GRAM_COSINE && kern->kind != VS_KTS_GRAM_RBF)
-        return fail(VS_ERR_INVALID, "kern->kind=%d is not a VS_KTS_GRAM_* kind", kern->kind);
-    if (kern->reserved != 0) return fail(VS_ERR_INVALID, "kern->reserved=%d must be 0", kern->reserved);
+        return vs_failf(VS_ERR_INVALID, "kern->kind=%d is not a VS_KTS_GRAM_* kind", kern->kind);
+    if (kern->reserved != 0) return vs_failf(VS_ERR_INVALID, "kern->reserved=%d must be 0", kern->reserved);
     if (kern->kind == VS_KTS_GRAM_RBF && !(std::isfinite(kern->gamma) && kern->gamma > 0.0))
-        return fail(VS_ERR_INVALID, "kern->gamma=%g must be finite and > 0 for VS_KTS_GRAM_RBF", kern->gamma);
+        return vs_failf(VS_ERR_INVALID, "kern->gamma=%g must be finite and > 0 for VS_KTS_GRAM_RBF", kern->gamma);
     return VS_OK;
 }
 
@@ -183,7 +159,7 @@ int plan_gram(const int32_t *cu, int32_t batch, Plan &P, int64_t off) {
         G.tile0 = (int32_t)tiles;
         const int64_t t = (G.n + KTS_GRAM_TILE - 1) / KTS_GRAM_TILE;
         tiles += t * (t + 1) / 2;
-        if (tiles > INT32_MAX) return fail(VS_ERR_INVALID, "the batch has more than 2^31 Gram tiles");
+        if (tiles > INT32_MAX) return vs_failf(VS_ERR_INVALID, "the batch has more than 2^31 Gram tiles");
     }
     P.tiles = (int32_t)tiles;
     P.gvids_off = off; off = align256(off + (int64_t)batch * (int64_t)sizeof(KtsGramVideo));
@@ -195,13 +171,13 @@ int plan_gram(const int32_t *cu, int32_t batch, Plan &P, int64_t off) {
 // row norms (cosine / rbf), the table, the one Gram launch: all enqueued, nothing copied from host memory
 int gram_k(const float *x, int32_t d, int32_t rows, const vs_kts_kernel &kern, const Plan &P, char *ws, void *kbase,
            hipStream_t st) {
-    KTS_LAUNCH(vsk_kts_put(P.gvids.data(), P.gvids.size() * sizeof(KtsGramVideo), ws + P.gvids_off, st));
+    VS_LAUNCH(vsk_kts_put(P.gvids.data(), P.gvids.size() * sizeof(KtsGramVideo), ws + P.gvids_off, st));
     double *nrm = nullptr;
     if (kern.kind != VS_KTS_GRAM_DOT) {
         nrm = (double *)(ws + P.nrm_off);
-        KTS_LAUNCH(vsk_kts_row_norms(x, d, rows, kern.kind == VS_KTS_GRAM_COSINE, nrm, st));
+        VS_LAUNCH(vsk_kts_row_norms(x, d, rows, kern.kind == VS_KTS_GRAM_COSINE, nrm, st));
     }
-    KTS_LAUNCH(vsk_kts_gram(x, d, (const KtsGramVideo *)(ws + P.gvids_off), (int)P.gvids.size(), P.tiles, kern.kind,
+    VS_LAUNCH(vsk_kts_gram(x, d, (const KtsGramVideo *)(ws + P.gvids_off), (int)P.gvids.size(), P.tiles, kern.kind,
                             kern.gamma, nrm, kbase, st));
     return VS_OK;
 }
@@ -211,7 +187,7 @@ int make_plan_k(const int32_t *cu, int32_t batch, int32_t d, int32_t input, cons
                 const int32_t *lmax, int32_t mode, const vs_kts_kernel *kern, Plan &P) {
     if (int rc = check_kernel(kern)) return rc;
     if (input == VS_KTS_KERNEL_F32 || input == VS_KTS_KERNEL_F64)
-        return fail(VS_ERR_INVALID, "a kernel-matrix input has its kernel already: kern needs VS_KTS_FEATURES_F32");
+        return vs_failf(VS_ERR_INVALID, "a kernel-matrix input has its kernel already: kern needs VS_KTS_FEATURES_F32");
     if (int rc = make_plan(cu, batch, d, input, ncp, lmin, lmax, mode, P)) return rc;
     if (int rc = plan_gram(cu, batch, P, P.total)) return rc;
     for (int32_t b = 0; b < batch; ++b) {
@@ -224,9 +200,9 @@ int make_plan_k(const int32_t *cu, int32_t batch, int32_t d, int32_t input, cons
 // features -> scatter table through the one-launch Gram
 int table_k(const float *x, int32_t d, const int32_t *cu, const vs_kts_kernel &kern, const Plan &P, char *ws, hipStream_t st) {
     const int B = (int)P.vids.size();
-    KTS_LAUNCH(vsk_kts_put(P.vids.data(), P.vids.size() * sizeof(KtsVideo), ws, st));
+    VS_LAUNCH(vsk_kts_put(P.vids.data(), P.vids.size() * sizeof(KtsVideo), ws, st));
     if (int rc = gram_k(x, d, cu[B], kern, P, ws, ws, st)) return rc;
-    KTS_LAUNCH(vsk_kts_scatter_table((const KtsVideo *)ws, B, P.n_max, ws, ws, 0, st));
+    VS_LAUNCH(vsk_kts_scatter_table((const KtsVideo *)ws, B, P.n_max, ws, ws, 0, st));
     return VS_OK;
 }
 
@@ -234,13 +210,13 @@ int table_k(const float *x, int32_t d, const int32_t *cu, const vs_kts_kernel &k
 int finish_segment(Plan &P, int32_t batch, const double *vmax, const double *desc_rate, int32_t mode, int64_t *cps,
                    int32_t *n_cps, double *scores, char *ws, hipStream_t st) {
     const KtsVideo *dv = (const KtsVideo *)ws;
-    KTS_LAUNCH(vsk_kts_dp_init(dv, batch, P.n_max, ws, st));
-    for (int32_t k = 1; k <= P.m_max; ++k) KTS_LAUNCH(vsk_kts_dp_step(dv, batch, P.n_max, k, ws, st));
+    VS_LAUNCH(vsk_kts_dp_init(dv, batch, P.n_max, ws, st));
+    for (int32_t k = 1; k <= P.m_max; ++k) VS_LAUNCH(vsk_kts_dp_step(dv, batch, P.n_max, k, ws, st));
 
     int64_t n_scores = 0, n_total_cps = 0;
     for (const KtsVideo &V : P.vids) { n_scores += V.m + 1; n_total_cps += V.m; }
-    KTS_HIP(hipMemcpyAsync(scores, ws + P.vids[0].s_off, (size_t)n_scores * 8, hipMemcpyDeviceToHost, st));
-    KTS_HIP(hipStreamSynchronize(st));
+    VS_HIP(hipMemcpyAsync(scores, ws + P.vids[0].s_off, (size_t)n_scores * 8, hipMemcpyDeviceToHost, st));
+    VS_HIP(hipStreamSynchronize(st));
     for (int64_t i = 0; i < n_scores; ++i)
         if (scores[i] > 1e99) scores[i] = INFINITY;           // scores[scores > 1e99] = np.inf
 
@@ -256,7 +232,7 @@ int finish_segment(Plan &P, int32_t batch, const double *vmax, const double *des
                 if (s[c] < s[best]) best = c;
             }
             if ((int64_t)V.n > (int64_t)(best + 1) * V.lmax)
-                return fail(VS_ERR_INVALID, "video %d: needs n <= (m_best + 1) * lmax (n=%d m_best=%d lmax=%d)", b, V.n, best,
+                return vs_failf(VS_ERR_INVALID, "video %d: needs n <= (m_best + 1) * lmax (n=%d m_best=%d lmax=%d)", b, V.n, best,
                             V.lmax);
             V.mbest = best;
             s += V.m + 1;
@@ -269,10 +245,10 @@ int finish_segment(Plan &P, int32_t batch, const double *vmax, const double *des
         return VS_OK;
     }
     if (int rc = upload(P, ws, st)) return rc;               // m_best
-    KTS_LAUNCH(vsk_kts_backtrack(dv, batch, ws, st));
+    VS_LAUNCH(vsk_kts_backtrack(dv, batch, ws, st));
     std::vector<int32_t> c32((size_t)n_total_cps + 1);
-    KTS_HIP(hipMemcpyAsync(c32.data(), ws + P.vids[0].c_off, (size_t)n_total_cps * 4, hipMemcpyDeviceToHost, st));
-    KTS_HIP(hipStreamSynchronize(st));
+    VS_HIP(hipMemcpyAsync(c32.data(), ws + P.vids[0].c_off, (size_t)n_total_cps * 4, hipMemcpyDeviceToHost, st));
+    VS_HIP(hipStreamSynchronize(st));
     for (int32_t b = 0; b < batch; ++b) {
         const KtsVideo &V = P.vids[b];
         n_cps[b] = V.mbest;
@@ -297,14 +273,14 @@ int vs_kts_segment(const void *x, int32_t input, int32_t d, const int32_t *cu, i
                    int64_t *cps, int32_t *n_cps, double *scores, void *workspace, size_t workspace_bytes, void *stream) {
     Plan P;
     if (int rc = make_plan(cu, batch, d, input, ncp, lmin, lmax, mode, P)) return rc;
-    if (!x || !cps || !n_cps || !scores) return fail(VS_ERR_INVALID, "x / cps / n_cps / scores is NULL");
+    if (!x || !cps || !n_cps || !scores) return vs_failf(VS_ERR_INVALID, "x / cps / n_cps / scores is NULL");
     if (mode == VS_KTS_AUTO) {
-        if (!vmax) return fail(VS_ERR_INVALID, "vmax is NULL (needed by VS_KTS_AUTO)");
+        if (!vmax) return vs_failf(VS_ERR_INVALID, "vmax is NULL (needed by VS_KTS_AUTO)");
         for (int32_t b = 0; b < batch; ++b)
-            if (desc_rate && !(desc_rate[b] > 0)) return fail(VS_ERR_INVALID, "video %d: desc_rate=%g must be > 0", b, desc_rate[b]);
+            if (desc_rate && !(desc_rate[b] > 0)) return vs_failf(VS_ERR_INVALID, "video %d: desc_rate=%g must be > 0", b, desc_rate[b]);
     }
     if (!workspace || workspace_bytes < (size_t)P.total)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
     if (int rc = table(x, input, d, cu, P, ws, st)) return rc;
@@ -316,14 +292,14 @@ int vs_kts_scatters(const void *x, int32_t input, int32_t d, int32_t n, double *
     const int32_t cu[2] = {0, n}, zero = 0;
     Plan P;
     if (int rc = make_plan(cu, 1, d, input, &zero, nullptr, nullptr, VS_KTS_SCORES, P)) return rc;
-    if (!x || !scatters) return fail(VS_ERR_INVALID, "x / scatters is NULL");
+    if (!x || !scatters) return vs_failf(VS_ERR_INVALID, "x / scatters is NULL");
     if (!workspace || workspace_bytes < (size_t)P.total)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
     if (int rc = table(x, input, d, cu, P, ws, st)) return rc;
-    KTS_LAUNCH(vsk_kts_scatters_out((const KtsVideo *)ws, n, ws, scatters, st));
-    KTS_HIP(hipStreamSynchronize(st));                        // the plan's host copy of the descriptors ends here
+    VS_LAUNCH(vsk_kts_scatters_out((const KtsVideo *)ws, n, ws, scatters, st));
+    VS_HIP(hipStreamSynchronize(st));                        // the plan's host copy of the descriptors ends here
     return VS_OK;
 }
 
@@ -331,7 +307,7 @@ size_t vs_kts_gram_workspace_bytes(const int32_t *cu, int32_t batch, int32_t d) 
     const vs_kts_kernel dot = {VS_KTS_GRAM_DOT, 0, 0.0};
     Plan P;
     std::vector<int32_t> zeros(batch > 0 ? batch : 0, 0);
-    if (!cu || batch <= 0) { fail(VS_ERR_INVALID, "cu is NULL or batch=%d is not positive", batch); return 0; }
+    if (!cu || batch <= 0) { vs_failf(VS_ERR_INVALID, "cu is NULL or batch=%d is not positive", batch); return 0; }
     if (make_plan_k(cu, batch, d, VS_KTS_FEATURES_F32, zeros.data(), nullptr, nullptr, VS_KTS_SCORES, &dot, P) != VS_OK)
         return 0;                                            // the same checks of cu / d as every other entry point
     if (plan_gram(cu, batch, P, 0) != VS_OK) return 0;
@@ -341,10 +317,10 @@ size_t vs_kts_gram_workspace_bytes(const int32_t *cu, int32_t batch, int32_t d) 
 int vs_kts_gram(const void *x, int32_t d, const int32_t *cu, int32_t batch, const vs_kts_kernel *kern, float *K_out,
                 void *workspace, size_t workspace_bytes, void *stream) {
     Plan P;
-    if (!cu || batch <= 0) return fail(VS_ERR_INVALID, "cu is NULL or batch=%d is not positive", batch);
+    if (!cu || batch <= 0) return vs_failf(VS_ERR_INVALID, "cu is NULL or batch=%d is not positive", batch);
     std::vector<int32_t> zeros(batch, 0);
     if (int rc = make_plan_k(cu, batch, d, VS_KTS_FEATURES_F32, zeros.data(), nullptr, nullptr, VS_KTS_SCORES, kern, P)) return rc;
-    if (!x || !K_out) return fail(VS_ERR_INVALID, "x / K_out is NULL");
+    if (!x || !K_out) return vs_failf(VS_ERR_INVALID, "x / K_out is NULL");
     if (int rc = plan_gram(cu, batch, P, 0)) return rc;
     int64_t k_off = 0;
     for (int32_t b = 0; b < batch; ++b) {                    // dense, one video after the other
@@ -354,7 +330,7 @@ int vs_kts_gram(const void *x, int32_t d, const int32_t *cu, int32_t batch, cons
         k_off += (int64_t)G.n * G.n * 4;
     }
     if (!workspace || workspace_bytes < (size_t)P.total)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
     return gram_k((const float *)x, d, cu[batch], *kern, P, (char *)workspace, K_out, (hipStream_t)stream);
 }
 
@@ -371,14 +347,14 @@ int vs_kts_segment_k(const void *x, int32_t input, int32_t d, const int32_t *cu,
                      size_t workspace_bytes, void *stream) {
     Plan P;
     if (int rc = make_plan_k(cu, batch, d, input, ncp, lmin, lmax, mode, kern, P)) return rc;
-    if (!x || !cps || !n_cps || !scores) return fail(VS_ERR_INVALID, "x / cps / n_cps / scores is NULL");
+    if (!x || !cps || !n_cps || !scores) return vs_failf(VS_ERR_INVALID, "x / cps / n_cps / scores is NULL");
     if (mode == VS_KTS_AUTO) {
-        if (!vmax) return fail(VS_ERR_INVALID, "vmax is NULL (needed by VS_KTS_AUTO)");
+        if (!vmax) return vs_failf(VS_ERR_INVALID, "vmax is NULL (needed by VS_KTS_AUTO)");
         for (int32_t b = 0; b < batch; ++b)
-            if (desc_rate && !(desc_rate[b] > 0)) return fail(VS_ERR_INVALID, "video %d: desc_rate=%g must be > 0", b, desc_rate[b]);
+            if (desc_rate && !(desc_rate[b] > 0)) return vs_failf(VS_ERR_INVALID, "video %d: desc_rate=%g must be > 0", b, desc_rate[b]);
     }
     if (!workspace || workspace_bytes < (size_t)P.total)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
     if (int rc = table_k((const float *)x, d, cu, *kern, P, ws, st)) return rc;
@@ -390,7 +366,7 @@ int vs_kts_eval_score(const void *x, int32_t input, int32_t d, const vs_kts_kern
                       void *stream) {
     const vs_kts_kernel dot = {VS_KTS_GRAM_DOT, 0, 0.0};
     const bool feats = input == VS_KTS_FEATURES_F32;
-    if (!n_cps) return fail(VS_ERR_INVALID, "n_cps is NULL");
+    if (!n_cps) return vs_failf(VS_ERR_INVALID, "n_cps is NULL");
     Plan P;
     if (feats) {
         if (int rc = make_plan_k(cu, batch, d, input, n_cps, nullptr, nullptr, VS_KTS_SCORES, kern ? kern : &dot, P)) return rc;
@@ -399,7 +375,7 @@ int vs_kts_eval_score(const void *x, int32_t input, int32_t d, const vs_kts_kern
     }
     int64_t total_cps = 0;
     for (int32_t b = 0; b < batch; ++b) total_cps += n_cps[b];
-    if (!x || !scores_out || (total_cps && !cps)) return fail(VS_ERR_INVALID, "x / cps / scores_out is NULL");
+    if (!x || !scores_out || (total_cps && !cps)) return vs_failf(VS_ERR_INVALID, "x / cps / scores_out is NULL");
     std::vector<int32_t> c32((size_t)total_cps + 1);
     int64_t at = 0;
     for (int32_t b = 0; b < batch; ++b) {
@@ -408,14 +384,14 @@ int vs_kts_eval_score(const void *x, int32_t input, int32_t d, const vs_kts_kern
         for (int32_t i = 0; i < n_cps[b]; ++i, ++at) {
             const int64_t c = cps[at];
             if (c <= prev || c > n - 1)
-                return fail(VS_ERR_INVALID, "video %d: change point %d = %lld must be in 1 .. n - 1 = %d and above the one before it",
+                return vs_failf(VS_ERR_INVALID, "video %d: change point %d = %lld must be in 1 .. n - 1 = %d and above the one before it",
                             b, i, (long long)c, n - 1);
             c32[(size_t)at] = (int32_t)c;
             prev = c;
         }
     }
     if (!workspace || workspace_bytes < (size_t)P.total)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
     if (feats) {
@@ -423,14 +399,14 @@ int vs_kts_eval_score(const void *x, int32_t input, int32_t d, const vs_kts_kern
     } else if (int rc = table(x, input, d, cu, P, ws, st)) {
         return rc;
     }
-    if (total_cps) KTS_LAUNCH(vsk_kts_put(c32.data(), (size_t)total_cps * 4, ws + P.vids[0].c_off, st));
-    KTS_LAUNCH(vsk_kts_eval((const KtsVideo *)ws, batch, ws, st));
+    if (total_cps) VS_LAUNCH(vsk_kts_put(c32.data(), (size_t)total_cps * 4, ws + P.vids[0].c_off, st));
+    VS_LAUNCH(vsk_kts_eval((const KtsVideo *)ws, batch, ws, st));
     // every video's s_off is (m + 1) doubles after the one before: gather the first of each on the host
     int64_t n_scores = 0;
     for (const KtsVideo &V : P.vids) n_scores += V.m + 1;
     std::vector<double> s((size_t)n_scores);
-    KTS_HIP(hipMemcpyAsync(s.data(), ws + P.vids[0].s_off, (size_t)n_scores * 8, hipMemcpyDeviceToHost, st));
-    KTS_HIP(hipStreamSynchronize(st));
+    VS_HIP(hipMemcpyAsync(s.data(), ws + P.vids[0].s_off, (size_t)n_scores * 8, hipMemcpyDeviceToHost, st));
+    VS_HIP(hipStreamSynchronize(st));
     int64_t si = 0;
     for (int32_t b = 0; b < batch; ++b) {
         scores_out[b] = s[(size_t)si];

@@ -4,40 +4,17 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
+#include "vs_error.h"
 #include "vs_eval_device_kernels.h"
 #include "vs_scorer.h"
 #include "vs_summary.h"
 #include "vs_summary_kernels.h"
 
-int vs_fail_msg(int code, const char *msg);     // vs_scorer.cpp: sets the thread-local error text
-
 namespace {
-
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return vs_fail_msg(code, buf);
-}
-
-#define SM_HIP(call)                                                                               \
-    do {                                                                                           \
-        const hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return fail(VS_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));     \
-    } while (0)
-
-#define SM_LAUNCH(call)                                                                            \
-    do {                                                                                           \
-        const int e_ = (call);                                                                     \
-        if (e_ != 0) return fail(VS_ERR_HIP, "%s: %s", #call, hipGetErrorString((hipError_t)e_));  \
-    } while (0)
 
 constexpr int32_t kMaxFrames = 1 << 18;          // the shot mean's pairwise walk (vs_keyshot_device.h) is sized for it
 constexpr int32_t kMaxSummary = 1 << 24;         // frames of one summary
@@ -62,19 +39,19 @@ struct Plan {
 // segments are not built, only counted by their upper bound n_positions + 1 per video - the layout is the same.
 int make_plan(int32_t n_videos, const int32_t *n_scores, const int32_t *n_positions, const int32_t *n_frames, const int32_t *n_shots,
               const int32_t *positions, const int32_t *change_points, double proportion, Plan &P) {
-    if (n_videos < 1 || n_videos > kMaxVideos) return fail(VS_ERR_INVALID, "summarize: n_videos=%d outside [1, %d]", n_videos, kMaxVideos);
+    if (n_videos < 1 || n_videos > kMaxVideos) return vs_failf(VS_ERR_INVALID, "summarize: n_videos=%d outside [1, %d]", n_videos, kMaxVideos);
     if (!n_positions || !n_frames || !n_shots || !change_points)
-        return fail(VS_ERR_INVALID, "summarize: n_positions / n_frames / n_shots / change_points is NULL");
+        return vs_failf(VS_ERR_INVALID, "summarize: n_positions / n_frames / n_shots / change_points is NULL");
     if (!(proportion >= 0.0 && proportion <= 1.0))             // also false for a NaN
-        return fail(VS_ERR_INVALID, "summarize: proportion=%g is not in [0, 1]", proportion);
+        return vs_failf(VS_ERR_INVALID, "summarize: proportion=%g is not in [0, 1]", proportion);
     P.vid.resize(n_videos);
     int64_t pos_at = 0, score_at = 0, bits = 0, rows = 0;
     for (int32_t v = 0; v < n_videos; ++v) {
         const int32_t nf = n_frames[v], ns = n_shots[v], np0 = n_positions[v], nsc = n_scores ? n_scores[v] : 0;
         if (ns < 1 || np0 < 1 || nf < 0 || nsc < 0)
-            return fail(VS_ERR_INVALID, "summarize: video %d has an empty or negative field (n_shots=%d n_positions=%d n_frames=%d n_scores=%d)",
+            return vs_failf(VS_ERR_INVALID, "summarize: video %d has an empty or negative field (n_shots=%d n_positions=%d n_frames=%d n_scores=%d)",
                         v, ns, np0, nf, nsc);
-        if (nf > kMaxFrames) return fail(VS_ERR_INVALID, "summarize: video %d: n_frames=%d above %d", v, nf, kMaxFrames);
+        if (nf > kMaxFrames) return vs_failf(VS_ERR_INVALID, "summarize: video %d: n_frames=%d above %d", v, nf, kMaxFrames);
         SmVideo &E = P.vid[v];
         E = SmVideo{};
         E.n_frames = nf; E.n_shots = ns;
@@ -86,11 +63,11 @@ int make_plan(int32_t n_videos, const int32_t *n_scores, const int32_t *n_positi
             const int32_t *pos = positions + pos_at;
             for (int i = 1; i < np0; ++i)
                 if (pos[i] < pos[i - 1])
-                    return fail(VS_ERR_INVALID, "summarize: video %d: positions decrease at %d (%d after %d)", v, i, pos[i], pos[i - 1]);
+                    return vs_failf(VS_ERR_INVALID, "summarize: video %d: positions decrease at %d (%d after %d)", v, i, pos[i], pos[i - 1]);
             const int np_ = np0 + (pos[np0 - 1] != nf ? 1 : 0);
             auto at = [&](int i) { return std::max(0, std::min(i < np0 ? pos[i] : nf, nf)); };
             if (np_ - 1 > nsc + 1)
-                return fail(VS_ERR_INVALID, "summarize: video %d: more pick segments (%d) than scores + 1 (%d)", v, np_ - 1, nsc + 1);
+                return vs_failf(VS_ERR_INVALID, "summarize: video %d: more pick segments (%d) than scores + 1 (%d)", v, np_ - 1, nsc + 1);
             const int first = np_ > 1 ? at(0) : nf;             // frames before the first segment hold 0
             if (first > 0) P.seg.push_back(SmSeg{E.frame_off, 0, first, -1, 0});
             for (int i = 0; i + 1 < np_; ++i) {
@@ -103,22 +80,22 @@ int make_plan(int32_t n_videos, const int32_t *n_scores, const int32_t *n_positi
         // shots: generate_summary.py:41-46 and the summary's frames
         const int32_t *cp = change_points + 2 * P.n_shots;
         const int32_t last_end = cp[2 * (ns - 1) + 1];
-        if (last_end < 0) return fail(VS_ERR_INVALID, "summarize: video %d: the last shot ends before frame 0", v);
-        if (last_end >= kMaxSummary) return fail(VS_ERR_INVALID, "summarize: video %d: the last shot ends at %d, above %d", v, last_end, kMaxSummary - 1);
+        if (last_end < 0) return vs_failf(VS_ERR_INVALID, "summarize: video %d: the last shot ends before frame 0", v);
+        if (last_end >= kMaxSummary) return vs_failf(VS_ERR_INVALID, "summarize: video %d: the last shot ends at %d, above %d", v, last_end, kMaxSummary - 1);
         E.L = last_end + 1;
         E.W = (int)((double)(last_end + 1) * proportion);
         int prev_end = -1;
         for (int s = 0; s < ns; ++s) {
             const int32_t a = cp[2 * s], b = cp[2 * s + 1];
             const int64_t wt = (int64_t)b - a + 1;
-            if (wt < 0) return fail(VS_ERR_INVALID, "summarize: video %d: shot %d has a negative length", v, s);
-            if (wt > INT32_MAX) return fail(VS_ERR_INVALID, "summarize: video %d: shot %d is longer than 2^31 - 1 frames", v, s);
+            if (wt < 0) return vs_failf(VS_ERR_INVALID, "summarize: video %d: shot %d has a negative length", v, s);
+            if (wt > INT32_MAX) return vs_failf(VS_ERR_INVALID, "summarize: video %d: shot %d is longer than 2^31 - 1 frames", v, s);
             const int lo = std::max(0, std::min(a, nf)), hi = std::max(lo, (int)std::min<int64_t>((int64_t)b + 1, nf));
             P.shot_lo.push_back(lo); P.shot_hi.push_back(hi); P.shot_wt.push_back((int32_t)wt);
             const int ca = std::max(0, a), cb = std::min(last_end, b);
             const int clip = std::max(0, cb - ca + 1);
             if (clip > 0) {
-                if (ca <= prev_end) return fail(VS_ERR_INVALID, "summarize: video %d: shot %d overlaps or precedes an earlier shot", v, s);
+                if (ca <= prev_end) return vs_failf(VS_ERR_INVALID, "summarize: video %d: shot %d overlaps or precedes an earlier shot", v, s);
                 prev_end = cb;
                 P.ne_start.push_back(ca); P.ne_end.push_back(cb); P.ne_shot.push_back(s);
             }
@@ -166,15 +143,15 @@ int vs_summarize(int32_t n_videos, const int32_t *n_scores, const int32_t *n_pos
                  const int32_t *positions, const int32_t *change_points, double proportion, const float *scores_dev,
                  int8_t *summary_dev, int32_t *frames_dev, int32_t *n_selected_frames, int8_t *selected_shots_or_null,
                  double *shot_means_or_null, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!n_scores || !positions) return fail(VS_ERR_INVALID, "summarize: n_scores / positions is NULL");
+    if (!n_scores || !positions) return vs_failf(VS_ERR_INVALID, "summarize: n_scores / positions is NULL");
     Plan P;
     if (int rc = make_plan(n_videos, n_scores, n_positions, n_frames, n_shots, positions, change_points, proportion, P)) return rc;
     if (!scores_dev || !summary_dev || !frames_dev || !n_selected_frames)
-        return fail(VS_ERR_INVALID, "summarize: scores_dev / summary_dev / frames_dev / n_selected_frames is NULL");
-    if (!workspace) return fail(VS_ERR_INVALID, "summarize: workspace is NULL");
+        return vs_failf(VS_ERR_INVALID, "summarize: scores_dev / summary_dev / frames_dev / n_selected_frames is NULL");
+    if (!workspace) return vs_failf(VS_ERR_INVALID, "summarize: workspace is NULL");
     if (workspace_bytes < (size_t)P.total)
-        return fail(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
-    if (((uintptr_t)workspace & 255) != 0) return fail(VS_ERR_INVALID, "summarize: workspace is not 256-byte aligned");
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %lld needed", workspace_bytes, (long long)P.total);
+    if (((uintptr_t)workspace & 255) != 0) return vs_failf(VS_ERR_INVALID, "summarize: workspace is not 256-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
 
@@ -186,7 +163,7 @@ int vs_summarize(int32_t n_videos, const int32_t *n_scores, const int32_t *n_pos
     put(P.o_wt, P.shot_wt.data(), P.shot_wt.size() * 4); put(P.o_clip, P.shot_clip.data(), P.shot_clip.size() * 4);
     put(P.o_ns, P.ne_start.data(), P.ne_start.size() * 4); put(P.o_ne, P.ne_end.data(), P.ne_end.size() * 4);
     put(P.o_nshot, P.ne_shot.data(), P.ne_shot.size() * 4);
-    SM_HIP(hipMemcpyAsync(ws, up.data(), up.size(), hipMemcpyHostToDevice, st));
+    VS_HIP(hipMemcpyAsync(ws, up.data(), up.size(), hipMemcpyHostToDevice, st));
 
     SmArgs A{};
     A.vid = (const SmVideo *)(ws + P.o_vid); A.seg = (const SmSeg *)(ws + P.o_seg); A.n_seg = (int64_t)P.seg.size();
@@ -196,17 +173,17 @@ int vs_summarize(int32_t n_videos, const int32_t *n_scores, const int32_t *n_pos
     A.frame_src = (int32_t *)(ws + P.o_src); A.shot_dst = (int32_t *)(ws + P.o_dst); A.vidout = (int64_t *)(ws + P.o_vidout);
     A.val = (double *)(ws + P.o_val); A.sel = (int8_t *)(ws + P.o_sel); A.bits = (unsigned long long *)(ws + P.o_bits);
     A.rows = (double *)(ws + P.o_rows); A.summary = summary_dev; A.frames = frames_dev;
-    SM_LAUNCH(vsk_summary_expand_picks(A, st));
-    SM_LAUNCH(vsk_summary_select(A, n_videos, st));
-    SM_LAUNCH(vsk_summary_fill(A, n_videos, P.max_L, st));
+    VS_LAUNCH_HIP(vsk_summary_expand_picks(A, st));
+    VS_LAUNCH_HIP(vsk_summary_select(A, n_videos, st));
+    VS_LAUNCH_HIP(vsk_summary_fill(A, n_videos, P.max_L, st));
     std::vector<char> down((size_t)(P.down_end - P.o_vidout));
-    SM_HIP(hipMemcpyAsync(down.data(), ws + P.o_vidout, down.size(), hipMemcpyDeviceToHost, st));
-    SM_HIP(hipStreamSynchronize(st));
+    VS_HIP(hipMemcpyAsync(down.data(), ws + P.o_vidout, down.size(), hipMemcpyDeviceToHost, st));
+    VS_HIP(hipStreamSynchronize(st));
 
     const int64_t *vidout = (const int64_t *)down.data();
     for (int32_t v = 0; v < n_videos; ++v)
         if (vidout[2 * (size_t)v + 1] != 0)
-            return fail(VS_ERR_INVALID, "summarize: video %d: capacity index out of range in the knapsack back-track (IndexError in the reference)", v);
+            return vs_failf(VS_ERR_INVALID, "summarize: video %d: capacity index out of range in the knapsack back-track (IndexError in the reference)", v);
     for (int32_t v = 0; v < n_videos; ++v) n_selected_frames[v] = (int32_t)vidout[2 * (size_t)v];
     if (shot_means_or_null) std::memcpy(shot_means_or_null, down.data() + (P.o_val - P.o_vidout), (size_t)P.n_shots * 8);
     if (selected_shots_or_null) std::memcpy(selected_shots_or_null, down.data() + (P.o_sel - P.o_vidout), (size_t)P.n_shots);

@@ -2,50 +2,26 @@
 // and the backward pass.  Launch sequences only; the kernels are in vs_kernels.hip (NT GEMMs, reused for every
 // forward Linear and — against transposed weights — for every dgrad), vs_train_kernels.hip and
 // vs_train_attention.hip.  Which form the record has and which mode word each launch gets is decided once per call, in
-// vs_train_plan.h; forward_impl / backward_impl only read that plan.
+// vs_train_plan.h; forward_impl / backward_impl only read that plan.  The transposed weights of the
+// backward are image families of the handle like the scoring side's: vsw_ensure (vs_weights.cpp) builds them.
 #include "vs_train.h"
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
-#include <mutex>
 #include <string>
 
+#include "vs_error.h"
 #include "vs_train_device_sites.h"
 #include "vs_train_kernels.h"
 #include "vs_weights_impl.h"
 
 namespace {
 
-int failf(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return vs_fail_msg(code, buf);
-}
-
-#define VST_LAUNCH(call)                                                                         \
-    do {                                                                                         \
-        int e_ = (call);                                                                         \
-        if (e_ > 0) return failf(VS_ERR_HIP, "%s: %s", #call, hipGetErrorString((hipError_t)e_)); \
-        if (e_ < 0) return failf(VS_ERR_INVALID, "%s: unsupported shape", #call);                \
-    } while (0)
-#define VST_HIP(call)                                                                            \
-    do {                                                                                         \
-        hipError_t e_ = (call);                                                                  \
-        if (e_ != hipSuccess) return failf(VS_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));   \
-    } while (0)
-
 size_t align_floats(size_t n) { return (n + 63) / 64 * 64; }      // 256-byte granules
 
 thread_local uint32_t g_last_format = 0;      // VsTrainPlan::format of this thread's last forward (vs_train_last_format)
-
-// the weight images (re)built in this scope are ordered behind `s` when it ends (vs_weights_impl.h)
-struct Mark { const vs_weights *w; void *s; ~Mark() { vsw_mark(w, s); } };
 
 // A packed ragged batch (vs_train_forward_packed) as the host sees it: every row-wise kernel runs it as ONE "video" of Mtot
 // rows (B = 1, T = Mtot below); the positional rows, the attention, its keep words and the loss know the boundaries.
@@ -56,19 +32,19 @@ struct PackedCtx {
 };
 
 int packed_ctx(const vs_model_desc &D, const int32_t *lengths, int32_t B, PackedCtx &pc) {
-    if (!lengths || B <= 0) return failf(VS_ERR_INVALID, "lengths is NULL or B=%d", B);
+    if (!lengths || B <= 0) return vs_failf(VS_ERR_INVALID, "lengths is NULL or B=%d", B);
     pc = PackedCtx{};
     pc.B = B;
     long long rows = 0, words = 0, nwork = 0;
     for (int b = 0; b < B; ++b) {
         const int t = lengths[b];
-        if (t <= 0) return failf(VS_ERR_INVALID, "lengths[%d]=%d", b, t);
+        if (t <= 0) return vs_failf(VS_ERR_INVALID, "lengths[%d]=%d", b, t);
         if (D.max_len > 0 && t > D.max_len)
-            return failf(VS_ERR_INVALID, "lengths[%d]=%d exceeds the positional table (max_len=%d)", b, t, D.max_len);
+            return vs_failf(VS_ERR_INVALID, "lengths[%d]=%d exceeds the positional table (max_len=%d)", b, t, D.max_len);
         rows += t; words += (long long)t * ((t + 31) / 32); nwork += (t + 127) / 128;
         pc.tmax = t > pc.tmax ? t : pc.tmax;
     }
-    if (rows > (1ll << 28) || words >= (1ll << 31)) return failf(VS_ERR_INVALID, "too many frames (%lld rows, %lld keep words per head)", rows, words);
+    if (rows > (1ll << 28) || words >= (1ll << 31)) return vs_failf(VS_ERR_INVALID, "too many frames (%lld rows, %lld keep words per head)", rows, words);
     pc.Mtot = (int)rows; pc.words = (size_t)words; pc.nwork = (int)nwork;
     return VS_OK;
 }
@@ -144,7 +120,7 @@ int saved_field(const vs_weights *w, int B, int T, const PackedCtx *pc, int laye
         case 3: off = A.y2; n = Md; break;
         case 4: if (pc) { off = A.lse; n = M * w->desc.num_heads; break; }
             [[fallthrough]];
-        default: return failf(VS_ERR_INVALID, "saved_field: unknown field %d", field);
+        default: return vs_failf(VS_ERR_INVALID, "saved_field: unknown field %d", field);
     }
     *offset_bytes = off * sizeof(float);
     *count = n;
@@ -155,15 +131,15 @@ int saved_field(const vs_weights *w, int B, int T, const PackedCtx *pc, int laye
 // dropout probabilities - and, in the backward, a handed-back record form), x's alignment, the device.  No device work yet.
 int plan_call(const vs_weights *w, const float *x, int B, int T, const vs_dropout_cfg *drop, bool packed, bool backward,
               VsTrainPlan *plan) {
-    if (!w || !x) return failf(VS_ERR_INVALID, "weights/x is NULL");
+    if (!w || !x) return vs_failf(VS_ERR_INVALID, "weights/x is NULL");
     const VsTrainIn in{w->desc.d_model, w->desc.num_heads, w->desc.max_len, w->has_pe, B, T, packed, drop ? drop->flags : 0u,
                        drop ? drop->p : 0.f, drop ? drop->p_embed : 0.f, drop ? drop->reserved : 0u, backward};
     std::string err;
     if (int rc = vs_train_plan(in, vsk_options(), plan, &err)) return vs_fail_msg(rc, err.c_str());
-    if ((uintptr_t)x & 15) return failf(VS_ERR_INVALID, "x must be 16-byte aligned");
+    if ((uintptr_t)x & 15) return vs_failf(VS_ERR_INVALID, "x must be 16-byte aligned");
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != w->device)
-        return failf(VS_ERR_INVALID, "called on device %d, the weights handle lives on device %d", dev, w->device);
+        return vs_failf(VS_ERR_INVALID, "called on device %d, the weights handle lives on device %d", dev, w->device);
     return VS_OK;
 }
 
@@ -171,89 +147,11 @@ int plan_call(const vs_weights *w, const float *x, int B, int T, const vs_dropou
 int check_buffers(const SavedLayout &S, const WorkLayout &W, const void *saved, size_t saved_bytes, const void *workspace,
                   size_t workspace_bytes, bool forward, const void *hidden) {
     if (saved_bytes < S.total * sizeof(float))
-        return failf(VS_ERR_WORKSPACE, "saved %zu bytes < %zu needed", saved_bytes, S.total * sizeof(float));
+        return vs_failf(VS_ERR_WORKSPACE, "saved %zu bytes < %zu needed", saved_bytes, S.total * sizeof(float));
     if (workspace_bytes < W.total * sizeof(float))
-        return failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, W.total * sizeof(float));
+        return vs_failf(VS_ERR_WORKSPACE, "workspace %zu bytes < %zu needed", workspace_bytes, W.total * sizeof(float));
     if (((uintptr_t)saved & 255) || ((uintptr_t)workspace & 255) || (hidden && ((uintptr_t)hidden & 15)))
         return vs_fail_msg(VS_ERR_INVALID, forward ? "saved/workspace must be 256-byte, hidden 16-byte aligned" : "saved/workspace must be 256-byte aligned");
-    return VS_OK;
-}
-
-std::mutex g_tmu;
-
-// W^T copies for the dgrad GEMMs + a zero "bias"; rebuilt when the handle's parameters changed.  `frags`: also the
-// fragment-major copies of W^T (only the latency kernels, rows <= VS_SKINNY_ROWS, read them).  The buffer is allocated
-// by the first call: vs_train_prepare() lets a caller do that outside its backward pass.
-int ensure_transposed(vs_weights *w, hipStream_t st, bool frags) {
-    std::lock_guard<std::mutex> lk(g_tmu);
-    const size_t d = w->desc.d_model, din = w->desc.in_features;
-    if (!w->tblob) {
-        size_t off = 0;
-        auto take = [&](size_t n) { size_t o = off; off += align_floats(n); return o; };
-        w->t_embed_w = take(d * din);
-        w->tf_embed_w = take(d * din);
-        w->tlayers.resize(w->desc.num_layers);
-        for (auto &L : w->tlayers) {
-            L.t_wqkv = take(3 * d * d); L.t_wo = take(d * d); L.t_w1 = take(4 * d * d); L.t_w2 = take(4 * d * d);
-            L.t16_w2 = take(4 * d * d / 2);
-            L.tf_wqkv = take(3 * d * d); L.tf_wo = take(d * d); L.tf_w1 = take(4 * d * d); L.tf_w2 = take(4 * d * d);
-        }
-        const size_t nz = 4 * d > din ? 4 * d : din;
-        w->zeros = take(nz);
-        VST_HIP(hipMalloc((void **)&w->tblob, off * sizeof(float)));
-        VST_HIP(hipMemsetAsync(w->tblob + w->zeros, 0, nz * sizeof(float), st));
-        w->t_version = ~0ull;
-        w->tf_version = ~0ull;
-        w->t16_version = ~0ull;
-    }
-    // W [N,K] -> W^T [K,N] row-major, and its fragment-major copy for the latency kernels (as vsw_ensure does for W)
-    vsw_order(w, (void *)st);
-    const bool do_t = w->t_version != w->version, do_f = frags && w->tf_version != w->version;
-    if (!do_t && !do_f) return VS_OK;
-    Mark mark{w, (void *)st};
-    // one launch per family (was one per matrix: 17 transposes + 17 fragment packs + 4 conversions per optimizer step)
-    VskMatJobs tj{}, fj{};
-    auto add = [&](const float *W, size_t t_off, size_t tf_off, int N, int K) {
-        tj.in[tj.n] = W; tj.out[tj.n] = w->tblob + t_off; tj.rows[tj.n] = N; tj.cols[tj.n] = K; ++tj.n;
-        fj.in[fj.n] = w->tblob + t_off; fj.out[fj.n] = w->tblob + tf_off; fj.rows[fj.n] = K; fj.cols[fj.n] = N; ++fj.n;      // W^T is [K, N]
-    };
-    auto flush = [&]() -> int {
-        if (tj.n == 0) return 0;
-        if (do_t) if (int rc = vst_transpose_batch(tj, st)) return rc;
-        if (do_f) if (int rc = vsk_pack_fragments_batch(fj, st)) return rc;
-        tj.n = fj.n = 0;
-        return 0;
-    };
-    add(w->p(w->embed_w), w->t_embed_w, w->tf_embed_w, (int)d, (int)din);                                    // [d,din] -> [din,d]
-    for (int l = 0; l < w->desc.num_layers; ++l) {
-        const LayerOff &P = w->layers[l];
-        const LayerOffT &Q = w->tlayers[l];
-        if (tj.n + 4 > VskMatJobs::MAX) VST_LAUNCH(flush());
-        add(w->p(P.wqkv), Q.t_wqkv, Q.tf_wqkv, (int)(3 * d), (int)d);                                        // [3d,d] -> [d,3d]
-        add(w->p(P.wo), Q.t_wo, Q.tf_wo, (int)d, (int)d);
-        add(w->p(P.w1), Q.t_w1, Q.tf_w1, (int)(4 * d), (int)d);                                              // [4d,d] -> [d,4d]
-        add(w->p(P.w2), Q.t_w2, Q.tf_w2, (int)d, (int)(4 * d));                                              // [d,4d] -> [4d,d]
-    }
-    VST_LAUNCH(flush());
-    // (the bf16 copy of W2^T feeds the A-stationary dgrad of the bf16 training mode only: built when that form runs - t16_version)
-    if (do_t) w->t_version = w->version;
-    if (do_f) w->tf_version = w->version;
-    return VS_OK;
-}
-
-// bf16 copy of every W2^T (vst_gemm_rows16's weight operand in the backward of the bf16 training mode): after ensure_transposed,
-// only when that form runs
-int ensure_t16(vs_weights *w, hipStream_t st) {
-    std::lock_guard<std::mutex> lk(g_tmu);
-    if (w->t16_version == w->version) return VS_OK;
-    vsw_order(w, (void *)st);
-    Mark mark{w, (void *)st};
-    const size_t d = w->desc.d_model;
-    for (int l = 0; l < w->desc.num_layers; ++l) {
-        const LayerOffT &Q = w->tlayers[l];
-        VST_LAUNCH(vsk_to_bf16(w->tblob + Q.t_w2, w->tblob + Q.t16_w2, 4 * d * d, st));
-    }
-    w->t16_version = w->version;
     return VS_OK;
 }
 
@@ -262,11 +160,11 @@ int ensure_t16(vs_weights *w, hipStream_t st) {
 extern "C" {
 
 int vs_train_prepare(vs_weights *w, void *stream) {
-    if (!w) return failf(VS_ERR_INVALID, "weights is NULL");
+    if (!w) return vs_failf(VS_ERR_INVALID, "weights is NULL");
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != w->device)
-        return failf(VS_ERR_INVALID, "called on device %d, the weights handle lives on device %d", dev, w->device);
-    return ensure_transposed(w, (hipStream_t)stream, false);
+        return vs_failf(VS_ERR_INVALID, "called on device %d, the weights handle lives on device %d", dev, w->device);
+    return vsw_ensure(w, VSW_TRANSPOSED, stream);       // allocates the second blob: a caller can do that outside its backward pass
 }
 
 size_t vs_train_saved_bytes(const vs_weights *w, int32_t B, int32_t T) {
@@ -282,7 +180,7 @@ size_t vs_train_workspace_bytes(const vs_weights *w, int32_t B, int32_t T) {
 int vs_train_saved_field(const vs_weights *w, int32_t B, int32_t T, int32_t layer, int32_t field, size_t *offset_bytes,
                          size_t *count) {
     if (!w || !offset_bytes || !count || B <= 0 || T <= 0 || layer < 0 || layer >= w->desc.num_layers)
-        return failf(VS_ERR_INVALID, "saved_field: bad arguments");
+        return vs_failf(VS_ERR_INVALID, "saved_field: bad arguments");
     return saved_field(w, B, T, nullptr, layer, field, offset_bytes, count);
 }
 
@@ -298,12 +196,12 @@ static int attention_forward(const VsTrainPlan &plan, const float *qkv, const ui
                              const unsigned *dbits, const VstPackedPlan &pk, hipStream_t st) {
     const float *q = qkv, *k = qkv + plan.kv_stride, *v = qkv + 2 * plan.kv_stride;
     switch (plan.attention) {
-        case VST_ATT_PACKED16: VST_LAUNCH(vst_attention_fwd_bf16_packed(q, k, v, out, lse, H, dh, scale, p, dbits, st, plan.form.f16, pk)); break;
-        case VST_ATT_PACKED_EXACT: VST_LAUNCH(vst_attention_fwd_packed(q, k, v, out, lse, H, dh, scale, seed, site, p, st, dbits, pk)); break;
+        case VST_ATT_PACKED16: VS_LAUNCH(vst_attention_fwd_bf16_packed(q, k, v, out, lse, H, dh, scale, p, dbits, st, plan.form.f16, pk)); break;
+        case VST_ATT_PACKED_EXACT: VS_LAUNCH(vst_attention_fwd_packed(q, k, v, out, lse, H, dh, scale, seed, site, p, st, dbits, pk)); break;
         case VST_ATT_PADDED16:
-            VST_LAUNCH(vst_attention_fwd_bf16(q, k, v, key_pad_mask, out, lse, B, H, T, dh, scale, p, dbits, st, plan.mode_attention));
+            VS_LAUNCH(vst_attention_fwd_bf16(q, k, v, key_pad_mask, out, lse, B, H, T, dh, scale, p, dbits, st, plan.mode_attention));
             break;
-        case VST_ATT_PADDED_EXACT: VST_LAUNCH(vst_attention_fwd(q, k, v, key_pad_mask, out, lse, B, H, T, dh, scale, seed, site, p, st, dbits)); break;   // :155-161
+        case VST_ATT_PADDED_EXACT: VS_LAUNCH(vst_attention_fwd(q, k, v, key_pad_mask, out, lse, B, H, T, dh, scale, seed, site, p, st, dbits)); break;   // :155-161
     }
     return VS_OK;
 }
@@ -314,17 +212,17 @@ static int attention_backward(const VsTrainPlan &plan, const float *qkv, const u
     const float *q = qkv, *k = qkv + plan.kv_stride, *v = qkv + 2 * plan.kv_stride;
     switch (plan.attention) {
         case VST_ATT_PACKED16:
-            VST_LAUNCH(vst_attention_bwd_bf16_packed(q, k, v, datt, lse, delta, dqkv, H, dh, scale, p, dbits, st, plan.form.f16, pk));
+            VS_LAUNCH(vst_attention_bwd_bf16_packed(q, k, v, datt, lse, delta, dqkv, H, dh, scale, p, dbits, st, plan.form.f16, pk));
             break;
         case VST_ATT_PACKED_EXACT:
-            VST_LAUNCH(vst_attention_bwd_packed(q, k, v, datt, lse, delta, dqkv, H, dh, scale, seed, site, p, st, dbits, pk));
+            VS_LAUNCH(vst_attention_bwd_packed(q, k, v, datt, lse, delta, dqkv, H, dh, scale, seed, site, p, st, dbits, pk));
             break;
         case VST_ATT_PADDED16:
-            VST_LAUNCH(vst_attention_bwd_bf16(q, k, v, key_pad_mask, datt, lse, delta, dqkv, B, H, T, dh, scale, p, dbits, st,
+            VS_LAUNCH(vst_attention_bwd_bf16(q, k, v, key_pad_mask, datt, lse, delta, dqkv, B, H, T, dh, scale, p, dbits, st,
                                               plan.mode_attention, plan.attention_out16));
             break;
         case VST_ATT_PADDED_EXACT:
-            VST_LAUNCH(vst_attention_bwd(q, k, v, key_pad_mask, datt, lse, delta, dqkv, B, H, T, dh, scale, seed, site, p, st, dbits));
+            VS_LAUNCH(vst_attention_bwd(q, k, v, key_pad_mask, datt, lse, delta, dqkv, B, H, T, dh, scale, seed, site, p, st, dbits));
             break;
     }
     return VS_OK;
@@ -336,7 +234,7 @@ static int forward_impl(const vs_weights *w, const float *x, const uint8_t *key_
                         void *workspace, size_t workspace_bytes, void *stream, const PackedCtx *pc) {
     VsTrainPlan plan;
     if (int rc = plan_call(w, x, B, T, drop, pc != nullptr, false, &plan)) return rc;
-    if (!scores || !saved || !workspace) return failf(VS_ERR_INVALID, "scores/saved/workspace is NULL");
+    if (!scores || !saved || !workspace) return vs_failf(VS_ERR_INVALID, "scores/saved/workspace is NULL");
     const vs_model_desc &D = w->desc;
     const SavedLayout S = saved_layout(D, B, T, pc);
     const WorkLayout W = work_layout(D, B, T, pc);
@@ -360,17 +258,17 @@ static int forward_impl(const vs_weights *w, const float *x, const uint8_t *key_
     VstPackedPlan pk{};
     const float *pe = w->has_pe ? w->p(w->pe) : nullptr;
     if (pc) {
-        VST_LAUNCH(vst_plan_packed(pc->lengths_dev, pc->B, M, pc->tmax, pc->words, (int *)(ws + W.plan), pc->nwork, st, &pk));
+        VS_LAUNCH(vst_plan_packed(pc->lengths_dev, pc->B, M, pc->tmax, pc->words, (int *)(ws + W.plan), pc->nwork, st, &pk));
         if (w->has_pe) {
-            VST_LAUNCH(vsk_gather_rows(w->p(w->pe), pk.cu, pc->B, pc->tmax, d, ws + W.pe, st));
+            VS_LAUNCH(vsk_gather_rows(w->p(w->pe), pk.cu, pc->B, pc->tmax, d, ws + W.pe, st));
             pe = ws + W.pe;
         }
     }
     // Embedding + positional table + dropout(sparsity)   simnet.py:211, 237-238
     float *h0 = sv + S.h0;
-    VST_LAUNCH(vsk_linear(x, w->p(w->embed_w), w->p(w->f_embed_w), w->p(w->embed_b), h0, M, d, D.in_features, 0,
+    VS_LAUNCH(vsk_linear(x, w->p(w->embed_w), w->p(w->f_embed_w), w->p(w->embed_b), h0, M, d, D.in_features, 0,
                           pe, T, plan.mode_linear, st));
-    if (p_embed > 0.f) VST_LAUNCH(vst_dropout_rows(h0, M, d, seed, VS_SITE_EMBED, p_embed, st));
+    if (p_embed > 0.f) VS_LAUNCH(vst_dropout_rows(h0, M, d, seed, VS_SITE_EMBED, p_embed, st));
     const float *h_in = h0;
     for (int l = 0; l < L; ++l) {
         const LayerOff &P = w->layers[l];
@@ -379,30 +277,30 @@ static int forward_impl(const vs_weights *w, const float *x, const uint8_t *key_
         float *qkv = sv + A.qkv;
         // (16-bit q / k / v: q arrives times scale * log2 e, the scoring path's form)
         if (plan.qkv_rows16)       // A-stationary form (bit-identical to the tiled one)
-            VST_LAUNCH(vst_gemm_rows16(h_in, w->p(P.r_wqkv), w->p(P.bqkv), qkv, nullptr, M, 3 * d, d, 3, vsk_attention_qscale(scale), 0ull, 0u,
+            VS_LAUNCH(vst_gemm_rows16(h_in, w->p(P.r_wqkv), w->p(P.bqkv), qkv, nullptr, M, 3 * d, d, 3, vsk_attention_qscale(scale), 0ull, 0u,
                                        0.f, st, T, H, d / H));
         else
-            VST_LAUNCH(vsk_qkv(h_in, w->p(P.wqkv), w->p(P.f_wqkv), w->p(P.bqkv), qkv, B, T, d, H, plan.mode_qkv, st,
+            VS_LAUNCH(vsk_qkv(h_in, w->p(P.wqkv), w->p(P.f_wqkv), w->p(P.bqkv), qkv, B, T, d, H, plan.mode_qkv, st,
                                plan.form.qkv16 ? vsk_attention_qscale(scale) : 1.0f));         // :148-153
         unsigned *dbits = p > 0.f ? (unsigned *)(sv + A.dbits) : nullptr;
-        if (dbits && pc) VST_LAUNCH(vst_attention_dropout_bits_packed(dbits, pc->B, H, pc->tmax, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st, pk));
-        else if (dbits) VST_LAUNCH(vst_attention_dropout_bits(dbits, B, H, T, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st));
+        if (dbits && pc) VS_LAUNCH(vst_attention_dropout_bits_packed(dbits, pc->B, H, pc->tmax, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st, pk));
+        else if (dbits) VS_LAUNCH(vst_attention_dropout_bits(dbits, B, H, T, seed, VS_SITE_LAYER(l, VS_SITE_ATTN), p, st));
         if (int rc = attention_forward(plan, qkv, key_pad_mask, sv + A.att, sv + A.lse, B, H, T, d / H, scale, seed,
                                        VS_SITE_LAYER(l, VS_SITE_ATTN), p, dbits, pk, st)) return rc;
-        VST_LAUNCH(vsk_linear(sv + A.att, w->p(P.wo), w->p(P.f_wo), w->p(P.bo), a, M, d, d, 0, nullptr, 1, plan.mode_linear, st));      // :163
-        VST_LAUNCH(vst_rows_fwd(a, h_in, w->p(P.ln1g), w->p(P.ln1b), sv + A.z1, sv + A.y1, nullptr, sv + A.st1, M, d,
+        VS_LAUNCH(vsk_linear(sv + A.att, w->p(P.wo), w->p(P.f_wo), w->p(P.bo), a, M, d, d, 0, nullptr, 1, plan.mode_linear, st));      // :163
+        VS_LAUNCH(vst_rows_fwd(a, h_in, w->p(P.ln1g), w->p(P.ln1b), sv + A.z1, sv + A.y1, nullptr, sv + A.st1, M, d,
                                 seed, VS_SITE_LAYER(l, VS_SITE_DROP1), p, nullptr, nullptr, 0, nullptr, st, dn));              // :107
         // fc1 (+ ReLU + mlp.dropout in the GEMM epilogue, :181) writes the MLP hidden tensor, fc2 reads it
         if (plan.form.rows16)         // the A-stationary form (vs_train_gemm_rows.hip), bit-identical to the tiled one
-            VST_LAUNCH(vst_gemm_rows16(sv + A.y1, w->p(P.r_w1), w->p(P.b1), sv + A.ffn, nullptr, M, 4 * d, d, p > 0.f ? 0 : 2, 0.f, seed,
+            VS_LAUNCH(vst_gemm_rows16(sv + A.y1, w->p(P.r_w1), w->p(P.b1), sv + A.ffn, nullptr, M, 4 * d, d, p > 0.f ? 0 : 2, 0.f, seed,
                                        VS_SITE_LAYER(l, VS_SITE_MLP), p, st));
         else if (p > 0.f)
-            VST_LAUNCH(vsk_linear_relu_dropout(sv + A.y1, w->p(P.w1), w->p(P.f_w1), w->p(P.b1), sv + A.ffn, M, 4 * d, d, seed,
+            VS_LAUNCH(vsk_linear_relu_dropout(sv + A.y1, w->p(P.w1), w->p(P.f_w1), w->p(P.b1), sv + A.ffn, M, 4 * d, d, seed,
                                                VS_SITE_LAYER(l, VS_SITE_MLP), p, st, plan.mode_fc1));
         else
-            VST_LAUNCH(vsk_linear(sv + A.y1, w->p(P.w1), w->p(P.f_w1), w->p(P.b1), sv + A.ffn, M, 4 * d, d, 1, nullptr, 1, plan.mode_fc1, st));
-        VST_LAUNCH(vsk_linear(sv + A.ffn, w->p(P.w2), w->p(P.f_w2), w->p(P.b2), a, M, d, 4 * d, 0, nullptr, 1, plan.mode_fc2, st));  // :182
-        VST_LAUNCH(vst_rows_fwd(a, sv + A.y1, w->p(P.ln2g), w->p(P.ln2b), sv + A.z2, sv + A.y2, last ? hidden : nullptr,
+            VS_LAUNCH(vsk_linear(sv + A.y1, w->p(P.w1), w->p(P.f_w1), w->p(P.b1), sv + A.ffn, M, 4 * d, d, 1, nullptr, 1, plan.mode_fc1, st));
+        VS_LAUNCH(vsk_linear(sv + A.ffn, w->p(P.w2), w->p(P.f_w2), w->p(P.b2), a, M, d, 4 * d, 0, nullptr, 1, plan.mode_fc2, st));  // :182
+        VS_LAUNCH(vst_rows_fwd(a, sv + A.y1, w->p(P.ln2g), w->p(P.ln2b), sv + A.z2, sv + A.y2, last ? hidden : nullptr,
                                 sv + A.st2, M, d, seed, VS_SITE_LAYER(l, VS_SITE_DROP2), p,
                                 last ? w->p(w->final_w) : nullptr, last ? w->p(w->final_b) : nullptr, D.num_classes,
                                 last ? scores : nullptr, st, dn));                                                              // :110, :42
@@ -419,14 +317,15 @@ static int backward_impl(vs_weights *w, const float *x, const uint8_t *key_pad_m
     if (int rc = plan_call(w, x, B, T, drop, pc != nullptr, true, &plan)) return rc;
     if (!saved || !workspace || !grads || !grads->layers || !grads->embed_w || !grads->embed_b || !grads->final_w ||
         !grads->final_b)
-        return failf(VS_ERR_INVALID, "saved/workspace/grads is NULL");
+        return vs_failf(VS_ERR_INVALID, "saved/workspace/grads is NULL");
     const vs_model_desc &D = w->desc;
     const SavedLayout S = saved_layout(D, B, T, pc);
     const WorkLayout W = work_layout(D, B, T, pc);
     if (int rc = check_buffers(S, W, saved, saved_bytes, workspace, workspace_bytes, false, nullptr)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = ensure_transposed(w, st, plan.transposed_fragments)) return rc;
-    if (plan.t16) if (int rc = ensure_t16(w, st)) return rc;
+    // W^T for the dgrad GEMMs, and the copies of it only some kernels read (the second blob is allocated by the first such call)
+    if (int rc = vsw_ensure(w, VSW_TRANSPOSED | (plan.transposed_fragments ? (unsigned)VSW_TRANSPOSED_FRAGMENTS : 0u) |
+                                   (plan.t16 ? (unsigned)VSW_TRANSPOSED_W2_16 : 0u), stream)) return rc;
     const int d = D.d_model, H = D.num_heads, L = D.num_layers, M = B * T, nc = D.num_classes;
     const float p = drop ? drop->p : 0.f;
     // the embedding dropout lives INSIDE PositionalEncoding (simnet.py:224,237): a use_pos=False model has none
@@ -442,20 +341,20 @@ static int backward_impl(vs_weights *w, const float *x, const uint8_t *key_pad_m
     const float *zeros = w->tp(w->zeros);
     const int nblk = vst_ln_bwd_blocks(M);
     VstPackedPlan pk{};       // packed: the plan is rebuilt from the device lengths (one small launch), not kept in the record
-    if (pc) VST_LAUNCH(vst_plan_packed(pc->lengths_dev, pc->B, M, pc->tmax, pc->words, (int *)(ws + W.plan), pc->nwork, st, &pk));
+    if (pc) VS_LAUNCH(vst_plan_packed(pc->lengths_dev, pc->B, M, pc->tmax, pc->words, (int *)(ws + W.plan), pc->nwork, st, &pk));
 
     // final_layer (simnet.py:42): d_W = d_scores^T hidden, d_b = column sums of d_scores
     {
         const float *y_last = sv + S.layers[L - 1].y2;
         if (d_scores) {
             for (int c = 0; c < nc; ++c) {
-                VST_LAUNCH(vst_weighted_colsum(d_scores + c, nc, y_last, part, M, d, st));
-                VST_LAUNCH(vst_reduce_rows(part, nblk, 1, d, grads->final_w + (size_t)c * d, nullptr, nullptr, 1, st));
-                VST_LAUNCH(vst_reduce_rows(part + (size_t)nblk * d, nblk, 1, 1, grads->final_b + c, nullptr, nullptr, 1, st));
+                VS_LAUNCH(vst_weighted_colsum(d_scores + c, nc, y_last, part, M, d, st));
+                VS_LAUNCH(vst_reduce_rows(part, nblk, 1, d, grads->final_w + (size_t)c * d, nullptr, nullptr, 1, st));
+                VS_LAUNCH(vst_reduce_rows(part + (size_t)nblk * d, nblk, 1, 1, grads->final_b + c, nullptr, nullptr, 1, st));
             }
         } else {
-            VST_HIP(hipMemsetAsync(grads->final_w, 0, (size_t)nc * d * sizeof(float), st));
-            VST_HIP(hipMemsetAsync(grads->final_b, 0, (size_t)nc * sizeof(float), st));
+            VS_HIP(hipMemsetAsync(grads->final_w, 0, (size_t)nc * d * sizeof(float), st));
+            VS_HIP(hipMemsetAsync(grads->final_b, 0, (size_t)nc * sizeof(float), st));
         }
     }
 
@@ -468,46 +367,46 @@ static int backward_impl(vs_weights *w, const float *x, const uint8_t *key_pad_m
         const bool last = l == L - 1;
         const float *h_in = l == 0 ? sv + S.h0 : sv + S.layers[l - 1].y2;
         // norm2 (+ the score head's pull on the last layer); d(fc2 output) = dropout2 mask on dz2
-        VST_LAUNCH(vst_ln_bwd(last ? d_hidden : g[cur], last ? d_scores : nullptr, w->p(w->final_w), nc, sv + A.z2, sv + A.st2,
+        VS_LAUNCH(vst_ln_bwd(last ? d_hidden : g[cur], last ? d_scores : nullptr, w->p(w->final_w), nc, sv + A.z2, sv + A.st2,
                               w->p(P.ln2g), dz, p > 0.f ? dbr : nullptr, part, M, d, seed, VS_SITE_LAYER(l, VS_SITE_DROP2), p, st, dn));
-        VST_LAUNCH(vst_reduce_rows(part, nblk, 2, d, G.ln2_g, G.ln2_b, nullptr, 1, st));
+        VS_LAUNCH(vst_reduce_rows(part, nblk, 2, d, G.ln2_g, G.ln2_b, nullptr, 1, st));
         const float *dm = p > 0.f ? dbr : dz;
         // mlp.fc2: weight/bias gradient, then the gradient of its input
-        VST_LAUNCH(vst_wgrad(dm, d, sv + A.ffn, 4 * d, M, d, 4 * d, G.w2, nullptr, nullptr, G.b2, nullptr, nullptr, d, wg, st, plan.mode_wgrad_w2));
+        VS_LAUNCH(vst_wgrad(dm, d, sv + A.ffn, 4 * d, M, d, 4 * d, G.w2, nullptr, nullptr, G.b2, nullptr, nullptr, d, wg, st, plan.mode_wgrad_w2));
         // ... through mlp.dropout + ReLU in the GEMM's epilogue: the saved activation is > 0 exactly where both let
         // the value through (the gated gradient gf is stored the way the activation is: plan.mode_gate)
         const float gate_scale = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
         if (plan.form.rows16)
-            VST_LAUNCH(vst_gemm_rows16(dm, w->tp(Q.t16_w2), zeros, gf, sv + A.ffn, M, 4 * d, d, 1, gate_scale, 0ull, 0u, 0.f, st));
+            VS_LAUNCH(vst_gemm_rows16(dm, w->tp(Q.t16_w2), zeros, gf, sv + A.ffn, M, 4 * d, d, 1, gate_scale, 0ull, 0u, 0.f, st));
         else
-            VST_LAUNCH(vsk_linear_gate(dm, w->tp(Q.t_w2), w->tp(Q.tf_w2), zeros, sv + A.ffn, gate_scale, gf, M, 4 * d, d, st, plan.mode_gate));
-        VST_LAUNCH(vst_wgrad(gf, 4 * d, sv + A.y1, d, M, 4 * d, d, G.w1, nullptr, nullptr, G.b1, nullptr, nullptr, 4 * d, wg, st, plan.mode_wgrad_w1));
+            VS_LAUNCH(vsk_linear_gate(dm, w->tp(Q.t_w2), w->tp(Q.tf_w2), zeros, sv + A.ffn, gate_scale, gf, M, 4 * d, d, st, plan.mode_gate));
+        VS_LAUNCH(vst_wgrad(gf, 4 * d, sv + A.y1, d, M, 4 * d, d, G.w1, nullptr, nullptr, G.b1, nullptr, nullptr, 4 * d, wg, st, plan.mode_wgrad_w1));
         // d y1 = dz2 (residual) + d(fc1 input): the residual rides in the GEMM epilogue
-        VST_LAUNCH(vsk_linear(gf, w->tp(Q.t_w1), w->tp(Q.tf_w1), zeros, dy1, M, d, 4 * d, 0, dz, M, plan.mode_dgrad_fc1, st));
+        VS_LAUNCH(vsk_linear(gf, w->tp(Q.t_w1), w->tp(Q.tf_w1), zeros, dy1, M, d, 4 * d, 0, dz, M, plan.mode_dgrad_fc1, st));
         // norm1; d(feature_projection output) = dropout1 mask on dz1
-        VST_LAUNCH(vst_ln_bwd(dy1, nullptr, nullptr, 0, sv + A.z1, sv + A.st1, w->p(P.ln1g), dz, p > 0.f ? dbr : nullptr, part,
+        VS_LAUNCH(vst_ln_bwd(dy1, nullptr, nullptr, 0, sv + A.z1, sv + A.st1, w->p(P.ln1g), dz, p > 0.f ? dbr : nullptr, part,
                               M, d, seed, VS_SITE_LAYER(l, VS_SITE_DROP1), p, st, dn));
-        VST_LAUNCH(vst_reduce_rows(part, nblk, 2, d, G.ln1_g, G.ln1_b, nullptr, 1, st));
+        VS_LAUNCH(vst_reduce_rows(part, nblk, 2, d, G.ln1_g, G.ln1_b, nullptr, 1, st));
         const float *da = p > 0.f ? dbr : dz;
-        VST_LAUNCH(vst_wgrad(da, d, sv + A.att, d, M, d, d, G.wo, nullptr, nullptr, G.bo, nullptr, nullptr, d, wg, st, plan.mode_linear));
+        VS_LAUNCH(vst_wgrad(da, d, sv + A.att, d, M, d, d, G.wo, nullptr, nullptr, G.bo, nullptr, nullptr, d, wg, st, plan.mode_linear));
         // d(attention output), then delta = its row dot with the saved output, then the attention itself
-        VST_LAUNCH(vsk_linear(da, w->tp(Q.t_wo), w->tp(Q.tf_wo), zeros, datt, M, d, d, 0, nullptr, 1, plan.mode_datt, st));
-        VST_LAUNCH(vst_head_rowdot(datt, sv + A.att, delta, M, T, H, d / H, st, plan.mode_rowdot));
+        VS_LAUNCH(vsk_linear(da, w->tp(Q.t_wo), w->tp(Q.tf_wo), zeros, datt, M, d, d, 0, nullptr, 1, plan.mode_datt, st));
+        VS_LAUNCH(vst_head_rowdot(datt, sv + A.att, delta, M, T, H, d / H, st, plan.mode_rowdot));
         if (int rc = attention_backward(plan, sv + A.qkv, key_pad_mask, datt, sv + A.lse, delta, dqkv, B, H, T, d / H, scale, seed,
                                         VS_SITE_LAYER(l, VS_SITE_ATTN), p, p > 0.f ? (const unsigned *)(sv + A.dbits) : nullptr, pk, st))
             return rc;
         // q / k / v projections: one [3d, d] weight gradient dealt to the three parameters
-        VST_LAUNCH(vst_wgrad(dqkv, 3 * d, h_in, d, M, 3 * d, d, G.wq, G.wk, G.wv, G.bq, G.bk, G.bv, d, wg, st, plan.mode_wgrad_qkv));
+        VS_LAUNCH(vst_wgrad(dqkv, 3 * d, h_in, d, M, 3 * d, d, G.wq, G.wk, G.wv, G.bq, G.bk, G.bv, d, wg, st, plan.mode_wgrad_qkv));
         // gradient of the layer input = dz1 (residual) + dqkv Wqkv
-        VST_LAUNCH(vsk_linear(dqkv, w->tp(Q.t_wqkv), w->tp(Q.tf_wqkv), zeros, g[cur ^ 1], M, d, 3 * d, 0, dz, M, plan.mode_dgrad_qkv, st));
+        VS_LAUNCH(vsk_linear(dqkv, w->tp(Q.t_wqkv), w->tp(Q.tf_wqkv), zeros, g[cur ^ 1], M, d, 3 * d, 0, dz, M, plan.mode_dgrad_qkv, st));
         cur ^= 1;
     }
     // Embedding (simnet.py:211, 237-238): dropout(sparsity) mask, then the Linear
     float *gh0 = g[cur];
-    if (p_embed > 0.f) VST_LAUNCH(vst_dropout_rows(gh0, M, d, seed, VS_SITE_EMBED, p_embed, st));
-    VST_LAUNCH(vst_wgrad(gh0, d, x, D.in_features, M, d, D.in_features, grads->embed_w, nullptr, nullptr, grads->embed_b,
+    if (p_embed > 0.f) VS_LAUNCH(vst_dropout_rows(gh0, M, d, seed, VS_SITE_EMBED, p_embed, st));
+    VS_LAUNCH(vst_wgrad(gh0, d, x, D.in_features, M, d, D.in_features, grads->embed_w, nullptr, nullptr, grads->embed_b,
                          nullptr, nullptr, d, wg, st, plan.mode_linear));
-    if (dx) VST_LAUNCH(vsk_linear(gh0, w->tp(w->t_embed_w), w->tp(w->tf_embed_w), zeros, dx, M, D.in_features, d, 0, nullptr, 1, plan.mode_linear, st));
+    if (dx) VS_LAUNCH(vsk_linear(gh0, w->tp(w->t_embed_w), w->tp(w->tf_embed_w), zeros, dx, M, D.in_features, d, 0, nullptr, 1, plan.mode_linear, st));
     return VS_OK;
 }
 
@@ -527,7 +426,7 @@ int vs_train_backward(vs_weights *w, const float *x, const uint8_t *key_pad_mask
 
 // ---- packed ragged batches ----
 int vs_train_check_packed(const vs_model_desc *desc, const int32_t *lengths, int32_t B) {
-    if (!desc) return failf(VS_ERR_INVALID, "desc is NULL");
+    if (!desc) return vs_failf(VS_ERR_INVALID, "desc is NULL");
     PackedCtx pc;
     return packed_ctx(*desc, lengths, B, pc);
 }
@@ -554,7 +453,7 @@ int vs_train_saved_field_packed(const vs_weights *w, const int32_t *lengths, int
                                 size_t *offset_bytes, size_t *count) {
     PackedCtx pc;
     if (!w || !offset_bytes || !count || layer < 0 || layer >= w->desc.num_layers)
-        return failf(VS_ERR_INVALID, "saved_field: bad arguments");
+        return vs_failf(VS_ERR_INVALID, "saved_field: bad arguments");
     if (int rc = packed_ctx(w->desc, lengths, B, pc)) return rc;
     return saved_field(w, 1, pc.Mtot, &pc, layer, field, offset_bytes, count);
 }
@@ -562,8 +461,8 @@ int vs_train_saved_field_packed(const vs_weights *w, const int32_t *lengths, int
 int vs_train_forward_packed(const vs_weights *w, const float *x, const int32_t *lengths, const int32_t *lengths_dev, int32_t B,
                             const vs_dropout_cfg *drop, float *scores, float *hidden, void *saved, size_t saved_bytes,
                             void *workspace, size_t workspace_bytes, void *stream) {
-    if (!w) return failf(VS_ERR_INVALID, "weights is NULL");
-    if (!lengths_dev) return failf(VS_ERR_INVALID, "lengths_dev is NULL");
+    if (!w) return vs_failf(VS_ERR_INVALID, "weights is NULL");
+    if (!lengths_dev) return vs_failf(VS_ERR_INVALID, "lengths_dev is NULL");
     PackedCtx pc;
     if (int rc = packed_ctx(w->desc, lengths, B, pc)) return rc;
     pc.lengths_dev = lengths_dev;
@@ -574,8 +473,8 @@ int vs_train_backward_packed(vs_weights *w, const float *x, const int32_t *lengt
                              const vs_dropout_cfg *drop, const float *d_scores, const float *d_hidden, const void *saved,
                              size_t saved_bytes, const vs_model_grads *grads, float *dx, void *workspace,
                              size_t workspace_bytes, void *stream) {
-    if (!w) return failf(VS_ERR_INVALID, "weights is NULL");
-    if (!lengths_dev) return failf(VS_ERR_INVALID, "lengths_dev is NULL");
+    if (!w) return vs_failf(VS_ERR_INVALID, "weights is NULL");
+    if (!lengths_dev) return vs_failf(VS_ERR_INVALID, "lengths_dev is NULL");
     PackedCtx pc;
     if (int rc = packed_ctx(w->desc, lengths, B, pc)) return rc;
     pc.lengths_dev = lengths_dev;
@@ -585,15 +484,15 @@ int vs_train_backward_packed(vs_weights *w, const float *x, const int32_t *lengt
 
 int vs_mse_packed_loss_forward(const float *output, const float *target, int32_t n, double denom, float *scratch, float *loss,
                                void *stream) {
-    if (!output || !target || !scratch || !loss || n <= 0 || !(denom > 0.0)) return failf(VS_ERR_INVALID, "mse_packed_loss: bad arguments");
-    VST_LAUNCH(vst_mse_scaled_fwd(output, target, n, (float)(1.0 / denom), scratch, loss, (hipStream_t)stream));
+    if (!output || !target || !scratch || !loss || n <= 0 || !(denom > 0.0)) return vs_failf(VS_ERR_INVALID, "mse_packed_loss: bad arguments");
+    VS_LAUNCH(vst_mse_scaled_fwd(output, target, n, (float)(1.0 / denom), scratch, loss, (hipStream_t)stream));
     return VS_OK;
 }
 
 int vs_mse_packed_loss_backward(const float *output, const float *target, const float *d_loss, int32_t n, double denom,
                                 float *d_output, void *stream) {
-    if (!output || !target || !d_loss || !d_output || n <= 0 || !(denom > 0.0)) return failf(VS_ERR_INVALID, "mse_packed_loss: bad arguments");
-    VST_LAUNCH(vst_mse_scaled_bwd(output, target, d_loss, n, (float)(1.0 / denom), d_output, (hipStream_t)stream));
+    if (!output || !target || !d_loss || !d_output || n <= 0 || !(denom > 0.0)) return vs_failf(VS_ERR_INVALID, "mse_packed_loss: bad arguments");
+    VS_LAUNCH(vst_mse_scaled_bwd(output, target, d_loss, n, (float)(1.0 / denom), d_output, (hipStream_t)stream));
     return VS_OK;
 }
 
@@ -610,16 +509,16 @@ int vs_train_attention_forward_packed(const float *q, const float *k, const floa
                                       const int32_t *lengths, const int32_t *lengths_dev, int32_t B, int32_t H, int32_t dh,
                                       float scale, uint64_t seed, uint32_t site, float p, void *scratch, size_t scratch_bytes,
                                       void *stream) {
-    if (!q || !k || !v || !out || !lse2 || !lengths_dev || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
+    if (!q || !k || !v || !out || !lse2 || !lengths_dev || !scratch) return vs_failf(VS_ERR_INVALID, "NULL pointer");
     PackedCtx pc;
-    if (H <= 0) return failf(VS_ERR_INVALID, "H=%d", H);
+    if (H <= 0) return vs_failf(VS_ERR_INVALID, "H=%d", H);
     if (int rc = packed_lengths(lengths, B, pc)) return rc;
     if (scratch_bytes < vs_train_attention_packed_scratch_bytes(lengths, B, H) || ((uintptr_t)scratch & 255))
-        return failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, vs_train_attention_packed_scratch_bytes(lengths, B, H));
+        return vs_failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, vs_train_attention_packed_scratch_bytes(lengths, B, H));
     hipStream_t st = (hipStream_t)stream;
     VstPackedPlan pk{};
-    VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
-    VST_LAUNCH(vst_attention_fwd_packed(q, k, v, out, lse2, H, dh, scale, seed, site, p, st, nullptr, pk));
+    VS_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
+    VS_LAUNCH(vst_attention_fwd_packed(q, k, v, out, lse2, H, dh, scale, seed, site, p, st, nullptr, pk));
     return VS_OK;
 }
 
@@ -627,18 +526,18 @@ int vs_train_attention_backward_packed(const float *q, const float *k, const flo
                                        const float *lse2, float *dqkv, const int32_t *lengths, const int32_t *lengths_dev,
                                        int32_t B, int32_t H, int32_t dh, float scale, uint64_t seed, uint32_t site, float p,
                                        void *scratch, size_t scratch_bytes, void *stream) {
-    if (!q || !k || !v || !out || !d_out || !lse2 || !dqkv || !lengths_dev || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
+    if (!q || !k || !v || !out || !d_out || !lse2 || !dqkv || !lengths_dev || !scratch) return vs_failf(VS_ERR_INVALID, "NULL pointer");
     PackedCtx pc;
-    if (H <= 0) return failf(VS_ERR_INVALID, "H=%d", H);
+    if (H <= 0) return vs_failf(VS_ERR_INVALID, "H=%d", H);
     if (int rc = packed_lengths(lengths, B, pc)) return rc;
     if (scratch_bytes < vs_train_attention_packed_scratch_bytes(lengths, B, H) || ((uintptr_t)scratch & 255))
-        return failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, vs_train_attention_packed_scratch_bytes(lengths, B, H));
+        return vs_failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, vs_train_attention_packed_scratch_bytes(lengths, B, H));
     hipStream_t st = (hipStream_t)stream;
     float *delta = (float *)scratch + attention_packed_plan_floats(pc);
     VstPackedPlan pk{};
-    VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
-    VST_LAUNCH(vst_head_rowdot(d_out, out, delta, pc.Mtot, pc.Mtot, H, dh, st));
-    VST_LAUNCH(vst_attention_bwd_packed(q, k, v, d_out, lse2, delta, dqkv, H, dh, scale, seed, site, p, st, nullptr, pk));
+    VS_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
+    VS_LAUNCH(vst_head_rowdot(d_out, out, delta, pc.Mtot, pc.Mtot, H, dh, st));
+    VS_LAUNCH(vst_attention_bwd_packed(q, k, v, d_out, lse2, delta, dqkv, H, dh, scale, seed, site, p, st, nullptr, pk));
     return VS_OK;
 }
 
@@ -655,13 +554,13 @@ PackedLpScratch packed_lp_scratch(const PackedCtx &pc, int H) {
 // the argument checks of the two entry points (before any device access); pc out
 int packed_lp_check(const int32_t *lengths, int32_t B, int32_t H, int32_t dh, float p, const void *scratch, size_t scratch_bytes,
                     PackedCtx &pc) {
-    if (H <= 0) return failf(VS_ERR_INVALID, "H=%d", H);
-    if (!vst_attention_bf16_supported(dh)) return failf(VS_ERR_INVALID, "head dim %d: the 16-bit attention kernels take 32 / 64 / 128", dh);
-    if (!(p >= 0.f && p < 1.f)) return failf(VS_ERR_INVALID, "dropout probability must be in [0, 1): p=%g", p);
+    if (H <= 0) return vs_failf(VS_ERR_INVALID, "H=%d", H);
+    if (!vst_attention_bf16_supported(dh)) return vs_failf(VS_ERR_INVALID, "head dim %d: the 16-bit attention kernels take 32 / 64 / 128", dh);
+    if (!(p >= 0.f && p < 1.f)) return vs_failf(VS_ERR_INVALID, "dropout probability must be in [0, 1): p=%g", p);
     if (int rc = packed_lengths(lengths, B, pc)) return rc;
     const size_t need = packed_lp_scratch(pc, H).total * sizeof(float);
     if (scratch_bytes < need || ((uintptr_t)scratch & 255))
-        return failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, need);
+        return vs_failf(VS_ERR_WORKSPACE, "scratch %zu bytes < %zu needed (256-byte aligned)", scratch_bytes, need);
     return VS_OK;
 }
 }  // namespace
@@ -676,16 +575,16 @@ int vs_train_attention_forward_packed_lp(const float *q, const float *k, const f
                                          const int32_t *lengths, const int32_t *lengths_dev, int32_t B, int32_t H, int32_t dh,
                                          float scale, uint64_t seed, uint32_t site, float p, int32_t f16, void *scratch,
                                          size_t scratch_bytes, void *stream) {
-    if (!q || !k || !v || !out || !lse2 || !lengths_dev || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
+    if (!q || !k || !v || !out || !lse2 || !lengths_dev || !scratch) return vs_failf(VS_ERR_INVALID, "NULL pointer");
     PackedCtx pc;
     if (int rc = packed_lp_check(lengths, B, H, dh, p, scratch, scratch_bytes, pc)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const PackedLpScratch S = packed_lp_scratch(pc, H);
     unsigned *dbits = p > 0.f ? (unsigned *)((float *)scratch + S.dbits) : nullptr;
     VstPackedPlan pk{};
-    VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
-    if (dbits) VST_LAUNCH(vst_attention_dropout_bits_packed(dbits, B, H, pc.tmax, seed, site, p, st, pk));
-    VST_LAUNCH(vst_attention_fwd_bf16_packed(q, k, v, out, lse2, H, dh, scale, p, dbits, st, f16 != 0, pk));
+    VS_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
+    if (dbits) VS_LAUNCH(vst_attention_dropout_bits_packed(dbits, B, H, pc.tmax, seed, site, p, st, pk));
+    VS_LAUNCH(vst_attention_fwd_bf16_packed(q, k, v, out, lse2, H, dh, scale, p, dbits, st, f16 != 0, pk));
     return VS_OK;
 }
 
@@ -693,7 +592,7 @@ int vs_train_attention_backward_packed_lp(const float *q, const float *k, const 
                                           const float *lse2, float *dqkv, const int32_t *lengths, const int32_t *lengths_dev,
                                           int32_t B, int32_t H, int32_t dh, float scale, uint64_t seed, uint32_t site, float p,
                                           int32_t f16, void *scratch, size_t scratch_bytes, void *stream) {
-    if (!q || !k || !v || !out || !d_out || !lse2 || !dqkv || !lengths_dev || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
+    if (!q || !k || !v || !out || !d_out || !lse2 || !dqkv || !lengths_dev || !scratch) return vs_failf(VS_ERR_INVALID, "NULL pointer");
     PackedCtx pc;
     if (int rc = packed_lp_check(lengths, B, H, dh, p, scratch, scratch_bytes, pc)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -701,22 +600,22 @@ int vs_train_attention_backward_packed_lp(const float *q, const float *k, const 
     float *delta = (float *)scratch + S.delta;
     unsigned *dbits = p > 0.f ? (unsigned *)((float *)scratch + S.dbits) : nullptr;
     VstPackedPlan pk{};
-    VST_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
-    if (dbits) VST_LAUNCH(vst_attention_dropout_bits_packed(dbits, B, H, pc.tmax, seed, site, p, st, pk));
-    VST_LAUNCH(vst_head_rowdot(d_out, out, delta, pc.Mtot, pc.Mtot, H, dh, st, 2 | (f16 ? VSK_F16 : 0)));      // dO enters delta as the kernels see it: rounded
-    VST_LAUNCH(vst_attention_bwd_bf16_packed(q, k, v, d_out, lse2, delta, dqkv, H, dh, scale, p, dbits, st, f16 != 0, pk));
+    VS_LAUNCH(vst_plan_packed(lengths_dev, B, pc.Mtot, pc.tmax, pc.words, (int *)scratch, pc.nwork, st, &pk));
+    if (dbits) VS_LAUNCH(vst_attention_dropout_bits_packed(dbits, B, H, pc.tmax, seed, site, p, st, pk));
+    VS_LAUNCH(vst_head_rowdot(d_out, out, delta, pc.Mtot, pc.Mtot, H, dh, st, 2 | (f16 ? VSK_F16 : 0)));      // dO enters delta as the kernels see it: rounded
+    VS_LAUNCH(vst_attention_bwd_bf16_packed(q, k, v, d_out, lse2, delta, dqkv, H, dh, scale, p, dbits, st, f16 != 0, pk));
     return VS_OK;
 }
 
 int vs_train_dropout_mask_attention_packed(uint8_t *keep, const int32_t *lengths, int32_t B, int32_t H, uint64_t seed,
                                            uint32_t site, float p, void *stream) {
     PackedCtx pc;
-    if (!keep || H <= 0) return failf(VS_ERR_INVALID, "bad arguments");
+    if (!keep || H <= 0) return vs_failf(VS_ERR_INVALID, "bad arguments");
     if (int rc = packed_lengths(lengths, B, pc)) return rc;
     size_t off = 0;
     int row0 = 0;
     for (int b = 0; b < B; ++b) {
-        VST_LAUNCH(vst_attention_dropout_mask_video(keep + off, H, lengths[b], pc.Mtot, row0, seed, site, p, (hipStream_t)stream));
+        VS_LAUNCH(vst_attention_dropout_mask_video(keep + off, H, lengths[b], pc.Mtot, row0, seed, site, p, (hipStream_t)stream));
         off += (size_t)H * lengths[b] * lengths[b];
         row0 += lengths[b];
     }
@@ -725,15 +624,15 @@ int vs_train_dropout_mask_attention_packed(uint8_t *keep, const int32_t *lengths
 
 int vs_mse_mask_loss_forward(const float *output, const float *target, const uint8_t *mask, int32_t n, int32_t mean,
                              float *scratch, float *loss, void *stream) {
-    if (!output || !target || !scratch || !loss || n <= 0) return failf(VS_ERR_INVALID, "mse_mask_loss: bad arguments");
-    VST_LAUNCH(vst_mse_mask_fwd(output, target, mask, n, mean, scratch, loss, (hipStream_t)stream));
+    if (!output || !target || !scratch || !loss || n <= 0) return vs_failf(VS_ERR_INVALID, "mse_mask_loss: bad arguments");
+    VS_LAUNCH(vst_mse_mask_fwd(output, target, mask, n, mean, scratch, loss, (hipStream_t)stream));
     return VS_OK;
 }
 
 int vs_mse_mask_loss_backward(const float *output, const float *target, const uint8_t *mask, const float *d_loss,
                               int32_t n, int32_t mean, float *d_output, void *stream) {
-    if (!output || !target || !d_loss || !d_output || n <= 0) return failf(VS_ERR_INVALID, "mse_mask_loss: bad arguments");
-    VST_LAUNCH(vst_mse_mask_bwd(output, target, mask, d_loss, n, mean, d_output, (hipStream_t)stream));
+    if (!output || !target || !d_loss || !d_output || n <= 0) return vs_failf(VS_ERR_INVALID, "mse_mask_loss: bad arguments");
+    VS_LAUNCH(vst_mse_mask_bwd(output, target, mask, d_loss, n, mean, d_output, (hipStream_t)stream));
     return VS_OK;
 }
 
@@ -760,10 +659,10 @@ HeadWork head_work(int B, int T, int d, int F) {
 // gradient of the hidden state (NT GEMM against W^T)
 int head_backward_tail(const float *hidden, const float *vt_w, int M, int d, int F, float *d_hidden, float *d_vt_w, float *d_vt_b,
                        float *ws, const HeadWork &W, hipStream_t st) {
-    VST_LAUNCH(vst_wgrad(ws + W.dfeats, F, hidden, d, M, F, d, d_vt_w, nullptr, nullptr, d_vt_b, nullptr, nullptr, F, ws + W.wg, st));
-    VST_LAUNCH(vst_transpose(vt_w, ws + W.wt, F, d, st));                                     // [F,d] -> [d,F]
-    VST_HIP(hipMemsetAsync(ws + W.zeros, 0, (size_t)(d > F ? d : F) * sizeof(float), st));
-    VST_LAUNCH(vsk_linear(ws + W.dfeats, ws + W.wt, nullptr, ws + W.zeros, d_hidden, M, d, F, 0, nullptr, 1, 0, st));
+    VS_LAUNCH(vst_wgrad(ws + W.dfeats, F, hidden, d, M, F, d, d_vt_w, nullptr, nullptr, d_vt_b, nullptr, nullptr, F, ws + W.wg, st));
+    VS_LAUNCH(vst_transpose(vt_w, ws + W.wt, F, d, st));                                     // [F,d] -> [d,F]
+    VS_HIP(hipMemsetAsync(ws + W.zeros, 0, (size_t)(d > F ? d : F) * sizeof(float), st));
+    VS_LAUNCH(vsk_linear(ws + W.dfeats, ws + W.wt, nullptr, ws + W.zeros, d_hidden, M, d, F, 0, nullptr, 1, 0, st));
     return VS_OK;
 }
 }  // namespace
@@ -778,12 +677,12 @@ int vs_pretrain_head_forward(const float *hidden, const float *logits, const uin
                              float temp, int32_t entropy_penalty, float *feats, void *head_state, float *losses,
                              void *stream) {
     if (!hidden || !logits || !vid || !vt_w || !vt_b || !feats || !head_state || !losses)
-        return failf(VS_ERR_INVALID, "pretrain head: NULL pointer");
+        return vs_failf(VS_ERR_INVALID, "pretrain head: NULL pointer");
     if (B <= 0 || T <= 0 || d <= 0 || d % 32 || (F != 256 && F != 512 && F != 768 && F != 1024) || !(temp > 0.f))
-        return failf(VS_ERR_INVALID, "pretrain head: B=%d T=%d d=%d F=%d temp=%g unsupported (d %% 32 == 0, F in {256,512,768,1024})", B, T, d, F, temp);
+        return vs_failf(VS_ERR_INVALID, "pretrain head: B=%d T=%d d=%d F=%d temp=%g unsupported (d %% 32 == 0, F in {256,512,768,1024})", B, T, d, F, temp);
     hipStream_t st = (hipStream_t)stream;
-    VST_LAUNCH(vsk_linear(hidden, vt_w, nullptr, vt_b, feats, B * T, F, d, 0, nullptr, 1, 0, st));           // :79
-    VST_LAUNCH(vsp_head_forward(feats, logits, key_pad_mask, vid, B, T, F, 1.0f / temp, entropy_penalty,
+    VS_LAUNCH(vsk_linear(hidden, vt_w, nullptr, vt_b, feats, B * T, F, d, 0, nullptr, 1, 0, st));           // :79
+    VS_LAUNCH(vsp_head_forward(feats, logits, key_pad_mask, vid, B, T, F, 1.0f / temp, entropy_penalty,
                                 (float *)head_state, losses, st));
     return VS_OK;
 }
@@ -795,16 +694,16 @@ int vs_pretrain_head_backward(const float *hidden, const float *logits, const ui
                               size_t workspace_bytes, void *stream) {
     if (!hidden || !logits || !vid || !vt_w || !feats || !head_state || !d_losses || !d_hidden || !d_logits || !d_vt_w ||
         !d_vt_b || !workspace)
-        return failf(VS_ERR_INVALID, "pretrain head: NULL pointer");
+        return vs_failf(VS_ERR_INVALID, "pretrain head: NULL pointer");
     if (B <= 0 || T <= 0 || d <= 0 || d % 32 || (F != 256 && F != 512 && F != 768 && F != 1024) || !(temp > 0.f))
-        return failf(VS_ERR_INVALID, "pretrain head: B=%d T=%d d=%d F=%d temp=%g unsupported", B, T, d, F, temp);
+        return vs_failf(VS_ERR_INVALID, "pretrain head: B=%d T=%d d=%d F=%d temp=%g unsupported", B, T, d, F, temp);
     const HeadWork W = head_work(B, T, d, F);
     if (workspace_bytes < W.total * sizeof(float) || ((uintptr_t)workspace & 255))
-        return failf(VS_ERR_WORKSPACE, "pretrain head: workspace %zu bytes < %zu needed (256-byte aligned)", workspace_bytes, W.total * sizeof(float));
+        return vs_failf(VS_ERR_WORKSPACE, "pretrain head: workspace %zu bytes < %zu needed (256-byte aligned)", workspace_bytes, W.total * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     float *ws = (float *)workspace;
     const int M = B * T;
-    VST_LAUNCH(vsp_head_backward(feats, logits, key_pad_mask, vid, B, T, F, 1.0f / temp, entropy_penalty,
+    VS_LAUNCH(vsp_head_backward(feats, logits, key_pad_mask, vid, B, T, F, 1.0f / temp, entropy_penalty,
                                  (const float *)head_state, d_losses, ws + W.dfeats, d_logits, st));
     return head_backward_tail(hidden, vt_w, M, d, F, d_hidden, d_vt_w, d_vt_b, ws, W, st);
 }
@@ -837,10 +736,10 @@ size_t vs_pretrain_head_workspace_bytes_packed(const int32_t *lengths, int32_t B
 
 static int head_packed_check(const int32_t *lengths, int32_t B, int32_t ref_len, int32_t d, int32_t F, float temp, HeadPacked &hp) {
     if (int rc = head_packed_ctx(lengths, B, hp)) return rc;
-    if (ref_len < hp.tmax) return failf(VS_ERR_INVALID, "pretrain head: ref_len=%d is below max(lengths)=%d", ref_len, hp.tmax);
-    if (ref_len > (1 << 24)) return failf(VS_ERR_INVALID, "pretrain head: ref_len=%d too large", ref_len);
+    if (ref_len < hp.tmax) return vs_failf(VS_ERR_INVALID, "pretrain head: ref_len=%d is below max(lengths)=%d", ref_len, hp.tmax);
+    if (ref_len > (1 << 24)) return vs_failf(VS_ERR_INVALID, "pretrain head: ref_len=%d too large", ref_len);
     if (!head_shape_ok(d, F) || !(temp > 0.f))
-        return failf(VS_ERR_INVALID, "pretrain head: d=%d F=%d temp=%g unsupported (d %% 32 == 0, F in {256,512,768,1024}, temp > 0)", d, F, temp);
+        return vs_failf(VS_ERR_INVALID, "pretrain head: d=%d F=%d temp=%g unsupported (d %% 32 == 0, F in {256,512,768,1024}, temp > 0)", d, F, temp);
     return VS_OK;
 }
 
@@ -849,12 +748,12 @@ int vs_pretrain_head_forward_packed(const float *hidden, const float *logits, co
                                     int32_t d, int32_t F, float temp, int32_t entropy_penalty, float *feats, void *head_state,
                                     float *losses, void *stream) {
     if (!hidden || !logits || !lengths || !lengths_dev || !vid || !vt_w || !vt_b || !feats || !head_state || !losses)
-        return failf(VS_ERR_INVALID, "pretrain head: NULL pointer");
+        return vs_failf(VS_ERR_INVALID, "pretrain head: NULL pointer");
     HeadPacked hp;
     if (int rc = head_packed_check(lengths, B, ref_len, d, F, temp, hp)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    VST_LAUNCH(vsk_linear(hidden, vt_w, nullptr, vt_b, feats, hp.Mtot, F, d, 0, nullptr, 1, 0, st));
-    VST_LAUNCH(vsp_head_forward_packed(feats, logits, lengths_dev, vid, B, hp.Mtot, hp.tmax, hp.NC, ref_len, F, 1.0f / temp,
+    VS_LAUNCH(vsk_linear(hidden, vt_w, nullptr, vt_b, feats, hp.Mtot, F, d, 0, nullptr, 1, 0, st));
+    VS_LAUNCH(vsp_head_forward_packed(feats, logits, lengths_dev, vid, B, hp.Mtot, hp.tmax, hp.NC, ref_len, F, 1.0f / temp,
                                        entropy_penalty, (float *)head_state, losses, st));
     return VS_OK;
 }
@@ -866,16 +765,16 @@ int vs_pretrain_head_backward_packed(const float *hidden, const float *logits, c
                                      void *workspace, size_t workspace_bytes, void *stream) {
     if (!hidden || !logits || !lengths || !lengths_dev || !vid || !vt_w || !feats || !head_state || !d_losses || !d_hidden ||
         !d_logits || !d_vt_w || !d_vt_b || !workspace)
-        return failf(VS_ERR_INVALID, "pretrain head: NULL pointer");
+        return vs_failf(VS_ERR_INVALID, "pretrain head: NULL pointer");
     HeadPacked hp;
     if (int rc = head_packed_check(lengths, B, ref_len, d, F, temp, hp)) return rc;
     const HeadWork W = head_work(1, hp.Mtot, d, F);
     if (workspace_bytes < W.total * sizeof(float) || ((uintptr_t)workspace & 255))
-        return failf(VS_ERR_WORKSPACE, "pretrain head: workspace %zu bytes < %zu needed (256-byte aligned)", workspace_bytes, W.total * sizeof(float));
+        return vs_failf(VS_ERR_WORKSPACE, "pretrain head: workspace %zu bytes < %zu needed (256-byte aligned)", workspace_bytes, W.total * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     float *ws = (float *)workspace;
     const int M = hp.Mtot;
-    VST_LAUNCH(vsp_head_backward_packed(feats, logits, lengths_dev, B, M, hp.tmax, hp.NC, ref_len, F, 1.0f / temp, entropy_penalty,
+    VS_LAUNCH(vsp_head_backward_packed(feats, logits, lengths_dev, B, M, hp.tmax, hp.NC, ref_len, F, 1.0f / temp, entropy_penalty,
                                         (float *)head_state, d_losses, ws + W.dfeats, d_logits, st));
     return head_backward_tail(hidden, vt_w, M, d, F, d_hidden, d_vt_w, d_vt_b, ws, W, st);      // M = the Mtot packed rows
 }
@@ -883,9 +782,9 @@ int vs_pretrain_head_backward_packed(const float *hidden, const float *logits, c
 int vs_train_attention_forward(const float *q, const float *k, const float *v, const uint8_t *key_pad_mask, float *out,
                                float *lse2, int32_t B, int32_t H, int32_t T, int32_t dh, float scale, uint64_t seed,
                                uint32_t site, float p, void *stream) {
-    if (!q || !k || !v || !out || !lse2) return failf(VS_ERR_INVALID, "NULL pointer");
-    if (B <= 0 || H <= 0 || T <= 0) return failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
-    VST_LAUNCH(vst_attention_fwd(q, k, v, key_pad_mask, out, lse2, B, H, T, dh, scale, seed, site, p, (hipStream_t)stream));
+    if (!q || !k || !v || !out || !lse2) return vs_failf(VS_ERR_INVALID, "NULL pointer");
+    if (B <= 0 || H <= 0 || T <= 0) return vs_failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
+    VS_LAUNCH(vst_attention_fwd(q, k, v, key_pad_mask, out, lse2, B, H, T, dh, scale, seed, site, p, (hipStream_t)stream));
     return VS_OK;
 }
 
@@ -893,11 +792,11 @@ int vs_train_attention_backward(const float *q, const float *k, const float *v, 
                                 const float *out, const float *d_out, const float *lse2, float *dqkv, float *scratch,
                                 int32_t B, int32_t H, int32_t T, int32_t dh, float scale, uint64_t seed, uint32_t site,
                                 float p, void *stream) {
-    if (!q || !k || !v || !out || !d_out || !lse2 || !dqkv || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
-    if (B <= 0 || H <= 0 || T <= 0) return failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
+    if (!q || !k || !v || !out || !d_out || !lse2 || !dqkv || !scratch) return vs_failf(VS_ERR_INVALID, "NULL pointer");
+    if (B <= 0 || H <= 0 || T <= 0) return vs_failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
     hipStream_t st = (hipStream_t)stream;
-    VST_LAUNCH(vst_head_rowdot(d_out, out, scratch, B * T, T, H, dh, st));
-    VST_LAUNCH(vst_attention_bwd(q, k, v, key_pad_mask, d_out, lse2, scratch, dqkv, B, H, T, dh, scale, seed, site, p, st));
+    VS_LAUNCH(vst_head_rowdot(d_out, out, scratch, B * T, T, H, dh, st));
+    VS_LAUNCH(vst_attention_bwd(q, k, v, key_pad_mask, d_out, lse2, scratch, dqkv, B, H, T, dh, scale, seed, site, p, st));
     return VS_OK;
 }
 
@@ -908,17 +807,17 @@ size_t vs_train_attention_dropout_bits_bytes(int32_t B, int32_t H, int32_t T) {
 
 int vs_train_attention_dropout_bits(void *dbits, int32_t B, int32_t H, int32_t T, uint64_t seed, uint32_t site, float p,
                                     void *stream) {
-    if (!dbits || B <= 0 || H <= 0 || T <= 0) return failf(VS_ERR_INVALID, "dropout_bits: bad arguments");
-    VST_LAUNCH(vst_attention_dropout_bits((unsigned *)dbits, B, H, T, seed, site, p, (hipStream_t)stream));
+    if (!dbits || B <= 0 || H <= 0 || T <= 0) return vs_failf(VS_ERR_INVALID, "dropout_bits: bad arguments");
+    VS_LAUNCH(vst_attention_dropout_bits((unsigned *)dbits, B, H, T, seed, site, p, (hipStream_t)stream));
     return VS_OK;
 }
 
 int vs_train_attention_forward_bf16(const float *q, const float *k, const float *v, const uint8_t *key_pad_mask, float *out,
                                     float *lse2, int32_t B, int32_t H, int32_t T, int32_t dh, float scale, float p,
                                     const void *dbits, int32_t in16, void *stream) {
-    if (!q || !k || !v || !out || !lse2) return failf(VS_ERR_INVALID, "NULL pointer");
-    if (B <= 0 || H <= 0 || T <= 0) return failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
-    VST_LAUNCH(vst_attention_fwd_bf16(q, k, v, key_pad_mask, out, lse2, B, H, T, dh, scale, p, (const unsigned *)dbits,
+    if (!q || !k || !v || !out || !lse2) return vs_failf(VS_ERR_INVALID, "NULL pointer");
+    if (B <= 0 || H <= 0 || T <= 0) return vs_failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
+    VS_LAUNCH(vst_attention_fwd_bf16(q, k, v, key_pad_mask, out, lse2, B, H, T, dh, scale, p, (const unsigned *)dbits,
                                       (hipStream_t)stream, ((in16 & ~VSK_F16) ? 1 : 0) | (in16 & VSK_F16)));
     return VS_OK;
 }
@@ -927,11 +826,11 @@ int vs_train_attention_backward_bf16(const float *q, const float *k, const float
                                      const float *out, const float *d_out, const float *lse2, float *dqkv, float *scratch,
                                      int32_t B, int32_t H, int32_t T, int32_t dh, float scale, float p, const void *dbits,
                                      int32_t in16, void *stream) {
-    if (!q || !k || !v || !out || !d_out || !lse2 || !dqkv || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
-    if (B <= 0 || H <= 0 || T <= 0) return failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
+    if (!q || !k || !v || !out || !d_out || !lse2 || !dqkv || !scratch) return vs_failf(VS_ERR_INVALID, "NULL pointer");
+    if (B <= 0 || H <= 0 || T <= 0) return vs_failf(VS_ERR_INVALID, "B=%d H=%d T=%d", B, H, T);
     hipStream_t st = (hipStream_t)stream;
-    VST_LAUNCH(vst_head_rowdot(d_out, out, scratch, B * T, T, H, dh, st, 2 | (in16 & VSK_F16)));       // dO enters delta as the kernels see it: bf16 / f16
-    VST_LAUNCH(vst_attention_bwd_bf16(q, k, v, key_pad_mask, d_out, lse2, scratch, dqkv, B, H, T, dh, scale, p,
+    VS_LAUNCH(vst_head_rowdot(d_out, out, scratch, B * T, T, H, dh, st, 2 | (in16 & VSK_F16)));       // dO enters delta as the kernels see it: bf16 / f16
+    VS_LAUNCH(vst_attention_bwd_bf16(q, k, v, key_pad_mask, d_out, lse2, scratch, dqkv, B, H, T, dh, scale, p,
                                       (const unsigned *)dbits, st, ((in16 & ~VSK_F16) ? 1 : 0) | (in16 & VSK_F16)));
     return VS_OK;
 }
@@ -943,31 +842,31 @@ size_t vs_train_wgrad_scratch_floats(int32_t M, int32_t N, int32_t K) {
 
 int vs_train_wgrad(const float *dY, const float *X, int32_t M, int32_t N, int32_t K, float *dW, float *db,
                    float *scratch, void *stream) {
-    if (!dY || !X || !dW || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
-    if (M <= 0 || N <= 0 || K <= 0 || N % 4 || K % 4) return failf(VS_ERR_INVALID, "M=%d N=%d K=%d unsupported (N, K multiples of 4)", M, N, K);
-    VST_LAUNCH(vst_wgrad(dY, N, X, K, M, N, K, dW, nullptr, nullptr, db, nullptr, nullptr, N, scratch, (hipStream_t)stream));
+    if (!dY || !X || !dW || !scratch) return vs_failf(VS_ERR_INVALID, "NULL pointer");
+    if (M <= 0 || N <= 0 || K <= 0 || N % 4 || K % 4) return vs_failf(VS_ERR_INVALID, "M=%d N=%d K=%d unsupported (N, K multiples of 4)", M, N, K);
+    VS_LAUNCH(vst_wgrad(dY, N, X, K, M, N, K, dW, nullptr, nullptr, db, nullptr, nullptr, N, scratch, (hipStream_t)stream));
     return VS_OK;
 }
 
 int vs_train_wgrad_bf16(const float *dY, const float *X, int32_t M, int32_t N, int32_t K, float *dW, float *db,
                         float *scratch, void *stream) {
-    if (!dY || !X || !dW || !scratch) return failf(VS_ERR_INVALID, "NULL pointer");
-    if (M <= 0 || N <= 0 || K <= 0 || N % 4 || K % 4) return failf(VS_ERR_INVALID, "M=%d N=%d K=%d unsupported (N, K multiples of 4)", M, N, K);
-    VST_LAUNCH(vst_wgrad(dY, N, X, K, M, N, K, dW, nullptr, nullptr, db, nullptr, nullptr, N, scratch, (hipStream_t)stream, 1));
+    if (!dY || !X || !dW || !scratch) return vs_failf(VS_ERR_INVALID, "NULL pointer");
+    if (M <= 0 || N <= 0 || K <= 0 || N % 4 || K % 4) return vs_failf(VS_ERR_INVALID, "M=%d N=%d K=%d unsupported (N, K multiples of 4)", M, N, K);
+    VS_LAUNCH(vst_wgrad(dY, N, X, K, M, N, K, dW, nullptr, nullptr, db, nullptr, nullptr, N, scratch, (hipStream_t)stream, 1));
     return VS_OK;
 }
 
 int vs_train_dropout_mask_attention(uint8_t *keep, int32_t B, int32_t H, int32_t T, uint64_t seed, uint32_t site,
                                     float p, void *stream) {
-    if (!keep || B <= 0 || H <= 0 || T <= 0) return failf(VS_ERR_INVALID, "bad arguments");
-    VST_LAUNCH(vst_attention_dropout_mask(keep, B, H, T, seed, site, p, (hipStream_t)stream));
+    if (!keep || B <= 0 || H <= 0 || T <= 0) return vs_failf(VS_ERR_INVALID, "bad arguments");
+    VS_LAUNCH(vst_attention_dropout_mask(keep, B, H, T, seed, site, p, (hipStream_t)stream));
     return VS_OK;
 }
 
 int vs_train_dropout_mask_rows(uint8_t *keep, int32_t M, int32_t cols, uint64_t seed, uint32_t site, float p,
                                void *stream) {
-    if (!keep || M <= 0 || cols <= 0) return failf(VS_ERR_INVALID, "bad arguments");
-    VST_LAUNCH(vst_rows_dropout_mask(keep, M, cols, seed, site, p, (hipStream_t)stream));
+    if (!keep || M <= 0 || cols <= 0) return vs_failf(VS_ERR_INVALID, "bad arguments");
+    VS_LAUNCH(vst_rows_dropout_mask(keep, M, cols, seed, site, p, (hipStream_t)stream));
     return VS_OK;
 }
 
