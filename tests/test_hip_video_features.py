@@ -1,0 +1,272 @@
+"""GPU: the R3D-18 video-level feature (video_features.R3D18Features, include/features/vs_video_features.h) against tests/r3d_ref.py,
+our float64 restatement of torchvision's network in torch functions.
+
+Tolerance: the project's parity bar, 1e-4 of the float64 tensor's largest entry (README, smoke()).  Every case that uses the bar
+also asserts that torch's own fp32 CPU forward of the restatement is inside it, so a failure cannot be blamed on the bar.  Batch
+independence, the two key forms, the device resize in front and the re-pack are bit-equal: no tolerance.  Each case prints its
+distance ("video_features_parity ..." lines, collected in profiles/video_features_parity.txt)."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import r3d_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+BAR = 1e-4
+CANARY = -777.25
+GUARD = 256         # floats of canary on either side of a raw kernel's output
+
+
+def _dev():
+    assert torch.cuda.is_available(), "these tests need a HIP device"
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def vsa():
+    return importlib.import_module("video-summarization_amd")
+
+
+def _report(case, got, want64, fp32_cpu=None):
+    """asserts the parity bar on ``got`` (and on torch's own fp32 forward, where given), prints and returns the distance"""
+    top = want64.abs().max().item()
+    d = (got.double().cpu() - want64).abs().max().item() / top
+    line = "video_features_parity %-50s ours %.3e" % (case, d)
+    d32 = None
+    if fp32_cpu is not None:
+        d32 = (fp32_cpu.double() - want64).abs().max().item() / top
+        line += "  torch fp32 cpu %.3e" % d32
+    print(line + "  (of max |float64| = %.4g; bar %.0e)" % (top, BAR))
+    assert top > 0 and torch.isfinite(got).all()
+    if d32 is not None:
+        assert d32 < BAR, (case, d32)
+    assert d < BAR, (case, d)
+    return d
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# single convs: conv + folded BatchNorm3d (+ residual) (+ ReLU) through vs_cnn3d_pack_conv / vs_cnn3d_conv
+# ------------------------------------------------------------------------------------------------------------------------
+class _Conv:
+    """one seeded conv + BatchNorm3d: the float64 / float32 restatement and the kernel, on inputs the caller chooses"""
+
+    def __init__(self, vsa, seed, cin, cout, kt, ks, st, ss, pt, ps):
+        self.L = vsa._lib
+        self.lib = self.L.load()
+        self.geom = (cin, cout, kt, ks, st, ss, pt, ps)
+        self.g = g = torch.Generator().manual_seed(seed)
+        self.wt = torch.randn(cout, cin, kt, ks, ks, generator=g) * (2.0 / (cin * kt * ks * ks)) ** 0.5
+        self.gamma, self.var = 0.5 + torch.rand(cout, generator=g), 0.5 + torch.rand(cout, generator=g)
+        self.beta, self.mean = 0.3 * torch.randn(cout, generator=g), 0.3 * torch.randn(cout, generator=g)
+        dev = _dev()
+        P = self.L.Cnn3dConvParams()
+        self.keep = [t.to(dev).contiguous() for t in (self.wt, self.gamma, self.beta, self.mean, self.var)]
+        for f, t in zip(("weight", "gamma", "beta", "running_mean", "running_var"), self.keep):
+            setattr(P, f, t.data_ptr())
+        self.packed = torch.empty(self.lib.vs_cnn3d_packed_floats(cout, cin, kt, ks), dtype=torch.float32, device=dev)
+        assert self.packed.numel() > 0
+        self.L.check(self.lib.vs_cnn3d_pack_conv(C.byref(P), cout, cin, kt, ks, self.packed.data_ptr(), None))
+
+    def restated(self, x, dt, residual=None, relu=True):
+        """x: [N, Cin, T, H, W] -> channels-last [N, To, Ho, Wo, Cout]; residual channels-last"""
+        cin, cout, kt, ks, st, ss, pt, ps = self.geom
+        y = F.conv3d(x.to(dt), self.wt.to(dt), None, (st, ss, ss), (pt, ps, ps))
+        y = F.batch_norm(y, self.mean.to(dt), self.var.to(dt), self.gamma.to(dt), self.beta.to(dt), training=False, eps=1e-5)
+        y = y.permute(0, 2, 3, 4, 1)
+        if residual is not None:
+            y = y + residual.to(dt)
+        return (F.relu(y) if relu else y).contiguous()
+
+    def run(self, given, kind, n, t, h, w, out_shape, residual=None, relu=True):
+        """the kernel on ``given`` (in the layout of ``kind``); the output sits between canaries"""
+        cin, cout, kt, ks, st, ss, pt, ps = self.geom
+        dev = _dev()
+        given = given.contiguous().to(dev)
+        res = None if residual is None else residual.contiguous().to(dev)
+        count = int(np.prod(out_shape))
+        out = torch.full((GUARD + count + GUARD,), CANARY, dtype=torch.float32, device=dev)
+        self.L.check(self.lib.vs_cnn3d_conv(given.data_ptr(), kind, n, t, h, w, cin, self.packed.data_ptr(), cout, kt, ks, st, ss, pt, ps,
+                                            None if res is None else res.data_ptr(), int(relu), out[GUARD:].data_ptr(), None))
+        torch.cuda.synchronize()
+        out = out.cpu()
+        assert (out[:GUARD] == CANARY).all() and (out[GUARD + count:] == CANARY).all()
+        return out[GUARD:GUARD + count].view(out_shape)
+
+
+def test_stem_from_float_ncdhw_and_from_uint8_frames(vsa):
+    """3x7x7, stride (1,2,2), pad (1,3,3), 3 -> 64 on 2 x 5 x 19 x 23, from the normalised float tensor and from the uint8 frames it
+    was made of: equal distances say that the LDS table is ToTensor + Normalize and that a padding tap is 0 after normalisation,
+    in time as in space (a raw 0 would read as -mean / std there)"""
+    L = vsa._lib
+    n, t, h, w = 2, 5, 19, 23
+    conv = _Conv(vsa, 500, 3, 64, 3, 7, 1, 2, 1, 3)
+    frames = torch.randint(0, 256, (n, t, h, w, 3), generator=conv.g, dtype=torch.uint8)
+    x64, x32 = ref.normalise(frames, torch.float64), ref.normalise(frames, torch.float32)
+    assert (x32 < 0).any() and (x32 > 0).any()                                                      # signed
+    want, cpu32 = conv.restated(x64, torch.float64), conv.restated(x32, torch.float32)
+    assert (want == 0).any() and (want > 0).any() and want.shape == (n, 5, 10, 12, 64)
+    from_f32 = conv.run(x32, L.VS_CNN3D_INPUT_F32_NCDHW, n, t, h, w, want.shape)
+    from_u8 = conv.run(frames, L.VS_CNN3D_INPUT_U8_NDHWC, n, t, h, w, want.shape)
+    d_f32 = _report("conv stem 3x7x7 3->64 2x5x19x23 f32 ncdhw", from_f32, want, cpu32)
+    d_u8 = _report("conv stem 3x7x7 3->64 2x5x19x23 uint8", from_u8, want, cpu32)
+    assert d_f32 == d_u8 and _same_bits(from_f32, from_u8)
+
+
+def _ndhwc_case(vsa, name, seed, n, t, h, w, cin, cout, kt, ks, s, p, residual, relu):
+    L = vsa._lib
+    conv = _Conv(vsa, seed, cin, cout, kt, ks, s, s, p, p)
+    x = torch.randn(n, cin, t, h, w, generator=conv.g)                                            # signed
+    shape = tuple(conv.restated(x, torch.float32, relu=False).shape)
+    res = torch.randn(shape, generator=conv.g) if residual else None
+    want, cpu32 = conv.restated(x, torch.float64, res, relu), conv.restated(x, torch.float32, res, relu)
+    got = conv.run(x.permute(0, 2, 3, 4, 1), L.VS_CNN3D_INPUT_F32_NDHWC, n, t, h, w, shape, res, relu)
+    _report("conv " + name, got, want, cpu32)
+    return conv, x, res, got, want
+
+
+def test_conv_3x3x3_with_residual_and_relu_on_a_partial_row_tile(vsa):
+    """64 -> 64 on 1 x 3 x 5 x 7: 105 rows, not a multiple of the 64-row tile"""
+    conv, x, res, got, want = _ndhwc_case(vsa, "3x3x3 s1 64->64 1x3x5x7 +residual +relu", 501, 1, 3, 5, 7, 64, 64, 3, 3, 1, 1, True, True)
+    assert got.shape == (1, 3, 5, 7, 64) and got.numel() // 64 == 105
+    assert (want == 0).any() and (got == 0).any() and (got > 0).any()                               # the ReLU cuts something
+    plain = conv.run(x.permute(0, 2, 3, 4, 1), vsa._lib.VS_CNN3D_INPUT_F32_NDHWC, 1, 3, 5, 7, got.shape, None, True)
+    assert (plain != got).any()                                                                     # the residual changes the result
+    _report("conv 3x3x3 s1 64->64 1x3x5x7 +relu, no residual", plain, conv.restated(x, torch.float64), conv.restated(x, torch.float32))
+
+
+def test_conv_3x3x3_stride_2_long_k_loop(vsa):
+    """128 -> 256 on 1 x 4 x 6 x 5: K = 3456 (108 k-steps), even sizes under stride 2"""
+    _, _, _, got, _ = _ndhwc_case(vsa, "3x3x3 s2 128->256 1x4x6x5 +relu", 502, 1, 4, 6, 5, 128, 256, 3, 3, 2, 1, False, True)
+    assert got.shape == (1, 2, 3, 3, 256)
+
+
+def test_conv_3x3x3_one_frame_fewer_rows_than_a_tile(vsa):
+    """256 -> 256 on 1 x 1 x 2 x 3: with T = 1 two of the three temporal taps are padding; 6 rows"""
+    _, _, _, got, _ = _ndhwc_case(vsa, "3x3x3 s1 256->256 1x1x2x3 +relu", 503, 1, 1, 2, 3, 256, 256, 3, 3, 1, 1, False, True)
+    assert got.shape == (1, 1, 2, 3, 256)
+
+
+def test_conv_1x1x1_stride_2_without_relu_or_residual(vsa):
+    """the downsample: 64 -> 128 on 2 x 5 x 7 x 9; negative outputs survive"""
+    _, _, _, got, want = _ndhwc_case(vsa, "1x1x1 s2 64->128 2x5x7x9", 504, 2, 5, 7, 9, 64, 128, 1, 1, 2, 0, False, False)
+    assert got.shape == (2, 3, 4, 5, 128) and (want < 0).any() and (got < 0).any()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the whole network
+# ------------------------------------------------------------------------------------------------------------------------
+WSEED = 21
+SHAPES = ((1, 1, 1, 1), (1, 5, 17, 15), (2, 9, 23, 31), (1, 16, 32, 40))
+
+
+@pytest.fixture(scope="module")
+def sd(vsa):
+    return vsa.video_features.make_state_dict(WSEED)
+
+
+@pytest.fixture(scope="module")
+def model(vsa, sd):
+    m = vsa.R3D18Features()
+    m.load_state_dict(sd, strict=True)
+    return m.to(_dev())
+
+
+def _frames(shape, seed):
+    return torch.randint(0, 256, tuple(shape) + (3,), generator=torch.Generator().manual_seed(seed), dtype=torch.uint8)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%dx%dx%d" % s)
+def test_whole_network_against_float64(model, sd, shape):
+    frames = _frames(shape, 600 + SHAPES.index(shape))
+    want = ref.forward(ref.cast(sd, torch.float64), ref.normalise(frames, torch.float64))
+    cpu32 = ref.forward(ref.cast(sd, torch.float32), ref.normalise(frames, torch.float32))
+    from_u8 = model.extract(frames.to(_dev()))
+    from_f32 = model(ref.normalise(frames, torch.float32).to(_dev()))
+    for got in (from_u8, from_f32):
+        assert got.shape == (shape[0], 512) and got.dtype == torch.float32 and got.is_cuda
+    d_u8 = _report("network %dx%dx%dx%d uint8 frames (extract)" % shape, from_u8, want, cpu32)
+    d_f32 = _report("network %dx%dx%dx%d float32 ncdhw (forward)" % shape, from_f32, want, cpu32)
+    assert d_u8 == d_f32 and _same_bits(from_u8, from_f32)
+
+
+def test_a_video_does_not_depend_on_its_batch(model):
+    dev = _dev()
+    frames = _frames((3, 5, 17, 15), 700).to(dev)
+    x = ref.normalise(frames.cpu(), torch.float32).to(dev)
+    for run, data in ((model.extract, frames), (model.forward, x)):
+        three = run(data)
+        for i in range(3):
+            assert _same_bits(run(data[i:i + 1])[0], three[i]), i                                   # alone
+            other = (i + 1) % 3
+            assert _same_bits(run(data[[other, i]])[1], three[i]), i                                # last in a batch of 2
+        assert (three[0] != three[1]).any()
+    assert _same_bits(model.extract(frames[1]), model.extract(frames)[1:2])                         # [T, H, W, 3] is one video
+
+
+def test_reference_sequential_names_give_the_same_bits(vsa, model, sd):
+    dev = _dev()
+    other = vsa.R3D18Features()
+    other.load_state_dict(vsa.video_features.to_sequential_names(sd), strict=True)
+    other = other.to(dev)
+    frames = _frames((2, 5, 17, 15), 701).to(dev)
+    assert _same_bits(other.extract(frames), model.extract(frames))
+
+
+def test_extract_with_size_is_the_device_resize_in_front(vsa, model):
+    dev = _dev()
+    frames = _frames((5, 30, 40), 702).to(dev)
+    small = vsa.resize_frames_device(frames, 17)
+    assert tuple(small.shape) == (5, 17, 22, 3)
+    assert _same_bits(model.extract(frames, size=17), model.extract(small))
+    assert _same_bits(model.extract(frames, bgr=True), model.extract(frames.flip(-1)))
+
+
+def test_get_video_feature_device_resize_equals_host_resize(vsa, model):
+    """the device resize is bit-equal to PIL's, so the features are too"""
+    video = _frames((6, 36, 48), 703).numpy()
+    host = vsa.get_video_feature(video, size=20, model=model, resize="host")
+    device = vsa.get_video_feature(video, size=20, model=model, resize="device")
+    assert isinstance(host, np.ndarray) and host.shape == (512,) and host.dtype == np.float32
+    assert np.array_equal(host.view(np.int32), device.view(np.int32)) and np.isfinite(host).all() and np.abs(host).max() > 0
+
+
+def test_repack_after_a_batchnorm_buffer_changes_in_place(vsa, sd):
+    """the packed model follows (data_ptr, _version): an in-place change of one statistic changes the feature, restoring it
+    restores the bits"""
+    dev = _dev()
+    m = vsa.R3D18Features()
+    m.load_state_dict(sd, strict=True)
+    m = m.to(dev)
+    frames = _frames((1, 5, 17, 15), 704).to(dev)
+    a = m.extract(frames)
+    packed = m._packed
+    assert m.extract(frames) is not None and m._packed is packed                 # cached
+    var = m.layer3[0].conv2[1].running_var
+    saved = var.clone()
+    var.mul_(4.0)
+    b = m.extract(frames)
+    assert m._packed is not packed and (a != b).any()
+    var.copy_(saved)
+    assert _same_bits(m.extract(frames), a)
+    assert _same_bits(m.train().extract(frames), a)                              # train(): still the running statistics
+
+
+def test_one_upload_gives_both_pretraining_tensors(vsa, model):
+    """the frames of a video, uploaded once: the scorer's [T, 1024] input and the [512] distillation target"""
+    dev = _dev()
+    frames = _frames((6, 33, 47), 705).to(dev)
+    goog = vsa.GoogLeNetFeatures()
+    goog.load_state_dict(vsa.features.make_state_dict(11), strict=True)
+    goog = goog.to(dev)
+    per_frame, video_level = goog.extract(frames), model.extract(frames)
+    assert per_frame.shape == (6, 1024) and video_level.shape == (1, 512) and per_frame.is_cuda and video_level.is_cuda
+    assert torch.isfinite(per_frame).all() and torch.isfinite(video_level).all()

@@ -18,8 +18,11 @@ from . import summary  # noqa: F401
 from .summary import summarize, summarize_scores  # noqa: F401
 from . import features  # noqa: F401
 from .features import GoogLeNetFeatures, get_google_net_features, resize_frames_device, resize_output_size  # noqa: F401
+from . import video_features  # noqa: F401
+from .video_features import R3D18Features, get_video_feature  # noqa: F401
 
 __all__ = ["SimNet", "PretrainModel", "score_frames", "synth", "mse_with_mask_loss", "mse_packed_loss", "segmentation", "get_segment_fn", "kts_seg",
            "kts_seg_batch", "optim", "Adam", "AdamW", "clip_grad_norm_", "grad_norm", "collate_fn_pretrain_packed", "pretrain_step_packed", "summary", "summarize",
            "summarize_scores", "TrainSet", "PretrainSet", "epoch_plan", "train_epoch_resident", "pretrain_epoch_resident", "features",
-           "GoogLeNetFeatures", "get_google_net_features", "resize_frames_device", "resize_output_size"]
+           "GoogLeNetFeatures", "get_google_net_features", "resize_frames_device", "resize_output_size", "video_features", "R3D18Features",
+           "get_video_feature"]

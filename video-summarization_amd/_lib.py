@@ -22,7 +22,7 @@ SOURCES = ("vs_kernels.hip", "vs_attention.hip", "vs_attention_w64.hip", "vs_mlp
            "vs_train_kernels.hip", "vs_train_attention.hip", "vs_train_attention_bf16.hip", "vs_train_gemm_rows.hip", "vs_pretrain_kernels.hip",
            "vs_train.cpp", "vs_segment.hip", "vs_segment_gram.hip", "vs_segment.cpp", "vs_optim.hip", "vs_attention_maps.hip",
            "vs_eval_device.hip", "vs_eval_device.cpp", "vs_summary.hip", "vs_summary.cpp", "vs_batch.hip", "vs_cnn.hip", "vs_cnn.cpp",
-           "vs_resize.hip", "vs_resize.cpp", "vs_weights.cpp", "vs_error.cpp")
+           "vs_resize.hip", "vs_resize.cpp", "vs_cnn3d.hip", "vs_cnn3d.cpp", "vs_weights.cpp", "vs_error.cpp")
 # vs_resize.cpp computes PIL's coefficient tables in double: no multiply-add of it may be contracted, whatever the host
 EXTRA_FLAGS = {"vs_resize.cpp": ("-ffp-contract=off",)}
 ABI_VERSION = 3
@@ -46,6 +46,8 @@ VS_KTS_SCORES, VS_KTS_BACKTRACK, VS_KTS_AUTO = 0, 1, 2
 VS_KTS_GRAM_DOT, VS_KTS_GRAM_COSINE, VS_KTS_GRAM_RBF = 0, 1, 2
 VS_CNN_INPUT_F32_NCHW, VS_CNN_INPUT_U8_NHWC, VS_CNN_INPUT_F32_NHWC = 0, 1, 2
 VS_CNN_NUM_CONVS, VS_CNN_FEATURES = 57, 1024
+VS_CNN3D_INPUT_F32_NCDHW, VS_CNN3D_INPUT_U8_NDHWC, VS_CNN3D_INPUT_F32_NDHWC = 0, 1, 2
+VS_R3D_NUM_CONVS, VS_R3D_FEATURES = 20, 512
 VS_RESIZE_SWAP_RB = 1
 VS_RESIZE_PATH_FUSED, VS_RESIZE_PATH_SMALL_TILE = 0, 1
 NUM_STAGES = 6
@@ -111,6 +113,14 @@ class CnnConvParams(C.Structure):   # vs_cnn_conv_params (include/features/vs_fe
 
 class CnnParams(C.Structure):       # vs_cnn_params
     _fields_ = [("conv", CnnConvParams * VS_CNN_NUM_CONVS)]
+
+
+class Cnn3dConvParams(C.Structure):     # vs_cnn3d_conv_params (include/features/vs_video_features.h)
+    _fields_ = [(n, C.c_void_p) for n in ("weight", "gamma", "beta", "running_mean", "running_var")]
+
+
+class R3dParams(C.Structure):           # vs_r3d_params
+    _fields_ = [("conv", Cnn3dConvParams * VS_R3D_NUM_CONVS)]
 
 
 # --------------------------------------------------------------------------------------------
@@ -308,6 +318,21 @@ _RESIZE_BINDINGS = {
 }
 RESIZE_EXPORTS = tuple(_RESIZE_BINDINGS)
 
+# The R3D-18 video-level feature: include/features/vs_video_features.h, a table of its own (tests/test_video_features_host.py).
+VIDEO_FEATURES_HEADER = os.path.join("features", "vs_video_features.h")
+_VIDEO_FEATURES_BINDINGS = {
+    "vs_r3d_pack": (_RC, [_ref(R3dParams), _P, _ref(_P)]),
+    "vs_r3d_free": (None, [_P]),
+    "vs_r3d_workspace_bytes": (_Z, [_I] * 4),
+    "vs_r3d_flops": (_D, [_I] * 4),
+    "vs_r3d_normalisation": (_RC, [_ref(_F)]),
+    "vs_r3d_forward": (_RC, [_P, _P] + [_I] * 5 + [_P, _P, _Z, _P]),
+    "vs_cnn3d_packed_floats": (_Z, [_I] * 4),
+    "vs_cnn3d_pack_conv": (_RC, [_ref(Cnn3dConvParams)] + [_I] * 4 + [_P, _P]),
+    "vs_cnn3d_conv": (_RC, [_P] + [_I] * 6 + [_P] + [_I] * 7 + [_P, _I, _P, _P]),
+}
+VIDEO_FEATURES_EXPORTS = tuple(_VIDEO_FEATURES_BINDINGS)
+
 
 def hipcc_path() -> str:
     for p in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc"):
@@ -324,6 +349,7 @@ def needs_build() -> bool:
     deps.append(os.path.join(INCLUDE, PACKED_INSPECT_HEADER))
     deps.append(os.path.join(INCLUDE, FEATURES_HEADER))
     deps.append(os.path.join(INCLUDE, RESIZE_HEADER))
+    deps.append(os.path.join(INCLUDE, VIDEO_FEATURES_HEADER))
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -411,6 +437,11 @@ def _bind_resize(lib) -> None:
     _bind_table(lib, _RESIZE_BINDINGS)
 
 
+def _bind_video_features(lib) -> None:
+    """``_bind`` for the table of include/features/vs_video_features.h."""
+    _bind_table(lib, _VIDEO_FEATURES_BINDINGS)
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -435,6 +466,7 @@ def load() -> C.CDLL:
         _bind_packed_inspect(lib)
         _bind_features(lib)
         _bind_resize(lib)
+        _bind_video_features(lib)
         _lib = lib
     return _lib
 
