@@ -56,7 +56,9 @@ extern "C" {
                                 mode and the same video scored in a large batch are no longer bit-identical.  Also with
                                 VS_FLAG_F16X3_LINEAR (the split-K kernels emulated on the f16 pipe; the attention is then the
                                 exact split-key kernel).  d_model 128 / 256 / 512, head dim 32 / 64 / 128.  Ignored (the default
-                                kernels run) for larger inputs, other shapes, the bf16 mode and packed / class-token calls. */
+                                kernels run) for larger inputs, other shapes, the bf16 mode and packed / class-token calls; the
+                                embedding alone keeps its default kernel where an eighth of in_features is not a multiple of 128
+                                or, above 256, of 256 (in_features 1000, 3072, 5120). */
 #define VS_FLAG_F16X3_ATTENTION 16u /* opt-in: the two attention products emulated on the f16 pipe the same way
                                 (q*scale, k, v, p split into hi + lo halves, three MFMAs per product, fp32
                                 softmax and accumulation).  Head dim 32 or 64.  Exclusive with

@@ -1,6 +1,7 @@
 // csrc/vs_forward_plan.h alone, as plain C++17 (no HIP): tests/test_forward_plan_host.py builds this with the host compiler and
 // -fsanitize=address,undefined.  Part 1: named cases -> the expected plan (every enumerator of every plan enum is reached);
-// part 2: what each A/B switch flips; part 3: invariants and the refusals over a grid.
+// part 2: what each A/B switch flips; part 3: invariants and the refusals over a grid, and for every accepted
+// plan the support predicate of each kernel it names (kernels_exist).
 // Prints "OK" or the first failed check.
 #include <cstdio>
 #include <cstring>
@@ -167,6 +168,18 @@ const Case kCases[] = {
      but(EXACT_STAGES, [](Want &w) { w.attention_arith = VS_ARITH_F16X3; w.attention = VS_ATT_PACKED; w.mode_attention = 2; })},
     {"packed, d 512, bf16: no ring", packed(rows(model(512, 8), 8193, BF16)), defaults(),
      but(WIDE_BF16_LIN, [](Want &w) { w.attention_arith = VS_ARITH_BF16; w.attention = VS_ATT_PACKED; w.mode_attention = 1; })},
+    // head dim 128 at d_model <= 256: q/k/v are bf16 planes there too, so the packed attention is asked for its bf16-stored form
+    {"packed, d 256 x 2 heads (head dim 128), bf16", packed(rows(model(256, 2), 1000, BF16)), defaults(),
+     but(BF16_FUSED, [](Want &w) { w.attention = VS_ATT_PACKED; })},
+    {"packed, d 128 x 1 head (head dim 128), bf16", packed(rows(model(128, 1), 8193, BF16)), defaults(),
+     Want{VS_ARITH_BF16, VS_ARITH_BF16, VSW_BF16, VS_EMBED_GEMM, VS_ATT_PACKED, VS_LAYER_STAGES, VS_LN_FUSED, VS_LN_FUSED, true, true, false, true, 1, S16, S16, S16}},
+    // latency mode, wider embeddings: an eighth of in_features has to be a slice vsk_linear_parts takes (3072 / 8 = 384 is not)
+    {"split-K, d 256, in_features 2048", rows(model(256, 4, 2048), 320, SPLITK), defaults(),
+     but(EXACT_STAGES, [](Want &w) { w.embed = VS_EMBED_SPLITK; w.attention = VS_ATT_SPLITKV; w.ln1 = w.ln2 = VS_LN_SPLITK_ROWS; })},
+    {"split-K, d 256, in_features 3072: default embedding", rows(model(256, 4, 3072), 320, SPLITK), defaults(),
+     but(EXACT_STAGES, [](Want &w) { w.attention = VS_ATT_SPLITKV; w.ln1 = w.ln2 = VS_LN_SPLITK_ROWS; })},
+    {"split-K, d 512, in_features 5120: default embedding", rows(model(512, 8, 5120), 320, SPLITK), defaults(),
+     but(EXACT_STAGES, [](Want &w) { w.attention = VS_ATT_SPLITKV; w.ln1 = w.ln2 = VS_LN_SPLITK_ROWS; })},
     // an embedded model's LayerNorm is narrower than its rows: no fused kernel normalises it, and nothing is stored as bf16
     {"embedded model, bf16", embedded(rows(MA, 8193, BF16)), defaults(),
      Want{VS_ARITH_BF16, VS_ARITH_BF16, VSW_BF16, VS_EMBED_GEMM, VS_ATT_LOWPREC, VS_LAYER_STAGES, VS_LN_GEMM_ROWS, VS_LN_GEMM_ROWS, false, false, false, false, 1, 1, 1, 1}},
@@ -216,7 +229,57 @@ std::string expected_refusal(const VsForwardIn &in) {
     else if (((f & (VS_FLAG_BF16_ATTENTION | VS_FLAG_F16X3_ATTENTION)) && dh == 256) || ((f & VS_FLAG_F16X3_ATTENTION) && !(f & VS_FLAG_BF16_ATTENTION) && dh == 128))
         snprintf(msg, sizeof msg, "VS_FLAG_BF16_ATTENTION needs head_dim 32, 64 or 128, VS_FLAG_F16X3_ATTENTION 32 or 64 (got %d)", dh);
     else if ((f & VS_FLAG_BF16_ATTENTION) && (f & VS_FLAG_F16X3_ATTENTION)) snprintf(msg, sizeof msg, "VS_FLAG_BF16_ATTENTION and VS_FLAG_F16X3_ATTENTION are exclusive");
+    else if (in.packed && dh == 256) snprintf(msg, sizeof msg, "packed batches need head_dim 32, 64 or 128 (got %d)", dh);     // no packed attention kernel
     return msg;
+}
+
+// every kernel an accepted plan names exists: the support predicate of each launcher it sends forward_core to holds (the
+// attention launchers of the padded forms have no predicate: their head-dim rules are restated here)
+int kernels_exist(const VsForwardIn &in, const VskOptions &opt, const VsForwardPlan &p) {
+    const int d = in.d_model, dh = d / in.num_heads;
+    switch (p.attention) {
+    case VS_ATT_PACKED: {     // the tiling is a fact of the lengths: both answers vs_packed_waves has, from lengths that give them
+        const long long tilings[][2] = {{1024, 1024}, {105, 100}, {106, 100}, {256, 128}};
+        for (auto &t : tilings) CHECK(vsk_attention_packed_supported(dh, vs_packed_waves(dh, p.attention_arith, t[0], t[1]), p.mode_attention));
+    } break;
+    case VS_ATT_DH256: CHECK(dh == 256 && p.mode_attention == 0); break;
+    case VS_ATT_SPLITKV: CHECK((dh == 32 || dh == 64 || dh == 128) && p.attention_arith != VS_ARITH_BF16); break;      // (exact whatever the word says)
+    case VS_ATT_LOWPREC: CHECK(dh == 32 || dh == 64 || (dh == 128 && p.mode_attention != 2)); CHECK(p.mode_attention == 1 || p.mode_attention == 2 || p.mode_attention == S16); break;
+    case VS_ATT_EXACT: CHECK((dh == 32 || dh == 64 || dh == 128) && p.mode_attention == 0); break;
+    }
+    if (p.embed == VS_EMBED_SPLITK) CHECK(vsk_linear_parts_supported(d, in.in_features, 8));
+    if (p.ln1 == VS_LN_SPLITK_ROWS) CHECK(vsk_linear_parts_supported(d, d, 2));
+    if (p.ln2 == VS_LN_SPLITK_ROWS) CHECK(vsk_linear_parts_supported(d, 4 * d, 4));
+    if (p.embed == VS_EMBED_BF16_QKV) CHECK(vsk_mlp_bf16_supported(d) && in.has_b_embed);
+    if (p.layer == VS_LAYER_BF16_TAIL || p.layer == VS_LAYER_BF16_MLP) CHECK(vsk_mlp_bf16_supported(d));
+    if (p.layer == VS_LAYER_RING)
+        CHECK(vsk_gemm16_supported(p.M, 3 * d, d) && vsk_gemm16_supported(p.M, d, d) && vsk_gemm16_supported(p.M, 4 * d, d) && vsk_gemm16_supported(p.M, d, 4 * d));
+    if (p.layer == VS_LAYER_EXACT_PAIR) CHECK(vsk_layer_fused_supported(p.M, d, opt.skinny_rows));
+    return 0;
+}
+
+// latency mode over embedding widths: the embedding splits K exactly where vsk_linear_parts takes an eighth of in_features
+int latency_grid(const int (*dims)[2], int ndims, long long *points) {
+    const int widths[] = {1000, 1024, 2048, 3072, 4096, 5120};
+    const int frames[] = {65, 320};
+    const unsigned modes[] = {SPLITK, SPLITK | VS_FLAG_F16X3_LINEAR};
+    for (int i = 0; i < ndims; ++i) for (int w : widths) for (int T : frames) for (unsigned flags : modes) for (int kind = 0; kind < 3; ++kind) {
+        VsForwardIn in = rows(model(dims[i][0], dims[i][1], w), T, flags);
+        if (kind == 1) in = with_cls(in);
+        if (kind == 2) in = packed(in);
+        VsForwardPlan p;
+        std::string err;
+        const int rc = vs_forward_plan(in, defaults(), &p, &err);
+        ++*points;
+        if (!expected_refusal(in).empty()) { CHECK(rc == VS_ERR_INVALID && err == expected_refusal(in)); continue; }
+        CHECK(rc == VS_OK);
+        if (kernels_exist(in, defaults(), p)) { std::printf("  (latency grid: d %d, %d heads, in_features %d, T %d, flags %u, kind %d)\n", dims[i][0], dims[i][1], w, T, flags, kind); return 1; }
+        const int d = dims[i][0];
+        const bool latency = kind == 0 && (d == 128 || d == 256 || d == 512);
+        CHECK((p.ln2 == VS_LN_SPLITK_ROWS) == latency);
+        CHECK((p.embed == VS_EMBED_SPLITK) == (latency && (w == 1024 || w == 2048 || w == 4096)));
+    }
+    return 0;
 }
 
 int grid(long long *points) {
@@ -273,8 +336,12 @@ int grid(long long *points) {
             const bool latency = p.embed == VS_EMBED_SPLITK || p.attention == VS_ATT_SPLITKV || p.ln1 == VS_LN_SPLITK_ROWS || p.ln2 == VS_LN_SPLITK_ROWS;
             CHECK(!latency || ((flags & VS_FLAG_SPLITK) && !in.packed && !in.cls && p.linear != VS_ARITH_BF16 && p.M <= opt.skinny_rows && p.ln2 == VS_LN_SPLITK_ROWS));
             if (emb) CHECK(!p.qkv16 && !p.ffn16 && !tail_family && p.layer != VS_LAYER_EXACT_PAIR && p.ln1 != VS_LN_FUSED && p.ln2 != VS_LN_FUSED);
+            if (kernels_exist(in, opt, p)) {
+                std::printf("  (grid: d %d, %d heads, B %d, T %d, flags %u, kind %d, embedded %d)\n", dm[0], dm[1], s[0], s[1], flags, kind, emb);
+                return 1;
+            }
         }
-    return 0;
+    return latency_grid(dims, (int)(sizeof dims / sizeof dims[0]), points);
 }
 
 }  // namespace
@@ -320,6 +387,17 @@ int main() {
     CHECK(vs_packed_waves(64, 1, 1024, 1024) == 8 && vs_packed_waves(64, 2, 1024, 1024) == 8);
     CHECK(vs_packed_waves(32, 0, 1024, 1024) == 8 && vs_packed_waves(32, 1, 1024, 1024) == 4 && vs_packed_waves(32, 2, 1024, 1024) == 4);
     CHECK(vs_packed_waves(128, 0, 1024, 1024) == 4 && vs_packed_waves(128, 1, 1024, 1024) == 8 && vs_packed_waves(128, 1, 256, 128) == 8);
+
+    // ... and the kernels vsk_attention_packed has for them, per mode word: bf16 at head dim 128 on 8-wave blocks in both storage forms
+    CHECK(vsk_attention_packed_supported(128, 8, S16) && vsk_attention_packed_supported(128, 8, 1) && vsk_attention_packed_supported(128, 4, 0));
+    CHECK(!vsk_attention_packed_supported(128, 4, S16) && !vsk_attention_packed_supported(128, 4, 1) && !vsk_attention_packed_supported(128, 8, 0));
+    CHECK(!vsk_attention_packed_supported(128, 8, 2) && !vsk_attention_packed_supported(128, 4, 2) && !vsk_attention_packed_supported(256, 4, 0));
+    CHECK(vsk_attention_packed_supported(32, 8, 0) && !vsk_attention_packed_supported(32, 8, 1) && !vsk_attention_packed_supported(32, 8, 2) && !vsk_attention_packed_supported(32, 8, S16));
+    CHECK(!vsk_attention_packed_supported(64, 2, 0) && !vsk_attention_packed_supported(64, 8, 3) && !vsk_attention_packed_supported(48, 4, 0));
+    // split-K slices: multiples of 128, whole 256-k phases above 256
+    CHECK(vsk_linear_parts_supported(256, 1024, 8) && vsk_linear_parts_supported(256, 2048, 8) && vsk_linear_parts_supported(256, 4096, 8));
+    CHECK(!vsk_linear_parts_supported(256, 3072, 8) && !vsk_linear_parts_supported(256, 5120, 8) && !vsk_linear_parts_supported(256, 1000, 8));
+    CHECK(!vsk_linear_parts_supported(250, 1024, 8) && !vsk_linear_parts_supported(256, 1024, 0) && !vsk_linear_parts_supported(256, 1024, 3));
 
     long long points = 0;
     if (grid(&points)) return 1;

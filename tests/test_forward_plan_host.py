@@ -2,7 +2,9 @@
 of the model's shape, the call and the switches.  tests/cabi/forward_plan_demo.cpp includes that header alone and is built with
 the host C++17 compiler under AddressSanitizer and UBSan: a table of named cases gives the expected plan and reaches every
 enumerator of every plan enum, each A/B switch flips exactly the fields DESIGN.md section 10 names, and over a grid of shapes,
-flags, switches and call forms the plan's invariants hold and every invalid combination is refused with its documented message."""
+flags, switches and call forms the plan's invariants hold, every invalid combination is refused with its documented message, and
+every accepted plan names only kernels its launchers have (their support predicates, which live in the same header; a second
+grid walks the latency mode over embedding widths)."""
 import os
 import shutil
 import subprocess

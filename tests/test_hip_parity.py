@@ -1006,16 +1006,17 @@ def test_bf16_compute_long_video(vsa, lp_linear_everywhere):
     assert err < BF16_FULL_LOGIT_TOL
 
 
-@pytest.mark.parametrize("cfg", ["M-A", "M-B8", "M-A-short"])
+@pytest.mark.parametrize("cfg", ["M-A", "M-B8", "M-A-short", "H2-d256", "H2-d256-short", "H1-d128", "H1-d128-short"])
 def test_bf16_storage_is_bit_identical_to_fp32_storage(vsa, lp_linear_everywhere, cfg):
     """In the bf16 mode q*scale, k, v, the attention output and the MLP hidden tensor are written to HBM as bf16 by
     their producers (every consumer rounds them to bf16 on entry anyway).  VS_LP_STORE32=1 keeps them fp32: the two
     must agree BIT FOR BIT - padded batch, masked batch, packed ragged batch, 4- and 8-wave attention blocks, head dim
-    64 and 32, the score head and the hidden state."""
+    64, 32 and 128 (two heads at d_model 256, one at d_model 128: the 8-wave bf16 kernel in both call forms, fed by
+    vsk_qkv's bf16 planes), the score head and the hidden state."""
     synth = vsa.synth
-    d, H, L = (256, 8, 3) if cfg == "M-B8" else (256, 4, 2)
+    d, H, L = {"M-B8": (256, 8, 3), "H2-d256": (256, 2, 2), "H1-d128": (128, 1, 2)}.get(cfg.replace("-short", ""), (256, 4, 2))
     sd = synth.make_state_dict(d, L, 171, trained_like=True)
-    lengths = [130, 77, 64, 1] if cfg == "M-A-short" else [512, 333, 256, 31]
+    lengths = [130, 77, 64, 1] if cfg.endswith("-short") else [512, 333, 256, 31]
     x = synth.make_features(4, max(lengths), 172, "pool5", lengths=lengths)
     mask = synth.padding_mask(x)
     m = vsa.SimNet(num_heads=H, d_model=d, num_layers=L, sparsity=0.0, dropout=0.3)
@@ -1090,7 +1091,7 @@ def test_mlp_block_bf16_kernel(vsa, M, nc, sig):
 
 
 @pytest.mark.parametrize("tile256", [0, 1])
-@pytest.mark.parametrize("cfg", ["M-A", "M-B8", "M-A-ragged"])
+@pytest.mark.parametrize("cfg", ["M-A", "M-B8", "M-A-ragged", "H2-d256", "H2-d256-ragged"])
 def test_bf16_layer_tail_kernel_is_bit_identical_to_outproj_then_mlp_kernel(vsa, lp_linear_everywhere, cfg, tile256):
     """With the attention output stored as bf16, the bf16 mode runs out-projection + residual + norm1 + MLP block + norm2
     (+ score head) as ONE kernel (vs_mlp_fused.hip, TAIL), which then also projects its rows to the NEXT layer's q/k/v
@@ -1098,11 +1099,12 @@ def test_bf16_layer_tail_kernel_is_bit_identical_to_outproj_then_mlp_kernel(vsa,
     three multiply in the same order as the stand-alone kernels they replace (gemm_ln_rows; gemm_nt_128<EPI_QKV, C16>;
     gemm_nt_128<EPI_PE>) and share their epilogue arithmetic, so against VS_LP_TAIL_UNFUSED=1 / VS_LP_QKV_UNFUSED=1 / VS_LP_EMBED_UNFUSED=1
     (those kernels, h1 and the layer output re-read from HBM) logits, scores and hidden state must agree BIT FOR BIT -
-    padded, masked and packed batches, head dim 64 and 32, in-place (middle layers) and out-of-place (last layer)."""
+    padded, masked and packed batches, head dim 64, 32 and 128 (two heads: the QKV epilogues write the bf16 planes the 8-wave
+    head-dim-128 attention reads), in-place (middle layers) and out-of-place (last layer)."""
     synth = vsa.synth
-    d, H, L = (256, 8, 3) if cfg == "M-B8" else (256, 4, 3)
+    d, H, L = (256, 8, 3) if cfg == "M-B8" else (256, 2, 3) if cfg.startswith("H2-") else (256, 4, 3)
     sd = synth.make_state_dict(d, L, 371, trained_like=True)
-    lengths = [257, 1, 100, 513, 7] if cfg == "M-A-ragged" else [512, 333, 256, 31]
+    lengths = [257, 1, 100, 513, 7] if cfg.endswith("-ragged") else [512, 333, 256, 31]
     x = synth.make_features(len(lengths), max(lengths), 372, "pool5", lengths=lengths)
     mask = synth.padding_mask(x)
     m = vsa.SimNet(num_heads=H, d_model=d, num_layers=L, sparsity=0.0, dropout=0.3)

@@ -1455,16 +1455,17 @@ int vsk_attention_packed(const float *q, const float *k, const float *v, float *
                          float scale, const int *cu, const int *work, int nwork, int nw, int prec, hipStream_t st) {
     const float sl2 = vsk_attention_qscale(scale);
     if (nwork <= 0) return 0;
+    // the supported (head dim, waves per block) rows of each precision: the rule the planner reads too (vs_forward_plan.h);
+    // what it does not list has no kernel: -1
+    if (!vsk_attention_packed_supported(dh, nw, prec)) return -1;
     if (prec == (1 | VSK_STORE16) && dh == 64 && nw == 8 && vsk_options().attn_w64)      // one wave per SIMD: the same 256-row work items
         return vsk_attention_bf16_w64_packed(q, k, v, out, H, Mtot, cu, work, nwork, st);
     dim3 grid(nwork, H);
     const int2 *wk = (const int2 *)work;
-    // the supported (head dim, waves per block) rows of each precision; what is not listed has no kernel: -1
-    if (nw != 4 && nw != 8) return -1;
     const int r = row(dh, nw);
     bool found;
-    if (prec == (1 | VSK_STORE16))      // bf16 q (pre-scaled) / k / v in, bf16 out
-        found = vsk_pick_int<row(64, 8), row(64, 4), row(32, 4)>(r, [&](auto ROW) {
+    if (prec == (1 | VSK_STORE16))      // bf16 q (pre-scaled) / k / v in, bf16 out; head dim 128: d_model <= 256 with one or two heads
+        found = vsk_pick_int<row(64, 8), row(64, 4), row(32, 4), row(128, 8)>(r, [&](auto ROW) {
             constexpr int DH = ROW() / 16, NW = ROW() % 16;
             hipLaunchKernelGGL((attn_fwd_lp_pipe<DH, NW, 1, true, true>), grid, dim3(64 * NW), 0, st, q, k, v, nullptr, out, H, 0, sl2, 0,
                                cu, wk, Mtot);

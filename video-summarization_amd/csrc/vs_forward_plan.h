@@ -50,6 +50,32 @@ inline bool vsk_mlp_bf16_supported(int d) { return d == 256; }
 inline bool vsk_gemm16_supported(int M, int N, int K) { return M > 0 && N > 0 && N % 32 == 0 && K >= 32 && K % 32 == 0; }
 // the exact fused pair layer_outproj_ln_fc1 / layer_fc2_ln_qkv of vs_kernels.hip: throughput batches only
 inline bool vsk_layer_fused_supported(int M, int d, int skinny_rows) { return d == 256 && M > skinny_rows && M <= (1 << 20); }
+// vsk_attention_packed (vs_attention.hip): the (head dim, waves per block) rows each mode word has a kernel for.  bf16 at head
+// dim 128 (both storage forms) has 8-wave blocks only, the exact kernel there 4-wave blocks only; the low-precision
+// kernels have no 8-wave form at head dim 32
+inline bool vsk_attention_packed_supported(int dh, int nw, int mode) {
+    if (nw != 4 && nw != 8) return false;
+    if (mode == (1 | VSK_STORE16) || mode == 1) return (dh == 128 && nw == 8) || dh == 64 || (dh == 32 && nw == 4);
+    if (mode == 2) return dh == 64 || (dh == 32 && nw == 4);
+    if (mode == 0) return (dh == 128 && nw == 4) || dh == 64 || dh == 32;
+    return false;
+}
+// vsk_linear_parts (vs_kernels.hip), latency mode: K in nsplit slices that are multiples of 128, staged in phases of <= 256 k
+// (33 KiB of LDS, no opt-in attribute) - a slice above 256 has to be whole phases
+inline bool vsk_linear_parts_supported(int N, int K, int nsplit) {
+    if (N <= 0 || N % 32 || K <= 0 || nsplit < 1 || K % nsplit) return false;
+    const int kslice = K / nsplit;
+    return kslice % 128 == 0 && !(kslice > 256 && kslice % 256);
+}
+
+// ---- packed ragged batches: the query tile, in waves of 32 rows ----
+// r8 / r4: the batch's rows with every video rounded up to 256- / 128-row tiles.  256-row tiles unless the ragged tails
+// waste too much; the low-precision attention has no 8-wave form for head dim 32; head dim 128 (round 4): the exact kernel
+// has 4-wave blocks, the bf16 one 8-wave blocks only
+inline int vs_packed_waves(int dh, int aprec, long long r8, long long r4) {
+    if (dh == 128) return aprec == 1 ? 8 : 4;
+    return (!(aprec != 0 && dh == 32) && r8 * 100 <= r4 * 105) ? 8 : 4;
+}
 
 // ---- the plan ----
 enum VsArith { VS_ARITH_EXACT = 0, VS_ARITH_BF16 = 1, VS_ARITH_F16X3 = 2 };      // the values are the kernels' mode words
@@ -158,8 +184,10 @@ inline int vs_forward_plan(const VsForwardIn &in, const VskOptions &opt, VsForwa
     p.linear = (flags & VS_FLAG_F16X3_LINEAR) ? VS_ARITH_F16X3 : ((flags & VS_FLAG_BF16_LINEAR) && M > lp_min_rows) ? VS_ARITH_BF16 : VS_ARITH_EXACT;
     const bool bf16 = p.linear == VS_ARITH_BF16;
     // latency mode (VS_FLAG_SPLITK): exact or fp16x3 kernels, latency-sized inputs, plain padded batches only
-    // (d_model 128 .. 512 - M-A and the reference's argparse default M-B: K slices that are multiples of 128, partials in the free regions)
-    const bool splitk = (flags & VS_FLAG_SPLITK) && !bf16 && !in.packed && !in.cls && M <= opt.skinny_rows && (d == 128 || d == 256 || d == 512);
+    // (d_model 128 .. 512 - M-A and the reference's argparse default M-B: K slices that are multiples of 128, partials in the free regions;
+    // the slices of fc2, K = 4 d in four, and from d_model 256 on of the out-projection, K = d in two, are ones vsk_linear_parts takes)
+    const bool splitk = (flags & VS_FLAG_SPLITK) && !bf16 && !in.packed && !in.cls && M <= opt.skinny_rows && (d == 128 || d == 256 || d == 512) &&
+                        vsk_linear_parts_supported(d, 4 * d, 4) && (d < 256 || vsk_linear_parts_supported(d, d, 2));
     // weight images: bf16 mode reads the LDS images (d_model > 256: the bf16-operand GEMM's row-major copies too); the other
     // modes read the fragment-major copies wherever a GEMM of this forward is small enough for the latency kernels
     const int rows_min = in.cls ? in.B * in.T : M;
@@ -188,7 +216,7 @@ inline int vs_forward_plan(const VsForwardIn &in, const VskOptions &opt, VsForwa
 
     p.embed = in.cls ? VS_EMBED_CLS
             : bf16 && in.has_b_embed && p.next_qkv && in.num_layers > 0 && !opt.lp_embed_unfused ? VS_EMBED_BF16_QKV
-            : splitk && in.in_features % 1024 == 0 ? VS_EMBED_SPLITK
+            : splitk && vsk_linear_parts_supported(d, in.in_features, 8) ? VS_EMBED_SPLITK     // (in_features 3072, 5120: the default kernels)
             : VS_EMBED_GEMM;
     p.attention = in.packed ? VS_ATT_PACKED
                 : dh == 256 ? VS_ATT_DH256       // (round 4, correctness first)
@@ -211,15 +239,15 @@ inline int vs_forward_plan(const VsForwardIn &in, const VskOptions &opt, VsForwa
     p.mode_qkv = p.qkv16 ? (1 | VSK_STORE16) : p.linear;
     p.mode_ffn = p.ffn16 ? (1 | VSK_STORE16) : p.linear;
     p.mode_attention = (p.qkv16 || ring) ? (1 | VSK_STORE16) : aprec;
+    // the plan names only kernels that exist: a packed batch's tiling is a fact of its lengths (vs_packed_waves), so both
+    // tilings this head dim and arithmetic can get must have a kernel in this mode
+    if (in.packed)
+        for (long long r8 = 1; r8 <= 2; ++r8)
+            if (!vsk_attention_packed_supported(dh, vs_packed_waves(dh, aprec, r8, 1), p.mode_attention)) {
+                if (dh != 32 && dh != 64 && dh != 128) snprintf(msg, sizeof msg, "packed batches need head_dim 32, 64 or 128 (got %d)", dh);
+                else snprintf(msg, sizeof msg, "packed batches: no attention kernel for head_dim %d in mode %d", dh, p.mode_attention);
+                return fail(VS_ERR_INVALID);
+            }
     *plan = p;
     return VS_OK;
-}
-
-// ---- packed ragged batches: the query tile, in waves of 32 rows ----
-// r8 / r4: the batch's rows with every video rounded up to 256- / 128-row tiles.  256-row tiles unless the ragged tails
-// waste too much; the low-precision attention has no 8-wave form for head dim 32; head dim 128 (round 4): the exact kernel
-// has 4-wave blocks, the bf16 one 8-wave blocks only
-inline int vs_packed_waves(int dh, int aprec, long long r8, long long r4) {
-    if (dh == 128) return aprec == 1 ? 8 : 4;
-    return (!(aprec != 0 && dh == 32) && r8 * 100 <= r4 * 105) ? 8 : 4;
 }

@@ -1979,9 +1979,8 @@ int vsk_skinny_max_rows() { return vsk_options().skinny_rows; }
 
 // latency mode: K-slice partial products of A [M, K] x W^T (Wf: fragment-major copy) -> parts [nsplit][M][N], no bias
 int vsk_linear_parts(const float *A, const float *Wf, float *parts, int M, int N, int K, int nsplit, hipStream_t st, int f16x3) {
-    if (Wf == nullptr || nsplit < 1 || K % nsplit) return -1;
+    if (Wf == nullptr || !vsk_linear_parts_supported(N, K, nsplit)) return -1;     // (the rule the planner reads too: vs_forward_plan.h)
     const int kslice = K / nsplit;
-    if (kslice % 128 || (kslice > 256 && kslice % 256) || N % 32) return -1;      // phases of <= 256 k: 33 KiB of LDS, no opt-in attribute
     dim3 grid((M + 31) / 32, (N + 127) / 128, nsplit);
     if (f16x3) hipLaunchKernelGGL(skinny2_gemm_parts<2>, grid, dim3(256), vsk_skinny2_lds(kslice < 256 ? kslice : 256), st, A, Wf, parts, M, N, K, kslice);
     else hipLaunchKernelGGL(skinny2_gemm_parts<0>, grid, dim3(256), vsk_skinny2_lds(kslice < 256 ? kslice : 256), st, A, Wf, parts, M, N, K, kslice);
