@@ -51,11 +51,9 @@ def _report(case, got, want64, fp32_cpu=None):
 # ------------------------------------------------------------------------------------------------------------------------
 # single convs: conv + folded BatchNorm + ReLU through vs_cnn_pack_conv / vs_cnn_conv
 # ------------------------------------------------------------------------------------------------------------------------
-def _conv_case(vsa, seed, n, h, w, cin, cout, k, stride, pad, kind, c0=0, ldc=None):
-    L = vsa._lib
-    lib = L.load()
-    dev = _dev()
-    ldc = cout if ldc is None else ldc
+def _conv_tensors(L, seed, n, h, w, cin, cout, k, stride, pad, kind):
+    """one seeded conv + BatchNorm + ReLU on the CPU: (weights, (gamma, beta, mean, var), the input in the layout of ``kind``,
+    the float64 restatement, torch's fp32 forward), both outputs NHWC"""
     g = torch.Generator().manual_seed(seed)
     wt = torch.randn(cout, cin, k, k, generator=g) * (2.0 / (cin * k * k)) ** 0.5
     gamma, var = 0.5 + torch.rand(cout, generator=g), 0.5 + torch.rand(cout, generator=g)
@@ -76,6 +74,16 @@ def _conv_case(vsa, seed, n, h, w, cin, cout, k, stride, pad, kind, c0=0, ldc=No
 
     want, cpu32 = restated(x64, torch.float64), restated(x32, torch.float32)
     assert (want == 0).any() and (want > 0).any()                                                  # the ReLU cuts something
+    return wt, (gamma, beta, mean, var), given, want, cpu32
+
+
+def _conv_case(vsa, seed, n, h, w, cin, cout, k, stride, pad, kind, c0=0, ldc=None, shift=0):
+    """shift: the input is handed over ``shift`` floats past a 16-byte boundary (the kernel may not assume the alignment)"""
+    L = vsa._lib
+    lib = L.load()
+    dev = _dev()
+    ldc = cout if ldc is None else ldc
+    wt, (gamma, beta, mean, var), given, want, cpu32 = _conv_tensors(L, seed, n, h, w, cin, cout, k, stride, pad, kind)
     ho, wo = want.shape[1], want.shape[2]
     m = n * ho * wo
     P = L.CnnConvParams()
@@ -85,6 +93,14 @@ def _conv_case(vsa, seed, n, h, w, cin, cout, k, stride, pad, kind, c0=0, ldc=No
     packed = torch.empty(lib.vs_cnn_packed_floats(cout, cin, k), dtype=torch.float32, device=dev)
     assert packed.numel() > 0
     given = given.to(dev)
+    if shift:
+        assert given.dtype == torch.float32 and 0 < shift < 4
+        room = torch.empty(given.numel() + shift, dtype=torch.float32, device=dev)
+        room[shift:] = given.reshape(-1)
+        given = room[shift:]
+        assert given.data_ptr() % 16 == 4 * shift
+    else:
+        assert given.data_ptr() % 16 == 0
     out = torch.full((GUARD + m * ldc + GUARD,), CANARY, dtype=torch.float32, device=dev)
     L.check(lib.vs_cnn_pack_conv(C.byref(P), cout, cin, k, packed.data_ptr(), None))
     L.check(lib.vs_cnn_conv(given.data_ptr(), kind, n, h, w, cin, packed.data_ptr(), cout, k, stride, pad,
@@ -116,6 +132,60 @@ def test_single_conv_against_float64(vsa, name):
     got, want, cpu32 = _conv_case(vsa, 100 + list(CONVS).index(name), n, h, w, cin, cout, k, stride, pad, kind, c0, ldc)
     assert got.shape == want.shape
     _report("conv " + name, got, want, cpu32)
+
+
+# the forms of conv_igemm the network's own shapes never reach (kind 0: f32 NCHW, 2: f32 NHWC).  The scalar gather runs from NHWC
+# when Cin % 4 != 0 and from NCHW; the store guard meets one column and one column past a tile; a row tile holds 1, 64 and 65 rows;
+# k, stride and pad are not the network's k in {1, 3, 7} with pad = k / 2.  Each seed was checked on the CPU: the
+# helper's "the ReLU cuts something, something survives" holds for it.
+EDGE_CONVS = {   # name: (seed, n, h, w, cin, cout, k, stride, pad, kind, c0, ldc)
+    "3x3p1 6->32 2x5x7 nhwc scalar (K=54, 4 k across two taps)": (1100, 2, 5, 7, 6, 32, 3, 1, 1, 2, 0, None),
+    "3x3p1 1->16 1x6x5 nhwc scalar": (1200, 1, 6, 5, 1, 16, 3, 1, 1, 2, 0, None),
+    "1x1 5->24 2x4x5 nhwc scalar (K=5)": (1300, 2, 4, 5, 5, 24, 1, 1, 0, 2, 0, None),
+    "3x3p1 5->32 2x6x7 f32 nchw": (1400, 2, 6, 7, 5, 32, 3, 1, 1, 0, 0, None),
+    "3x3p1 64->1 2x5x6": (1500, 2, 5, 6, 64, 1, 3, 1, 1, 2, 0, None),
+    "3x3p1 64->1 2x5x6 at c0=3 of 7": (1500, 2, 5, 6, 64, 1, 3, 1, 1, 2, 3, 7),
+    "3x3p1 32->65 1x5x6": (1600, 1, 5, 6, 32, 65, 3, 1, 1, 2, 0, None),
+    "3x3p1 32->65 1x5x6 at c0=5 of 80": (1600, 1, 5, 6, 32, 65, 3, 1, 1, 2, 5, 80),
+    "1x1 64->32 1x1x1 (M=1)": (1700, 1, 1, 1, 64, 32, 1, 1, 0, 2, 0, None),
+    "3x3p1 8->16 1x8x8 (M=64)": (1800, 1, 8, 8, 8, 16, 3, 1, 1, 2, 0, None),
+    "3x3p1 8->16 1x5x13 (M=65)": (1900, 1, 5, 13, 8, 16, 3, 1, 1, 2, 0, None),
+    "5x5s3p2 8->16 1x11x14": (2000, 1, 11, 14, 8, 16, 5, 3, 2, 2, 0, None),
+    "3x3s2p0 8->16 1x8x9 (the last row is never read)": (2100, 1, 8, 9, 8, 16, 3, 2, 0, 2, 0, None),
+    "2x2s1p1 8->16 1x4x5": (2200, 1, 4, 5, 8, 16, 2, 1, 1, 2, 0, None),
+    "3x3p2 4->16 1x4x5 (a corner output has one real tap)": (2300, 1, 4, 5, 4, 16, 3, 1, 2, 2, 0, None),
+}
+
+
+@pytest.mark.parametrize("name", list(EDGE_CONVS))
+def test_single_conv_edges_against_float64(vsa, name):
+    seed, n, h, w, cin, cout, k, stride, pad, kind, c0, ldc = EDGE_CONVS[name]
+    got, want, cpu32 = _conv_case(vsa, seed, n, h, w, cin, cout, k, stride, pad, kind, c0, ldc)
+    assert got.shape == want.shape == (n, (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1, cout)
+    if "(M=" in name:
+        assert "(M=%d)" % (want.numel() // cout) in name
+    if "never read" in name:
+        assert (want.shape[1] - 1) * stride + k < h and (want.shape[2] - 1) * stride + k == w
+    if "corner" in name:            # pad = k - 1, the most the ABI takes: a corner output has one tap inside the input, the corner pixel
+        wt, (gamma, beta, mean, var), x, _, _ = _conv_tensors(vsa._lib, seed, n, h, w, cin, cout, k, stride, pad, kind)
+        scale = gamma.double() / torch.sqrt(var.double() + 0.001)
+        bias = beta.double() - mean.double() * scale
+        for (i, j), (dh, dw) in (((0, 0), (2, 2)), ((0, -1), (2, 0)), ((-1, 0), (0, 2)), ((-1, -1), (0, 0))):
+            one_tap = F.relu(bias + scale * (wt[:, :, dh, dw].double() @ x[0, i, j].double()))
+            assert torch.allclose(want[0, i, j], one_tap, rtol=0, atol=1e-12), (i, j)
+        assert (want[0, 0, 0] > 0).any() and (want[0, 0, 0] != F.relu(bias)).any()
+    _report("conv " + name, got, want, cpu32)
+
+
+def test_conv_from_a_misaligned_nhwc_pointer_is_bit_equal_to_the_aligned_run(vsa):
+    """Cin = 64 takes the 16-byte gather only where the pointer allows it; 4 bytes past a 16-byte boundary the same tensor goes
+    through the scalar gather.  Both are one multiply-add chain over k ascending per output, so the bits are equal."""
+    case = (1000, 2, 5, 6, 64, 48, 3, 1, 1, vsa._lib.VS_CNN_INPUT_F32_NHWC)
+    aligned, want, cpu32 = _conv_case(vsa, *case)
+    shifted, _, _ = _conv_case(vsa, *case, shift=1)
+    _report("conv 3x3p1 64->48 2x5x6 nhwc at +4 bytes", shifted, want, cpu32)
+    assert torch.equal(aligned.contiguous().view(torch.int32), shifted.contiguous().view(torch.int32))
+    print("features_parity %-44s bit-equal to the aligned run" % "conv 3x3p1 64->48 2x5x6 nhwc at +4 bytes")
 
 
 def test_conv_padding_tap_of_uint8_frames_is_zero_after_normalisation(vsa):
@@ -175,6 +245,60 @@ def test_maxpool_is_bit_equal_to_torch(vsa, name):
     got = out[GUARD:GUARD + want.numel()].view(want.shape)
     assert torch.equal(got.view(torch.int32), want.view(torch.int32))
     print("features_parity %-44s bit-equal to F.max_pool2d" % ("maxpool " + name))
+
+
+def _maxpool(vsa, x, k, stride, pad, ceil_mode):
+    """the kernel on NCHW ``x`` (given as NHWC), between canaries; the output NHWC, shaped by F.max_pool2d"""
+    L = vsa._lib
+    lib, dev = L.load(), _dev()
+    n, c, h, w = x.shape
+    want = F.max_pool2d(x, k, stride, pad, ceil_mode=bool(ceil_mode)).permute(0, 2, 3, 1).contiguous()
+    xd = x.permute(0, 2, 3, 1).contiguous().to(dev)
+    out = torch.full((GUARD + want.numel() + GUARD,), CANARY, dtype=torch.float32, device=dev)
+    L.check(lib.vs_cnn_maxpool(xd.data_ptr(), n, h, w, c, k, stride, pad, ceil_mode, out[GUARD:].data_ptr(), None))
+    torch.cuda.synchronize()
+    out = out.cpu()
+    assert (out[:GUARD] == CANARY).all() and (out[GUARD + want.numel():] == CANARY).all()
+    return out[GUARD:GUARD + want.numel()].view(want.shape), want
+
+
+POOL_EDGES = {   # name: (n, h, w, c, k, stride, pad, ceil_mode, (ho, wo))
+    "k3s2 floor 8x9": (2, 8, 9, 8, 3, 2, 0, 0, (3, 4)),
+    "k3s2p1 floor 7x7": (2, 7, 7, 8, 3, 2, 1, 0, (4, 4)),
+    "k2s2p1 ceil 3x3 (the last window is dropped)": (2, 3, 3, 8, 2, 2, 1, 1, (2, 2)),
+    "k1s1 5x4 (the identity)": (2, 5, 4, 8, 1, 1, 0, 1, (5, 4)),
+    "k3s2 ceil 7x6 C=4": (2, 7, 6, 4, 3, 2, 0, 1, (3, 3)),
+}
+
+
+@pytest.mark.parametrize("name", list(POOL_EDGES))
+def test_maxpool_edges_are_bit_equal_to_torch(vsa, name):
+    n, h, w, c, k, stride, pad, ceil_mode, shape = POOL_EDGES[name]
+    x = torch.randn(n, c, h, w, generator=torch.Generator().manual_seed(250 + list(POOL_EDGES).index(name))) - 2.0
+    x[:, :, 0, 0] = -0.0
+    if "dropped" in name:           # without torch's rule ("the last window starts inside the input or its left padding"): 3, not 2
+        assert -(-(h + 2 * pad - k) // stride) + 1 == 3 and (3 - 1) * stride >= h + pad
+    got, want = _maxpool(vsa, x, k, stride, pad, ceil_mode)
+    assert want.shape == (n,) + shape + (c,) and (want < 0).any()
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    if "identity" in name:
+        assert torch.equal(want.view(torch.int32), x.permute(0, 2, 3, 1).contiguous().view(torch.int32))
+    print("features_parity %-44s bit-equal to F.max_pool2d" % ("maxpool " + name))
+
+
+def test_maxpool_carries_a_nan_and_keeps_minus_infinity(vsa):
+    """a NaN wins every window it lies in, as in torch; -inf is an ordinary value, also where it is a window's maximum"""
+    x = torch.randn(1, 8, 7, 7, generator=torch.Generator().manual_seed(260)) - 2.0
+    x[0, 1, 2, 2] = float("nan")
+    x[0, 2, 2, 4] = float("-inf")
+    x[0, 5, :3, :3] = float("-inf")                                 # the whole first window of channel 5
+    x[0, 6, 0, 0] = float("nan")                                    # a window's first value; x[0, 1, 2, 2] lies in four windows
+    got, want = _maxpool(vsa, x, 3, 2, 0, 1)
+    nan = torch.isnan(want)
+    assert nan.sum() == 5 and want[0, 0, 0, 5] == float("-inf") and torch.isinf(want).sum() == 1
+    assert torch.equal(torch.isnan(got), nan)
+    assert torch.equal(got[~nan].view(torch.int32), want[~nan].view(torch.int32))
+    print("features_parity %-44s NaN mask equal, the rest bit-equal to F.max_pool2d" % "maxpool k3s2 ceil 7x7 with NaN and -inf")
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -86,11 +86,18 @@ class _Conv:
             y = y + residual.to(dt)
         return (F.relu(y) if relu else y).contiguous()
 
-    def run(self, given, kind, n, t, h, w, out_shape, residual=None, relu=True):
-        """the kernel on ``given`` (in the layout of ``kind``); the output sits between canaries"""
+    def run(self, given, kind, n, t, h, w, out_shape, residual=None, relu=True, shift=0):
+        """the kernel on ``given`` (in the layout of ``kind``); the output sits between canaries.  shift: the input is handed
+        over ``shift`` floats past a 16-byte boundary (the kernel may not assume the alignment)"""
         cin, cout, kt, ks, st, ss, pt, ps = self.geom
         dev = _dev()
         given = given.contiguous().to(dev)
+        if shift:
+            assert given.dtype == torch.float32 and 0 < shift < 4
+            room = torch.empty(given.numel() + shift, dtype=torch.float32, device=dev)
+            room[shift:] = given.reshape(-1)
+            given = room[shift:]
+        assert given.data_ptr() % 16 == 4 * shift
         res = None if residual is None else residual.contiguous().to(dev)
         count = int(np.prod(out_shape))
         out = torch.full((GUARD + count + GUARD,), CANARY, dtype=torch.float32, device=dev)
@@ -159,6 +166,64 @@ def test_conv_1x1x1_stride_2_without_relu_or_residual(vsa):
     """the downsample: 64 -> 128 on 2 x 5 x 7 x 9; negative outputs survive"""
     _, _, _, got, want = _ndhwc_case(vsa, "1x1x1 s2 64->128 2x5x7x9", 504, 2, 5, 7, 9, 64, 128, 1, 1, 2, 0, False, False)
     assert got.shape == (2, 3, 4, 5, 128) and (want < 0).any() and (got < 0).any()
+
+
+# the forms of conv3d_igemm the network's own shapes never reach.  In the network every channels-last conv has kt == ks, st == ss,
+# pt == ps and Cin, Cout multiples of 64; only the stem tells time from space, through the scalar and uint8 gathers.
+NDHWC, NCDHW = 2, 0         # = VS_CNN3D_INPUT_F32_NDHWC, VS_CNN3D_INPUT_F32_NCDHW (asserted in _edge_case)
+EDGE_CONVS = {   # name: (seed, (n, t, h, w), (cin, cout, kt, ks, st, ss, pt, ps), kind, residual, (n, to, ho, wo))
+    # the 16-byte gather with time and space apart; T, H, W all differ, so a stride or pad taken from the other axis shows
+    "3x1x1 s(1,2) p(1,0) 64->64 1x5x7x9 +relu": (800, (1, 5, 7, 9), (64, 64, 3, 1, 1, 2, 1, 0), NDHWC, False, (1, 5, 4, 5)),
+    "1x3x3 s(2,1) p(0,1) 64->64 1x5x7x9 +relu": (801, (1, 5, 7, 9), (64, 64, 1, 3, 2, 1, 0, 1), NDHWC, False, (1, 3, 7, 9)),
+    "3x3x3 s1 p(0,1) 64->64 1x5x4x3 +relu (To = T - 2)": (802, (1, 5, 4, 3), (64, 64, 3, 3, 1, 1, 0, 1), NDHWC, False, (1, 3, 4, 3)),
+    # the scalar gather: from channels-last with Cin % 4 != 0 (K = 162, 4 k across two taps), and from NCDHW with Cin != 3
+    "3x3x3 s1 p1 6->32 1x3x4x5 ndhwc scalar +relu": (803, (1, 3, 4, 5), (6, 32, 3, 3, 1, 1, 1, 1), NDHWC, False, (1, 3, 4, 5)),
+    "3x3x3 s1 p1 5->32 2x3x4x5 f32 ncdhw +relu": (804, (2, 3, 4, 5), (5, 32, 3, 3, 1, 1, 1, 1), NCDHW, False, (2, 3, 4, 5)),
+    # one column, and one column past a tile: the store and the residual read share the column guard
+    "3x3x3 s1 p1 64->1 1x3x4x5 +residual +relu": (805, (1, 3, 4, 5), (64, 1, 3, 3, 1, 1, 1, 1), NDHWC, True, (1, 3, 4, 5)),
+    "3x3x3 s1 p1 32->65 1x3x4x5 +residual +relu": (806, (1, 3, 4, 5), (32, 65, 3, 3, 1, 1, 1, 1), NDHWC, True, (1, 3, 4, 5)),
+    # 1, 64 and 65 rows
+    "1x1x1 64->32 1x1x1x1 +relu (M=1)": (807, (1, 1, 1, 1), (64, 32, 1, 1, 1, 1, 0, 0), NDHWC, False, (1, 1, 1, 1)),
+    "3x3x3 s1 p1 8->16 1x4x4x4 +relu (M=64)": (808, (1, 4, 4, 4), (8, 16, 3, 3, 1, 1, 1, 1), NDHWC, False, (1, 4, 4, 4)),
+    "3x3x3 s1 p1 8->16 1x1x5x13 +relu (M=65)": (809, (1, 1, 5, 13), (8, 16, 3, 3, 1, 1, 1, 1), NDHWC, False, (1, 1, 5, 13)),
+}
+
+
+def _edge_case(vsa, name, shift=0):
+    """(the conv, the kernel's output, the float64 restatement, torch's fp32 forward) of an EDGE_CONVS entry"""
+    L = vsa._lib
+    assert (NDHWC, NCDHW) == (L.VS_CNN3D_INPUT_F32_NDHWC, L.VS_CNN3D_INPUT_F32_NCDHW)
+    seed, (n, t, h, w), geom, kind, residual, out_shape = EDGE_CONVS[name]
+    conv = _Conv(vsa, seed, *geom)
+    x = torch.randn(n, geom[0], t, h, w, generator=conv.g)                                          # signed
+    shape = tuple(conv.restated(x, torch.float32, relu=False).shape)
+    assert shape == out_shape + (geom[1],)
+    res = torch.randn(shape, generator=conv.g) if residual else None
+    want, cpu32 = conv.restated(x, torch.float64, res, True), conv.restated(x, torch.float32, res, True)
+    assert (want == 0).any() and (want > 0).any()                                                   # the ReLU cuts something
+    given = x if kind == NCDHW else x.permute(0, 2, 3, 4, 1)
+    got = conv.run(given, kind, n, t, h, w, shape, res, True, shift=shift)
+    if residual:
+        assert (conv.restated(x, torch.float64) != want).any()                                      # the residual changes the result
+    return conv, got, want, cpu32
+
+
+@pytest.mark.parametrize("name", list(EDGE_CONVS))
+def test_single_conv_edges_against_float64(vsa, name):
+    _, got, want, cpu32 = _edge_case(vsa, name)
+    if "(M=" in name:
+        assert "(M=%d)" % (want.numel() // want.shape[-1]) in name
+    _report("conv " + name, got, want, cpu32)
+
+
+def test_conv_from_a_misaligned_ndhwc_pointer_is_bit_equal_to_the_aligned_run(vsa):
+    """Cin = 64 takes the 16-byte gather only where the pointer allows it; 4 bytes past a 16-byte boundary the same tensor goes
+    through the scalar gather.  Both are one multiply-add chain over k ascending per output, so the bits are equal."""
+    name = "3x1x1 s(1,2) p(1,0) 64->64 1x5x7x9 +relu"
+    _, aligned, want, cpu32 = _edge_case(vsa, name)
+    _, shifted, _, _ = _edge_case(vsa, name, shift=1)
+    _report("conv " + name + " at +4 bytes", shifted, want, cpu32)
+    assert _same_bits(aligned, shifted)
 
 
 # ------------------------------------------------------------------------------------------------------------------------

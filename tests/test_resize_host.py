@@ -20,16 +20,20 @@ PLAN_HEADER = os.path.join(ROOT, "video-summarization_amd", "csrc", "vs_resize_p
 GPU_GEOMETRIES = ((3, 17, 15, 40, 33), (1, 64, 80, 15, 19), (2, 33, 47, 33, 20), (2, 33, 47, 20, 47), (1, 300, 40, 15, 40),
                   (2, 360, 640, 224, 398))
 EXTRA_GEOMETRIES = ((1, 1080, 1920, 224, 398), (1, 224, 300, 224, 224), (1, 5, 3, 1, 1), (1, 2, 2, 9, 9))
+# (n, h, w, oh, ow) of tests/test_hip_resize_tiles.py: the tiles narrower or shorter than the default one, and its edges
+TILE_GEOMETRIES = tuple(c[0] + c[1] for c in resize_ref.TILE_CASES.values())
+NEW_TILE_GEOMETRIES = tuple(g for g in TILE_GEOMETRIES if g not in GPU_GEOMETRIES + EXTRA_GEOMETRIES)
 AXES = ((360, 224), (640, 398), (1080, 224), (1920, 398), (2160, 224), (60, 224), (300, 15))
 GRID = 40
 
 
-@pytest.mark.parametrize("geometry", GPU_GEOMETRIES + EXTRA_GEOMETRIES, ids=lambda g: "%dx%d-%dx%d" % g[1:])
+@pytest.mark.parametrize("geometry", GPU_GEOMETRIES + EXTRA_GEOMETRIES + NEW_TILE_GEOMETRIES,
+                         ids=lambda g: "%dx%d-%dx%d" % g[1:])
 def test_resize_ref_is_pil_bit_for_bit(geometry):
     Image = pytest.importorskip("PIL.Image")
     _, h, w, oh, ow = geometry
-    for kind in ("random", "ramp", "checker"):
-        x = resize_ref.content(kind, 1, h, w, seed=11)
+    for kind in ("random", "ramp", "checker", "blocks"):
+        x = resize_ref.blocks(1, h, w, oh, ow, seed=11) if kind == "blocks" else resize_ref.content(kind, 1, h, w, seed=11)
         want = np.asarray(Image.fromarray(x[0]).resize((ow, oh), Image.BILINEAR))
         got = resize_ref.resize(x, (oh, ow))[0]
         assert got.shape == want.shape and np.array_equal(got, want), (geometry, kind)
@@ -83,7 +87,7 @@ def test_tables_equal_resize_ref(demo):
 def test_every_tile_address_is_in_bounds_and_every_output_byte_written_once(demo):
     # 4K, the smaller tiles in each axis, input rows staged in several chunks at changing address phases
     extra = ((1, 2160, 3840, 224, 398), (1, 7, 2000, 7, 3), (1, 3000, 5, 2, 5), (2, 120, 1500, 16, 40), (2, 120, 1501, 16, 40))
-    args = [str(v) for g in GPU_GEOMETRIES + EXTRA_GEOMETRIES + extra for v in g]
+    args = [str(v) for g in GPU_GEOMETRIES + EXTRA_GEOMETRIES + extra + NEW_TILE_GEOMETRIES for v in g]
     run = subprocess.run([demo, "walk"] + args, capture_output=True, text=True, timeout=600)
     assert run.returncode == 0 and run.stdout.endswith("OK\n"), (run.stdout[-500:], run.stderr[-2000:])
     geoms = {}
@@ -91,11 +95,16 @@ def test_every_tile_address_is_in_bounds_and_every_output_byte_written_once(demo
         f = line.split()
         if f and f[0] == "geom":
             geoms[tuple(int(v) for v in f[1:6])] = (int(f[7]), int(f[9]), int(f[10]))          # path, tile_oh, tile_ow
-    assert len(geoms) == len(GPU_GEOMETRIES + EXTRA_GEOMETRIES + extra)
+    assert len(geoms) == len(GPU_GEOMETRIES + EXTRA_GEOMETRIES + extra + NEW_TILE_GEOMETRIES)
     assert geoms[(2, 360, 640, 224, 398)] == (0, 32, 64) and geoms[(1, 1080, 1920, 224, 398)] == (0, 32, 64)
     path, tile_oh, tile_ow = geoms[(1, 300, 40, 15, 40)]            # ksize 41, 20 input rows per output row: the smaller tile
     assert path == 1 and tile_oh < 32 and tile_ow == 64
     assert geoms[(1, 2160, 3840, 224, 398)][0] == 1 and geoms[(1, 3000, 5, 2, 5)][0] == 1 and geoms[(1, 3000, 5, 2, 5)][2] < 64
+    # every tile the GPU cases name is the tile walked here: widths 16, 4 and 1, heights 8, 4, 2 and 1 among them
+    for (shape, size, path, tile) in resize_ref.TILE_CASES.values():
+        assert geoms[shape + size] == (path,) + tile, (shape, size)
+    assert geoms[(1, 2, 20000, 2, 33)][2] == 4 and geoms[(1, 2, 65536, 2, 130)][2] == 4 and geoms[(1, 2, 65536, 2, 40)][2] == 1
+    assert {g[2] for g in geoms.values()} >= {64, 16, 4, 1} and {g[1] for g in geoms.values()} >= {32, 8, 4, 2, 1}
 
 
 def test_plan_header_has_no_hip_include():
